@@ -7,7 +7,7 @@ launches through the C ABI of libcloudsc2_hip.so.  Inputs are synthetic columns 
 in HBM (gt4py_dwarf_p_cloudsc2_tl_ad_amd/synthetic.py; the reference's data/input.h5 is not
 available) and are resident before the timed region starts.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]            # N > 1: starts its own N ranks (see below)
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--full] [--dump-outputs DIR]   # N > 1: starts its own N ranks
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W  # same thing, ranks started by the caller
 
@@ -36,6 +36,11 @@ addresses decides how 26 concurrent streams fall onto HBM channels and banks, wo
 state is placed there; `--placement separate` gives one torch allocation per field instead.  The record says what was done
 (`placement`).
 
+A plain run does what the headline figure needs: build, resident state, field placement, warm-up, the K timed steps, the
+outputs of the last step if `--dump-outputs DIR` is given, the line.  Everything below beside `value` / `ms_per_step` (the
+rooflines, `cpu_baseline`, `fused_step`, `value_default_placement`, `validation_norm`; --config 3 / 4: `variants` and the
+per-stencil times) is measured only with `--full`.
+
 Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel of the step (the `cloudsc2_nl` kernel; its name
 is the one the launcher reports): algorithmic bytes per launch (3 567 words per column) / the kernel's
 mean duration measured with HIP events on the launch stream.  At N = 1 the line also carries `roofline_tl`,
@@ -60,6 +65,9 @@ sys.path.insert(0, ROOT)
 from gt4py_dwarf_p_cloudsc2_tl_ad_amd.benchlib import (  # noqa: E402  (no torch import at module level there)
     CONFIG5_COLUMNS, HBM_PEAK_GBS, NL_WORDS_PER_COL, TLAD_WORDS_PER_COL, StdoutToStderr, base_record, gather_rank_reports,
     harness_bench, make_resident_state, rank0_then_everyone, roofline_entry)
+
+DUMP_COLUMNS = 4096     # --dump-outputs: at most 11 fields x 138 levels x 4096 columns x 8 B = 50 MB
+DUMP_SEED = 20240607
 
 
 def parse_args(argv=None):
@@ -105,9 +113,21 @@ def parse_args(argv=None):
     ap.add_argument("--dry-run", action="store_true",
                     help="plumbing rehearsal without a GPU: gloo instead of RCCL, shard bookkeeping and the "
                          "reductions only, NO kernels (value is null) - used by the CPU tests of the launcher")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beside the headline figure: the event-timed rooflines of the "
+                         "NL kernel and of the TL / AD / fp32 legs, the default-placement and fused-step figures, the "
+                         "validation norms, the CPU baseline with its parity check and, --config 3 / 4, the variants and the "
+                         "per-stencil times.  Without it a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed (qsat and the cloudsc2_nl outputs, "
+                         f"valid levels only) as DIR/<name>.npy in the run's precision; fields of more than {DUMP_COLUMNS} "
+                         f"columns are cut to a fixed sample of {DUMP_COLUMNS} columns (seed {DUMP_SEED}, ascending).  "
+                         "N > 1: rank 0's shard")
     args = ap.parse_args(argv)
     if args.gpus < 1:
         ap.error("--gpus must be >= 1")
+    if args.dump_outputs is not None and (args.dry_run or args.config in (3, 4)):
+        ap.error("--dump-outputs: the headline step of --config 2 / 5 only (no kernels run in a dry run)")
     if args.tune_shifts_mb is not None:
         try:
             args.tune_shifts_mb = tuple(int(x) for x in args.tune_shifts_mb.split(","))
@@ -270,6 +290,26 @@ def cpu_baseline(cols: int, nz: int, np_dtype, budget_s: float = 8.0, hip_step=N
     return res
 
 
+def dump_outputs(dirname, fields, nx, nz):
+    """`--dump-outputs DIR`: every field of `fields` (logical (nx, 1, nz+1) device storages) as DIR/<name>.npy in [level][column]
+    layout and the field's own dtype - the fluxes (f*) with their nz + 1 levels, the others with nz - on the columns of a
+    fixed seeded sample when nx > DUMP_COLUMNS, so that two builds run with the same arguments can be compared array by array."""
+    import numpy as np
+    import torch
+
+    from gt4py_dwarf_p_cloudsc2_tl_ad_amd import storage
+
+    os.makedirs(dirname, exist_ok=True)
+    if nx <= DUMP_COLUMNS:
+        cols = np.arange(nx)
+    else:
+        cols = np.sort(np.random.default_rng(DUMP_SEED).choice(nx, DUMP_COLUMNS, replace=False))
+    for name, f in fields.items():
+        kc = storage.klayout(f)[: nz + 1 if name.startswith("f") else nz]
+        a = kc.index_select(1, torch.as_tensor(cols, device=kc.device)).cpu().numpy()
+        np.save(os.path.join(dirname, name + ".npy"), np.ascontiguousarray(a))
+
+
 def dry_run(args, rank, world):
     """Launcher / rendezvous / shard bookkeeping rehearsal on the CPU (gloo): no kernels, no GPU."""
     import numpy as np
@@ -313,7 +353,7 @@ def dry_run(args, rank, world):
         res["roofline"] = {"kernel": None, "bound": "hbm", "achieved": None, "peak": HBM_PEAK_GBS, "unit": "GB/s", "frac": None,
                            "traffic": None, "bytes_per_launch": NL_WORDS_PER_COL * wsize * nx, "columns": nx,
                            "note": "dry run: no kernel was launched; the object's shape is what main() fills in"}
-        if args.cpu_cols > 0:
+        if args.full and args.cpu_cols > 0:
             res["cpu_baseline"] = cpu_baseline(args.cpu_cols, nz, np.float64, budget_s=args.cpu_budget_s)
         print(json.dumps(res), flush=True)
 
@@ -531,9 +571,10 @@ def main(argv=None):
     nl_ms = nl_train_ms = copy_gbs = None
     nl_kernel_name = None
     extra = {}
-    if not args.no_roofline_events:
-        for _ in range(70):          # untimed, >= 25 ms of the same work: the GPU needs 10-15 ms after an idle period to
-            step()                   # reach its steady clocks (profiles/r02/window_probe.txt); 20 steps were not enough
+    roofline_events = args.full and not args.no_roofline_events
+    for _ in range(70):              # untimed, >= 25 ms of the same work: the GPU needs 10-15 ms after an idle period to
+        step()                       # reach its steady clocks (profiles/r02/window_probe.txt); 20 steps were not enough
+    if roofline_events:
         nl_kernel_name = last_kernel()
         reps = max(10, min(args.steps, 50))
         nl_window_first = nl_launches[0] + 2          # event_times discards its first two intervals
@@ -703,12 +744,14 @@ def main(argv=None):
         t = torch.tensor([elapsed], dtype=torch.float64, device=red_device)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
+    if args.dump_outputs is not None and rank == 0:
+        dump_outputs(args.dump_outputs, {"qsat": qsat, **{n: outs["out_" + n] for n in NL_OUT}}, nx, nz)
 
     # the same step on the DEFAULT placement (one torch allocation per field - what `storage.zeros` and the drivers give a
     # caller who does not opt into the tuner), timed right after the headline window on a copy of the state: reported
     # beside `value` so that the record never describes only the opt-in path
     default_placement = None
-    if placement.get("mode") == "tuned" and not args.no_roofline_events and nx <= 1 << 20:
+    if placement.get("mode") == "tuned" and roofline_events and nx <= 1 << 20:
         try:
             Fd = {k: storage.from_klayout(storage.klayout(v).clone(), np_dtype, device) for k, v in F.items()}
             for _ in range(max(70, args.warmup)):
@@ -728,7 +771,7 @@ def main(argv=None):
     # the same step as ONE launch (build extension: saturation evaluated inside the NL kernel, stencil
     # `cloudsc2_nl_saturation`); reported beside the headline, never as `value`
     fused = None
-    if not args.no_roofline_events and world == 1:
+    if roofline_events and world == 1:
         try:
             nls = compile_stencil("cloudsc2_nl_saturation", ext)
             qsat2 = storage.zeros(nx, nz, np_dtype, device)
@@ -759,7 +802,7 @@ def main(argv=None):
     # timed window: their tuning runs other sizes and frees GBs of arenas, and a 20-step window that followed them was
     # 2 % slower than one that did not (profiles/r02/window_vs_extras.txt).  A failure here (e.g. out of memory on a
     # shared device) must not cost the headline line: it is recorded and the run goes on.
-    if (not args.no_roofline_events and world == 1 and not args.no_extra_rooflines and args.config == 2
+    if (roofline_events and world == 1 and not args.no_extra_rooflines and args.config == 2
             and nx <= 131072):
         try:
             extra.update(extra_rooflines())
@@ -768,12 +811,14 @@ def main(argv=None):
             torch.cuda.empty_cache()
 
     # validation norm (the only data reduction across ranks): sum of every NL output
-    norm = torch.stack([storage.klayout(outs["out_" + n]).double().abs().sum() for n in NL_OUT])
-    finite = all(bool(torch.isfinite(storage.klayout(v)[: nz]).all()) for v in outs.values())
-    if dist is not None:
-        norm = norm.to(red_device)
-        dist.all_reduce(norm, op=dist.ReduceOp.SUM)
-    norm = [float(x) for x in norm.cpu()]
+    norm = finite = None
+    if args.full:
+        norm = torch.stack([storage.klayout(outs["out_" + n]).double().abs().sum() for n in NL_OUT])
+        finite = all(bool(torch.isfinite(storage.klayout(v)[: nz]).all()) for v in outs.values())
+        if dist is not None:
+            norm = norm.to(red_device)
+            dist.all_reduce(norm, op=dist.ReduceOp.SUM)
+        norm = [float(x) for x in norm.cpu()]
     mine = {"rank": rank, "device": f"cuda:{local_rank}", "ms_per_step": per_rank_ms[rank] if dist is not None else per_rank_ms[0],
             "nl_kernel_ms": nl_ms, "startup_s": startup}
     mine.update({k: placement[k] for k in ("mode", "chosen", "arena_GB", "tuning_s", "tuned_ms", "default_ms", "recheck_tuned_ms",
@@ -816,8 +861,9 @@ def main(argv=None):
             else:
                 res["value_default_placement"] = None
                 res["default_placement_error"] = default_placement.get("error")
-        res["outputs_finite"] = finite
-        res["validation_norm"] = dict(zip(NL_OUT, norm))
+        if norm is not None:
+            res["outputs_finite"] = finite
+            res["validation_norm"] = dict(zip(NL_OUT, norm))
         if nl_ms is not None:
             res["roofline"] = roofline_entry(nl_kernel_name, NL_WORDS_PER_COL, wsize, nx, args.precision, nl_ms,
                                              avg_launch_ms_back_to_back=nl_train_ms, box_torch_copy_GBs=copy_gbs,
@@ -825,7 +871,7 @@ def main(argv=None):
         res.update(extra)
         if fused is not None:
             res["fused_step"] = fused
-        if args.cpu_cols > 0:
+        if args.full and args.cpu_cols > 0:
             # the CPU baseline beside the GPU figure at EVERY world size (north_star: "in the same run"), on rank 0, after
             # the closing barrier and every reduction; the other ranks wait in rank0_then_everyone without spinning
             def hip_step(Fh, eta_h, dt_h):

@@ -179,7 +179,8 @@ def harness_bench(args, rank, local_rank, world):
     """BASELINE configs[2] / configs[3]: the TL Taylor test / the AD symmetry test as the timed step, through the
     harness classes that mirror the reference's (`harness.TaylorTest`, `harness.SymmetryTest`) on the state the driver
     mirror builds (`drivers._common.setup`: the reader path by default).  Same protocol as the headline: pre-warm >= 25 ms,
-    W warm-up steps, EXACTLY K steps between barrier + synchronize pairs, MAX over ranks."""
+    W warm-up steps, EXACTLY K steps between barrier + synchronize pairs, MAX over ranks.  The per-stencil times of one
+    instrumented step and the timed variants only with `--full`."""
     import argparse
     import gc
 
@@ -310,20 +311,22 @@ def harness_bench(args, rank, local_rank, world):
         elapsed = float(t.item())
     gc.enable()
 
-    # per-stencil device times of ONE instrumented step (HIP events around every stencil call)
-    gcfg.exec_info = {}
-    if taylor:
-        head.run(state, dt)
-    else:
-        head(state, dt, enable_validation=False)
-    finalize_exec_info(gcfg.exec_info)
-    kernels = {k: {"ncalls": v["ncalls"], "device_ms": 1e3 * v.get("total_run_time", 0.0)}
-               for k, v in gcfg.exec_info.items() if isinstance(v, dict) and "ncalls" in v}
-    gcfg.exec_info = None
+    # per-stencil device times of ONE instrumented step (HIP events around every stencil call), --full only
+    kernels = None
+    if args.full:
+        gcfg.exec_info = {}
+        if taylor:
+            head.run(state, dt)
+        else:
+            head(state, dt, enable_validation=False)
+        finalize_exec_info(gcfg.exec_info)
+        kernels = {k: {"ncalls": v["ncalls"], "device_ms": 1e3 * v.get("total_run_time", 0.0)}
+                   for k, v in gcfg.exec_info.items() if isinstance(v, dict) and "ncalls" in v}
+        gcfg.exec_info = None
     last_kernel = _lib.last_kernel()
 
     var_out = {}
-    if not args.no_variants and world == 1:
+    if args.full and not args.no_variants and world == 1:
         for name, kw, seq in variants:
             try:
                 h = make(**kw)
@@ -362,10 +365,10 @@ def harness_bench(args, rank, local_rank, world):
                            "bytes_per_launch": nbytes, "bytes_per_column": seq_words["plain"] * wsize,
                            "avg_launch_ms": ms, "columns": nx, "dtype": "f64" if wsize == 8 else "f32",
                            "what": "algorithmic bytes of the step's whole stencil sequence (SURVEY.md 8d per-stencil "
-                                   "figures; the norms' reductions are not counted) / the step's wall time, host side included",
-                           "stencils_one_step": kernels,
-                           "device_ms_one_step": sum(k["device_ms"] for k in kernels.values())}
-        res["variants"] = var_out
+                                   "figures; the norms' reductions are not counted) / the step's wall time, host side included"}
+        if kernels is not None:
+            res["roofline"].update(stencils_one_step=kernels, device_ms_one_step=sum(k["device_ms"] for k in kernels.values()))
+            res["variants"] = var_out
         print(json.dumps(res), flush=True)
     if dist is not None:
         dist.destroy_process_group()

@@ -8,13 +8,13 @@ TAG=${1:-r03}; PART=${2:-all}; D=gpurun_out/${TAG}_collect
 mkdir -p $D
 if [ "$PART" != "b" ]; then
 timeout -k 10 900 python -m pytest tests -m gpu -q > $D/pytest_gpu.log 2>&1; tail -3 $D/pytest_gpu.log
-python bench.py --steps 20 --warmup 5 > $D/bench_20_5.json 2> $D/bench_20_5.err
-python bench.py --steps 100 --warmup 20 > $D/bench_100_20.json 2> $D/bench_100_20.err
-python bench.py > $D/bench_default.json 2> $D/bench_default.err
-python bench.py --config 3 --steps 20 --warmup 5 > $D/bench_config3.json 2> $D/bench_config3.err
-python bench.py --config 4 --steps 20 --warmup 5 > $D/bench_config4.json 2> $D/bench_config4.err
+python bench.py --full --steps 20 --warmup 5 > $D/bench_20_5.json 2> $D/bench_20_5.err
+python bench.py --full --steps 100 --warmup 20 > $D/bench_100_20.json 2> $D/bench_100_20.err
+python bench.py --full > $D/bench_default.json 2> $D/bench_default.err
+python bench.py --full --config 3 --steps 20 --warmup 5 > $D/bench_config3.json 2> $D/bench_config3.err
+python bench.py --full --config 4 --steps 20 --warmup 5 > $D/bench_config4.json 2> $D/bench_config4.err
 # the N-rank path with REAL kernels on this box's one GPU (gloo carries barrier + reductions; at most 6 processes may have the GPU open, the launcher included: 4 ranks)
-python bench.py --gpus 4 --collective gloo --steps 20 --warmup 5 --cpu-cols 2048 --cpu-budget-s 1 --no-extra-rooflines > $D/bench_rehearsal_4ranks_one_gpu.json 2> $D/bench_rehearsal_4ranks.err
+python bench.py --full --gpus 4 --collective gloo --steps 20 --warmup 5 --cpu-cols 2048 --cpu-budget-s 1 --no-extra-rooflines > $D/bench_rehearsal_4ranks_one_gpu.json 2> $D/bench_rehearsal_4ranks.err
 # (the 8-rank dry run needs no GPU and is taken in the build container: `python bench.py --gpus 8 --dry-run`; on a GPU box
 #  its nine processes map the HIP runtime and can trip the pool's limit of 6 processes per GPU)
 fi

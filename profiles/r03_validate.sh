@@ -6,9 +6,9 @@ timeout -k 10 300 python profiles/probe_fp32_verdicts.py > $D/fp32_verdicts.txt 
 if ls build/variants/lib_nf4.so > /dev/null 2>&1; then
 timeout -k 10 200 python profiles/ab_taylor_multi.py nf5=gt4py_dwarf_p_cloudsc2_tl_ad_amd/libcloudsc2_hip.so nf4=build/variants/lib_nf4.so nf3=build/variants/lib_nf3.so nf2=build/variants/lib_nf2.so > $D/ab_taylor_multi.txt 2>&1; tail -8 $D/ab_taylor_multi.txt
 fi
-python bench.py --config 3 --steps 20 --warmup 5 > $D/bench_c3.json 2> $D/bench_c3.err
-python bench.py --config 4 --steps 20 --warmup 5 > $D/bench_c4.json 2> $D/bench_c4.err
-python bench.py --steps 20 --warmup 5 > $D/bench_c2.json 2> $D/bench_c2.err
+python bench.py --full --config 3 --steps 20 --warmup 5 > $D/bench_c3.json 2> $D/bench_c3.err
+python bench.py --full --config 4 --steps 20 --warmup 5 > $D/bench_c4.json 2> $D/bench_c4.err
+python bench.py --full --steps 20 --warmup 5 > $D/bench_c2.json 2> $D/bench_c2.err
 python - "$D" <<PY
 import json, sys
 D = sys.argv[1]

@@ -7,9 +7,9 @@ OUT=gpurun_out/pmc_${TAG}_c3
 mkdir -p $OUT
 export TMPDIR=/tmp
 rocprofv3 --pmc SQ_WAVES SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_INSTS_VALU SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU \
-    --kernel-trace --output-format csv -d $OUT/pmc_sq -- python3 bench.py --config 3 --steps 5 --warmup 2 > $OUT/pmc_sq.log 2>&1
+    --kernel-trace --output-format csv -d $OUT/pmc_sq -- python3 bench.py --full --config 3 --steps 5 --warmup 2 > $OUT/pmc_sq.log 2>&1
 rocprofv3 --pmc SQ_INSTS_SALU SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR SQ_ACTIVE_INST_LDS SQ_INST_CYCLES_VMEM_RD SQ_WAIT_INST_LDS \
-    --kernel-trace --output-format csv -d $OUT/pmc_sq2 -- python3 bench.py --config 3 --steps 5 --warmup 2 > $OUT/pmc_sq2.log 2>&1
+    --kernel-trace --output-format csv -d $OUT/pmc_sq2 -- python3 bench.py --full --config 3 --steps 5 --warmup 2 > $OUT/pmc_sq2.log 2>&1
 python3 - "$OUT" <<'PY'
 import collections, csv, glob, json, sys
 out = sys.argv[1]

@@ -9,7 +9,7 @@ export TMPDIR=/tmp
 for C in 3 4; do
   OUT=gpurun_out/prof_${TAG}_c$C
   mkdir -p $OUT
-  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --config $C --steps 20 --warmup 5 > $OUT/trace.log 2>&1
+  rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -- python3 bench.py --full --config $C --steps 20 --warmup 5 > $OUT/trace.log 2>&1
 done
 python3 - "$TAG" <<'PY'
 import csv, glob, json, sys

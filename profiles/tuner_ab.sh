@@ -5,7 +5,7 @@ mkdir -p gpurun_out/tuner_ab
 WIDE=0,4096,8192,12288,16384,20480,24576,28672,32768
 for i in 1 2 3 4; do
 for w in "" $WIDE; do
-python bench.py --steps 100 --warmup 20 --cpu-cols 0 --no-extra-rooflines ${w:+--tune-shifts-mb $w} "$@" 2>/dev/null | python -c "
+python bench.py --full --steps 100 --warmup 20 --cpu-cols 0 --no-extra-rooflines ${w:+--tune-shifts-mb $w} "$@" 2>/dev/null | python -c "
 import json,sys
 d=json.loads([l for l in sys.stdin if l.startswith('{')][0])
 p=d['placement']

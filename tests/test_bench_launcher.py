@@ -12,7 +12,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 BENCH = os.path.join(ROOT, "bench.py")
 
 
-DRY = ("--dry-run", "--cpu-cols", "256", "--cpu-budget-s", "0.2")     # the CPU-baseline leg runs, on a sample of a fraction of a second
+DRY = ("--dry-run", "--full", "--cpu-cols", "256", "--cpu-budget-s", "0.2")     # the CPU-baseline leg runs, on a sample of a fraction of a second
 
 
 def _nrank_record_is_complete(d, world, real_kernels):
@@ -173,6 +173,29 @@ def test_concurrent_builds_of_eight_ranks_run_make_once(tmp_path):
             fh.write(saved)
 
 
+def test_build_of_an_up_to_date_tree_only_reads(hip_lib, monkeypatch):
+    """bench.py calls `build()` at start-up, possibly as a user who may not write the tree another user built: with both
+    libraries up to date, `build()` opens nothing for writing (no lock file, no stamp) and runs no `make`."""
+    import builtins
+
+    import __graft_entry__ as ge
+
+    real_open, real_os_open = builtins.open, os.open
+
+    def read_only_open(file, mode="r", *a, **k):
+        assert not set(mode) & set("wax+"), (file, mode)
+        return real_open(file, mode, *a, **k)
+
+    def read_only_os_open(path, flags, *a, **k):
+        assert not flags & (os.O_WRONLY | os.O_RDWR | os.O_CREAT), (path, flags)
+        return real_os_open(path, flags, *a, **k)
+
+    monkeypatch.setattr(builtins, "open", read_only_open)
+    monkeypatch.setattr(os, "open", read_only_os_open)
+    monkeypatch.setattr(ge.subprocess, "run", lambda *a, **k: pytest.fail(f"build() ran {a}"))
+    ge.build()
+
+
 def test_world_size_mismatch_and_bad_splits_are_refused():
     p = _run("--gpus", "2", *DRY, env={"WORLD_SIZE": "3", "RANK": "0"})
     assert p.returncode != 0 and "WORLD_SIZE=3" in (p.stderr + p.stdout)
@@ -191,11 +214,57 @@ def test_launcher_parent_never_imports_torch():
     assert main_src.index("launch_ranks(args, argv)") < main_src.index("import torch")
 
 
+def test_plain_dry_run_leaves_the_extras_to_full():
+    """Without `--full` the run does what the headline needs and no more: no CPU-baseline leg.  `--dump-outputs` is refused
+    where no kernel runs (dry run) or where the step is not the headline's (--config 3 / 4)."""
+    p = _run("--dry-run", "--steps", "3", "--warmup", "1", "--cpu-cols", "256", "--cpu-budget-s", "0.2")
+    assert p.returncode == 0, p.stderr[-3000:]
+    lines = [l for l in p.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, p.stdout
+    d = json.loads(lines[0])
+    assert "cpu_baseline" not in d and d["steps"] == 3 and d["warmup"] == 1 and d["n_gpus"] == 1
+    for extra in (("--dry-run",), ("--config", "3"), ("--config", "4")):
+        q = _run(*extra, "--dump-outputs", "unused_dir")
+        assert q.returncode != 0 and "--dump-outputs" in q.stderr, q.stderr[-2000:]
+
+
+@pytest.mark.gpu
+def test_plain_run_is_lean_and_dumps_the_last_steps_outputs(gpu, tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR`: the line carries the headline figure and nothing measured
+    beside it; DIR holds qsat and the ten cloudsc2_nl outputs of the last timed step, valid levels only, on a fixed sample
+    of 4 096 columns, and two runs with the same arguments write the same arrays bit for bit."""
+    import numpy as np
+
+    from gt4py_dwarf_p_cloudsc2_tl_ad_amd.stencils import NL_OUT
+
+    dumps = []
+    for i in range(2):
+        out = tmp_path / f"run{i}"
+        p = _run("--steps", "4", "--warmup", "2", "--cols", "8192", "--dump-outputs", str(out))
+        assert p.returncode == 0, p.stderr[-3000:]
+        lines = [l for l in p.stdout.splitlines() if l.strip()]
+        assert len(lines) == 1, p.stdout[-2000:]
+        d = json.loads(lines[0])
+        assert d["steps"] == 4 and d["warmup"] == 2 and d["unit"] == "columns/s" and d["dtype"] == "f64"
+        assert d["ms_per_step"] > 0 and d["value"] == pytest.approx(8192 * 1e3 / d["ms_per_step"], rel=1e-9)
+        for k in ("roofline", "roofline_tl", "cpu_baseline", "fused_step", "validation_norm"):
+            assert k not in d, k
+        if "value_default_placement" in d:      # only when the timed steps themselves ran on plain allocations: a copy
+            assert d["default_placement_is_value"] is True and d["value_default_placement"] == d["value"]
+        dumps.append({f.stem: np.load(f) for f in sorted(out.glob("*.npy"))})
+    assert set(dumps[0]) == {"qsat", *NL_OUT}
+    assert sum(a.nbytes for a in dumps[0].values()) <= 64 << 20
+    for name, a in dumps[0].items():
+        assert a.dtype == np.float64 and a.shape == (138 if name.startswith("f") else 137, 4096), (name, a.shape)
+        assert np.isfinite(a).all() and np.array_equal(a, dumps[1][name]), name
+    assert np.abs(dumps[0]["tnd_t"]).max() > 0 and np.abs(dumps[0]["qsat"]).max() > 0
+
+
 @pytest.mark.gpu
 def test_bench_line_carries_the_contract_on_the_gpu(gpu):
     """`python bench.py` (small sizes for speed) as a child process on the GPU: ONE JSON line with the driver's contract
     keys, the `roofline` / `roofline_tl` / `roofline_ad` / `roofline_nl_f32` objects and a `cpu_baseline`."""
-    p = _run("--steps", "3", "--warmup", "1", "--cpu-cols", "256")
+    p = _run("--full", "--steps", "3", "--warmup", "1", "--cpu-cols", "256")
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -236,7 +305,7 @@ def test_two_ranks_with_real_kernels_reproduce_the_one_process_result(gpu):
     """`--collective gloo`: the N-rank path with REAL kernels on fewer GPUs than ranks (both ranks on this box's one GPU; barrier
     and reductions through gloo).  Two shards of 8 192 columns must give the validation norms of ONE process on the same
     16 384 global columns - the shards are slices of one problem, eta comes from global column 0, the SUM all-reduce adds up."""
-    common = ("--steps", "3", "--warmup", "1", "--no-extra-rooflines", "--placement", "separate")
+    common = ("--full", "--steps", "3", "--warmup", "1", "--no-extra-rooflines", "--placement", "separate")
     one = _run("--cols", "16384", "--cpu-cols", "0", "--no-roofline-events", *common)
     assert one.returncode == 0, one.stderr[-3000:]
     two = _run("--gpus", "2", "--collective", "gloo", "--cols", "8192", "--cpu-cols", "256", "--cpu-budget-s", "0.5", *common)
@@ -260,7 +329,7 @@ def test_bench_lines_of_configs_3_and_4(gpu, config):
     """`python bench.py --config 3 | 4`: BASELINE configs[2] / configs[3] as timed steps with the same JSON contract; the
     record carries the reference's verdict string, a sequence-level `roofline` (sum of the algorithmic bytes of the step's
     stencils / the step's time) and the opt-in variants, each with its own verdict."""
-    p = _run("--config", str(config), "--steps", "3", "--warmup", "1", "--cols", "8192")
+    p = _run("--config", str(config), "--full", "--steps", "3", "--warmup", "1", "--cols", "8192")
     assert p.returncode == 0, p.stderr[-3000:]
     lines = [l for l in p.stdout.splitlines() if l.strip()]
     assert len(lines) == 1, p.stdout[-2000:]
@@ -292,7 +361,7 @@ def test_config5_whole_problem_on_one_gpu(gpu):
     """BASELINE configs[4] at its FULL size - 4 194 304 fp32 columns x 137 levels, 60 GB of fields - resident on the one GPU
     of the box (`--config 5 --gpus 1`; the 8-GPU split of the same global problem needs hardware the pool does not have):
     the record names the configuration, every output is finite, and the NL kernel is the fp32 ring at a sane rate."""
-    p = _run("--config", "5", "--steps", "3", "--warmup", "1", "--cpu-cols", "0", "--no-extra-rooflines",
+    p = _run("--config", "5", "--full", "--steps", "3", "--warmup", "1", "--cpu-cols", "0", "--no-extra-rooflines",
              "--placement", "separate")
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.strip()][0])
@@ -304,7 +373,7 @@ def test_config5_whole_problem_on_one_gpu(gpu):
     assert r["bytes_per_launch"] == 14268 * 4194304
     # the same global problem split over 4 ranks (real kernels, the ranks share this GPU, gloo for the reductions): the
     # shards are slices of ONE problem, so the validation norms of the split run are those of the whole
-    q = _run("--config", "5", "--gpus", "4", "--collective", "gloo", "--steps", "3", "--warmup", "1", "--cpu-cols", "0",
+    q = _run("--config", "5", "--full", "--gpus", "4", "--collective", "gloo", "--steps", "3", "--warmup", "1", "--cpu-cols", "0",
              "--no-extra-rooflines", "--no-roofline-events", "--placement", "separate")
     assert q.returncode == 0, q.stderr[-3000:]
     d4 = json.loads([l for l in q.stdout.splitlines() if l.strip()][0])
@@ -319,7 +388,7 @@ def test_a_rank_that_started_too_slowly_skips_the_tuner_and_says_so(gpu):
     """start-up is bounded - a rank that needed longer than `--startup-budget-s` to reach the placement
     tuner (a cold node paging in torch, eight ranks queueing for the build lock) runs on plain allocations, and the record
     says so for that rank; here the budget is 0 s, so the one rank must skip."""
-    p = _run("--steps", "3", "--warmup", "1", "--cols", "8192", "--cpu-cols", "0", "--no-extra-rooflines",
+    p = _run("--full", "--steps", "3", "--warmup", "1", "--cols", "8192", "--cpu-cols", "0", "--no-extra-rooflines",
              "--startup-budget-s", "0")
     assert p.returncode == 0, p.stderr[-3000:]
     d = json.loads([l for l in p.stdout.splitlines() if l.strip()][0])
@@ -344,7 +413,7 @@ def test_one_rank_under_torchrun_takes_the_rccl_path(gpu):
     e = {k: v for k, v in os.environ.items() if k not in ("WORLD_SIZE", "RANK", "LOCAL_RANK")}
     e.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=1", "--master-addr", "127.0.0.1",
-           "--master-port", str(port), BENCH, "--gpus", "1", "--steps", "3", "--warmup", "1", "--cols", "8192",
+           "--master-port", str(port), BENCH, "--full", "--gpus", "1", "--steps", "3", "--warmup", "1", "--cols", "8192",
            "--no-extra-rooflines", "--cpu-cols", "256", "--cpu-budget-s", "0.3"]
     p = subprocess.run(cmd, capture_output=True, text=True, timeout=600, env=e)
     assert p.returncode == 0, p.stderr[-3000:]

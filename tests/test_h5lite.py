@@ -1,14 +1,24 @@
 """`framework/h5lite.py`: the reader path's own HDF5 reader (h5py is not part of the image).  Held against (a) a committed
 fixture file of the build's own data written by h5py with default format settings (tests/golden/make_h5lite_fixture.py) and
-its .npz twin, (b) when the reference checkout is present, the reference's golden files against their committed .npz
+its .npz twin, (b) the reference's golden files (stored xz-compressed under tests/golden/) against their committed .npz
 conversions (made with h5py) - and through the reader path itself (`HDF5GridOperator` on the real `reference_double.h5`)."""
+import lzma
 import os
 
 import numpy as np
 import pytest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF_DATA = "/root/reference/data"
+
+
+@pytest.fixture(scope="module")
+def ref_data(tmp_path_factory):
+    """The reference's reference_{double,single}.h5, byte for byte, unpacked from tests/golden/*.h5.xz into a directory."""
+    d = tmp_path_factory.mktemp("reference_data")
+    for prec in ("double", "single"):
+        with lzma.open(os.path.join(HERE, "golden", f"reference_{prec}.h5.xz")) as src:
+            (d / f"reference_{prec}.h5").write_bytes(src.read())
+    return str(d)
 
 
 def test_fixture_file_reads_back_bit_for_bit():
@@ -67,20 +77,18 @@ def test_non_hdf5_files_are_refused(tmp_path):
         h5lite.File(str(p))
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason="reference checkout not present (GPU box)")
 @pytest.mark.parametrize("prec", ["double", "single"])
-def test_reference_golden_files_match_their_npz_conversions(prec):
+def test_reference_golden_files_match_their_npz_conversions(prec, ref_data):
     from gt4py_dwarf_p_cloudsc2_tl_ad_amd.framework import h5lite
 
     want = np.load(os.path.join(HERE, "golden", f"reference_{prec}.npz"))
-    with h5lite.File(os.path.join(REF_DATA, f"reference_{prec}.h5")) as f:
+    with h5lite.File(os.path.join(ref_data, f"reference_{prec}.h5")) as f:
         assert sorted(f.keys()) == sorted(want.files)
         for k in want.files:
             assert f[k].dtype == want[k].dtype and np.array_equal(f[k], want[k]), k
 
 
-@pytest.mark.skipif(not os.path.isdir(REF_DATA), reason="reference checkout not present (GPU box)")
-def test_reader_path_reads_the_real_hdf5_file(monkeypatch):
+def test_reader_path_reads_the_real_hdf5_file(monkeypatch, ref_data):
     """`HDF5GridOperator.get_field` on the reference's own `reference_double.h5` (through h5lite, h5py being absent): same
     field as from the .npz conversion, tiled to the grid's columns."""
     import oracle_backend
@@ -92,7 +100,7 @@ def test_reader_path_reads_the_real_hdf5_file(monkeypatch):
     cfg = GT4PyConfig(backend="numpy", rebuild=False, validate_args=True, verbose=False,
                       dtypes=DataTypes(bool=bool, float=np.float64, int=np.int64))
     grid = ComputationalGrid(GridConfig(nx=150, ny=1, nz=137))
-    op = iox.HDF5GridOperator(os.path.join(REF_DATA, "reference_double.h5"), grid, gt4py_config=cfg)
+    op = iox.HDF5GridOperator(os.path.join(ref_data, "reference_double.h5"), grid, gt4py_config=cfg)
     assert type(op.f).__module__.endswith(("h5lite", "h5py._hl.files"))      # the file itself, not the .npz stand-in
     f = op.get_field((I, J, K - 1 / 2), "float", "", "PFPLSN", (K - 1 / 2, IJ), (IJ, ExpandedDim, K - 1 / 2))
     want = np.load(os.path.join(HERE, "golden", "reference_double.npz"))["PFPLSN"]
