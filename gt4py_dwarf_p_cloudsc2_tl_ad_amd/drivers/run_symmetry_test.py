@@ -68,7 +68,8 @@ def main(argv=None):
                     help="use the AD kernel whose freezing tests match NL/TL (build extension, docs/DESIGN_r03_detail.md 3.3)")
     ap.add_argument("--fused", action="store_true",
                     help="timed call: state_increment fused into cloudsc2_tl (build extension cloudsc2_tl_incremented) and "
-                         "cloudsc2_ad without its forward sweep, fed with the TL call's fluxes (cloudsc2_ad_from_trajectory)")
+                         "with --ad-traj-fix, cloudsc2_ad without its forward sweep, fed with the TL call's fluxes "
+                         "(cloudsc2_ad_from_trajectory)")
     ap.add_argument("--graph", action="store_true",
                     help="capture the timed call (saturation, state_increment, cloudsc2_tl, cloudsc2_ad) in a HIP graph and "
                          "replay it (one host call per run)")

@@ -397,7 +397,9 @@ class Cloudsc2ADFromTrajectory(Cloudsc2AD):
     (adjoint/validation.py:135-151) - without the forward sweep that recomputes the NL trajectory (stencil
     `cloudsc2_ad_from_trajectory`).  The state must carry the TL call's NL flux outputs `f_fplsl` / `f_fplsn` (the harness
     puts the TL diagnostics into the state anyway, :149-150).  Only the adjoint fields are written; the NL tendencies /
-    diagnostics of the output dicts are NOT (they are the TL call's).  Driver switches only."""
+    diagnostics of the output dicts are NOT (they are the TL call's).  Driver switches only.  The adjoints are Cloudsc2AD's to
+    rounding only with `ad_traj_fix=True` or where no column's saturation adjustment crosses RTT: without the fix (quirk
+    Q4) the TL fluxes differ from the ones Cloudsc2AD recomputes in such columns."""
 
     _stencil_name = "cloudsc2_ad_from_trajectory"
 

@@ -235,7 +235,10 @@ int32_t cloudsc2_ad_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t
  * cloudsc2_tl write them) and the forward sweep is skipped: 44 words per level and column instead of 70.  Nothing but
  * `out_adj` is written (the recomputed NL outputs of cloudsc2_ad_* are not produced: they are the TL call's).  With fluxes
  * that come from cloudsc2_ad_*'s own `out` the adjoints are bit-identical to that call's; with a TL call's they agree to
- * rounding (the two kernels contract the same formulas differently).  Driver switches only: LEVAPLS2 / LDRAIN1D are
+ * rounding (the two kernels contract the same formulas differently) only if AD_TRAJ_FIX = 1 or no column's saturation
+ * adjustment crosses RTT: with AD_TRAJ_FIX = 0 (quirk Q4) cloudsc2_ad's forward sweep freezes on the pre-adjustment
+ * temperature and cloudsc2_tl on the post-adjustment one, so in such columns the TL fluxes are not cloudsc2_ad's and the
+ * result is neither cloudsc2_ad's adjoint nor the TL transpose.  Driver switches only: LEVAPLS2 / LDRAIN1D are
  * refused (CLOUDSC2_E_UNSUPPORTED), as are fields of 4 GiB and more. */
 int32_t cloudsc2_ad_from_trajectory_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
                                         const double* const* in, const double* const* in_adj, const double* eta,

@@ -996,13 +996,20 @@ AD_ADJ_IN = tuple("in_" + n + "_i" for n in
 AD_ADJ_OUT = tuple("out_" + n[3:] + "_i" for n in NL_INPUTS)
 
 
-def cloudsc2_ad(fields: Dict[str, np.ndarray], in_eta: np.ndarray, dt, externals) -> None:
+def cloudsc2_ad(fields: Dict[str, np.ndarray], in_eta: np.ndarray, dt, externals, traj_fluxes=None,
+                diag=None) -> None:
     """adjoint/_stencils/cloudsc2.py:124-996.
 
     `fields`: the 16 trajectory inputs `in_*`, the 10 adjoint forcings `in_{clc,...}_i`
     (NOT modified here; the reference zeroes them in place, Q1), the 10 NL outputs `out_*` and the
     16 adjoint outputs `out_{ap,aph,...,tnd_cml_t}_i`.  Outputs the reference only accumulates into
-    (`out_lude_i`, :526) start from 0.  Temporaries never assigned at a level read as 0 (Q8)."""
+    (`out_lude_i`, :526) start from 0.  Temporaries never assigned at a level read as 0 (Q8).
+
+    `traj_fluxes` (build extension `cloudsc2_ad_from_trajectory`): a pair (fplsl, fplsn) of (nz+1, nx) fields.  Level k
+    of the forward sweep then starts from fplsl[k] / fplsn[k] instead of the fluxes carried from level k-1 - what the
+    trajectory kernel's adjoint sweep reads.  Everything else is unchanged; the NL outputs are those of the levels so
+    computed.  `diag`: a dict that receives `straddle`, the (nx,) mask of columns where at some level the Q4 freezing
+    test (pre-adjustment t3 < RTT) and the NL/TL one (post-adjustment t < RTT) disagree."""
     e = externals
     F = fields
     in_ap, in_aph, in_lu, in_lude = F["in_ap"], F["in_aph"], F["in_lu"], F["in_lude"]
@@ -1049,13 +1056,20 @@ def cloudsc2_ad(fields: Dict[str, np.ndarray], in_eta: np.ndarray, dt, externals
         lcrit = 1.9 * e["RCLCRIT"] if LEV else 2.0 * e["RCLCRIT"]
         icrit = 0.0001 if LEV else 2.0 * e["RCLCRIT"]
         scalm_k = np.array([e["ZSCAL"] * max(eta[k] - 0.2, ZEPS1) ** 0.2 for k in range(nz)], dtype)
+        if traj_fluxes is not None:
+            traj_l, traj_n = (np.asarray(f, dtype) for f in traj_fluxes)
+        straddle = np.zeros(nx, bool)
 
         for k in range(nz):
             ap, qs_in = in_ap[k], in_qsat[k]
             t = t3d[k]
             t2 = t
-            rfl = tmp_rfln                                      # :149-150
-            sfl = tmp_sfln
+            if traj_fluxes is None:
+                rfl = tmp_rfln                                  # :149-150
+                sfl = tmp_sfln
+            else:
+                rfl = traj_l[k].copy()
+                sfl = traj_n[k].copy()
             q = F["in_q"][k] + dt * F["in_tnd_cml_q"][k] + F["in_supsat"][k]
             ql = F["in_ql"][k] + dt * F["in_tnd_cml_ql"][k]
             qi = F["in_qi"][k] + dt * F["in_tnd_cml_qi"][k]
@@ -1196,6 +1210,7 @@ def cloudsc2_ad(fields: Dict[str, np.ndarray], in_eta: np.ndarray, dt, externals
             dq = np.maximum(qold1 - q, 0.0)
             dr2 = cons2 * dp * dq
             frz2 = (t < RTT) if FIX else (t3 < RTT)             # Q4: literal = pre-adjustment temperature
+            straddle |= (t3 < RTT) != (t < RTT)
             rfreeze2 = _where(frz2, fwat * dr2, 0.0)
             fwatr2 = _where(frz2, 0.0, 1.0)
             rn = fwatr2 * dr2
@@ -1229,6 +1244,8 @@ def cloudsc2_ad(fields: Dict[str, np.ndarray], in_eta: np.ndarray, dt, externals
                 T[n_][k] = loc[n_]
             T["scalm"][k] = scalm
 
+        if diag is not None:
+            diag["straddle"] = straddle
         # :459-475  (rfl/sfl at level nz take the value left by level nz-1)
         T["rfl"][nz] = tmp_rfln
         T["sfl"][nz] = tmp_sfln

@@ -118,16 +118,27 @@ def run_oracle_tl(fields, fields_i, eta, dt, ext):
     return ({n: F["out_" + n] for n in NL_OUT}, {n: F["out_" + n + "_i"] for n in NL_OUT})
 
 
-def run_oracle_ad(fields, forcing, eta, dt, ext):
-    """forcing: dict NL_OUT name -> adjoint forcing array.  Returns (nl_outputs, adjoint_outputs)."""
+def run_oracle_ad(fields, forcing, eta, dt, ext, traj=None, diag=None):
+    """forcing: dict NL_OUT name -> adjoint forcing array.  Returns (nl_outputs, adjoint_outputs).
+    traj: dict with "fplsl" / "fplsn" - the fluxes entering each level are read from it instead of carried
+    (`cloudsc2_ad_from_trajectory`); diag: dict that receives the oracle's per-column `straddle` mask."""
     F = dict(fields)
     for n in NL_OUT:
         F["in_" + n + "_i"] = forcing[n].copy()
         F["out_" + n] = np.zeros_like(fields["in_ap"])
     for n in NL_IN:
         F["out_" + n + "_i"] = np.zeros_like(fields["in_ap"])
-    oracle.cloudsc2_ad(F, eta, dt, ext)
+    fluxes = None if traj is None else (traj["fplsl"], traj["fplsn"])
+    oracle.cloudsc2_ad(F, eta, dt, ext, traj_fluxes=fluxes, diag=diag)
     return ({n: F["out_" + n] for n in NL_OUT}, {n: F["out_" + n + "_i"] for n in NL_IN})
+
+
+def straddle_columns(fields, forcing, eta, dt, ext) -> np.ndarray:
+    """indices of the columns where the saturation adjustment crosses RTT at some level, by the oracle's forward sweep:
+    there the reference AD's freezing test (Q4, pre-adjustment t) differs from NL/TL's (AD_TRAJ_FIX off)"""
+    diag = {}
+    run_oracle_ad(fields, forcing, eta, dt, ext, diag=diag)
+    return np.flatnonzero(diag["straddle"])
 
 
 def nlev_of(name: str, nz: int) -> int:

@@ -280,17 +280,25 @@ def test_exec_info_and_stencil_csv_on_hip(gpu, tmp_path, capsys):
 
 
 @pytest.mark.gpu
-def test_stencil_csv_of_the_validation_drivers_on_hip(gpu, tmp_path, capsys):
+def test_stencil_csv_of_the_validation_drivers_and_the_fused_ad_choice(gpu, tmp_path, capsys):
     """per-stencil CSV (HIP events in exec_info) of run_taylor_test in its fused-all mode and of run_symmetry_test --fused: the
-    build extensions appear under their own stencil names with their own byte counts"""
+    build extensions appear under their own stencil names with their own byte counts.  The symmetry test's timed AD is
+    cloudsc2_ad_from_trajectory with --ad-traj-fix only; without it (quirk Q4) the timed calls run the full cloudsc2_ad."""
     from gt4py_dwarf_p_cloudsc2_tl_ad_amd.drivers import run_symmetry_test, run_taylor_test
 
     csv = tmp_path / "stencils.csv"
     run_taylor_test.main(["--backend", "hip", "--num-cols", "4096", "--num-runs", "2", "--fused-all",
                           "--output-csv-file-stencils", str(csv)])
-    run_symmetry_test.main(["--backend", "hip", "--num-cols", "4096", "--num-runs", "2", "--fused",
+    run_symmetry_test.main(["--backend", "hip", "--num-cols", "4096", "--num-runs", "2", "--fused", "--ad-traj-fix",
                             "--output-csv-file-stencils", str(csv)])
+    # without --ad-traj-fix the TL call's fluxes are not AD's in columns whose adjustment crosses RTT: the full cloudsc2_ad
+    csv_q4 = tmp_path / "stencils_q4.csv"
+    run_symmetry_test.main(["--backend", "hip", "--num-cols", "4096", "--num-runs", "2", "--fused",
+                            "--output-csv-file-stencils", str(csv_q4)])
     capsys.readouterr()
+    calls_q4 = {(r[2], r[6]): int(r[7]) for r in (r.split(",") for r in csv_q4.read_text().strip().splitlines()[1:])}
+    assert calls_q4[("ad-hip", "cloudsc2_tl_incremented")] == 2 and calls_q4[("ad-hip", "cloudsc2_ad")] == 2
+    assert ("ad-hip", "cloudsc2_ad_from_trajectory") not in calls_q4
     rows = [r.split(",") for r in csv.read_text().strip().splitlines()[1:]]
     calls = {(r[2], r[6]): int(r[7]) for r in rows}
     assert calls[("tl-hip", "cloudsc2_nl_taylor_multi")] == 2 and calls[("tl-hip", "cloudsc2_tl_incremented")] == 2

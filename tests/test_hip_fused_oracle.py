@@ -289,60 +289,292 @@ def test_symmetry_driver_graph_mode(gpu, capsys):
     assert "HOORAY" in capsys.readouterr().out
 
 
+def _lev(n, nz):
+    return nz + 1 if n in ("aph", "lu") else nz        # out_aph_i / out_lu_i are written on all nz+1 levels
+
+
+def _traj_case(gpu, nx, nz, dtype, flags, seed=20240807):
+    """the symmetry test's AD case: forcing = the oracle TL's perturbation outputs (adjoint/validation.py:135-151); the HIP
+    cloudsc2_ad (its fluxes, its adjoints) and the HIP cloudsc2_tl's fluxes on the same state"""
+    from helpers import increments, run_oracle_tl
+    from test_hip_tl_ad import run_hip_ad, run_hip_tl
+
+    ext = externals(NLEV=nz, **flags)
+    fields, eta, dt = nl_case(nx, nz=nz, dtype=dtype, seed=seed)
+    fi = increments(fields, 0.01, ignore_supsat=True)
+    _, tl_i = run_oracle_tl(fields, fi, eta, dt, ext)
+    forcing = {n: tl_i[n] for n in NL_OUT}
+    ad_nl, ad_adj = run_hip_ad(fields, forcing, eta, dt, ext, gpu, nx, nz)
+    tl_nl, _ = run_hip_tl(fields, fi, eta, dt, ext, gpu, nx, nz)
+    return ext, fields, eta, dt, forcing, ad_nl, ad_adj, tl_nl
+
+
+def _synthetic_fluxes(tl_nl, seed=3):
+    """non-negative fluxes whose two fields and levels are independent: the TL fluxes times per-level, per-column factors
+    in [0.5, 1.5] (independent for rain and snow), zero at level 0"""
+    rng = np.random.default_rng(seed)
+    out = {}
+    for n in ("fplsl", "fplsn"):
+        v = tl_nl[n] * rng.uniform(0.5, 1.5, size=tl_nl[n].shape).astype(tl_nl[n].dtype)
+        v[0] = 0
+        out[n] = v
+    return out
+
+
+def _run_from_trajectory(gpu, ext, fields, forcing, traj, eta, dt, window=None):
+    """`cloudsc2_ad_from_trajectory` with NaN-prefilled outputs; window = (W, c0): every field is the column window
+    [c0, c0 + nx) of a (nz+1, W) storage whose other columns hold a guard value that must stay untouched"""
+    import torch
+
+    from gt4py_dwarf_p_cloudsc2_tl_ad_amd import _lib, storage
+    from gt4py_dwarf_p_cloudsc2_tl_ad_amd.stencils import compile_stencil
+    from helpers import NL_IN, from_device
+
+    nz1, nx = fields["in_ap"].shape
+    dtype = fields["in_ap"].dtype
+    host = {**fields, **{"in_" + n + "_i": forcing[n] for n in NL_OUT},
+            "traj_fplsl": traj["fplsl"], "traj_fplsn": traj["fplsn"]}
+    nan = np.full((nz1, nx), np.nan, dtype=dtype)
+    outs_h = {"out_" + n + "_i": nan for n in NL_IN}
+    if window is None:
+        ins = to_device(host, gpu)
+        outs = to_device(outs_h, gpu)
+        view = lambda t: t  # noqa: E731
+        wide = {}
+    else:
+        W, c0 = window
+        guard = -3.0
+
+        def widen(v):
+            t = torch.full((nz1, W), guard, dtype=storage.torch_dtype(dtype), device=gpu)
+            t[:, c0:c0 + nx] = torch.as_tensor(v, device=gpu)
+            return t
+
+        wide = {k: widen(v) for k, v in {**host, **outs_h}.items()}
+        ins = {k: storage.logical_view(wide[k][:, c0:c0 + nx]) for k in host}
+        outs = {k: storage.logical_view(wide[k][:, c0:c0 + nx]) for k in outs_h}
+    before = {k: v.clone() for k, v in ins.items()}
+    compile_stencil("cloudsc2_ad_from_trajectory", ext)(
+        **ins, **outs, in_eta=torch.as_tensor(eta, device=gpu), dt=dtype.type(dt), origin=(0, 0, 0),
+        domain=(nx, 1, nz1), validate_args=True, exec_info=None)
+    torch.cuda.synchronize()
+    assert _lib.last_kernel() == "cs2::ad_kernel<trajectory>"
+    for k, v in before.items():
+        assert torch.equal(ins[k], v), k                                    # forcings, state and fluxes are read-only
+    if window is not None:
+        W, c0 = window
+        for k, t in wide.items():
+            assert bool((t[:, :c0] == -3.0).all()) and bool((t[:, c0 + nx:] == -3.0).all()), k   # guard columns
+    return {n: from_device(outs["out_" + n + "_i"]) for n in NL_IN}
+
+
+def _assert_matches_oracle(name, got, fields, forcing, eta, dt, ext, traj, cols=None):
+    """`got` (the 16 adjoints of the trajectory kernel) against the oracle fed with the same fluxes, at the default
+    tolerance, on the columns `cols` (all by default).
+    fp32: the reference is the oracle evaluated in fp64 on the same fp32 inputs.  out_lu_i / out_q_i carry a cancellation
+    (inside the clc adjoint) that leaves a few isolated points undetermined in fp32 arithmetic: there the fp32 oracle
+    itself is up to ~25x the tolerance away from the fp64 value, and inputs moved by one fp32 rounding move the fp64 value
+    by as much.  A point passes if the kernel is within the tolerance of the fp64 value plus the larger of two measures of
+    that point's fp32 noise: the fp32 oracle's distance from it, and the largest change of the fp64 value when the inputs
+    of the point's column are moved by up to one fp32 rounding (six seeded draws, computed only for failing columns)."""
+    from helpers import NL_IN, TOL, run_oracle_ad
+
+    dtype = fields["in_ap"].dtype
+    nz = fields["in_ap"].shape[0] - 1
+    cols = slice(None) if cols is None else cols
+    _, want = run_oracle_ad(fields, forcing, eta, dt, ext, traj=traj)
+    if dtype == np.float64:
+        for n in NL_IN:
+            k = _lev(n, nz)
+            assert_close(f"{name} vs oracle out_{n}_i", got[n][:k, cols], want[n][:k, cols], dtype,
+                         scale=float(np.abs(want[n][:k]).max()))
+        return want
+    up = lambda d: {k_: v.astype(np.float64) for k_, v in d.items()}  # noqa: E731
+    _, ref = run_oracle_ad(up(fields), up(forcing), eta.astype(np.float64), dt, ext, traj=up(traj))
+    tol = TOL[np.dtype(dtype)]
+    for n in NL_IN:
+        k = _lev(n, nz)
+        g, w, r = (a[:k, cols].astype(np.float64) for a in (got[n], want[n], ref[n]))
+        assert not np.isnan(g).any(), f"{name} out_{n}_i: NaN in result"
+        bound = tol["rtol"] * np.abs(r) + tol["atol_rel"] * float(np.abs(ref[n][:k]).max())
+        noise = np.abs(w - r)
+        bad = np.abs(g - r) > bound + noise
+        if bad.any():       # the fp64 value's sensitivity to one fp32 rounding of the inputs, on the failing columns
+            cc = np.flatnonzero(bad.any(axis=0))
+            col = np.arange(fields["in_ap"].shape[1])[cols][cc]
+            sub = lambda d: {k_: v[:, col].astype(np.float64) for k_, v in d.items()}  # noqa: E731
+            rng = np.random.default_rng(17)
+            for _ in range(6):
+                moved = {k_: v * (1.0 + rng.uniform(-1.2e-7, 1.2e-7, size=v.shape)) for k_, v in sub(fields).items()}
+                _, rp = run_oracle_ad(moved, sub(forcing), eta.astype(np.float64), dt, ext, traj=sub(traj))
+                noise[:, cc] = np.maximum(noise[:, cc], np.abs(rp[n][:k] - r[:, cc]))
+        err = np.abs(g - r)
+        bad = err > bound + noise
+        if bad.any():
+            i = np.unravel_index(np.argmax(err - bound - noise), err.shape)
+            raise AssertionError(f"{name} vs oracle out_{n}_i: {int(bad.sum())}/{bad.size} points outside tolerance; worst "
+                                 f"at {i}: got {g[i]!r}, fp32 oracle {w[i]!r}, fp64 oracle {r[i]!r}, bound {bound[i]:.3e}, "
+                                 f"fp32 noise {noise[i]:.3e}")
+    return want
+
+
+def _check_against_the_oracle(gpu, ext, fields, forcing, eta, dt, ad_nl, ad_adj, tl_nl, window=None):
+    """the kernel fed with AD's own fluxes, the TL call's fluxes and synthetic fluxes against the oracle fed with the
+    SAME fluxes, at the default tolerance; with its own fluxes it is cloudsc2_ad bit for bit"""
+    from helpers import NL_IN
+
+    nz = fields["in_ap"].shape[0] - 1
+    got = {}
+    for name, traj in (("own", ad_nl), ("tl", tl_nl), ("synthetic", _synthetic_fluxes(tl_nl))):
+        got[name] = _run_from_trajectory(gpu, ext, fields, forcing, traj, eta, dt, window)
+        _assert_matches_oracle(f"ad_from_trajectory({name} fluxes)", got[name], fields, forcing, eta, dt, ext, traj)
+        for n in NL_IN:
+            k = _lev(n, nz)
+            if k == nz:
+                assert np.isnan(got[name][n][nz]).all(), n                  # level nz of a full-level field: not written
+    for n in NL_IN:
+        k = _lev(n, nz)
+        assert np.array_equal(got["own"][n][:k], ad_adj[n][:k]), n          # cloudsc2_ad's own fluxes: its bits
+    return got
+
+
+_TRAJ_SHAPES = [(1, 137), (63, 137), (65, 137), (333, 137),
+                (2011, 137),      # 8 workgroups: XCD remap on, ragged last workgroup
+                (2305, 137),      # 10 workgroups: identity mapping
+                (4096, 137), (333, 5), (65, 5), (333, 2), (65, 2)]
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("nx,nz", _TRAJ_SHAPES)
+def test_ad_from_trajectory_matches_the_oracle_fed_with_the_same_fluxes(gpu, nx, nz, dtype):
+    """BUILD EXTENSION `cloudsc2_ad_from_trajectory` (r04): cloudsc2_ad without its forward sweep, reading the fluxes
+    entering each level.  Its oracle is oracle.cloudsc2_ad with the same fluxes (`traj_fluxes`).  Default switches; the
+    level table and LDS parking area scale with nz, the column mapping with nx."""
+    ext, fields, eta, dt, forcing, ad_nl, ad_adj, tl_nl = _traj_case(gpu, nx, nz, dtype, {})
+    _check_against_the_oracle(gpu, ext, fields, forcing, eta, dt, ad_nl, ad_adj, tl_nl)
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("nx,nz,W,c0", [(190, 137, 300, 37), (65, 5, 200, 70)])
+def test_ad_from_trajectory_on_a_strided_column_window(gpu, nx, nz, W, c0, dtype):
+    """lev_stride > nx, window starting at column c0 != 0: the same as the oracle, guard columns untouched"""
+    ext, fields, eta, dt, forcing, ad_nl, ad_adj, tl_nl = _traj_case(gpu, nx, nz, dtype, {}, seed=59)
+    _check_against_the_oracle(gpu, ext, fields, forcing, eta, dt, ad_nl, ad_adj, tl_nl, window=(W, c0))
+
+
+@pytest.mark.parametrize("dtype", [np.float64, np.float32])
+@pytest.mark.parametrize("fix", [0, 1])
+@pytest.mark.parametrize("regcl", [True, False])
+def test_ad_from_trajectory_switches_and_the_tl_flux_contract(gpu, regcl, fix, dtype):
+    """{LREGCL} x {AD_TRAJ_FIX} at a case with columns whose saturation adjustment crosses RTT (asserted non-empty):
+    against the oracle fed with the same fluxes, and what feeding the TL call's fluxes means -
+    AD_TRAJ_FIX = 1: it IS cloudsc2_ad at the default tolerance in every column, crossing columns included;
+    AD_TRAJ_FIX = 0 (quirk Q4): it is cloudsc2_ad outside the crossing columns, the oracle fed with the TL fluxes inside
+    them, and there it differs from cloudsc2_ad in at least one column (the case exercises the quirk)."""
+    from helpers import NL_IN, TOL, straddle_columns
+
+    nx, nz = 4096, 137
+    ext, fields, eta, dt, forcing, ad_nl, ad_adj, tl_nl = _traj_case(gpu, nx, nz, dtype, dict(LREGCL=regcl, AD_TRAJ_FIX=fix))
+    got = _check_against_the_oracle(gpu, ext, fields, forcing, eta, dt, ad_nl, ad_adj, tl_nl)["tl"]
+    cross = straddle_columns(fields, forcing, eta, dt, ext)
+    assert cross.size > 0
+    rest = np.setdiff1d(np.arange(nx), cross)
+    assert rest.size > 0
+    if fix:
+        for n in NL_IN:
+            k = _lev(n, nz)
+            assert_close(f"fix: ad_from_trajectory(TL fluxes) vs cloudsc2_ad out_{n}_i", got[n][:k], ad_adj[n][:k], dtype)
+        return
+    _assert_matches_oracle("ad_from_trajectory(TL fluxes), crossing columns", got, fields, forcing, eta, dt, ext, tl_nl,
+                           cols=cross)
+    tol = TOL[np.dtype(dtype)]
+    differs = np.zeros(nx, bool)
+    for n in NL_IN:
+        k = _lev(n, nz)
+        scale = float(np.abs(ad_adj[n][:k]).max())
+        assert_close(f"ad_from_trajectory(TL fluxes) vs cloudsc2_ad out_{n}_i, other columns", got[n][:k, rest],
+                     ad_adj[n][:k, rest], dtype, scale=scale)
+        err = np.abs(got[n][:k].astype(np.float64) - ad_adj[n][:k].astype(np.float64))
+        differs |= (err > tol["rtol"] * np.abs(ad_adj[n][:k].astype(np.float64)) + tol["atol_rel"] * scale).any(axis=0)
+    assert differs.any() and not differs[rest].any()
+
+
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
 @pytest.mark.parametrize("flags", [dict(), dict(LREGCL=False, AD_TRAJ_FIX=1)])
 def test_ad_from_trajectory_equals_cloudsc2_ad_and_the_oracle(gpu, flags, dtype):
     """BUILD EXTENSION `cloudsc2_ad_from_trajectory` (r04): cloudsc2_ad without its forward sweep, fed with the flux outputs of
     a call on the same state.  (a) With the fluxes cloudsc2_ad itself wrote, the 16 adjoint fields are the BITS of
-    cloudsc2_ad's; (b) with the fluxes of the cloudsc2_tl call that precedes it in the symmetry test
-    (adjoint/validation.py:135-151) they agree to rounding and match the oracle's cloudsc2_ad like cloudsc2_ad does; (c) the
-    forcings and the trajectory fields are left untouched, nothing but the adjoints is written; (d) the evaporation block is
+    cloudsc2_ad's; (b) with those, the TL call's and synthetic fluxes it matches the oracle fed with the same fluxes at the
+    default tolerance, and with AD_TRAJ_FIX the TL call's fluxes give cloudsc2_ad's adjoints at that tolerance; (c) the
+    forcings, the state and the fluxes are left untouched, nothing but the adjoints is written; (d) the evaporation block is
     refused by name."""
     import torch
 
-    from gt4py_dwarf_p_cloudsc2_tl_ad_amd import _lib, storage
+    from gt4py_dwarf_p_cloudsc2_tl_ad_amd import storage
     from gt4py_dwarf_p_cloudsc2_tl_ad_amd.stencils import compile_stencil
-    from helpers import NL_IN, from_device, increments, run_oracle_ad, run_oracle_tl
-    from test_hip_tl_ad import run_hip_ad, run_hip_tl
+    from helpers import NL_IN
 
-    lev = lambda n: nz + 1 if n in ("aph", "lu") else nz  # noqa: E731  (out_aph_i / out_lu_i are written on all nz+1 levels)
     nx, nz = 333, 137
-    ext = externals(NLEV=nz, **flags)
-    fields, eta, dt = nl_case(nx, dtype=dtype, seed=83)
-    fi = increments(fields, 0.01, ignore_supsat=True)
-    _, tl_i = run_oracle_tl(fields, fi, eta, dt, ext)
-    forcing = {n: tl_i[n] for n in NL_OUT}                       # the symmetry test's forcing: the TL perturbation outputs
-    want_nl, want_adj = run_oracle_ad(fields, forcing, eta, dt, ext)
-    ad_nl, ad_adj = run_hip_ad(fields, forcing, eta, dt, ext, gpu, nx, nz)
-    tl_nl, _ = run_hip_tl(fields, fi, eta, dt, ext, gpu, nx, nz)
-
-    dev = to_device(fields, gpu)
-    frc = to_device({"in_" + n + "_i": forcing[n] for n in NL_OUT}, gpu)
-    st = compile_stencil("cloudsc2_ad_from_trajectory", ext)
-    com = dict(in_eta=torch.as_tensor(eta, device=gpu), dt=dtype(dt), origin=(0, 0, 0), domain=(nx, 1, nz + 1),
-               validate_args=True, exec_info=None)
-
-    def run(traj):
-        tr = to_device({"traj_fplsl": traj["fplsl"], "traj_fplsn": traj["fplsn"]}, gpu)
-        before = {k: v.clone() for k, v in {**frc, **tr}.items()}
-        outs = {"out_" + n + "_i": storage.from_klayout(np.full((nz + 1, nx), np.nan, dtype=dtype), dtype, gpu) for n in NL_IN}
-        st(**dev, **frc, **tr, **outs, **com)
-        torch.cuda.synchronize()
-        assert _lib.last_kernel() == "cs2::ad_kernel<trajectory>"
-        for k, v in before.items():
-            assert torch.equal({**frc, **tr}[k], v), k                                        # (c) read-only
-        return {n: from_device(outs["out_" + n + "_i"]) for n in NL_IN}
-
-    own = run(ad_nl)                                              # (a) cloudsc2_ad's own recomputed fluxes
-    for n in NL_IN:
-        assert np.array_equal(own[n][:lev(n)], ad_adj[n][:lev(n)], equal_nan=True), n
-    from_tl = run(tl_nl)                                          # (b) the TL call's fluxes
-    rt = 1e3 if dtype == np.float64 else 1e2
-    for n in NL_IN:
-        k = lev(n)
-        assert_close(f"ad_from_trajectory(TL fluxes) vs cloudsc2_ad out_{n}_i", from_tl[n][:k], ad_adj[n][:k], dtype, rtol_mul=rt)
-        assert_close(f"ad_from_trajectory vs oracle out_{n}_i", from_tl[n][:k], want_adj[n][:k], dtype, rtol_mul=rt)
+    ext, fields, eta, dt, forcing, ad_nl, ad_adj, tl_nl = _traj_case(gpu, nx, nz, dtype, flags, seed=83)
+    got = _check_against_the_oracle(gpu, ext, fields, forcing, eta, dt, ad_nl, ad_adj, tl_nl)    # (a), (b), (c)
+    if flags.get("AD_TRAJ_FIX"):
+        for n in NL_IN:
+            k = _lev(n, nz)
+            assert_close(f"fix: ad_from_trajectory(TL fluxes) vs cloudsc2_ad out_{n}_i", got["tl"][n][:k], ad_adj[n][:k],
+                         dtype)
     with pytest.raises(ValueError, match="no evaporation"):      # (d)
         compile_stencil("cloudsc2_ad_from_trajectory", externals(NLEV=nz, LEVAPLS2=True))(
-            **dev, **frc, **to_device({"traj_fplsl": ad_nl["fplsl"], "traj_fplsn": ad_nl["fplsn"]}, gpu),
-            **{"out_" + n + "_i": storage.zeros(nx, nz, dtype, gpu) for n in NL_IN}, **com)
+            **to_device({**fields, **{"in_" + n + "_i": forcing[n] for n in NL_OUT},
+                         "traj_fplsl": ad_nl["fplsl"], "traj_fplsn": ad_nl["fplsn"]}, gpu),
+            **{"out_" + n + "_i": storage.zeros(nx, nz, dtype, gpu) for n in NL_IN},
+            in_eta=torch.as_tensor(eta, device=gpu), dt=dtype(dt), origin=(0, 0, 0), domain=(nx, 1, nz + 1),
+            validate_args=True, exec_info=None)
+
+
+def _symmetry(inp, fused, ad_traj_fix, yrphnc=None, nx=65536, runs=2):
+    """SymmetryTest as drivers/run_symmetry_test.py builds it: one validated call, then `runs` timed calls"""
+    import argparse
+
+    import torch
+
+    from gt4py_dwarf_p_cloudsc2_tl_ad_amd.drivers._common import add_common_options, setup
+    from gt4py_dwarf_p_cloudsc2_tl_ad_amd.harness import SymmetryTest
+
+    ap = argparse.ArgumentParser()
+    add_common_options(ap)
+    ctx = setup(ap.parse_args(["--backend", "hip", "--num-cols", str(nx), "--input", inp]))
+    cfg, p = ctx["config"], ctx["params"]
+    st = SymmetryTest(ctx["grid"], factor=0.01, kflag=1, lphylin=True, ldrain1d=False, yoethf_params=p["yoethf"],
+                      yomcst_params=p["yomcst"], yrecldp_params=p["yrecldp"], yrephli_params=p["yrephli"],
+                      yrncl_params=p["yrncl"], yrphnc_params={**p["yrphnc"], **(yrphnc or {})},
+                      enable_checks=cfg.sympl_enable_checks, gt4py_config=cfg.gt4py_config, ad_traj_fix=ad_traj_fix,
+                      fused=fused)
+    ok = st(ctx["state"], ctx["dt"], enable_validation=True)
+    for _ in range(runs):
+        st(ctx["state"], ctx["dt"], enable_validation=False)
+    torch.cuda.synchronize()
+    from gt4py_dwarf_p_cloudsc2_tl_ad_amd import storage
+
+    adj = {k: storage.klayout(v.data.as_subclass(torch.Tensor)).cpu().numpy()
+           for dct in (st.tends_ad, st.diags_ad) for k, v in dct.items() if k.endswith("_i")}
+    return ok, dict(st.last), adj, ctx["nz"], st.cloudsc2_ad_from_trajectory is not None
+
+
+@pytest.mark.parametrize("yrphnc", [None, dict(LEVAPLS2=True)])
+@pytest.mark.parametrize("ad_traj_fix", [False, True])
+@pytest.mark.parametrize("inp", ["synthetic", "auto"])
+def test_fused_symmetry_times_what_it_validates(gpu, inp, ad_traj_fix, yrphnc, capsys):
+    """`SymmetryTest(fused=True)`: the adjoint fields its TIMED calls leave are those of the unfused harness at the default
+    tolerance, and the verdict (which the validated call decides) is the same.  65 536 columns; the synthetic input has
+    distinct mixed-regime columns, among them columns whose saturation adjustment crosses RTT.  The trajectory kernel is
+    used only where its contract holds by construction: AD_TRAJ_FIX on, no evaporation block (LEVAPLS2 from the
+    parameter groups, as an input file may set it)."""
+    ok0, last0, adj0, nz, _ = _symmetry(inp, False, ad_traj_fix, yrphnc)
+    ok1, last1, adj1, _, traj = _symmetry(inp, True, ad_traj_fix, yrphnc)
+    capsys.readouterr()
+    assert set(adj1) == set(adj0) and len(adj0) == 16
+    for k in adj0:
+        lev = nz + 1 if k in ("f_aph_i", "f_lu_i") else nz
+        assert_close(f"fused vs unfused symmetry {k}", adj1[k][:lev], adj0[k][:lev], np.float64)
+    assert ok1 == ok0 and last1["columns_passing"] == last0["columns_passing"] and last1["columns"] == last0["columns"]
+    assert traj == (ad_traj_fix and not yrphnc)
