@@ -32,102 +32,23 @@
 #ifndef CS2_AD_DIAG
 #define CS2_AD_DIAG 0   // diagnostics only (wrong results): 1 = the kernel's memory traffic without the physics
 #endif
-// Tuning switches (A/B-tested with profiles/ab_kernels.py; the defaults are the fastest measured set).
-// CS2_AD_PARK: sweep 2 parks the part of a level's recomputed trajectory that the adjoint statements only read in
+// Parking (fp32 only): sweep 2 parks the part of a level's recomputed trajectory that the adjoint statements only read in
 // their second half (34 values per column, listed in CS2_AD_PARK_LIST) in LDS between ad_forward and that half, instead
 // of carrying them through the register-pressure peak (cuadj_bwd + the autoconversion adjoint), where hipcc otherwise
 // shuttles them through AGPRs (v_accvgpr_write / _read occupy a VALU issue slot each; ds_write / ds_read do not).
 // Measured (profiles/r02/ab_ad_variants.txt, one process, interleaved): fp64 65 536 columns 922.9 us parked vs 911.7 us
 // not parked - the fp64 kernel runs at 94 % of the time its memory traffic alone takes (CS2_AD_DIAG = 1), so issue slots
 // are not what it waits for; fp32 524 288 columns 3 689 us parked vs 3 817 us (199 -> 166 VGPRs: 3 waves per SIMD
-// instead of 2).  Hence the default: bit 0 = park in the fp64 kernels (off), bit 1 = in the fp32 kernels (on).
-#ifndef CS2_AD_PARK
-#define CS2_AD_PARK 2
-#endif
+// instead of 2).
 template <typename T>
-constexpr bool kADPark = ((CS2_AD_PARK) & (sizeof(T) == 8 ? 1 : 2)) != 0;
+constexpr bool kADPark = sizeof(T) == 4;
 #define CS2_AD_PARK_LIST(X)                                                                                            \
     X(fac4) X(dqsdz) X(dqc) X(dqsdtemp) X(dtdzmo) X(fac3) X(rodqsdp) X(fac2) X(rho) X(fac1) X(rt) X(clc) X(rlu) X(exlu) \
     X(lude) X(qt) X(qcrit) X(qsat) X(qpd) X(qcd) X(tmp3) X(rden) X(crh2) X(supsat) X(fac) X(cor) X(facw) X(faci) X(ri)  \
     X(rl) X(esdp1) X(foeew) X(sech2) X(qc3)
 #define CS2_AD_PARK_COUNT 34
-// CS2_AD_KEEP_MB: cache-resident turnaround.  Sweep 1 ends at level nz-1 and sweep 2 starts there, re-reading the 16
-// inputs + 2 fluxes of every level; the last levels sweep 1 touched can still be in the 256 MB memory-side cache when
-// sweep 2 asks for them - if neither side marked them non-temporal.  The launcher turns this budget into a number of
-// bottom levels (18 words x level stride each) whose sweep-1 loads, flux stores and sweep-2 loads use the default
-// policy; every other access of the kernel stays non-temporal.  0 = off.
-#ifndef CS2_AD_KEEP_MB
-#define CS2_AD_KEEP_MB 0
-#endif
-#ifndef CS2_AD_DRAIN
-#define CS2_AD_DRAIN 0  // bit 0 / bit 1: drain the level's stores before the next level is requested in sweep 1 / sweep 2
-#endif
-#ifndef CS2_AD_LANDED
-#define CS2_AD_LANDED 0 // 1: aph_k marked as landed before sweep 1's loop (see landed()): sweep 1 then keeps its stores in
-#endif                  // flight across levels - measured slower (+1.0 ... +1.5 %, docs/TUNING_LOG.md 3.9)
-#ifndef CS2_AD_PIN
-#define CS2_AD_PIN 3    // fp64 constants pinned in VGPRs: bit 0 = the physical constants, bit 1 = the exp coefficients
-#endif
 
 namespace cs2 {
-
-template <typename T>
-struct ADIn {
-    T ap, aph1, lu1, lude, mfd, mfu, q, qi, ql, qsat, supsat, t, tq, tqi, tql, tt;
-};
-
-// `keep`: wave-uniform; the level's 16 words are loaded with the default cache policy instead of non-temporally
-// (CS2_AD_KEEP_MB below: the levels where sweep 1 ends are the levels where sweep 2 starts).
-template <typename T, typename FP, typename O>
-__device__ __forceinline__ ADIn<T> ad_load(const FP& F, O lsb, O o, bool keep = false) {
-    ADIn<T> x;
-    if (keep) {
-        x.ap = ldg_keep(F.in(NL_IN_AP), o);
-        x.aph1 = ldg_keep(F.in(NL_IN_APH), o + lsb);
-        x.lu1 = ldg_keep(F.in(NL_IN_LU), o + lsb);
-        x.lude = ldg_keep(F.in(NL_IN_LUDE), o);
-        x.mfd = ldg_keep(F.in(NL_IN_MFD), o);
-        x.mfu = ldg_keep(F.in(NL_IN_MFU), o);
-        x.q = ldg_keep(F.in(NL_IN_Q), o);
-        x.qi = ldg_keep(F.in(NL_IN_QI), o);
-        x.ql = ldg_keep(F.in(NL_IN_QL), o);
-        x.qsat = ldg_keep(F.in(NL_IN_QSAT), o);
-        x.supsat = ldg_keep(F.in(NL_IN_SUPSAT), o);
-        x.t = ldg_keep(F.in(NL_IN_T), o);
-        x.tq = ldg_keep(F.in(NL_IN_TND_CML_Q), o);
-        x.tqi = ldg_keep(F.in(NL_IN_TND_CML_QI), o);
-        x.tql = ldg_keep(F.in(NL_IN_TND_CML_QL), o);
-        x.tt = ldg_keep(F.in(NL_IN_TND_CML_T), o);
-        return x;
-    }
-    x.ap = ldg(F.in(NL_IN_AP), o);
-    x.aph1 = ldg(F.in(NL_IN_APH), o + lsb);
-    x.lu1 = ldg(F.in(NL_IN_LU), o + lsb);
-    x.lude = ldg(F.in(NL_IN_LUDE), o);
-    x.mfd = ldg(F.in(NL_IN_MFD), o);
-    x.mfu = ldg(F.in(NL_IN_MFU), o);
-    x.q = ldg(F.in(NL_IN_Q), o);
-    x.qi = ldg(F.in(NL_IN_QI), o);
-    x.ql = ldg(F.in(NL_IN_QL), o);
-    x.qsat = ldg(F.in(NL_IN_QSAT), o);
-    x.supsat = ldg(F.in(NL_IN_SUPSAT), o);
-    x.t = ldg(F.in(NL_IN_T), o);
-    x.tq = ldg(F.in(NL_IN_TND_CML_Q), o);
-    x.tqi = ldg(F.in(NL_IN_TND_CML_QI), o);
-    x.tql = ldg(F.in(NL_IN_TND_CML_QL), o);
-    x.tt = ldg(F.in(NL_IN_TND_CML_T), o);
-    return x;
-}
-// store / load with the cache policy chosen by a wave-uniform flag (sweep 1's fluxes that sweep 2 reads back)
-template <typename T, typename O>
-__device__ __forceinline__ void stg_sel(T* base, O boff, T v, bool keep) {
-    if (keep) *reinterpret_cast<T*>(reinterpret_cast<char*>(base) + boff) = v;
-    else stg(base, boff, v);
-}
-template <typename T, typename O>
-__device__ __forceinline__ T ldg_sel(const T* base, O boff, bool keep) {
-    return keep ? ldg_keep(base, boff) : ldg(base, boff);
-}
 
 // Saved state of the two saturation-adjustment iterations (cuadjtqs:53-91), including the
 // reciprocals the reverse sweep divides by: r = 1/(targ - z4es), rden = 1/(1 + qsat cor z2s).
@@ -241,7 +162,7 @@ struct ADTraj {
 };
 
 template <typename T, bool FIX, bool EVAP>
-__device__ __forceinline__ void ad_forward(const Ext<T>& e, const NLK<T>& kc, const ExpK<T>& xk, const ADIn<T>& x,
+__device__ __forceinline__ void ad_forward(const Ext<T>& e, const NLK<T>& kc, const ExpK<T>& xk, const LevelIn<T>& x,
                                            T aph_k, int k, T eta_k, T scalm, const CrhCol<T>& crh, T dt, T rfl, T sfl,
                                            T covptot_in, T aph_s, ADTraj<T>& r) {
 #if CS2_AD_DIAG == 1
@@ -546,7 +467,7 @@ struct ADOut {
     T ap, t, q, ql, qi, qsat, lude, mfd, mfu, aph1, lu1;
 };
 
-// LDS parking of trajectory values across the first half of ad_backward (CS2_AD_PARK): one 8-byte (4-byte) slot per
+// LDS parking of trajectory values across the first half of ad_backward (kADPark): one 8-byte (4-byte) slot per
 // value and lane, [value][lane] - consecutive lanes hit consecutive banks.  The empty asm statements with a memory
 // clobber pin the stores before, and the loads after, everything in between: hipcc may neither forward the stored values
 // in registers nor hoist the loads back up to the stores.
@@ -570,7 +491,7 @@ __device__ __forceinline__ void ad_unpark(const T* __restrict__ lds, ADTraj<T>& 
 // Backward statements of one level (:494-967 + this level's share of :970-996).  Divisions use the
 // reciprocals saved with the trajectory.
 template <typename T, bool REG, bool FIX, bool EVAP>
-__device__ __forceinline__ ADOut<T> ad_backward(const Ext<T>& e, const NLK<T>& kc, const ADIn<T>& x, int k, T scalm,
+__device__ __forceinline__ ADOut<T> ad_backward(const Ext<T>& e, const NLK<T>& kc, const LevelIn<T>& x, int k, T scalm,
                                                 T dt, T sfl, ADTraj<T>& r, const ADForce<T>& f, ADBack<T>& b,
                                                 const T* park_lds = nullptr) {
     ADOut<T> o;
@@ -948,16 +869,11 @@ struct ADArgs {
     MPtrs<T, NL_NUM_OUT> out;
     MPtrs<T, NL_NUM_IN> oadj;
     T dt;
-    int keep_from;
     const T* traj_l;   // TRAJ instantiation only: the rain / snow fluxes ENTERING each level (= out_fplsl / out_fplsn of a
     const T* traj_n;   // cloudsc2_nl / cloudsc2_tl call on the same state), read instead of recomputed by sweep 1
 };
-#ifndef CS2_AD_KARG
-#define CS2_AD_KARG 1   // 1: field pointers are re-read from the kernarg segment (scalar loads) on every level
-#endif
 template <typename T>
 struct ADFields : KernArgs<ADArgs<T>> {
-    __device__ __forceinline__ void fresh() { KernArgs<ADArgs<T>>::template fresh<(CS2_AD_KARG != 0)>(); }
     __device__ __forceinline__ const T* in(int i) const { return this->ka->in.p[i]; }
     __device__ __forceinline__ const T* adj(int i) const { return this->ka->adj.p[i]; }
     __device__ __forceinline__ T* out(int i) const { return this->ka->out.p[i]; }
@@ -982,31 +898,26 @@ ad_kernel(const ADArgs<T> A) {
     Ext<T> e = A.e;
     NLK<T> kc = A.kc;
     ExpK<T> xk = A.xk;
-    const int nx = A.nx, nz = A.nz, keep_from = A.keep_from;
+    const int nx = A.nx, nz = A.nz;
     const int64_t ls = A.ls;
     const T* __restrict__ eta = A.eta;
     T dt = A.dt;
     ADFields<T> F;
+    const auto F_in = [&](int i) { return F.in(i); };
     extern __shared__ __align__(16) unsigned char smem_raw[];
     T* s_eta = reinterpret_cast<T*>(smem_raw);
     T* s_scalm = s_eta + (nz + 1);
     int klo, khi;
     build_level_table<T>(eta, nz, e, s_eta, s_scalm, klo, khi);
-    if constexpr (sizeof(T) == 8 && (CS2_AD_PIN & 1)) {
+    if constexpr (sizeof(T) == 8) {
         // fp64 constants of the level loops -> VGPRs (see pin_vgpr in cloudsc2_common.hpp)
-        pin_vgpr(e.RCPD); pin_vgpr(e.RLSTT); pin_vgpr(e.RLVTT); pin_vgpr(e.R4LES); pin_vgpr(e.R4IES);
-        pin_vgpr(e.RTT); pin_vgpr(e.R3IES); pin_vgpr(e.R3LES); pin_vgpr(e.R2ES); pin_vgpr(e.ZQMAX);
-        pin_vgpr(e.RETV); pin_vgpr(e.R5LES); pin_vgpr(e.R5IES); pin_vgpr(e.RG); pin_vgpr(e.RD);
-        pin_vgpr(kc.rdt); pin_vgpr(kc.cons2); pin_vgpr(kc.rRD); pin_vgpr(kc.rRCPD); pin_vgpr(dt);
-    }
-    if constexpr (sizeof(T) == 8 && (CS2_AD_PIN & 2)) {
-        pin_vgpr(xk.l2e); pin_vgpr(xk.ln2h); pin_vgpr(xk.ln2l); pin_vgpr(xk.c12); pin_vgpr(xk.c11);
-        pin_vgpr(xk.c10); pin_vgpr(xk.c9); pin_vgpr(xk.c8); pin_vgpr(xk.c7); pin_vgpr(xk.c6);
-        pin_vgpr(xk.c5); pin_vgpr(xk.c4); pin_vgpr(xk.c3);
+        pin_vgprs(e.RCPD, e.RLSTT, e.RLVTT, e.R4LES, e.R4IES, e.RTT, e.R3IES, e.R3LES, e.R2ES, e.ZQMAX, e.RETV, e.R5LES,
+                  e.R5IES, e.RG, e.RD, kc.rdt, kc.cons2, kc.rRD, kc.rRCPD, dt);
+        pin_expk(xk);
     }
 
     const int gcol = xcd_block() * kColBlock + threadIdx.x;
-    // CS2_AD_PARK: this lane's parking slots follow the level table (8-byte aligned)
+    // kADPark: this lane's parking slots follow the level table (8-byte aligned)
     T* const park_lds = s_scalm + (nz + 1) + threadIdx.x;
     (void)park_lds;
     if (gcol >= nx) return;  // no later workgroup barrier: whole lanes may retire
@@ -1033,13 +944,11 @@ ad_kernel(const ADArgs<T> A) {
         T rfl = T(0.0), sfl = T(0.0), covptot = T(0.0);
         T aph_k = ldg(F.in(NL_IN_APH), colb);
         O o = colb;
-        ADIn<T> xa = ad_load<T>(F, lsb, o, 0 >= keep_from);
-        if constexpr (CS2_AD_LANDED != 0) landed(aph_k);
+        LevelIn<T> xa = load_level<T>(F_in, lsb, o);
         for (int k = 0; k < nz; ++k) {
             F.fresh();
-            ADIn<T> xn = xa;
-            const bool keep_n = k + 1 >= keep_from;   // level k+1 (and the fluxes entering it) stay cacheable
-            if (k + 1 < nz) xn = ad_load<T>(F, lsb, o + lsb, keep_n);
+            LevelIn<T> xn = xa;
+            if (k + 1 < nz) xn = load_level<T>(F_in, lsb, o + lsb);
             ADTraj<T> r;
             ad_forward<T, FIX, EVAP>(e, kc, xk, xa, aph_k, k, s_eta[k], s_scalm[k], crh, dt, rfl, sfl, covptot, aph_s,
                                      r);
@@ -1051,11 +960,10 @@ ad_kernel(const ADArgs<T> A) {
             stg(F.out(NL_OUT_TND_T), o, r.tnd_t);
             stg(F.out(NL_OUT_TND_QL), o, r.tnd_ql);
             stg(F.out(NL_OUT_TND_QI), o, r.tnd_qi);
-            stg_sel(F.out(NL_OUT_FPLSL), o + lsb, r.rfln, keep_n);
-            stg_sel(F.out(NL_OUT_FPLSN), o + lsb, r.sfln, keep_n);
+            stg(F.out(NL_OUT_FPLSL), o + lsb, r.rfln);
+            stg(F.out(NL_OUT_FPLSN), o + lsb, r.sfln);
             stg(F.out(NL_OUT_FHPSL), o + lsb, -r.rfln * e.RLVTT);
             stg(F.out(NL_OUT_FHPSN), o + lsb, -r.sfln * e.RLSTT);
-            if constexpr ((CS2_AD_DRAIN & 1) != 0) drain_vmem();
             rfl = r.rfln;
             sfl = r.sfln;
             aph_k = xa.aph1;
@@ -1072,26 +980,25 @@ ad_kernel(const ADArgs<T> A) {
     {
         int k = nz - 1;
         O o = O(k) * lsb + colb;
-        ADIn<T> xa = ad_load<T>(F, lsb, o, k >= keep_from);
+        LevelIn<T> xa = load_level<T>(F_in, lsb, o);
         ADForce<T> fa = ad_load_force<T, EVAP>(F, e, lsb, o);
-        T aph_k = ldg_sel(F.in(NL_IN_APH), o, k >= keep_from);
-        T sfl = ldg_sel(TRAJ ? F.traj_n() : F.outc(NL_OUT_FPLSN), o, k >= keep_from);
-        T rfl = ldg_sel(TRAJ ? F.traj_l() : F.outc(NL_OUT_FPLSL), o, k >= keep_from);
+        T aph_k = ldg(F.in(NL_IN_APH), o);
+        T sfl = ldg(TRAJ ? F.traj_n() : F.outc(NL_OUT_FPLSN), o);
+        T rfl = ldg(TRAJ ? F.traj_l() : F.outc(NL_OUT_FPLSL), o);
         T cov = EVAP ? ldg(F.oadjc(NL_IN_MFD), o) : T(0.0);
         for (; k >= 0; --k) {
             F.fresh();
-            ADIn<T> xn = xa;
+            LevelIn<T> xn = xa;
             ADForce<T> fn = fa;
             T aph_n = aph_k, sfl_n = sfl, rfl_n = rfl, cov_n = cov;
             if (k > 0) {
                 const O om = o - lsb;
-                const bool keep_m = k - 1 >= keep_from;
-                xn = ad_load<T>(F, lsb, om, keep_m);
+                xn = load_level<T>(F_in, lsb, om);
                 xn.aph1 = aph_k;   // aph[k]: already here as this level's upper half level (the load above is dropped)
                 fn = ad_load_force<T, EVAP>(F, e, lsb, om);
-                aph_n = ldg_sel(F.in(NL_IN_APH), om, keep_m);
-                sfl_n = ldg_sel(TRAJ ? F.traj_n() : F.outc(NL_OUT_FPLSN), om, keep_m);
-                rfl_n = ldg_sel(TRAJ ? F.traj_l() : F.outc(NL_OUT_FPLSL), om, keep_m);
+                aph_n = ldg(F.in(NL_IN_APH), om);
+                sfl_n = ldg(TRAJ ? F.traj_n() : F.outc(NL_OUT_FPLSN), om);
+                rfl_n = ldg(TRAJ ? F.traj_l() : F.outc(NL_OUT_FPLSL), om);
                 if constexpr (EVAP) cov_n = ldg(F.oadjc(NL_IN_MFD), om);
             }
             ADTraj<T> r;
@@ -1114,7 +1021,6 @@ ad_kernel(const ADArgs<T> A) {
             stg(F.oadj(NL_IN_TND_CML_QI), o, dt * a.qi);
             stg(F.oadj(NL_IN_APH), o + lsb, a.aph1);
             stg(F.oadj(NL_IN_LU), o + lsb, a.lu1);
-            if constexpr ((CS2_AD_DRAIN & 2) != 0) drain_vmem();
             xa = xn;
             fa = fn;
             aph_k = aph_n;
@@ -1158,52 +1064,21 @@ int launch_ad(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* cons
     int dev = 0;
     if (smem > size_t(64) * 1024)
         if (const int rc = current_device(dev)) return rc;
-    const bool reg = p.LREGCL != 0;
-    const bool fix = p.AD_TRAJ_FIX != 0;
-    // cache-resident turnaround (CS2_AD_KEEP_MB): bottom levels whose 18 re-read words per column fit the budget
-    int keep_from = nz;
-    if (CS2_AD_KEEP_MB > 0) {
-        const uint64_t per_level = uint64_t(18) * uint64_t(ls) * sizeof(T);
-        const int levels = int((uint64_t(CS2_AD_KEEP_MB) << 20) / (per_level ? per_level : 1));
-        keep_from = levels >= nz ? 0 : nz - levels;
-    }
     if (traj && (evap || big)) return -2;   // the trajectory variant: driver switches, 32-bit offsets
-    const ADArgs<T> args = {e, kc, xk, nx, nz, ls, ci, ca, eta, co, coa, tdt, keep_from, traj_l, traj_n};
-#define CS2_AD_LAUNCH(R, F, E)                                                                                         \
-    do {                                                                                                               \
-        if (big) CS2_AD_LAUNCH_B(R, F, E, true); else CS2_AD_LAUNCH_B(R, F, E, false);                                 \
-    } while (0)
-#define CS2_AD_LAUNCH_B(R, F, E, B)                                                                                    \
-    do {                                                                                                               \
-        auto kern = ad_kernel<T, R, F, E, B>;                                                                             \
-        if (smem > size_t(64) * 1024) { /* > 64 KB of dynamic LDS needs the opt-in: once per instantiation and device */ \
-            static std::atomic<size_t> attr_set[kMaxDevices] = {};                                                     \
-            if (!lds_opt_in(kern, attr_set, dev, smem)) return -1;                                                     \
-        }                                                                                                              \
-        hipLaunchKernelGGL(kern, grid, block, smem, stream, args);         \
-    } while (0)
-#define CS2_AD_LAUNCH_T(R, F)                                                                                          \
-    do {                                                                                                               \
-        auto kern = ad_kernel<T, R, F, false, false, true>;                                                            \
-        if (smem > size_t(64) * 1024) {                                                                                \
-            static std::atomic<size_t> attr_set[kMaxDevices] = {};                                                     \
-            if (!lds_opt_in(kern, attr_set, dev, smem)) return -1;                                                     \
-        }                                                                                                              \
-        hipLaunchKernelGGL(kern, grid, block, smem, stream, args);                                                     \
-    } while (0)
-#define CS2_AD_LAUNCH_E(R, F) \
-    do {                      \
-        if (traj) CS2_AD_LAUNCH_T(R, F); \
-        else if (evap) CS2_AD_LAUNCH(R, F, true); else CS2_AD_LAUNCH(R, F, false); \
-    } while (0)
-    if (reg && !fix) CS2_AD_LAUNCH_E(true, false);
-    else if (!reg && !fix) CS2_AD_LAUNCH_E(false, false);
-    else if (reg && fix) CS2_AD_LAUNCH_E(true, true);
-    else CS2_AD_LAUNCH_E(false, true);
-#undef CS2_AD_LAUNCH_E
-#undef CS2_AD_LAUNCH_T
-#undef CS2_AD_LAUNCH
-#undef CS2_AD_LAUNCH_B
+    const ADArgs<T> args = {e, kc, xk, nx, nz, ls, ci, ca, eta, co, coa, tdt, traj_l, traj_n};
+    const int rc = with_flags(
+        [&](auto REG, auto FIX, auto TRAJ, auto EVAP, auto BIG) {
+            if constexpr (TRAJ && (EVAP || BIG)) {
+                return 0;   // refused above: no such instantiation
+            } else {
+                constexpr auto kern = ad_kernel<T, REG, FIX, EVAP, BIG, TRAJ>;
+                if (smem > size_t(64) * 1024 && !lds_opt_in<kern>(dev, smem)) return -1;
+                hipLaunchKernelGGL(kern, grid, block, smem, stream, args);
+                return 0;
+            }
+        },
+        p.LREGCL != 0, p.AD_TRAJ_FIX != 0, traj, evap, big);
+    if (rc) return rc;
     note_kernel(traj ? "cs2::ad_kernel<trajectory>" : big ? "cs2::ad_kernel<big>" : "cs2::ad_kernel");
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

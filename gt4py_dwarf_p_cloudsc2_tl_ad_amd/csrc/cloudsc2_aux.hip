@@ -12,18 +12,11 @@ namespace cs2 {
 constexpr int kAuxBlock = 256;
 // qsat stores: `keep` != 0 (launcher: the field fits the memory-side cache, qsat_fits_cache) -> default cache policy, the
 // consumer (cloudsc2_nl) follows immediately and finds the field there; otherwise non-temporal like every other store.
-// CS2_SAT_NT_STORE = 1 forces non-temporal stores (A/B switch).
-#ifndef CS2_SAT_NT_STORE
-#define CS2_SAT_NT_STORE 0
-#endif
-// CS2_SAT_KEEP_LOADS (r04): with `keep`, in_ap / in_t are LOADED with the default cache policy too.  cloudsc2_nl reads the same
+// Loads (r04): with `keep`, in_ap / in_t are LOADED with the default cache policy too.  cloudsc2_nl reads the same
 // two fields right after (run_nonlinear.py:117-118); allocated in the 256 MB memory-side cache by this kernel's loads, they
 // are served from there to the NL kernel's (non-temporal) LDS-DMAs: inside the step cloudsc2_nl 329.5 -> 314.4 us, the step
 // 368.9 -> 349.9 us on plain allocations (profiles/r04/ab_keep_step*.txt).  Making the NL kernel's OWN ap / t DMAs cacheable
 // instead does the opposite (+5 %): each DMA carries a second field (aph, supsat) that then sweeps the cache.
-#ifndef CS2_SAT_KEEP_LOADS
-#define CS2_SAT_KEEP_LOADS 1
-#endif
 
 // MODE 0: LPHYLIN; MODE 1: not LPHYLIN, KFLAG == 1 (f_foeewmcu); MODE 2: not LPHYLIN, KFLAG != 1 (f_foeewm)
 template <typename T, int MODE>
@@ -34,7 +27,7 @@ saturation_kernel(Ext<T> e, ExpK<T> xk, int nx, int64_t ls, const T* __restrict_
     if (col >= nx) return;
     const int64_t i = int64_t(blockIdx.y) * ls + col;
     const T r = saturation_point<T, MODE>(e, xk, ntload(t + i), ntload(ap + i));
-    if ((keep & 1) && !CS2_SAT_NT_STORE) qsat[i] = r;
+    if (keep & 1) qsat[i] = r;
     else ntstore(qsat + i, r);
 }
 
@@ -56,7 +49,7 @@ saturation_vec_kernel(Ext<T> e, ExpK<T> xk, int nxv, int nz, int64_t ls, const T
     for (int j = 0; j < kSatLPT; ++j) {
         const int k = k0 + j < nz ? k0 + j : nz - 1;
         const int64_t i = int64_t(k) * ls + int64_t(cv) * V;
-        if (CS2_SAT_KEEP_LOADS && (keep & 2)) {   // uniform: ap / t stay in the memory-side cache for the cloudsc2_nl that follows
+        if (keep & 2) {   // uniform: ap / t stay in the memory-side cache for the cloudsc2_nl that follows
             va[j] = *reinterpret_cast<const vec_t*>(ap + i);
             vt[j] = *reinterpret_cast<const vec_t*>(t + i);
         } else {
@@ -71,7 +64,7 @@ saturation_vec_kernel(Ext<T> e, ExpK<T> xk, int nxv, int nz, int64_t ls, const T
 #pragma unroll
         for (int v = 0; v < V; ++v) r[v] = saturation_point<T, MODE>(e, xk, vt[j][v], va[j][v]);
         vec_t* dst = reinterpret_cast<vec_t*>(qsat + int64_t(k0 + j) * ls + int64_t(cv) * V);
-        if ((keep & 1) && !CS2_SAT_NT_STORE) *dst = r;
+        if (keep & 1) *dst = r;
         else __builtin_nontemporal_store(r, dst);
     }
 }

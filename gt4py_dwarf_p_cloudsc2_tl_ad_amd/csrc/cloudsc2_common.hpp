@@ -25,10 +25,7 @@ constexpr int kWave = 64;  // CDNA wavefront
 // them double up on a SIMD while other SIMDs stay empty (profiles/census_placement.hip), which cost
 // cloudsc2_nl +65 us in the driver loop; the 4 waves of a 256-thread workgroup always go to the 4
 // different SIMDs of their CU.
-#ifndef CS2_COL_BLOCK
-#define CS2_COL_BLOCK 256
-#endif
-constexpr int kColBlock = CS2_COL_BLOCK;
+constexpr int kColBlock = 256;
 
 // XCD-aware workgroup -> column-block mapping.  Workgroups are dealt round-robin over the 8 XCDs (blocks b and b + 8
 // share one, MI355X_MICROARCH.md "Workgroup dispatch"); with the identity mapping every XCD's L2 and fabric port sees
@@ -36,12 +33,9 @@ constexpr int kColBlock = CS2_COL_BLOCK;
 // columns.  Measured on cloudsc2_nl (profiles/r02/ab_xcd_remap.txt, one process): neutral at 65 536 fp64 columns (one
 // workgroup per CU, everything in lockstep), -1.4 .. -2.2 % at 262 144 fp64 / 524 288 fp32 columns.  Grids that are not
 // a multiple of 8 keep the identity mapping (every block index must stay below gridDim.x).
-#ifndef CS2_XCD_REMAP
-#define CS2_XCD_REMAP 1
-#endif
 __device__ __forceinline__ int xcd_block() {
     const int b = blockIdx.x, n = gridDim.x;
-    if (CS2_XCD_REMAP && (n & 7) == 0) return (b & 7) * (n >> 3) + (b >> 3);
+    if ((n & 7) == 0) return (b & 7) * (n >> 3) + (b >> 3);
     return b;
 }
 
@@ -214,6 +208,15 @@ template <typename T>
 __device__ __forceinline__ void pin_vgpr(T& x) {
     asm volatile("" : "+v"(x));
 }
+// One pin per value, in argument order: register assignment follows that order, so each kernel keeps its own list.
+template <typename... Ts>
+__device__ __forceinline__ void pin_vgprs(Ts&... xs) {
+    (pin_vgpr(xs), ...);
+}
+template <typename T>
+__device__ __forceinline__ void pin_expk(ExpK<T>& xk) {
+    pin_vgprs(xk.l2e, xk.ln2h, xk.ln2l, xk.c12, xk.c11, xk.c10, xk.c9, xk.c8, xk.c7, xk.c6, xk.c5, xk.c4, xk.c3);
+}
 
 // "This loaded word has landed": the value must be in its register here, so hipcc waits for its load HERE.  Used on
 // words loaded before a level loop and first read inside it: a load still pending at the loop header makes hipcc's
@@ -226,40 +229,26 @@ __device__ __forceinline__ void landed(T& x) {
 
 // "Every memory operation of this wave has completed": the level's stores are drained before the next level's loads are
 // requested.  Costs the stores' completion latency once per level and buys HBM a cleaner read / write phase structure;
-// which one wins is measured per kernel (CS2_*_DRAIN switches, docs/TUNING_LOG.md 3.9).
-template <int LEFT = 0>   // LEFT: how many of the youngest operations may stay in flight (0 = a full drain)
+// the register-path NL and TL kernels measured faster with it, cloudsc2_ad without (docs/TUNING_LOG.md 3.9).
 __device__ __forceinline__ void drain_vmem() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(LEFT) : "memory");
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
 }
 
 // Field access by 32-bit BYTE offset from a uniform base pointer: hipcc then emits the
 // `global_load_dwordx2 v, v_off, s[base:base+1]` form (no per-access 64-bit VALU address arithmetic).
 // The launchers guarantee (nz+1) * lev_stride * sizeof(T) < 2^32.
-// CS2_NT (bit 0: loads, bit 1: stores) selects non-temporal accesses: every field element is touched
-// exactly once per launch, and streaming reads/writes that do not linger in L2 measured faster on the
-// mixed 16-read / 10-write stream pattern (profiles/microbench_stream.hip; A/B in profiles/ab_nl.py).
-#ifndef CS2_NT
-#define CS2_NT 3
-#endif
-// The offset type `O` is uint32_t in every kernel but the BIG instantiations (fields of 4 GiB and more, see kBigOffsets):
+// Loads and stores are non-temporal: every field element is touched exactly once per launch, and streaming reads/writes
+// that do not linger in L2 measured faster on the mixed 16-read / 10-write stream pattern (profiles/microbench_stream.hip;
+// A/B in profiles/ab_nl.py).
+// The offset type `O` is uint32_t in every kernel but the BIG instantiations (fields of 4 GiB and more, see offset_t):
 // there it is uint64_t and hipcc emits the `v[a:a+1], off` form after a 64-bit VALU add per access.
 template <typename T, typename O>
 __device__ __forceinline__ T ldg(const T* base, O boff) {
-    const T* a = reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + boff);
-#if CS2_NT & 1
-    return __builtin_nontemporal_load(a);
-#else
-    return *a;
-#endif
+    return __builtin_nontemporal_load(reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + boff));
 }
 template <typename T, typename O>
 __device__ __forceinline__ void stg(T* base, O boff, T v) {
-    T* a = reinterpret_cast<T*>(reinterpret_cast<char*>(base) + boff);
-#if CS2_NT & 2
-    __builtin_nontemporal_store(v, a);
-#else
-    *a = v;
-#endif
+    __builtin_nontemporal_store(v, reinterpret_cast<T*>(reinterpret_cast<char*>(base) + boff));
 }
 // Default-policy load for the ONE field with a producer just upstream: `in_qsat` is written by `saturation` right before
 // cloudsc2_nl reads it (run_nonlinear.py:117-118) and, at 72 MB for 65 536 columns, is still in the 256 MB
@@ -268,22 +257,14 @@ template <typename T, typename O>
 __device__ __forceinline__ T ldg_keep(const T* base, O boff) {
     return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + boff);
 }
-// streaming access for the pointwise helper kernels (64-bit indexing, same CS2_NT policy)
+// streaming access for the pointwise helper kernels (64-bit indexing, same non-temporal policy)
 template <typename T>
 __device__ __forceinline__ T ntload(const T* a) {
-#if CS2_NT & 1
     return __builtin_nontemporal_load(a);
-#else
-    return *a;
-#endif
 }
 template <typename T>
 __device__ __forceinline__ void ntstore(T* a, T v) {
-#if CS2_NT & 2
     __builtin_nontemporal_store(v, a);
-#else
-    *a = v;
-#endif
 }
 // Producer-consumer residency of `qsat` (saturation -> cloudsc2_nl, run_nonlinear.py:117-118): default cache policy
 // on that one store / load pays when the field fits the 256 MB memory-side cache beside the streams passing through
@@ -307,9 +288,120 @@ using offset_t = typename std::conditional<BIG, uint64_t, uint32_t>::type;
 
 // ---- field pointer bundles (kernel arguments, by value) --------------------------------------
 template <typename T, int N>
-struct CPtrs { const T* p[N]; };
+struct CPtrs {
+    const T* p[N];
+    __device__ __forceinline__ const T* operator()(int i) const { return p[i]; }   // a field-pointer source (load_level)
+};
 template <typename T, int N>
 struct MPtrs { T* p[N]; };
+
+// ---- one level of the 16 NL input fields (the level sweeps of cloudsc2_nl / _tl / _ad) -------------------------------
+template <typename T>
+struct LevelIn {
+    T ap, aph1, lu1, lude, mfd, mfu, q, qi, ql, qsat, supsat, t, tq, tqi, tql, tt;
+};
+
+// `ptr(i)`: base pointer of input field i (a CPtrs bundle, or a read from the kernarg segment); `o` = byte offset of
+// (level k, this lane's column); `lsb` = level stride in bytes (`O`: uint32_t, or uint64_t in the BIG instantiations).
+// aph and lu are read one half level below (aph[k+1], lu[k+1]).  skipq: in_qsat is not read (the fused-saturation NL
+// variant computes it); keepq: in_qsat was just written by `saturation` and fits the memory-side cache (launch_nl), so its
+// load uses the default cache policy and hits it.
+template <typename T, typename O, typename P>
+__device__ __forceinline__ LevelIn<T> load_level(const P& ptr, O lsb, O o, bool skipq = false, bool keepq = false) {
+    LevelIn<T> x;
+    x.ap = ldg(ptr(NL_IN_AP), o);
+    x.aph1 = ldg(ptr(NL_IN_APH), o + lsb);
+    x.lu1 = ldg(ptr(NL_IN_LU), o + lsb);
+    x.lude = ldg(ptr(NL_IN_LUDE), o);
+    x.mfd = ldg(ptr(NL_IN_MFD), o);
+    x.mfu = ldg(ptr(NL_IN_MFU), o);
+    x.q = ldg(ptr(NL_IN_Q), o);
+    x.qi = ldg(ptr(NL_IN_QI), o);
+    x.ql = ldg(ptr(NL_IN_QL), o);
+    x.qsat = skipq ? T(0.0) : (keepq ? ldg_keep(ptr(NL_IN_QSAT), o) : ldg(ptr(NL_IN_QSAT), o));
+    x.supsat = ldg(ptr(NL_IN_SUPSAT), o);
+    x.t = ldg(ptr(NL_IN_T), o);
+    x.tq = ldg(ptr(NL_IN_TND_CML_Q), o);
+    x.tqi = ldg(ptr(NL_IN_TND_CML_QI), o);
+    x.tql = ldg(ptr(NL_IN_TND_CML_QL), o);
+    x.tt = ldg(ptr(NL_IN_TND_CML_T), o);
+    return x;
+}
+
+// state_increment (common/_stencils/state_increment.py:61-80) applied on the fly: x_i = f * x, supsat_i = 0 with
+// IGNORE_SUPSAT - the very products the stand-alone increment kernel stores (cloudsc2_aux.hip), so the fused variants feed
+// the level function exactly the words the separate calls would load (rounded_product: never half of an fma).
+template <typename T>
+__device__ __forceinline__ LevelIn<T> increment(const LevelIn<T>& x, T f, bool zero_supsat) {
+    LevelIn<T> y;
+#define CS2_P(m) y.m = rounded_product<T>(f, x.m)
+    CS2_P(ap); CS2_P(aph1); CS2_P(lu1); CS2_P(lude); CS2_P(mfd); CS2_P(mfu); CS2_P(q); CS2_P(qi); CS2_P(ql); CS2_P(qsat);
+    CS2_P(t); CS2_P(tq); CS2_P(tqi); CS2_P(tql); CS2_P(tt);
+#undef CS2_P
+    y.supsat = zero_supsat ? T(0.0) : rounded_product<T>(f, x.supsat);
+    return y;
+}
+
+// ---- LDS-DMA ring (nl_ring_kernel, tl_ring_kernel) --------------------------------------------------------------------
+typedef __attribute__((address_space(3))) void* lds_void_ptr;
+typedef const __attribute__((address_space(1))) void* glb_void_ptr;
+constexpr int kDmaNT = 2;   // cache-policy operand of the ring's input DMAs: non-temporal (every byte is read once)
+
+// Slot of a ring whose level holds NF input fields (+ XDMA more DMA images of 16 B x 64 lanes).  One DMA instruction moves
+// 16 B per lane = NPL columns, so it carries NPL fields of the wave's 64 columns; field f of a slot starts at f * 64 * sizeof(T).
+template <typename T, int NF, int XDMA = 0>
+struct RingGeom {
+    static constexpr int NPL = 16 / int(sizeof(T));       // columns per lane per DMA = fields per DMA
+    static constexpr int NI = NF / NPL;                   // DMA instructions per level
+    static constexpr int DATA = NF * 64 * int(sizeof(T));  // the NF input fields of one level
+    static constexpr int SLOT = DATA + XDMA * 1024;
+};
+// LDS of a ring launch: [eta | scalm table][pad to 1 KB][wave 0: depth slots][wave 1: depth slots] ...
+template <typename G, typename T>
+inline size_t ring_lds_bytes(int nz, int depth) {
+    return ((2 * size_t(nz + 1) * sizeof(T) + 1023) & ~size_t(1023)) + size_t(kColBlock / 64) * depth * G::SLOT;
+}
+
+// The ring reads: this lane's column of 16 consecutive fields of a slot at LDS byte address %[a] into operands %0 .. %15.
+// Only the text is shared - every ring read stays ONE asm statement with its own `s_waitcnt vmcnt(N)` (nl_ring_kernel).
+#define CS2_DS_READ16_B64            \
+    "ds_read_b64 %0, %[a]\n\t"                \
+    "ds_read_b64 %1, %[a] offset:512\n\t"     \
+    "ds_read_b64 %2, %[a] offset:1024\n\t"    \
+    "ds_read_b64 %3, %[a] offset:1536\n\t"    \
+    "ds_read_b64 %4, %[a] offset:2048\n\t"    \
+    "ds_read_b64 %5, %[a] offset:2560\n\t"    \
+    "ds_read_b64 %6, %[a] offset:3072\n\t"    \
+    "ds_read_b64 %7, %[a] offset:3584\n\t"    \
+    "ds_read_b64 %8, %[a] offset:4096\n\t"    \
+    "ds_read_b64 %9, %[a] offset:4608\n\t"    \
+    "ds_read_b64 %10, %[a] offset:5120\n\t"   \
+    "ds_read_b64 %11, %[a] offset:5632\n\t"   \
+    "ds_read_b64 %12, %[a] offset:6144\n\t"   \
+    "ds_read_b64 %13, %[a] offset:6656\n\t"   \
+    "ds_read_b64 %14, %[a] offset:7168\n\t"   \
+    "ds_read_b64 %15, %[a] offset:7680\n\t"
+#define CS2_DS_READ16_B32            \
+    "ds_read_b32 %0, %[a]\n\t"                \
+    "ds_read_b32 %1, %[a] offset:256\n\t"     \
+    "ds_read_b32 %2, %[a] offset:512\n\t"     \
+    "ds_read_b32 %3, %[a] offset:768\n\t"     \
+    "ds_read_b32 %4, %[a] offset:1024\n\t"    \
+    "ds_read_b32 %5, %[a] offset:1280\n\t"    \
+    "ds_read_b32 %6, %[a] offset:1536\n\t"    \
+    "ds_read_b32 %7, %[a] offset:1792\n\t"    \
+    "ds_read_b32 %8, %[a] offset:2048\n\t"    \
+    "ds_read_b32 %9, %[a] offset:2304\n\t"    \
+    "ds_read_b32 %10, %[a] offset:2560\n\t"   \
+    "ds_read_b32 %11, %[a] offset:2816\n\t"   \
+    "ds_read_b32 %12, %[a] offset:3072\n\t"   \
+    "ds_read_b32 %13, %[a] offset:3328\n\t"   \
+    "ds_read_b32 %14, %[a] offset:3584\n\t"   \
+    "ds_read_b32 %15, %[a] offset:3840\n\t"
+// ... and their output operands %0 .. %15
+#define CS2_LEVEL_OUTS(x)                                                                                               \
+    "=&v"(x.ap), "=&v"(x.aph1), "=&v"(x.lu1), "=&v"(x.lude), "=&v"(x.mfd), "=&v"(x.mfu), "=&v"(x.q), "=&v"(x.qi),         \
+        "=&v"(x.ql), "=&v"(x.qsat), "=&v"(x.supsat), "=&v"(x.t), "=&v"(x.tq), "=&v"(x.tqi), "=&v"(x.tql), "=&v"(x.tt)
 
 // Field pointers fetched from the KERNARG SEGMENT at their point of use (cloudsc2_ad).  The AD kernel takes 52 field
 // pointers: 104 SGPRs, more than a wave has (102), before the first constant.  Passed as ordinary by-value arguments they
@@ -355,17 +447,38 @@ inline int device_cus(int dev) {
     }
     return n;
 }
-// > 64 KB of dynamic LDS needs an opt-in per kernel function: done once per instantiation (`done` is that
-// instantiation's own static array), device and size; sizes only grow.
-template <typename Kern>
-inline bool lds_opt_in(Kern kern, std::atomic<size_t>* done, int dev, size_t bytes) {
+// > 64 KB of dynamic LDS needs an opt-in per kernel function: done once per kernel K (one static array per
+// instantiation), device and size; sizes only grow.
+template <auto K>
+inline bool lds_opt_in(int dev, size_t bytes) {
+    static std::atomic<size_t> done[kMaxDevices] = {};
     if (done[dev].load(std::memory_order_relaxed) >= bytes) return true;
-    if (hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize,
-                            int(bytes)) != hipSuccess)
+    if (hipFuncSetAttribute(reinterpret_cast<const void*>(K), hipFuncAttributeMaxDynamicSharedMemorySize, int(bytes)) !=
+        hipSuccess)
         return false;
     size_t cur = done[dev].load(std::memory_order_relaxed);
     while (cur < bytes && !done[dev].compare_exchange_weak(cur, bytes, std::memory_order_relaxed)) {}
     return true;
+}
+
+// Host-side launch dispatch: runtime bools become compile-time flags.  with_flags(f, b0, b1, ...) calls
+// f(std::bool_constant<b0>{}, std::bool_constant<b1>{}, ...), so the generic lambda `f` is instantiated for exactly the
+// combinations of the flags passed here, and returns what f returns.  with_int<V...>(v, f) does the same for one int among
+// the listed values (std::integral_constant<int, V>; -2 when v is none of them).
+template <typename F>
+inline int with_flags(F&& f) {
+    return f();
+}
+template <typename F, typename... B>
+inline int with_flags(F&& f, bool b, B... bs) {
+    if (b) return with_flags([&](auto... c) { return f(std::true_type{}, c...); }, bs...);
+    return with_flags([&](auto... c) { return f(std::false_type{}, c...); }, bs...);
+}
+template <int... Vs, typename F>
+inline int with_int(int v, F&& f) {
+    int rc = -2;
+    (void)((v == Vs && ((rc = f(std::integral_constant<int, Vs>{})), true)) || ...);
+    return rc;
 }
 
 // Per-level LDS table: eta[k] and scalm[k] = ZSCAL * max(eta[k]-0.2, ZEPS1)^0.2
@@ -492,33 +605,6 @@ __device__ __forceinline__ T crh2_at(const CrhCol<T>& c, T eta) {
     if (eta < c.bound1) return rh3 + (c.rh2 - rh3) * (eta - c.trpaus) / T(0.3);
     if (eta < c.bound2) return c.rh2;
     return rh1 + (c.rh2 - rh1) * rsqrt_<T>((T(1.0) - eta) / c.deta1);
-}
-
-// One iteration of the saturation adjustment (nonlinear/_stencils/cuadjtqs.py:24-37).
-template <typename T>
-__device__ __forceinline__ void cuadjtqs_nl_0(const Ext<T>& e, T ap, T& t, T& q, T z3es, T z4es,
-                                              T z5alcp, T zaldcp) {
-    T foeew = e.R2ES * rexp<T>(z3es * (t - e.RTT) / (t - z4es));
-    T qsat = rmin<T>(foeew / ap, e.ZQMAX);
-    T cor = T(1.0) / (T(1.0) - e.RETV * qsat);
-    qsat *= cor;
-    T z2s = z5alcp / sq(t - z4es);
-    T cond = (q - qsat) / (T(1.0) + qsat * cor * z2s);
-    t += zaldcp * cond;
-    q -= cond;
-}
-
-// nonlinear/_stencils/cuadjtqs.py:40-68 (ICALL == 0, the only branch the reference implements).
-template <typename T>
-__device__ __forceinline__ void cuadjtqs_nl(const Ext<T>& e, T ap, T& t, T& q) {
-    T z3es, z4es, z5alcp, zaldcp;
-    if (t > e.RTT) {
-        z3es = e.R3LES; z4es = e.R4LES; z5alcp = e.R5ALVCP; zaldcp = e.RALVDCP;
-    } else {
-        z3es = e.R3IES; z4es = e.R4IES; z5alcp = e.R5ALSCP; zaldcp = e.RALSDCP;
-    }
-    cuadjtqs_nl_0(e, ap, t, q, z3es, z4es, z5alcp, zaldcp);
-    cuadjtqs_nl_0(e, ap, t, q, z3es, z4es, z5alcp, zaldcp);
 }
 
 }  // namespace cs2

@@ -19,75 +19,16 @@
 // 1.9*RCLCRIT / 1e-4 thresholds :250-266), LIN = LPHYLIN or LDRAIN1D (:141-155).
 #include "cloudsc2_common.hpp"
 
-// Tuning switches (A/B-tested with profiles/ab_nl.py; the defaults are the fastest measured set).
-#ifndef CS2_NL_FEXP
-#define CS2_NL_FEXP 1   // 1: cs2::fexp (coefficients as kernel arguments), 0: ocml exp
-#endif
-#ifndef CS2_NL_PINK
-#define CS2_NL_PINK 1   // pin the named physical constants in VGPRs (fp64 only)
-#endif
 #ifndef CS2_NL_DIAG
 #define CS2_NL_DIAG 0   // diagnostics only (wrong results): 1 = memory traffic without the physics,
 #endif                  // 2 = physics without HBM traffic (inputs from 2 cached levels, no stores)
-#ifndef CS2_NL_PINX
-#define CS2_NL_PINX 1   // pin the exp coefficients in VGPRs (fp64 only)
-#endif
-
-#ifndef CS2_NL_DRAIN
-#define CS2_NL_DRAIN 1   // register-path kernel: drain the level's stores before the next level is requested (see drain_vmem)
-#endif
 
 namespace cs2 {
 
-template <typename T>
-__device__ __forceinline__ T nl_exp(const ExpK<T>& xk, T x) {
-#if CS2_NL_FEXP
-    return fexp<T>(xk, x);
-#else
-    return rexp<T>(x);
-#endif
-}
-
-template <typename T>
-struct NLIn {
-    T ap, aph1, lu1, lude, mfd, mfu, q, qi, ql, qsat, supsat, t, tq, tqi, tql, tt;
-};
-
-// `o` = byte offset of (level k, this lane's column); `lsb` = level stride in bytes (`O`: uint32_t, or uint64_t in the BIG
-// instantiation).  SKIPQ: in_qsat is not read (the fused-saturation variant computes it).
-template <typename T, typename O>
-__device__ __forceinline__ NLIn<T> nl_load_impl(const CPtrs<T, NL_NUM_IN>& in, O lsb, O o, bool skipq,
-                                                 bool keepq = false) {
-    NLIn<T> x;
-    x.ap = ldg(in.p[NL_IN_AP], o);
-    x.aph1 = ldg(in.p[NL_IN_APH], o + lsb);
-    x.lu1 = ldg(in.p[NL_IN_LU], o + lsb);
-    x.lude = ldg(in.p[NL_IN_LUDE], o);
-    x.mfd = ldg(in.p[NL_IN_MFD], o);
-    x.mfu = ldg(in.p[NL_IN_MFU], o);
-    x.q = ldg(in.p[NL_IN_Q], o);
-    x.qi = ldg(in.p[NL_IN_QI], o);
-    x.ql = ldg(in.p[NL_IN_QL], o);
-    // in_qsat was just written by `saturation`: when the field fits the memory-side cache (keepq, launcher) let the load hit it
-    x.qsat = skipq ? T(0.0) : (keepq ? ldg_keep(in.p[NL_IN_QSAT], o) : ldg(in.p[NL_IN_QSAT], o));
-    x.supsat = ldg(in.p[NL_IN_SUPSAT], o);
-    x.t = ldg(in.p[NL_IN_T], o);
-    x.tq = ldg(in.p[NL_IN_TND_CML_Q], o);
-    x.tqi = ldg(in.p[NL_IN_TND_CML_QI], o);
-    x.tql = ldg(in.p[NL_IN_TND_CML_QL], o);
-    x.tt = ldg(in.p[NL_IN_TND_CML_T], o);
-    return x;
-}
-
-template <typename T, bool SKIPQ, typename O>
-__device__ __forceinline__ NLIn<T> nl_load(const CPtrs<T, NL_NUM_IN>& in, O lsb, O o, bool keepq = false) {
-    return nl_load_impl<T, O>(in, lsb, o, SKIPQ, keepq);
-}
-
 // perturbed_state (common/_stencils/perturbed_state.py:75-91) applied on the fly: x + f * x_i.
 template <typename T>
-__device__ __forceinline__ NLIn<T> nl_perturb(const NLIn<T>& a, const NLIn<T>& b, T f) {
-    NLIn<T> x;
+__device__ __forceinline__ LevelIn<T> nl_perturb(const LevelIn<T>& a, const LevelIn<T>& b, T f) {
+    LevelIn<T> x;
     x.ap = a.ap + f * b.ap; x.aph1 = a.aph1 + f * b.aph1; x.lu1 = a.lu1 + f * b.lu1; x.lude = a.lude + f * b.lude;
     x.mfd = a.mfd + f * b.mfd; x.mfu = a.mfu + f * b.mfu; x.q = a.q + f * b.q; x.qi = a.qi + f * b.qi;
     x.ql = a.ql + f * b.ql; x.qsat = a.qsat + f * b.qsat; x.supsat = a.supsat + f * b.supsat; x.t = a.t + f * b.t;
@@ -119,7 +60,7 @@ template <typename T>
 __device__ __forceinline__ void nl_cuadj_iter(const Ext<T>& e, const ExpK<T>& xk, T rap, T& t, T& q, T z3es, T z4es, T z5alcp,
                                               T zaldcp) {
     const T r = frcp<T>(t - z4es);
-    const T foeew = e.R2ES * nl_exp<T>(xk, z3es * (t - e.RTT) * r);
+    const T foeew = e.R2ES * fexp<T>(xk, z3es * (t - e.RTT) * r);
     T qsat = rmin<T>(foeew * rap, e.ZQMAX);
     const T cor = frcp<T>(T(1.0) - e.RETV * qsat);
     qsat *= cor;
@@ -133,7 +74,7 @@ __device__ __forceinline__ void nl_cuadj_iter(const Ext<T>& e, const ExpK<T>& xk
 // statements; divisions are x * frcp(y) with the reciprocals shared (1/zz, 1/(t-R4LES), 1/(t-R4IES),
 // 1/ap, 1/t, 1/dp, 1/clc), 0.545 (tanh(u) + 1) is evaluated as 1.09 / (1 + exp(-2u)).
 template <typename T, bool EVAP, bool LIN>
-__device__ __forceinline__ NLOut<T> nl_level(const Ext<T>& e, const NLK<T>& kc, const ExpK<T>& xk, const NLIn<T>& x, T eta_k, T scalm,
+__device__ __forceinline__ NLOut<T> nl_level(const Ext<T>& e, const NLK<T>& kc, const ExpK<T>& xk, const LevelIn<T>& x, T eta_k, T scalm,
                                              const CrhCol<T>& crh, T dt, T aph_s, NLCarry<T>& c) {
     NLOut<T> o;
 #if CS2_NL_DIAG == 1
@@ -165,7 +106,7 @@ __device__ __forceinline__ NLOut<T> nl_level(const Ext<T>& e, const NLK<T>& kc, 
     if constexpr (LIN) {
         T z3es, r4;
         if (t < e.RTT) {
-            fwat = T(1.09) * frcp<T>(T(1.0) + nl_exp<T>(xk, -kc.fw2 * (t - e.RLPTRC)));
+            fwat = T(1.09) * frcp<T>(T(1.0) + fexp<T>(xk, -kc.fw2 * (t - e.RLPTRC)));
             z3es = e.R3IES;
             r4 = ri;
         } else {
@@ -173,14 +114,14 @@ __device__ __forceinline__ NLOut<T> nl_level(const Ext<T>& e, const NLK<T>& kc, 
             z3es = e.R3LES;
             r4 = rl;
         }
-        foeew = e.R2ES * nl_exp<T>(xk, z3es * (t - e.RTT) * r4);
+        foeew = e.R2ES * fexp<T>(xk, z3es * (t - e.RTT) * r4);
         const T esdp = foeew * rap;
         cor = (esdp > e.ZQMAX) ? kc.cormax : frcp<T>(T(1.0) - e.RETV * esdp);
     } else {
         // f_foealfa / f_foeewm, common/_stencils/fcttre.py:22-46
         fwat = rmin<T>(T(1.0), sq((rmax<T>(e.RTICE, rmin<T>(e.RTWAT, t)) - e.RTICE) * e.RTWAT_RTICE_R));
-        foeew = e.R2ES * (fwat * nl_exp<T>(xk, e.R3LES * (t - e.RTT) * rl) +
-                          (T(1.0) - fwat) * nl_exp<T>(xk, e.R3IES * (t - e.RTT) * ri));
+        foeew = e.R2ES * (fwat * fexp<T>(xk, e.R3LES * (t - e.RTT) * rl) +
+                          (T(1.0) - fwat) * fexp<T>(xk, e.R3IES * (t - e.RTT) * ri));
         cor = frcp<T>(T(1.0) - e.RETV * (foeew * rap));
     }
     const T facw = e.R5LES * rl * rl;
@@ -211,7 +152,7 @@ __device__ __forceinline__ NLOut<T> nl_level(const Ext<T>& e, const NLK<T>& kc, 
     const T gdp = e.RG * rdp;
     const T lude = dt * x.lude * gdp;
     if (lude >= e.RLMIN && x.lu1 >= e.ZEPS2) {
-        clc += (T(1.0) - clc) * (T(1.0) - nl_exp<T>(xk, -lude * frcp<T>(x.lu1)));
+        clc += (T(1.0) - clc) * (T(1.0) - fexp<T>(xk, -lude * frcp<T>(x.lu1)));
         qc += lude;
     }
     // :218-224 compensating subsidence
@@ -248,12 +189,12 @@ __device__ __forceinline__ NLOut<T> nl_level(const Ext<T>& e, const NLK<T>& kc, 
     if (clc > e.ZEPS2) {
         const T rclc = frcp<T>(clc);
         const T cldl = qlwc * rclc;
-        const T dl = kc.ckcodtl * (T(1.0) - nl_exp<T>(xk, -sq(cldl * kc.rlcrit)));
-        prr = qlwc - clc * cldl * nl_exp<T>(xk, -dl);
+        const T dl = kc.ckcodtl * (T(1.0) - fexp<T>(xk, -sq(cldl * kc.rlcrit)));
+        prr = qlwc - clc * cldl * fexp<T>(xk, -dl);
         qlwc -= prr;
         const T cldi = qiwc * rclc;
-        const T di = kc.ckcodti * nl_exp<T>(xk, T(0.025) * (t - e.RTT)) * (T(1.0) - nl_exp<T>(xk, -sq(cldi * kc.ricrit)));
-        prs = qiwc - clc * cldi * nl_exp<T>(xk, -di);
+        const T di = kc.ckcodti * fexp<T>(xk, T(0.025) * (t - e.RTT)) * (T(1.0) - fexp<T>(xk, -sq(cldi * kc.ricrit)));
+        prs = qiwc - clc * cldi * fexp<T>(xk, -di);
         qiwc -= prs;
     }
     // :275-285 new precipitation
@@ -364,9 +305,16 @@ __device__ __forceinline__ T enthalpy_diff(T flux, T latent, T ref) {
     return h - ref;
 }
 
-#ifndef CS2_F32_WAVES
-#define CS2_F32_WAVES 1   // minimum waves per SIMD requested for the fp32 instantiations (register cap)
-#endif
+// The constants of the NL level loop, pinned in VGPRs (see pin_vgpr; fp64 kernels), then the exp coefficients.
+template <typename T>
+__device__ __forceinline__ void pin_nl_constants(Ext<T>& e, NLK<T>& kc, ExpK<T>& xk, T& dt) {
+    pin_vgprs(e.RCPD, e.RLSTT, e.RLVTT, e.R4LES, e.R4IES, e.RTT, e.RLPTRC, e.R3IES, e.R3LES, e.R2ES, e.ZQMAX, e.RETV, e.R5LES,
+              e.R5IES, e.RTICE, e.RG, e.RD, e.R5ALVCP, e.RALVDCP, e.R5ALSCP, e.RALSDCP, kc.rdt, kc.cons2, kc.rRD, kc.rRCPD,
+              kc.cormax, kc.fw2, dt);
+    pin_expk(xk);
+}
+
+constexpr int kF32Waves = 1;   // minimum waves per SIMD requested for the fp32 instantiations (register cap)
 // FUSE selects the fused variants (build extensions; results identical to the
 // separate stencil calls):
 //   1  `saturation` fused in: in_qsat is not read but computed from (in_ap, in_t) exactly as
@@ -381,7 +329,7 @@ __device__ __forceinline__ T enthalpy_diff(T flux, T latent, T ref) {
 //      workgroup, summed by the caller: deterministic, no atomics.
 // BIG: 64-bit byte offsets (fields of 4 GiB and more, see offset_t); instantiated for FUSE = 0 only.
 template <typename T, bool EVAP, bool LIN, bool PINK, int FUSE, bool BIG = false>
-__global__ void __launch_bounds__(kColBlock, (sizeof(T) == 4 ? CS2_F32_WAVES : 1))
+__global__ void __launch_bounds__(kColBlock, (sizeof(T) == 4 ? kF32Waves : 1))
 nl_kernel(Ext<T> e, NLK<T> kc, ExpK<T> xk, int nx, int nz, int64_t ls, CPtrs<T, NL_NUM_IN> in, const T* __restrict__ eta,
           MPtrs<T, NL_NUM_OUT> out, T dt, CPtrs<T, NL_NUM_IN> in_i, T pf, T* __restrict__ qsat_out,
           double* __restrict__ partials, int keepq) {
@@ -390,20 +338,7 @@ nl_kernel(Ext<T> e, NLK<T> kc, ExpK<T> xk, int nx, int nz, int64_t ls, CPtrs<T, 
     T* s_scalm = s_eta + (nz + 1);
     int klo, khi;
     build_level_table<T>(eta, nz, e, s_eta, s_scalm, klo, khi);
-    if constexpr (PINK && CS2_NL_PINK) {
-        // constants of the level loop -> VGPRs (see pin_vgpr)
-        pin_vgpr(e.RCPD); pin_vgpr(e.RLSTT); pin_vgpr(e.RLVTT); pin_vgpr(e.R4LES); pin_vgpr(e.R4IES);
-        pin_vgpr(e.RTT); pin_vgpr(e.RLPTRC); pin_vgpr(e.R3IES); pin_vgpr(e.R3LES); pin_vgpr(e.R2ES);
-        pin_vgpr(e.ZQMAX); pin_vgpr(e.RETV); pin_vgpr(e.R5LES); pin_vgpr(e.R5IES); pin_vgpr(e.RTICE);
-        pin_vgpr(e.RG); pin_vgpr(e.RD); pin_vgpr(e.R5ALVCP); pin_vgpr(e.RALVDCP); pin_vgpr(e.R5ALSCP);
-        pin_vgpr(e.RALSDCP); pin_vgpr(kc.rdt); pin_vgpr(kc.cons2); pin_vgpr(kc.rRD); pin_vgpr(kc.rRCPD);
-        pin_vgpr(kc.cormax); pin_vgpr(kc.fw2); pin_vgpr(dt);
-    }
-    if constexpr (PINK && CS2_NL_PINX && CS2_NL_FEXP) {
-        pin_vgpr(xk.l2e); pin_vgpr(xk.ln2h); pin_vgpr(xk.ln2l); pin_vgpr(xk.c12); pin_vgpr(xk.c11);
-        pin_vgpr(xk.c10); pin_vgpr(xk.c9); pin_vgpr(xk.c8); pin_vgpr(xk.c7); pin_vgpr(xk.c6);
-        pin_vgpr(xk.c5); pin_vgpr(xk.c4); pin_vgpr(xk.c3);
-    }
+    if constexpr (PINK) pin_nl_constants(e, kc, xk, dt);   // fp64: constants of the level loop -> VGPRs
 
     const int gcol = xcd_block() * kColBlock + threadIdx.x;
     // Lanes past the last column retire here.  They must not be carried along under an `if (live)` around the stores: that
@@ -463,20 +398,20 @@ nl_kernel(Ext<T> e, NLK<T> kc, ExpK<T> xk, int nx, int nz, int64_t ls, CPtrs<T, 
     // loads of every second level (the compiled ISA shows it: 16 / 32 loads, then the wait 0 / 19 instructions later), i.e.
     // every other level paid the full HBM latency.  Deeper register prefetch was measured in r01 (spills; 1 is best).
     constexpr bool PERT = FUSE == 2 || FUSE == 3;
-    NLIn<T> xa = nl_load<T, FUSE == 1, O>(in, lsb, colb, keepq != 0);
-    NLIn<T> xia;
-    if constexpr (PERT) xia = nl_load<T, false, O>(in_i, lsb, colb);
+    LevelIn<T> xa = load_level<T, O>(in, lsb, colb, FUSE == 1, keepq != 0);
+    LevelIn<T> xia;
+    if constexpr (PERT) xia = load_level<T, O>(in_i, lsb, colb);
     landed(c.aph_k);   // first read inside the loop: see landed()
     if constexpr (EVAP) landed(aph_s);
     double acc[FUSE == 3 ? NL_NUM_OUT : 1] = {};
     O o = colb;  // byte offset of (level k, column)
     for (int k = 0; k < nz; ++k) {
-        NLIn<T> xn = xa, xin = xia;
+        LevelIn<T> xn = xa, xin = xia;
         if (k + 1 < nz) {
-            xn = nl_load<T, FUSE == 1, O>(in, lsb, o + lsb, keepq != 0);
-            if constexpr (PERT) xin = nl_load<T, false, O>(in_i, lsb, o + lsb);
+            xn = load_level<T, O>(in, lsb, o + lsb, FUSE == 1, keepq != 0);
+            if constexpr (PERT) xin = load_level<T, O>(in_i, lsb, o + lsb);
         }
-        NLIn<T> x = xa;
+        LevelIn<T> x = xa;
         if constexpr (PERT) x = nl_perturb<T>(xa, xia, pf);
         T ref[FUSE == 3 ? NL_NUM_OUT : 1];
         if constexpr (FUSE == 3) {   // requested before the physics, consumed after it
@@ -505,7 +440,7 @@ nl_kernel(Ext<T> e, NLK<T> kc, ExpK<T> xk, int nx, int nz, int64_t ls, CPtrs<T, 
             acc[NL_OUT_FHPSN] += wlive * double(enthalpy_diff<T>(r.sfln, e.RLSTT, ref[NL_OUT_FHPSN]));
         } else {
             if (live) nl_store<T, O>(out, e, lsb, o, r);
-            if constexpr (CS2_NL_DRAIN != 0) drain_vmem();
+            drain_vmem();   // see drain_vmem
         }
         xa = xn;
         if constexpr (PERT) xia = xin;
@@ -548,111 +483,42 @@ nl_kernel(Ext<T> e, NLK<T> kc, ExpK<T> xk, int nx, int nz, int64_t ls, CPtrs<T, 
 //     the wait (the count must never exceed the operations really issued after level k's DMAs).
 // Used when the launcher can guarantee 16-byte aligned rows that hold the last DMA-wide column group (launch_nl; a partly
 // filled last wave: RAGGED); every other call takes the register-prefetch kernel above.  Results are bit-identical (same arithmetic on the same words).
-#ifndef CS2_NL_RING
-#define CS2_NL_RING 3   // slots per wave (levels in flight + the one being computed); 0 disables the variant
-#endif
-#ifndef CS2_NL_RING_AUX
-#define CS2_NL_RING_AUX (CS2_NT & 1 ? 2 : 0)   // cache policy of the input DMAs: 2 = nt (every byte is read once)
-#endif
-// 1: the sweep's own reads of t / tnd_cml_t on the tropopause-window levels use the default cache policy, hoping to hit
-// the rows the overlapped pre-scan fetched.  Measured and left OFF: it gains 9 us only in a back-to-back train of
-// launches, i.e. from what the PREVIOUS launch left in the memory-side cache; with the cache evicted between steps
-// it is 4 us slower (profiles/cold_cache_check.py).  The committed configuration times the same with or without
-// that eviction - only in_qsat, produced inside the step, is meant to be found in cache.
-#ifndef CS2_NL_PS_REUSE
-#define CS2_NL_PS_REUSE 0
-#endif
-// Cache policy of the DMA that carries in_qsat when the field fits the memory-side cache (`keepq`, see qsat_fits_cache):
-// default (0), not nt - `saturation` wrote the field just before (run_nonlinear.py:117-118).  -1: never, same policy
-// as the other inputs.
-#ifndef CS2_NL_QSAT_AUX
-#define CS2_NL_QSAT_AUX 0
-#endif
-// Which input fields (bit f = field NL_IN_*) take that policy: the DMA instruction that carries any of them does.  Default:
-// in_qsat only.  (A/B switch, r04: in_ap / in_t, which `saturation` read just before, measured in profiles/r04/ab_keep_*.)
-#ifndef CS2_NL_KEEP_FIELDS
-#define CS2_NL_KEEP_FIELDS (1 << NL_IN_QSAT)
-#endif
-typedef __attribute__((address_space(3))) void* lds_void_ptr;
-typedef const __attribute__((address_space(1))) void* glb_void_ptr;
-
+constexpr int kNLRing = 3;   // slots per wave (levels in flight + the one being computed); 2 in the shallow variant
+// The DMA that carries in_qsat uses the default cache policy, not nt, when the field fits the memory-side cache (`keepq`,
+// see qsat_fits_cache): `saturation` wrote it just before (run_nonlinear.py:117-118).
+// Slot: the 16 input fields + the tropopause pre-scan pair (one more DMA).
 template <typename T>
-struct RingGeom {
-    static constexpr int NPL = 16 / int(sizeof(T));               // columns per lane per DMA = fields per DMA
-    static constexpr int NI = NL_NUM_IN / NPL;                    // DMA instructions per level
-    static constexpr int DATA = NL_NUM_IN * 64 * int(sizeof(T));  // the 16 input fields of one level
-    static constexpr int SLOT = DATA + 1024;                      // + the tropopause pre-scan pair (one more DMA)
-    static constexpr int NSTORE = NL_NUM_OUT;                     // stores per level (nl_store)
-};
+using NLRingGeom = RingGeom<T, NL_NUM_IN, 1>;
+constexpr int kNLStores = NL_NUM_OUT;   // stores per level (nl_store)
 
 // Wait until at most N vector-memory operations are outstanding, then read this lane's column of the slot at LDS
 // byte address `a`: the 16 input fields, then the pre-scan pair (first-guess inputs t / tnd_cml_t of level klo + k + 1,
 // fields 16 and 17 of the slot); plus the table entries eta[k] (`ta`), scalm[k] (`tb`), eta[klo + k] (`tc`).
-template <int N>
-__device__ __forceinline__ void ring_read(uint32_t a, uint32_t ta, uint32_t tb, uint32_t tc, NLIn<double>& x, double& eta_k,
-                                          double& scalm_k, double& ps_t, double& ps_tt, double& eta_ps) {
-    asm volatile(
-        "s_waitcnt vmcnt(%25)\n\t"
-            "ds_read_b64 %0, %21\n\t"
-            "ds_read_b64 %1, %21 offset:512\n\t"
-            "ds_read_b64 %2, %21 offset:1024\n\t"
-            "ds_read_b64 %3, %21 offset:1536\n\t"
-            "ds_read_b64 %4, %21 offset:2048\n\t"
-            "ds_read_b64 %5, %21 offset:2560\n\t"
-            "ds_read_b64 %6, %21 offset:3072\n\t"
-            "ds_read_b64 %7, %21 offset:3584\n\t"
-            "ds_read_b64 %8, %21 offset:4096\n\t"
-            "ds_read_b64 %9, %21 offset:4608\n\t"
-            "ds_read_b64 %10, %21 offset:5120\n\t"
-            "ds_read_b64 %11, %21 offset:5632\n\t"
-            "ds_read_b64 %12, %21 offset:6144\n\t"
-            "ds_read_b64 %13, %21 offset:6656\n\t"
-            "ds_read_b64 %14, %21 offset:7168\n\t"
-            "ds_read_b64 %15, %21 offset:7680\n\t"
-            "ds_read_b64 %18, %21 offset:8192\n\t"
-            "ds_read_b64 %19, %21 offset:8704\n\t"
-            "ds_read_b64 %16, %22\n\t"
-            "ds_read_b64 %17, %23\n\t"
-            "ds_read_b64 %20, %24\n\t"
-        "s_waitcnt lgkmcnt(0)"
-        : "=&v"(x.ap), "=&v"(x.aph1), "=&v"(x.lu1), "=&v"(x.lude), "=&v"(x.mfd), "=&v"(x.mfu), "=&v"(x.q), "=&v"(x.qi),
-          "=&v"(x.ql), "=&v"(x.qsat), "=&v"(x.supsat), "=&v"(x.t), "=&v"(x.tq), "=&v"(x.tqi), "=&v"(x.tql), "=&v"(x.tt),
-          "=&v"(eta_k), "=&v"(scalm_k), "=&v"(ps_t), "=&v"(ps_tt), "=&v"(eta_ps)
-        : "v"(a), "v"(ta), "v"(tb), "v"(tc), "n"(N)
-        : "memory");
-}
-template <int N>
-__device__ __forceinline__ void ring_read(uint32_t a, uint32_t ta, uint32_t tb, uint32_t tc, NLIn<float>& x, float& eta_k,
-                                          float& scalm_k, float& ps_t, float& ps_tt, float& eta_ps) {
-    asm volatile(
-        "s_waitcnt vmcnt(%25)\n\t"
-            "ds_read_b32 %0, %21\n\t"
-            "ds_read_b32 %1, %21 offset:256\n\t"
-            "ds_read_b32 %2, %21 offset:512\n\t"
-            "ds_read_b32 %3, %21 offset:768\n\t"
-            "ds_read_b32 %4, %21 offset:1024\n\t"
-            "ds_read_b32 %5, %21 offset:1280\n\t"
-            "ds_read_b32 %6, %21 offset:1536\n\t"
-            "ds_read_b32 %7, %21 offset:1792\n\t"
-            "ds_read_b32 %8, %21 offset:2048\n\t"
-            "ds_read_b32 %9, %21 offset:2304\n\t"
-            "ds_read_b32 %10, %21 offset:2560\n\t"
-            "ds_read_b32 %11, %21 offset:2816\n\t"
-            "ds_read_b32 %12, %21 offset:3072\n\t"
-            "ds_read_b32 %13, %21 offset:3328\n\t"
-            "ds_read_b32 %14, %21 offset:3584\n\t"
-            "ds_read_b32 %15, %21 offset:3840\n\t"
-            "ds_read_b32 %18, %21 offset:4096\n\t"
-            "ds_read_b32 %19, %21 offset:4352\n\t"
-            "ds_read_b32 %16, %22\n\t"
-            "ds_read_b32 %17, %23\n\t"
-            "ds_read_b32 %20, %24\n\t"
-        "s_waitcnt lgkmcnt(0)"
-        : "=&v"(x.ap), "=&v"(x.aph1), "=&v"(x.lu1), "=&v"(x.lude), "=&v"(x.mfd), "=&v"(x.mfu), "=&v"(x.q), "=&v"(x.qi),
-          "=&v"(x.ql), "=&v"(x.qsat), "=&v"(x.supsat), "=&v"(x.t), "=&v"(x.tq), "=&v"(x.tqi), "=&v"(x.tql), "=&v"(x.tt),
-          "=&v"(eta_k), "=&v"(scalm_k), "=&v"(ps_t), "=&v"(ps_tt), "=&v"(eta_ps)
-        : "v"(a), "v"(ta), "v"(tb), "v"(tc), "n"(N)
-        : "memory");
+template <int N, typename T>
+__device__ __forceinline__ void ring_read(uint32_t a, uint32_t ta, uint32_t tb, uint32_t tc, LevelIn<T>& x, T& eta_k,
+                                          T& scalm_k, T& ps_t, T& ps_tt, T& eta_ps) {
+    if constexpr (sizeof(T) == 8)
+        asm volatile("s_waitcnt vmcnt(%[n])\n\t" CS2_DS_READ16_B64
+                     "ds_read_b64 %18, %[a] offset:8192\n\t"
+                     "ds_read_b64 %19, %[a] offset:8704\n\t"
+                     "ds_read_b64 %16, %[ta]\n\t"
+                     "ds_read_b64 %17, %[tb]\n\t"
+                     "ds_read_b64 %20, %[tc]\n\t"
+                     "s_waitcnt lgkmcnt(0)"
+                     : CS2_LEVEL_OUTS(x), "=&v"(eta_k), "=&v"(scalm_k), "=&v"(ps_t), "=&v"(ps_tt), "=&v"(eta_ps)
+                     : [a] "v"(a), [ta] "v"(ta), [tb] "v"(tb), [tc] "v"(tc), [n] "n"(N)
+                     : "memory");
+    else
+        asm volatile("s_waitcnt vmcnt(%[n])\n\t" CS2_DS_READ16_B32
+                     "ds_read_b32 %18, %[a] offset:4096\n\t"
+                     "ds_read_b32 %19, %[a] offset:4352\n\t"
+                     "ds_read_b32 %16, %[ta]\n\t"
+                     "ds_read_b32 %17, %[tb]\n\t"
+                     "ds_read_b32 %20, %[tc]\n\t"
+                     "s_waitcnt lgkmcnt(0)"
+                     : CS2_LEVEL_OUTS(x), "=&v"(eta_k), "=&v"(scalm_k), "=&v"(ps_t), "=&v"(ps_tt), "=&v"(eta_ps)
+                     : [a] "v"(a), [ta] "v"(ta), [tb] "v"(tb), [tc] "v"(tc), [n] "n"(N)
+                     : "memory");
 }
 
 // SATF: the fused-saturation variant (FUSE = 1 of nl_kernel): in_qsat is not read - its half of the (ql, qsat) DMA
@@ -667,27 +533,15 @@ template <typename T, bool EVAP, bool LIN, bool PINK, int RD, bool SATF, bool RA
 __global__ void __launch_bounds__(kColBlock, 1)
 nl_ring_kernel(Ext<T> e, NLK<T> kc, ExpK<T> xk, int nx, int nz, int64_t ls, CPtrs<T, NL_NUM_IN> in,
                const T* __restrict__ eta, MPtrs<T, NL_NUM_OUT> out, T dt, T* __restrict__ qsat_out, int keepq) {
-    using G = RingGeom<T>;
+    using G = NLRingGeom<T>;
     static_assert(kColBlock % 64 == 0 && RD >= 2, "whole waves, at least one level in flight");
-    static_assert((RD - 1) * (G::NI + G::NSTORE) < 64, "vmcnt is a 6-bit counter");
+    static_assert((RD - 1) * (G::NI + kNLStores) < 64, "vmcnt is a 6-bit counter");
     extern __shared__ __align__(16) unsigned char smem_raw[];
     T* s_eta = reinterpret_cast<T*>(smem_raw);
     T* s_scalm = s_eta + (nz + 1);
     int klo, khi;
     build_level_table<T>(eta, nz, e, s_eta, s_scalm, klo, khi);
-    if constexpr (PINK && CS2_NL_PINK) {
-        pin_vgpr(e.RCPD); pin_vgpr(e.RLSTT); pin_vgpr(e.RLVTT); pin_vgpr(e.R4LES); pin_vgpr(e.R4IES);
-        pin_vgpr(e.RTT); pin_vgpr(e.RLPTRC); pin_vgpr(e.R3IES); pin_vgpr(e.R3LES); pin_vgpr(e.R2ES);
-        pin_vgpr(e.ZQMAX); pin_vgpr(e.RETV); pin_vgpr(e.R5LES); pin_vgpr(e.R5IES); pin_vgpr(e.RTICE);
-        pin_vgpr(e.RG); pin_vgpr(e.RD); pin_vgpr(e.R5ALVCP); pin_vgpr(e.RALVDCP); pin_vgpr(e.R5ALSCP);
-        pin_vgpr(e.RALSDCP); pin_vgpr(kc.rdt); pin_vgpr(kc.cons2); pin_vgpr(kc.rRD); pin_vgpr(kc.rRCPD);
-        pin_vgpr(kc.cormax); pin_vgpr(kc.fw2); pin_vgpr(dt);
-    }
-    if constexpr (PINK && CS2_NL_PINX && CS2_NL_FEXP) {
-        pin_vgpr(xk.l2e); pin_vgpr(xk.ln2h); pin_vgpr(xk.ln2l); pin_vgpr(xk.c12); pin_vgpr(xk.c11);
-        pin_vgpr(xk.c10); pin_vgpr(xk.c9); pin_vgpr(xk.c8); pin_vgpr(xk.c7); pin_vgpr(xk.c6);
-        pin_vgpr(xk.c5); pin_vgpr(xk.c4); pin_vgpr(xk.c3);
-    }
+    if constexpr (PINK) pin_nl_constants(e, kc, xk, dt);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int wcol0 = xcd_block() * kColBlock + wave * 64;   // first column of this wave
     if (wcol0 >= nx) return;                                // whole waves retire; the only workgroup barrier is inside
@@ -764,23 +618,17 @@ nl_ring_kernel(Ext<T> e, NLK<T> kc, ExpK<T> xk, int nx, int nz, int64_t ls, CPtr
     const uint32_t tab_bytes = (2u * uint32_t(nz + 1) * uint32_t(sizeof(T)) + 1023u) & ~1023u;
     const uint32_t ring0 = tab_bytes + uint32_t(wave) * uint32_t(RD * G::SLOT);
     auto issue = [&](int slot, int level) {
-        const bool in_window = nps_dma > 0 && level > klo && level <= khi + 1;   // uniform
 #pragma unroll
         for (int i = 0; i < G::NI; ++i) {
             // (the cache-policy operand must be a literal constant at each call site)
-            if (CS2_NL_QSAT_AUX >= 0 && keepq && ((CS2_NL_KEEP_FIELDS >> (i * G::NPL)) & ((1 << G::NPL) - 1)) != 0)   // uniform
-                __builtin_amdgcn_global_load_lds((glb_void_ptr)src[i],
-                                                 (lds_void_ptr)(&smem_raw[ring0 + uint32_t(slot * G::SLOT + i * 1024)]),
-                                                 16, 0, CS2_NL_QSAT_AUX >= 0 ? CS2_NL_QSAT_AUX : 0);
-            else if (CS2_NL_PS_REUSE && in_window && (i == NL_IN_T / G::NPL || i == NL_IN_TND_CML_T / G::NPL))
-                // the pre-scan DMA fetched this row of t / tnd_cml_t (default policy) a few tens of levels ago
+            if (keepq && i == NL_IN_QSAT / G::NPL)   // uniform
                 __builtin_amdgcn_global_load_lds((glb_void_ptr)src[i],
                                                  (lds_void_ptr)(&smem_raw[ring0 + uint32_t(slot * G::SLOT + i * 1024)]),
                                                  16, 0, 0);
             else
                 __builtin_amdgcn_global_load_lds((glb_void_ptr)src[i],
                                                  (lds_void_ptr)(&smem_raw[ring0 + uint32_t(slot * G::SLOT + i * 1024)]),
-                                                 16, 0, CS2_NL_RING_AUX);
+                                                 16, 0, kDmaNT);
             src[i] += lsb;
         }
         if (level < nps_dma) {   // uniform
@@ -798,7 +646,7 @@ nl_ring_kernel(Ext<T> e, NLK<T> kc, ExpK<T> xk, int nx, int nz, int64_t ls, CPtr
     // The wait must never ALLOW more than were really issued, so it is set one level of stores short of that: the
     // stores it additionally retires are >= RD-1 levels old (long complete), and the count stays valid even if a
     // future compiler merged or dropped stores of a level.  First RD-1 levels: no stores counted at all.
-    constexpr int NFULL = (RD - 1) * G::NI + (RD - 2) * G::NSTORE;
+    constexpr int NFULL = (RD - 1) * G::NI + (RD - 2) * kNLStores;
     constexpr int NHEAD = (RD - 1) * G::NI;
     const uint32_t rd_lane = ring0 + uint32_t(lane) * uint32_t(sizeof(T));
     const uint32_t tb_off = uint32_t(nz + 1) * uint32_t(sizeof(T));
@@ -807,7 +655,7 @@ nl_ring_kernel(Ext<T> e, NLK<T> kc, ExpK<T> xk, int nx, int nz, int64_t ls, CPtr
     for (int k = 0; k < nz; ++k) {
         const bool more = k + RD - 1 < nz;
         if (more) issue(pslot, k + RD - 1);
-        NLIn<T> x;
+        LevelIn<T> x;
         T eta_k, scalm_k, ps_t, ps_tt, eta_ps;
         const uint32_t a = rd_lane + uint32_t(slot * G::SLOT);
         const uint32_t ta = uint32_t(k) * uint32_t(sizeof(T));
@@ -861,105 +709,53 @@ int launch_nl(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* cons
     if (big && fuse != 0) return -2;          // the fused build extensions keep 32-bit offsets
     const int keepq = qsat_fits_cache<T>(nz, ls) ? 1 : 0;   // in_qsat: default cache policy only when the field fits
     if (fuse == 1 && !p.LPHYLIN) return -2;   // only the LPHYLIN form of `saturation` is fused
-#define CS2_NL_LAUNCH(EV, LN, FU)                                                                                 \
-    hipLaunchKernelGGL((nl_kernel<T, EV, LN, sizeof(T) == 8, FU>), grid, block, smem, stream, e, kc, xk, nx, nz, \
-                       ls, ci, eta, co, tdt, cii, tpf, qsat_out, partials, keepq)
-#define CS2_NL_FLAGS(FU)                                   \
-    do {                                                   \
-        if (evap && lin) CS2_NL_LAUNCH(true, true, FU);    \
-        else if (evap && !lin) CS2_NL_LAUNCH(true, false, FU); \
-        else if (!evap && lin) CS2_NL_LAUNCH(false, true, FU); \
-        else CS2_NL_LAUNCH(false, false, FU);              \
-    } while (0)
-#if CS2_NL_RING
     // LDS-ring variant: whole waves, 16-byte aligned rows of every input field (the DMA moves 16 B per lane).
     // Ring depth by grid size (profiles/ab_nl.py, fp64, same box): with at most ~1.5 workgroups per CU the deep ring
     // wins (32 768 columns: 244 us vs 259 us at depth 2 vs 299 us register prefetch; 98 304: 609 / 633 / 651 us); with
     // more, LDS occupancy matters more than depth - depth 2 keeps two workgroups resident per CU (131 072 columns:
     // 655 us vs 692 us at depth 3; 262 144: 1 286 vs 1 350 us).
-    bool ring_deep = true;
     // 16-byte aligned rows that hold whole DMA-wide groups of columns up to the last valid one (lev_stride >= nx rounded up
     // to 2 fp64 / 4 fp32 columns: `storage.zeros` pads the level pitch to 512 B); a partly filled last wave takes the
     // RAGGED instantiation
-    constexpr int kNPL = RingGeom<T>::NPL;
-    bool ring = !big && fuse <= 1 && nx > 0 && nz >= CS2_NL_RING && (ls * int64_t(sizeof(T))) % 16 == 0 &&
+    constexpr int kNPL = NLRingGeom<T>::NPL;
+    bool ring = !big && fuse <= 1 && nx > 0 && nz >= kNLRing && (ls * int64_t(sizeof(T))) % 16 == 0 &&
                 ls >= int64_t((nx + kNPL - 1) / kNPL) * kNPL;
-    const bool ragged = nx % 64 != 0;
     for (int i = 0; i < NL_NUM_IN && ring; ++i)
         ring = (fuse == 1 && i == NL_IN_QSAT) || reinterpret_cast<uintptr_t>(in[i]) % 16 == 0;
     if (ring) {
-        using G = RingGeom<T>;
         int dev = 0;
         if (const int rc = current_device(dev)) return rc;
         const bool deep = int64_t(grid.x) * 2 <= int64_t(device_cus(dev)) * 3;
-        ring_deep = deep;
-        const int depth = deep ? CS2_NL_RING : 2;
-        const size_t tab = (2 * size_t(nz + 1) * sizeof(T) + 1023) & ~size_t(1023);
-        const size_t rsmem = tab + size_t(kColBlock / 64) * depth * G::SLOT;
-        ring = rsmem <= size_t(160) * 1024;   // LDS of a CU; very tall columns (table > 46 KB) take the register path
-    }
-    if (ring) {
-        using G = RingGeom<T>;
-        int dev = 0;
-        if (const int rc = current_device(dev)) return rc;
-        const bool deep = ring_deep;
-        const int depth = deep ? CS2_NL_RING : 2;
-        const size_t tab = (2 * size_t(nz + 1) * sizeof(T) + 1023) & ~size_t(1023);
-        const size_t rsmem = tab + size_t(kColBlock / 64) * depth * G::SLOT;
-#define CS2_NL_RING_LAUNCH(EV, LN, RD, SF)                                                                           \
-    do {                                                                                                             \
-        if (ragged) CS2_NL_RING_LAUNCH_R(EV, LN, RD, SF, true);                                                      \
-        else CS2_NL_RING_LAUNCH_R(EV, LN, RD, SF, false);                                                            \
-    } while (0)
-#define CS2_NL_RING_LAUNCH_R(EV, LN, RD, SF, RG)                                                                     \
-    do {                                                                                                             \
-        auto kern = nl_ring_kernel<T, EV, LN, sizeof(T) == 8, RD, SF, RG>;                                           \
-        /* > 64 KB of dynamic LDS needs the opt-in: once per instantiation, device and size */                       \
-        static std::atomic<size_t> attr_set[kMaxDevices] = {};                                                       \
-        if (!lds_opt_in(kern, attr_set, dev, rsmem)) return -1;                                                      \
-        hipLaunchKernelGGL(kern, grid, block, rsmem, stream, e, kc, xk, nx, nz, ls, ci, eta, co, tdt, qsat_out,      \
-                           keepq);                                                                                   \
-    } while (0)
-#define CS2_NL_RING_FLAGS(RD, SF)                                          \
-    do {                                                                   \
-        if (evap && lin) CS2_NL_RING_LAUNCH(true, true, RD, SF);           \
-        else if (evap && !lin) CS2_NL_RING_LAUNCH(true, false, RD, SF);    \
-        else if (!evap && lin) CS2_NL_RING_LAUNCH(false, true, RD, SF);    \
-        else CS2_NL_RING_LAUNCH(false, false, RD, SF);                     \
-    } while (0)
-        if (fuse == 1 && !p.LPHYLIN) return -2;   // only the LPHYLIN form of `saturation` is fused
-        if (fuse == 0) {
-            if (deep) CS2_NL_RING_FLAGS(CS2_NL_RING, false);
-            else CS2_NL_RING_FLAGS(2, false);
-        } else {
-            if (deep) CS2_NL_RING_FLAGS(CS2_NL_RING, true);
-            else CS2_NL_RING_FLAGS(2, true);
+        const size_t rsmem = ring_lds_bytes<NLRingGeom<T>, T>(nz, deep ? kNLRing : 2);
+        if (rsmem <= size_t(160) * 1024) {   // LDS of a CU; very tall columns (table > 46 KB) take the register path
+            const bool ragged = nx % 64 != 0;
+            const int rc = with_flags(
+                [&](auto EV, auto LN, auto DEEP, auto SF, auto RG) {
+                    constexpr auto kern = nl_ring_kernel<T, EV, LN, sizeof(T) == 8, (DEEP ? kNLRing : 2), SF, RG>;
+                    if (!lds_opt_in<kern>(dev, rsmem)) return -1;
+                    hipLaunchKernelGGL(kern, grid, block, rsmem, stream, e, kc, xk, nx, nz, ls, ci, eta, co, tdt, qsat_out,
+                                       keepq);
+                    return 0;
+                },
+                evap, lin, deep, fuse == 1, ragged);
+            if (rc) return rc;
+            note_kernel(ragged ? "cs2::nl_ring_kernel<ragged>" : "cs2::nl_ring_kernel");
+            return hipGetLastError() == hipSuccess ? 0 : -1;
         }
-#undef CS2_NL_RING_FLAGS
-#undef CS2_NL_RING_LAUNCH
-#undef CS2_NL_RING_LAUNCH_R
-        note_kernel(ragged ? "cs2::nl_ring_kernel<ragged>" : "cs2::nl_ring_kernel");
-        return hipGetLastError() == hipSuccess ? 0 : -1;
     }
-#endif
-    if (big) {       // fields of 4 GiB and more: the register-path kernel with 64-bit offsets
-#define CS2_NL_BIG(EV, LN)                                                                                         \
-    hipLaunchKernelGGL((nl_kernel<T, EV, LN, sizeof(T) == 8, 0, true>), grid, block, smem, stream, e, kc, xk, nx,  \
-                       nz, ls, ci, eta, co, tdt, cii, tpf, qsat_out, partials, keepq)
-        if (evap && lin) CS2_NL_BIG(true, true);
-        else if (evap && !lin) CS2_NL_BIG(true, false);
-        else if (!evap && lin) CS2_NL_BIG(false, true);
-        else CS2_NL_BIG(false, false);
-#undef CS2_NL_BIG
+    const auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, grid, block, smem, stream, e, kc, xk, nx, nz, ls, ci, eta, co, tdt, cii, tpf, qsat_out,
+                           partials, keepq);
+        return 0;
+    };
+    if (big) {       // fields of 4 GiB and more: the register-path kernel with 64-bit offsets (FUSE = 0 only)
+        with_flags([&](auto EV, auto LN) { return launch(nl_kernel<T, EV, LN, sizeof(T) == 8, 0, true>); }, evap, lin);
         note_kernel("cs2::nl_kernel<big>");
         return hipGetLastError() == hipSuccess ? 0 : -1;
     }
-    if (fuse == 0) CS2_NL_FLAGS(0);
-    else if (fuse == 1) CS2_NL_FLAGS(1);
-    else if (fuse == 2) CS2_NL_FLAGS(2);
-    else CS2_NL_FLAGS(3);
-#undef CS2_NL_FLAGS
-#undef CS2_NL_LAUNCH
+    with_int<0, 1, 2, 3>(fuse, [&](auto FU) {
+        return with_flags([&](auto EV, auto LN) { return launch(nl_kernel<T, EV, LN, sizeof(T) == 8, FU>); }, evap, lin);
+    });
     note_kernel("cs2::nl_kernel");
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
@@ -1044,59 +840,10 @@ __device__ __forceinline__ void trpaus_prescan_multi(const T* __restrict__ pt, c
     }
 }
 
-template <typename T>
-__device__ __forceinline__ NLIn<T> nl_increment(const NLIn<T>& a, T f, bool zero_supsat) {
-    NLIn<T> x;   // rounded_product: the STORED products of the increment kernel, never half of an fma (nl_perturb's x + f2 * x_i)
-#define CS2_P(m) x.m = rounded_product<T>(f, a.m)
-    CS2_P(ap); CS2_P(aph1); CS2_P(lu1); CS2_P(lude); CS2_P(mfd); CS2_P(mfu); CS2_P(q); CS2_P(qi); CS2_P(ql); CS2_P(qsat);
-    CS2_P(t); CS2_P(tq); CS2_P(tqi); CS2_P(tql); CS2_P(tt);
-#undef CS2_P
-    x.supsat = zero_supsat ? T(0.0) : rounded_product<T>(f, a.supsat);
-    return x;
-}
-
-template <typename T>
-__device__ __forceinline__ void nl_load_refs(const CPtrs<T, NL_NUM_OUT>& ref, uint32_t lsb, uint32_t o, T (&r)[NL_NUM_OUT]) {
-#pragma unroll
-    for (int f = 0; f < NL_NUM_OUT; ++f) {
-        const bool half = f == NL_OUT_FPLSL || f == NL_OUT_FPLSN || f == NL_OUT_FHPSL || f == NL_OUT_FHPSN;
-        r[f] = ldg(ref.p[f], half ? o + lsb : o);
-    }
-}
-
-// The running sums of one step size: ten fp64 words in LDS, field f of this lane at `addr + f * kColBlock * 8`.  Left to
-// hipcc, every `sum += d` became ds_read / s_waitcnt lgkmcnt(0) / add / ds_write back to back - fifty exposed LDS round
-// trips per level, a third of the kernel's time at one wave per SIMD (PMC: VALU-active 69 %).  So the ten reads of a step
-// size are ISSUED here, before its level is evaluated, and only waited for (acc_wait) when the differences are ready: the
-// latency hides behind ~570 VALU instructions.  The asm is a compiler barrier for memory operations (the previous level's
-// ds_write of the same words must stay ahead of it); lgkmcnt(0) also covers whatever LDS / scalar loads hipcc has in flight.
-#ifndef CS2_NL_MULTI_PREISSUE
-#define CS2_NL_MULTI_PREISSUE 0   // measured: 2.34 vs 2.28 ms for the ten step sizes - the LDS round trips are not what the kernel waits for
-#endif
-__device__ __forceinline__ void acc_issue(uint32_t addr, double (&v)[NL_NUM_OUT]) {
-    static_assert(NL_NUM_OUT == 10 && kColBlock * 8 == 2048, "offsets below are f * kColBlock * sizeof(double)");
-    asm volatile(
-        "ds_read_b64 %0, %10\n\t"
-        "ds_read_b64 %1, %10 offset:2048\n\t"
-        "ds_read_b64 %2, %10 offset:4096\n\t"
-        "ds_read_b64 %3, %10 offset:6144\n\t"
-        "ds_read_b64 %4, %10 offset:8192\n\t"
-        "ds_read_b64 %5, %10 offset:10240\n\t"
-        "ds_read_b64 %6, %10 offset:12288\n\t"
-        "ds_read_b64 %7, %10 offset:14336\n\t"
-        "ds_read_b64 %8, %10 offset:16384\n\t"
-        "ds_read_b64 %9, %10 offset:18432"
-        : "=&v"(v[0]), "=&v"(v[1]), "=&v"(v[2]), "=&v"(v[3]), "=&v"(v[4]), "=&v"(v[5]), "=&v"(v[6]), "=&v"(v[7]), "=&v"(v[8]),
-          "=&v"(v[9])
-        : "v"(addr)
-        : "memory");
-}
-__device__ __forceinline__ void acc_wait(double (&v)[NL_NUM_OUT]) {
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "+v"(v[0]), "+v"(v[1]), "+v"(v[2]), "+v"(v[3]), "+v"(v[4]), "+v"(v[5]), "+v"(v[6]), "+v"(v[7]), "+v"(v[8]),
-                   "+v"(v[9]));
-}
-
+// The running sums of one step size: ten fp64 words in LDS, field f of this lane at `s_acc + f * kColBlock`.  Left to hipcc,
+// every `sum += d` is ds_read / s_waitcnt lgkmcnt(0) / add / ds_write back to back; issuing the ten reads of a step size
+// before its level is evaluated and waiting for them only when the differences are ready measured no better (2.34 vs
+// 2.28 ms for the ten step sizes): the LDS round trips are not what the kernel waits for.
 // Kernel arguments as ONE struct (kernarg offset 0): the 42 field pointers are read from the kernarg segment at their point
 // of use (KernArgs in cloudsc2_common.hpp) instead of living in - and being spilled from - SGPRs.  This kernel is bound by
 // its VALU instructions, and 384 of the 3 996 of a level (NF = 5, fp64) were v_readlane_b32 fetching spilled SGPRs back.
@@ -1117,9 +864,6 @@ struct NLMArgs {
     T finc;
     int zero_supsat_i;
 };
-#ifndef CS2_NL_MULTI_KARG
-#define CS2_NL_MULTI_KARG 1   // 1: field pointers are re-read from the kernarg segment (scalar loads) on every level
-#endif
 
 template <typename T, bool EVAP, bool LIN, bool PINK, int NF, bool INC>
 __global__ void __launch_bounds__(kColBlock, 1)
@@ -1138,27 +882,6 @@ nl_taylor_multi_kernel(const NLMArgs<T, NF> A) {
     const auto P_in = [&](int i) -> const T* { return K->in.p[i]; };
     const auto P_ini = [&](int i) -> const T* { return K->in_i.p[i]; };
     const auto P_ref = [&](int i) -> const T* { return K->ref.p[i]; };
-    // the 16 words of a level through a pointer source (nl_load's statement order)
-    const auto load16 = [&](const auto& ptr, uint32_t lsb_, uint32_t o_) {
-        NLIn<T> x;
-        x.ap = ldg(ptr(NL_IN_AP), o_);
-        x.aph1 = ldg(ptr(NL_IN_APH), o_ + lsb_);
-        x.lu1 = ldg(ptr(NL_IN_LU), o_ + lsb_);
-        x.lude = ldg(ptr(NL_IN_LUDE), o_);
-        x.mfd = ldg(ptr(NL_IN_MFD), o_);
-        x.mfu = ldg(ptr(NL_IN_MFU), o_);
-        x.q = ldg(ptr(NL_IN_Q), o_);
-        x.qi = ldg(ptr(NL_IN_QI), o_);
-        x.ql = ldg(ptr(NL_IN_QL), o_);
-        x.qsat = ldg(ptr(NL_IN_QSAT), o_);
-        x.supsat = ldg(ptr(NL_IN_SUPSAT), o_);
-        x.t = ldg(ptr(NL_IN_T), o_);
-        x.tq = ldg(ptr(NL_IN_TND_CML_Q), o_);
-        x.tqi = ldg(ptr(NL_IN_TND_CML_QI), o_);
-        x.tql = ldg(ptr(NL_IN_TND_CML_QL), o_);
-        x.tt = ldg(ptr(NL_IN_TND_CML_T), o_);
-        return x;
-    };
     const auto load_refs = [&](uint32_t lsb_, uint32_t o_, T (&r)[NL_NUM_OUT]) {
 #pragma unroll
         for (int f = 0; f < NL_NUM_OUT; ++f) {
@@ -1176,28 +899,13 @@ nl_taylor_multi_kernel(const NLMArgs<T, NF> A) {
     build_level_table<T>(eta, nz, e, s_eta, s_scalm, klo, khi);
 #pragma unroll
     for (int i = 0; i < NF * NL_NUM_OUT; ++i) s_acc[i * kColBlock] = 0.0;   // this lane's own slots: no barrier needed
-    if constexpr (PINK && CS2_NL_PINK) {
-        pin_vgpr(e.RCPD); pin_vgpr(e.RLSTT); pin_vgpr(e.RLVTT); pin_vgpr(e.R4LES); pin_vgpr(e.R4IES);
-        pin_vgpr(e.RTT); pin_vgpr(e.RLPTRC); pin_vgpr(e.R3IES); pin_vgpr(e.R3LES); pin_vgpr(e.R2ES);
-        pin_vgpr(e.ZQMAX); pin_vgpr(e.RETV); pin_vgpr(e.R5LES); pin_vgpr(e.R5IES); pin_vgpr(e.RTICE);
-        pin_vgpr(e.RG); pin_vgpr(e.RD); pin_vgpr(e.R5ALVCP); pin_vgpr(e.RALVDCP); pin_vgpr(e.R5ALSCP);
-        pin_vgpr(e.RALSDCP); pin_vgpr(kc.rdt); pin_vgpr(kc.cons2); pin_vgpr(kc.rRD); pin_vgpr(kc.rRCPD);
-        pin_vgpr(kc.cormax); pin_vgpr(kc.fw2); pin_vgpr(dt);
-    }
-    if constexpr (PINK && CS2_NL_PINX && CS2_NL_FEXP) {
-        pin_vgpr(xk.l2e); pin_vgpr(xk.ln2h); pin_vgpr(xk.ln2l); pin_vgpr(xk.c12); pin_vgpr(xk.c11);
-        pin_vgpr(xk.c10); pin_vgpr(xk.c9); pin_vgpr(xk.c8); pin_vgpr(xk.c7); pin_vgpr(xk.c6);
-        pin_vgpr(xk.c5); pin_vgpr(xk.c4); pin_vgpr(xk.c3);
-    }
+    if constexpr (PINK) pin_nl_constants(e, kc, xk, dt);
     const int gcol = xcd_block() * kColBlock + threadIdx.x;
     const bool live = gcol < nx;
     const int col = live ? gcol : nx - 1;   // dead lanes shadow the last column and add nothing
     const uint32_t lsb = uint32_t(ls) * uint32_t(sizeof(T));
     const uint32_t colb = uint32_t(col) * uint32_t(sizeof(T));
 
-    // LDS byte address of this lane's first running sum (the low 32 bits of a generic pointer into LDS are its LDS offset)
-    const uint32_t acc_addr = uint32_t(reinterpret_cast<uintptr_t>(s_acc));
-    (void)acc_addr;
     T trpaus[NF];
     trpaus_prescan_multi<T, NF, INC>(P_in(NL_IN_T), P_in(NL_IN_TND_CML_T), P_ini(NL_IN_T), P_ini(NL_IN_TND_CML_T), lsb, colb,
                                      dt, s_eta, klo, khi, pf, finc, trpaus);
@@ -1227,39 +935,32 @@ nl_taylor_multi_kernel(const NLMArgs<T, NF> A) {
     // the next level (`cur = next`): the copy is the only consumer of the prefetched words, so they have a whole level of
     // arithmetic (~5 us) to arrive.  (A two-way unrolled double buffer without copies - the shape nl_kernel uses - made
     // hipcc consume ten of the 26 words 76 instructions after requesting them: VALU-active 69 %.)
-#ifndef CS2_NL_MULTI_COPYBUF
-#define CS2_NL_MULTI_COPYBUF 1
-#endif
-    NLIn<T> xa = load16(P_in, lsb, colb), xb;
-    if constexpr (!INC) xb = load16(P_ini, lsb, colb);
+    LevelIn<T> xa = load_level<T>(P_in, lsb, colb), xb;
+    if constexpr (!INC) xb = load_level<T>(P_ini, lsb, colb);
     T xr[NL_NUM_OUT];
     load_refs(lsb, colb, xr);
     uint32_t o = colb;
     for (int k = 0; k < nz; ++k) {
         // fp64 only: -4 ... -5 % there (2.24 -> 2.12 ms for the ten step sizes at 65 536 columns; bit-identical sums); in fp32 at
         // 524 288 columns the kernel waits for HBM and the per-level scalar loads measured 0 ... +2 % (profiles/r04/ab_multi_*)
-        K.template fresh<(CS2_NL_MULTI_KARG != 0 && sizeof(T) == 8)>();
-        NLIn<T> na = xa, nb = xb;
+        K.template fresh<(sizeof(T) == 8)>();
+        LevelIn<T> na = xa, nb = xb;
         T nr[NL_NUM_OUT];
 #pragma unroll
         for (int f = 0; f < NL_NUM_OUT; ++f) nr[f] = xr[f];
         if (k + 1 < nz) {
-            na = load16(P_in, lsb, o + lsb);
-            if constexpr (!INC) nb = load16(P_ini, lsb, o + lsb);
+            na = load_level<T>(P_in, lsb, o + lsb);
+            if constexpr (!INC) nb = load_level<T>(P_ini, lsb, o + lsb);
             load_refs(lsb, o + lsb, nr);
         }
         const T eta_k = s_eta[k], scalm_k = s_scalm[k];
-        NLIn<T> inc_k;
-        if constexpr (INC) inc_k = nl_increment<T>(xa, finc, zero_supsat_i != 0);
-        const NLIn<T>& xi = INC ? inc_k : xb;
+        LevelIn<T> inc_k;
+        if constexpr (INC) inc_k = increment<T>(xa, finc, zero_supsat_i != 0);
+        const LevelIn<T>& xi = INC ? inc_k : xb;
 #pragma unroll
         for (int j = 0; j < NF; ++j) {
             double* const a = s_acc + j * NL_NUM_OUT * kColBlock;
-            double sum[NL_NUM_OUT];
-#if CS2_NL_MULTI_PREISSUE
-            acc_issue(acc_addr + uint32_t(j * NL_NUM_OUT * kColBlock * sizeof(double)), sum);
-#endif
-            const NLIn<T> x = nl_perturb<T>(xa, xi, pf.f[j]);
+            const LevelIn<T> x = nl_perturb<T>(xa, xi, pf.f[j]);
             const NLOut<T> r = nl_level<T, EVAP, LIN>(e, kc, xk, x, eta_k, scalm_k, crh[j], dt, aph_s[j], c[j]);
             double d[NL_NUM_OUT];
             d[NL_OUT_CLC] = double(r.clc - xr[NL_OUT_CLC]);
@@ -1272,12 +973,9 @@ nl_taylor_multi_kernel(const NLMArgs<T, NF> A) {
             d[NL_OUT_FPLSN] = double(r.sfln - xr[NL_OUT_FPLSN]);
             d[NL_OUT_FHPSL] = double(enthalpy_diff<T>(r.rfln, e.RLVTT, xr[NL_OUT_FHPSL]));
             d[NL_OUT_FHPSN] = double(enthalpy_diff<T>(r.sfln, e.RLSTT, xr[NL_OUT_FHPSN]));
-#if CS2_NL_MULTI_PREISSUE
-            acc_wait(sum);
-#else
+            double sum[NL_NUM_OUT];
 #pragma unroll
             for (int f = 0; f < NL_NUM_OUT; ++f) sum[f] = a[f * kColBlock];
-#endif
             if (live) {
 #pragma unroll
                 for (int f = 0; f < NL_NUM_OUT; ++f) a[f * kColBlock] = sum[f] + d[f];
@@ -1308,9 +1006,7 @@ nl_taylor_multi_kernel(const NLMArgs<T, NF> A) {
     }
 }
 
-#ifndef CS2_NL_MULTI_NF
-#define CS2_NL_MULTI_NF 5   // step sizes per launch: 10 x NF fp64 running sums x 256 lanes must fit the CU's LDS
-#endif
+constexpr int kNLMultiNF = 5;   // step sizes per launch: 10 x NF fp64 running sums x 256 lanes must fit the CU's LDS
 template <typename T>
 int launch_nl_taylor_multi(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* const* in, const T* const* in_i,
                            int nf, const double* pfs, const T* eta, const T* const* ref_out, double* partials, double dt,
@@ -1333,39 +1029,27 @@ int launch_nl_taylor_multi(const Cloudsc2Params& p, int nx, int nz, int64_t ls, 
     int dev = 0;
     if (const int rc = current_device(dev)) return rc;
     const size_t tab = (2 * size_t(nz + 1) * sizeof(T) + 15) & ~size_t(15);
-#define CS2_NLM_LAUNCH(EV, LN, NFV)                                                                                    \
-    do {                                                                                                                \
-        if (inc) CS2_NLM_LAUNCH_I(EV, LN, NFV, true); else CS2_NLM_LAUNCH_I(EV, LN, NFV, false);                        \
-    } while (0)
-#define CS2_NLM_LAUNCH_I(EV, LN, NFV, INCV)                                                                            \
-    do {                                                                                                                \
-        auto kern = nl_taylor_multi_kernel<T, EV, LN, sizeof(T) == 8, NFV, INCV>;                                       \
-        const size_t smem = tab + size_t(NFV) * NL_NUM_OUT * kColBlock * sizeof(double);                                \
-        if (smem + sizeof(double) * (kColBlock / 64) * NFV * NL_NUM_OUT > size_t(160) * 1024) return -2;                \
-        static std::atomic<size_t> attr_set[kMaxDevices] = {};                                                          \
-        if (smem > size_t(64) * 1024 && !lds_opt_in(kern, attr_set, dev, smem)) return -1;                              \
-        PFs<T, NFV> pf;                                                                                                 \
-        for (int j = 0; j < NFV; ++j) pf.f[j] = static_cast<T>(pfs[f0 + j]);                                            \
-        const NLMArgs<T, NFV> margs = {e, kc, xk, nx, nz, ls, ci, cii, cr, eta, tdt, pf, partials, nf, f0, tinc, zsi};  \
-        hipLaunchKernelGGL(kern, grid, block, smem, stream, margs);                                                     \
-    } while (0)
-#define CS2_NLM_FLAGS(NFV)                                            \
-    do {                                                              \
-        if (evap && lin) CS2_NLM_LAUNCH(true, true, NFV);             \
-        else if (evap && !lin) CS2_NLM_LAUNCH(true, false, NFV);      \
-        else if (!evap && lin) CS2_NLM_LAUNCH(false, true, NFV);      \
-        else CS2_NLM_LAUNCH(false, false, NFV);                       \
-    } while (0)
     for (int f0 = 0; f0 < nf;) {
         const int left = nf - f0;
-        if (left >= CS2_NL_MULTI_NF) { CS2_NLM_FLAGS(CS2_NL_MULTI_NF); f0 += CS2_NL_MULTI_NF; }
-        else if (left >= 3 && CS2_NL_MULTI_NF > 3) { CS2_NLM_FLAGS(3); f0 += 3; }
-        else if (left == 2) { CS2_NLM_FLAGS(2); f0 += 2; }
-        else { CS2_NLM_FLAGS(1); f0 += 1; }
+        const int nfv = left >= kNLMultiNF ? kNLMultiNF : left >= 3 ? 3 : left;
+        const int rc = with_int<kNLMultiNF, 3, 2, 1>(nfv, [&](auto NFV) {
+            return with_flags(
+                [&](auto EV, auto LN, auto INC) {
+                    constexpr auto kern = nl_taylor_multi_kernel<T, EV, LN, sizeof(T) == 8, NFV, INC>;
+                    const size_t smem = tab + size_t(NFV) * NL_NUM_OUT * kColBlock * sizeof(double);
+                    if (smem + sizeof(double) * (kColBlock / 64) * NFV * NL_NUM_OUT > size_t(160) * 1024) return -2;
+                    if (smem > size_t(64) * 1024 && !lds_opt_in<kern>(dev, smem)) return -1;
+                    PFs<T, NFV> pf;
+                    for (int j = 0; j < NFV; ++j) pf.f[j] = static_cast<T>(pfs[f0 + j]);
+                    const NLMArgs<T, NFV> margs = {e, kc, xk, nx, nz, ls, ci, cii, cr, eta, tdt, pf, partials, nf, f0, tinc, zsi};
+                    hipLaunchKernelGGL(kern, grid, block, smem, stream, margs);
+                    return 0;
+                },
+                evap, lin, inc);
+        });
+        if (rc) return rc;
+        f0 += nfv;
     }
-#undef CS2_NLM_FLAGS
-#undef CS2_NLM_LAUNCH
-#undef CS2_NLM_LAUNCH_I
     note_kernel("cs2::nl_taylor_multi_kernel");
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

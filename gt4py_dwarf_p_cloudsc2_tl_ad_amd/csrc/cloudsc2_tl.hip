@@ -15,55 +15,7 @@
 #define CS2_TL_DIAG 0   // diagnostics only (wrong results): 1 = the kernel's memory traffic without the physics
 #endif
 
-#ifndef CS2_TL_DRAIN_LEFT
-#define CS2_TL_DRAIN_LEFT 0   // stores that may stay in flight at the drain: 0 / 5 / 10 / 15 / all = 694.8 / 697.7 / 706.1 / 714.1 / 717.5 us
-#endif
-#ifndef CS2_TL_DRAIN
-#define CS2_TL_DRAIN 1   // register-path kernel: drain the level's stores before the next level is requested (see drain_vmem)
-#endif
-
 namespace cs2 {
-
-template <typename T>
-struct TLIn {
-    T ap, aph1, lu1, lude, mfd, mfu, q, qi, ql, qsat, supsat, t, tq, tqi, tql, tt;
-};
-
-template <typename T, typename O>
-__device__ __forceinline__ TLIn<T> tl_load(const CPtrs<T, NL_NUM_IN>& in, O lsb, O o) {
-    TLIn<T> x;
-    x.ap = ldg(in.p[NL_IN_AP], o);
-    x.aph1 = ldg(in.p[NL_IN_APH], o + lsb);
-    x.lu1 = ldg(in.p[NL_IN_LU], o + lsb);
-    x.lude = ldg(in.p[NL_IN_LUDE], o);
-    x.mfd = ldg(in.p[NL_IN_MFD], o);
-    x.mfu = ldg(in.p[NL_IN_MFU], o);
-    x.q = ldg(in.p[NL_IN_Q], o);
-    x.qi = ldg(in.p[NL_IN_QI], o);
-    x.ql = ldg(in.p[NL_IN_QL], o);
-    x.qsat = ldg(in.p[NL_IN_QSAT], o);
-    x.supsat = ldg(in.p[NL_IN_SUPSAT], o);
-    x.t = ldg(in.p[NL_IN_T], o);
-    x.tq = ldg(in.p[NL_IN_TND_CML_Q], o);
-    x.tqi = ldg(in.p[NL_IN_TND_CML_QI], o);
-    x.tql = ldg(in.p[NL_IN_TND_CML_QL], o);
-    x.tt = ldg(in.p[NL_IN_TND_CML_T], o);
-    return x;
-}
-
-// state_increment (common/_stencils/state_increment.py:61-80) applied on the fly: x_i = f * x, supsat_i = 0 with
-// IGNORE_SUPSAT - the very products the stand-alone increment kernel stores (cloudsc2_aux.hip), so the fused variant
-// (INC, C ABI cloudsc2_tl_incremented_*) feeds the level function exactly the words the separate calls would load.
-template <typename T>
-__device__ __forceinline__ TLIn<T> tl_increment(const TLIn<T>& x, T f, bool zero_supsat) {
-    TLIn<T> y;   // rounded_product: these are the STORED products of the increment kernel, never half of an fma
-#define CS2_P(m) y.m = rounded_product<T>(f, x.m)
-    CS2_P(ap); CS2_P(aph1); CS2_P(lu1); CS2_P(lude); CS2_P(mfd); CS2_P(mfu); CS2_P(q); CS2_P(qi); CS2_P(ql); CS2_P(qsat);
-    CS2_P(t); CS2_P(tq); CS2_P(tqi); CS2_P(tql); CS2_P(tt);
-#undef CS2_P
-    y.supsat = zero_supsat ? T(0.0) : rounded_product<T>(f, x.supsat);
-    return y;
-}
 
 template <typename T>
 struct TLCarry {
@@ -113,8 +65,8 @@ __device__ __forceinline__ void tl_cuadj_iter(const Ext<T>& e, const ExpK<T>& xk
 // from ONE exponential: with ex = exp(-0.34 (t - RLPTRC)), rr = 1/(1 + ex):
 //   0.545 (tanh u + 1) = 1.09 rr,   1 / cosh(u)^2 = 4 ex rr^2      (u = 0.17 (t - RLPTRC)).
 template <typename T, bool REG, bool EVAP>
-__device__ __forceinline__ TLOut<T> tl_level(const Ext<T>& e, const NLK<T>& kc, const ExpK<T>& xk, const TLIn<T>& x,
-                                             const TLIn<T>& y, int k, T eta_k, T scalm, const CrhCol<T>& crh, T dt,
+__device__ __forceinline__ TLOut<T> tl_level(const Ext<T>& e, const NLK<T>& kc, const ExpK<T>& xk, const LevelIn<T>& x,
+                                             const LevelIn<T>& y, int k, T eta_k, T scalm, const CrhCol<T>& crh, T dt,
                                              TLCarry<T>& c) {
     TLOut<T> o;
 #if CS2_TL_DIAG == 1
@@ -564,7 +516,15 @@ __device__ __forceinline__ void tl_store(const MPtrs<T, NL_NUM_OUT>& out, const 
     stg(out_i.p[NL_OUT_FHPSN], i + lsb, -o.sfln_i * e.RLSTT);
 }
 
-// INC: the perturbation fields are not read but formed as finc * in (state_increment fused in, see tl_increment):
+// The constants of the TL level loop, pinned in VGPRs (see pin_vgpr), then the exp coefficients.
+template <typename T>
+__device__ __forceinline__ void pin_tl_constants(Ext<T>& e, NLK<T>& kc, ExpK<T>& xk, T& dt) {
+    pin_vgprs(e.RCPD, e.RLSTT, e.RLVTT, e.RLMLT, e.R4LES, e.R4IES, e.RTT, e.R3IES, e.R3LES, e.R2ES, e.ZQMAX, e.RETV, e.R5LES,
+              e.R5IES, e.RG, e.RD, kc.rdt, kc.cons2, kc.rRD, kc.rRCPD, dt);
+    pin_expk(xk);
+}
+
+// INC: the perturbation fields are not read but formed as finc * in (state_increment fused in, see increment):
 // 16 input streams instead of 32, no landing buffer for the second 16.
 // BIG: 64-bit byte offsets (fields of 4 GiB and more, see offset_t in cloudsc2_common.hpp); instantiated without INC only.
 template <typename T, bool REG, bool EVAP, bool INC = false, bool BIG = false>
@@ -577,16 +537,7 @@ tl_kernel(Ext<T> e, NLK<T> kc, ExpK<T> xk, int nx, int nz, int64_t ls, CPtrs<T, 
     T* s_scalm = s_eta + (nz + 1);
     int klo, khi;
     build_level_table<T>(eta, nz, e, s_eta, s_scalm, klo, khi);
-    if constexpr (sizeof(T) == 8) {
-        // fp64 constants of the level loop -> VGPRs (see pin_vgpr in cloudsc2_common.hpp)
-        pin_vgpr(e.RCPD); pin_vgpr(e.RLSTT); pin_vgpr(e.RLVTT); pin_vgpr(e.RLMLT); pin_vgpr(e.R4LES);
-        pin_vgpr(e.R4IES); pin_vgpr(e.RTT); pin_vgpr(e.R3IES); pin_vgpr(e.R3LES); pin_vgpr(e.R2ES);
-        pin_vgpr(e.ZQMAX); pin_vgpr(e.RETV); pin_vgpr(e.R5LES); pin_vgpr(e.R5IES); pin_vgpr(e.RG);
-        pin_vgpr(e.RD); pin_vgpr(kc.rdt); pin_vgpr(kc.cons2); pin_vgpr(kc.rRD); pin_vgpr(kc.rRCPD); pin_vgpr(dt);
-        pin_vgpr(xk.l2e); pin_vgpr(xk.ln2h); pin_vgpr(xk.ln2l); pin_vgpr(xk.c12); pin_vgpr(xk.c11);
-        pin_vgpr(xk.c10); pin_vgpr(xk.c9); pin_vgpr(xk.c8); pin_vgpr(xk.c7); pin_vgpr(xk.c6);
-        pin_vgpr(xk.c5); pin_vgpr(xk.c4); pin_vgpr(xk.c3);
-    }
+    if constexpr (sizeof(T) == 8) pin_tl_constants(e, kc, xk, dt);   // fp64 constants of the level loop -> VGPRs
 
     const int gcol = xcd_block() * kColBlock + threadIdx.x;
     // Lanes past the last column retire here (no workgroup barrier follows build_level_table).  They must not be carried
@@ -630,28 +581,28 @@ tl_kernel(Ext<T> e, NLK<T> kc, ExpK<T> xk, int nx, int nz, int64_t ls, CPtrs<T, 
 
     O o = colb;
     if constexpr (INC) {
-        TLIn<T> xa = tl_load<T, O>(in, lsb, o);
+        LevelIn<T> xa = load_level<T, O>(in, lsb, o);
         for (int k = 0; k < nz; ++k) {
-            TLIn<T> xn = xa;
-            if (k + 1 < nz) xn = tl_load<T, O>(in, lsb, o + lsb);
-            const TLIn<T> ya = tl_increment<T>(xa, finc, zero_supsat_i != 0);
+            LevelIn<T> xn = xa;
+            if (k + 1 < nz) xn = load_level<T, O>(in, lsb, o + lsb);
+            const LevelIn<T> ya = increment<T>(xa, finc, zero_supsat_i != 0);
             const TLOut<T> r = tl_level<T, REG, EVAP>(e, kc, xk, xa, ya, k, s_eta[k], s_scalm[k], crh, dt, c);
             tl_store<T, O>(out, out_i, e, lsb, o, r);
-            if constexpr (CS2_TL_DRAIN != 0) drain_vmem<CS2_TL_DRAIN_LEFT>();
+            drain_vmem();   // see drain_vmem
             xa = xn;
             o += lsb;
         }
     } else {
-        TLIn<T> xa = tl_load<T, O>(in, lsb, o), ya = tl_load<T, O>(in_i, lsb, o);
+        LevelIn<T> xa = load_level<T, O>(in, lsb, o), ya = load_level<T, O>(in_i, lsb, o);
         for (int k = 0; k < nz; ++k) {
-            TLIn<T> xn = xa, yn = ya;
+            LevelIn<T> xn = xa, yn = ya;
             if (k + 1 < nz) {
-                xn = tl_load<T, O>(in, lsb, o + lsb);
-                yn = tl_load<T, O>(in_i, lsb, o + lsb);
+                xn = load_level<T, O>(in, lsb, o + lsb);
+                yn = load_level<T, O>(in_i, lsb, o + lsb);
             }
             const TLOut<T> r = tl_level<T, REG, EVAP>(e, kc, xk, xa, ya, k, s_eta[k], s_scalm[k], crh, dt, c);
             tl_store<T, O>(out, out_i, e, lsb, o, r);
-            if constexpr (CS2_TL_DRAIN != 0) drain_vmem<CS2_TL_DRAIN_LEFT>();
+            drain_vmem();
             xa = xn;
             ya = yn;
             o += lsb;
@@ -677,82 +628,28 @@ tl_kernel(Ext<T> e, NLK<T> kc, ExpK<T> xk, int nx, int nz, int64_t ls, CPtrs<T, 
 //     issues exactly kTLStores stores per level (20 distinct fields; tests/test_ring_isa.py counts them in the compiled ISA, and __graft_entry__.build() runs that check whenever it recompiles).
 // Used when the launcher can guarantee 16-byte aligned rows and whole waves (launch_tl); every other call takes the
 // register-prefetch kernel above.  Results are bit-identical (same arithmetic on the same words).
-#ifndef CS2_TL_RING
-#define CS2_TL_RING 2   // slots per wave in fp64 (0 disables the variant)
-#endif
-#ifndef CS2_TL_RING_F32
-#define CS2_TL_RING_F32 2
-#endif
-#ifndef CS2_TL_RING_AUX
-#define CS2_TL_RING_AUX (CS2_NT & 1 ? 2 : 0)   // cache policy of the input DMAs: 2 = nt (every byte is read once)
-#endif
-typedef __attribute__((address_space(3))) void* tl_lds_ptr;
-typedef const __attribute__((address_space(1))) void* tl_glb_ptr;
+constexpr int kTLRing = 2;                  // slots per wave, fp64 and fp32
 constexpr int kTLFields = 2 * NL_NUM_IN;    // input words per level and column
 constexpr int kTLStores = 2 * NL_NUM_OUT;   // stores per level (tl_store)
-
 template <typename T>
-struct TLRingGeom {
-    static constexpr int NPL = 16 / int(sizeof(T));             // columns per lane per DMA = fields per DMA
-    static constexpr int NI = kTLFields / NPL;                   // DMA instructions per level
-    static constexpr int SLOT = kTLFields * 64 * int(sizeof(T));  // the 32 input fields of one level
-};
+using TLRingGeom = RingGeom<T, kTLFields>;
 
 // Wait until at most N vector-memory operations are outstanding, then read this lane's column of 16 fields of the slot
-// at LDS byte address `a` (+ table entries eta[k] at `ta`, scalm[k] at `tb` when TAB).  Two statements per level (x, y):
-// the wait and the LDS reads live in ONE asm statement with a memory clobber - hipcc would otherwise drain vmcnt(0)
-// before every LDS read that follows an LDS-DMA, and no store may move across the wait.
-template <int N>
-__device__ __forceinline__ void tl_ring_read16(uint32_t a, TLIn<double>& x) {
-    asm volatile(
-        "s_waitcnt vmcnt(%17)\n\t"
-            "ds_read_b64 %0, %16\n\t"
-            "ds_read_b64 %1, %16 offset:512\n\t"
-            "ds_read_b64 %2, %16 offset:1024\n\t"
-            "ds_read_b64 %3, %16 offset:1536\n\t"
-            "ds_read_b64 %4, %16 offset:2048\n\t"
-            "ds_read_b64 %5, %16 offset:2560\n\t"
-            "ds_read_b64 %6, %16 offset:3072\n\t"
-            "ds_read_b64 %7, %16 offset:3584\n\t"
-            "ds_read_b64 %8, %16 offset:4096\n\t"
-            "ds_read_b64 %9, %16 offset:4608\n\t"
-            "ds_read_b64 %10, %16 offset:5120\n\t"
-            "ds_read_b64 %11, %16 offset:5632\n\t"
-            "ds_read_b64 %12, %16 offset:6144\n\t"
-            "ds_read_b64 %13, %16 offset:6656\n\t"
-            "ds_read_b64 %14, %16 offset:7168\n\t"
-            "ds_read_b64 %15, %16 offset:7680\n\t"
-        "s_waitcnt lgkmcnt(0)"
-        : "=&v"(x.ap), "=&v"(x.aph1), "=&v"(x.lu1), "=&v"(x.lude), "=&v"(x.mfd), "=&v"(x.mfu), "=&v"(x.q), "=&v"(x.qi),
-          "=&v"(x.ql), "=&v"(x.qsat), "=&v"(x.supsat), "=&v"(x.t), "=&v"(x.tq), "=&v"(x.tqi), "=&v"(x.tql), "=&v"(x.tt)
-        : "v"(a), "n"(N)
-        : "memory");
-}
-template <int N>
-__device__ __forceinline__ void tl_ring_read16(uint32_t a, TLIn<float>& x) {
-    asm volatile(
-        "s_waitcnt vmcnt(%17)\n\t"
-            "ds_read_b32 %0, %16\n\t"
-            "ds_read_b32 %1, %16 offset:256\n\t"
-            "ds_read_b32 %2, %16 offset:512\n\t"
-            "ds_read_b32 %3, %16 offset:768\n\t"
-            "ds_read_b32 %4, %16 offset:1024\n\t"
-            "ds_read_b32 %5, %16 offset:1280\n\t"
-            "ds_read_b32 %6, %16 offset:1536\n\t"
-            "ds_read_b32 %7, %16 offset:1792\n\t"
-            "ds_read_b32 %8, %16 offset:2048\n\t"
-            "ds_read_b32 %9, %16 offset:2304\n\t"
-            "ds_read_b32 %10, %16 offset:2560\n\t"
-            "ds_read_b32 %11, %16 offset:2816\n\t"
-            "ds_read_b32 %12, %16 offset:3072\n\t"
-            "ds_read_b32 %13, %16 offset:3328\n\t"
-            "ds_read_b32 %14, %16 offset:3584\n\t"
-            "ds_read_b32 %15, %16 offset:3840\n\t"
-        "s_waitcnt lgkmcnt(0)"
-        : "=&v"(x.ap), "=&v"(x.aph1), "=&v"(x.lu1), "=&v"(x.lude), "=&v"(x.mfd), "=&v"(x.mfu), "=&v"(x.q), "=&v"(x.qi),
-          "=&v"(x.ql), "=&v"(x.qsat), "=&v"(x.supsat), "=&v"(x.t), "=&v"(x.tq), "=&v"(x.tqi), "=&v"(x.tql), "=&v"(x.tt)
-        : "v"(a), "n"(N)
-        : "memory");
+// at LDS byte address `a`.  Two statements per level (x, y): the wait and the LDS reads live in ONE asm statement with a
+// memory clobber - hipcc would otherwise drain vmcnt(0) before every LDS read that follows an LDS-DMA, and no store may
+// move across the wait.
+template <int N, typename T>
+__device__ __forceinline__ void tl_ring_read16(uint32_t a, LevelIn<T>& x) {
+    if constexpr (sizeof(T) == 8)
+        asm volatile("s_waitcnt vmcnt(%[n])\n\t" CS2_DS_READ16_B64 "s_waitcnt lgkmcnt(0)"
+                     : CS2_LEVEL_OUTS(x)
+                     : [a] "v"(a), [n] "n"(N)
+                     : "memory");
+    else
+        asm volatile("s_waitcnt vmcnt(%[n])\n\t" CS2_DS_READ16_B32 "s_waitcnt lgkmcnt(0)"
+                     : CS2_LEVEL_OUTS(x)
+                     : [a] "v"(a), [n] "n"(N)
+                     : "memory");
 }
 // eta[k] (LDS byte address ta) and scalm[k] (tb) from the level table; the table is written before the only workgroup
 // barrier and never again, so no vector-memory wait is involved
@@ -778,15 +675,7 @@ tl_ring_kernel(Ext<T> e, NLK<T> kc, ExpK<T> xk, int nx, int nz, int64_t ls, CPtr
     T* s_scalm = s_eta + (nz + 1);
     int klo, khi;
     build_level_table<T>(eta, nz, e, s_eta, s_scalm, klo, khi);
-    if constexpr (sizeof(T) == 8) {
-        pin_vgpr(e.RCPD); pin_vgpr(e.RLSTT); pin_vgpr(e.RLVTT); pin_vgpr(e.RLMLT); pin_vgpr(e.R4LES);
-        pin_vgpr(e.R4IES); pin_vgpr(e.RTT); pin_vgpr(e.R3IES); pin_vgpr(e.R3LES); pin_vgpr(e.R2ES);
-        pin_vgpr(e.ZQMAX); pin_vgpr(e.RETV); pin_vgpr(e.R5LES); pin_vgpr(e.R5IES); pin_vgpr(e.RG);
-        pin_vgpr(e.RD); pin_vgpr(kc.rdt); pin_vgpr(kc.cons2); pin_vgpr(kc.rRD); pin_vgpr(kc.rRCPD); pin_vgpr(dt);
-        pin_vgpr(xk.l2e); pin_vgpr(xk.ln2h); pin_vgpr(xk.ln2l); pin_vgpr(xk.c12); pin_vgpr(xk.c11);
-        pin_vgpr(xk.c10); pin_vgpr(xk.c9); pin_vgpr(xk.c8); pin_vgpr(xk.c7); pin_vgpr(xk.c6);
-        pin_vgpr(xk.c5); pin_vgpr(xk.c4); pin_vgpr(xk.c3);
-    }
+    if constexpr (sizeof(T) == 8) pin_tl_constants(e, kc, xk, dt);
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
     const int wcol0 = xcd_block() * kColBlock + wave * 64;   // first column of this wave
     if (wcol0 >= nx) return;                                // nx % 64 == 0 (launcher): whole waves retire; the only
@@ -846,9 +735,9 @@ tl_ring_kernel(Ext<T> e, NLK<T> kc, ExpK<T> xk, int nx, int nz, int64_t ls, CPtr
     auto issue = [&](int slot) {
 #pragma unroll
         for (int i = 0; i < G::NI; ++i) {
-            __builtin_amdgcn_global_load_lds((tl_glb_ptr)src[i],
-                                             (tl_lds_ptr)(&smem_raw[ring0 + uint32_t(slot * G::SLOT + i * 1024)]), 16, 0,
-                                             CS2_TL_RING_AUX);
+            __builtin_amdgcn_global_load_lds((glb_void_ptr)src[i],
+                                             (lds_void_ptr)(&smem_raw[ring0 + uint32_t(slot * G::SLOT + i * 1024)]), 16, 0,
+                                             kDmaNT);
             src[i] += lsb;
         }
     };
@@ -867,7 +756,7 @@ tl_ring_kernel(Ext<T> e, NLK<T> kc, ExpK<T> xk, int nx, int nz, int64_t ls, CPtr
     for (int k = 0; k < nz; ++k) {
         const bool more = k + RD - 1 < nz;
         if (more) issue(pslot);
-        TLIn<T> x, y;
+        LevelIn<T> x, y;
         T eta_k, scalm_k;
         const uint32_t a = rd_lane + uint32_t(slot * G::SLOT);
         const uint32_t ta = uint32_t(k) * uint32_t(sizeof(T));
@@ -903,80 +792,50 @@ int launch_tl(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* cons
     const NLK<T> kc = make_nlk<T>(p, dt, evap);
     const ExpK<T> xk = make_expk<T>();
     const bool big = !fits_u32_offsets<T>(nz, ls);
+    const auto launch = [&](auto kern) {
+        hipLaunchKernelGGL(kern, grid, block, smem, stream, e, kc, xk, nx, nz, ls, ci, cii, eta, co, coi, tdt, tinc, zsi);
+        return 0;
+    };
     if (big) {       // fields of 4 GiB and more: the register-path kernel with 64-bit offsets (not the fused-increment variant)
         if (inc) return -2;
-#define CS2_TL_BIG(REG, EVAP)                                                                                      \
-    hipLaunchKernelGGL((tl_kernel<T, REG, EVAP, false, true>), grid, block, smem, stream, e, kc, xk, nx, nz, ls,   \
-                       ci, cii, eta, co, coi, tdt, tinc, zsi)
-        if (p.LREGCL) {
-            if (evap) CS2_TL_BIG(true, true); else CS2_TL_BIG(true, false);
-        } else {
-            if (evap) CS2_TL_BIG(false, true); else CS2_TL_BIG(false, false);
-        }
-#undef CS2_TL_BIG
+        with_flags([&](auto REG, auto EVAP) { return launch(tl_kernel<T, REG, EVAP, false, true>); }, p.LREGCL != 0, evap);
         note_kernel("cs2::tl_kernel<big>");
         return hipGetLastError() == hipSuccess ? 0 : -1;
     }
-    constexpr int kRing = sizeof(T) == 8 ? CS2_TL_RING : CS2_TL_RING_F32;
-    if constexpr (kRing >= 2) {
-        // LDS-ring variant: whole waves, 16-byte aligned rows of every input field (the DMA moves 16 B per lane)
-        using G = TLRingGeom<T>;
-        bool ring = !inc && nx % 64 == 0 && nz >= kRing && (ls * int64_t(sizeof(T))) % 16 == 0;
-        for (int i = 0; i < NL_NUM_IN && ring; ++i)
-            ring = reinterpret_cast<uintptr_t>(in[i]) % 16 == 0 && reinterpret_cast<uintptr_t>(in_i[i]) % 16 == 0;
-        const size_t tab = (2 * size_t(nz + 1) * sizeof(T) + 1023) & ~size_t(1023);
-        const size_t rsmem = tab + size_t(kColBlock / 64) * kRing * G::SLOT;
-        ring = ring && rsmem <= size_t(160) * 1024;   // LDS of a CU; very tall columns take the register path
-        int dev = 0;
-        if (ring)
-            if (const int rc = current_device(dev)) return rc;
-#ifndef CS2_TL_RING_ALWAYS
-#define CS2_TL_RING_ALWAYS 0   // A/B switch: 1 = take the ring whenever it is legal, whatever the occupancy
-#endif
-        if (ring && sizeof(T) == 8 && !CS2_TL_RING_ALWAYS) {
-            // fp64 (two slots per wave = the register path's one level ahead): the ring wins wherever part of the chip is
-            // latency-bound - 8 192 .. 49 152 columns -3.5 .. -6 %, 98 304 (1.5 workgroups per CU) -3.7 % - and loses
-            // 1.5-2 % when every CU holds the same number of workgroups for the whole launch and HBM is saturated
-            // (65 536: 720 vs 710 us, 131 072: 1 518 vs 1 488 us; profiles/r02/ab_tl_ring.txt).  Rule: register path when
-            // at least 3/4 of the launch's workgroup rounds are full.  fp32 (8 KB slots): the ring wins at every size
-            // measured (65 536: 337 vs 389 us; 524 288: 2 986 vs 3 049 us).
-            const int64_t c = device_cus(dev), gx = grid.x;
-            const int64_t full = gx / c, rounds = (gx + c - 1) / c;
-            ring = 4 * full < 3 * rounds;
-        }
-        if (ring) {
-#define CS2_TL_RING_LAUNCH(REG, EVAP)                                                                                \
-    do {                                                                                                             \
-        auto kern = tl_ring_kernel<T, REG, EVAP, kRing>;                                                             \
-        /* > 64 KB of dynamic LDS needs the opt-in: once per instantiation, device and size */                       \
-        static std::atomic<size_t> attr_set[kMaxDevices] = {};                                                       \
-        if (!lds_opt_in(kern, attr_set, dev, rsmem)) return -1;                                                      \
-        hipLaunchKernelGGL(kern, grid, block, rsmem, stream, e, kc, xk, nx, nz, ls, ci, cii, eta, co, coi, tdt);     \
-    } while (0)
-            if (p.LREGCL) {
-                if (evap) CS2_TL_RING_LAUNCH(true, true); else CS2_TL_RING_LAUNCH(true, false);
-            } else {
-                if (evap) CS2_TL_RING_LAUNCH(false, true); else CS2_TL_RING_LAUNCH(false, false);
-            }
-#undef CS2_TL_RING_LAUNCH
-            note_kernel("cs2::tl_ring_kernel");
-            return hipGetLastError() == hipSuccess ? 0 : -1;
-        }
+    // LDS-ring variant: whole waves, 16-byte aligned rows of every input field (the DMA moves 16 B per lane)
+    bool ring = !inc && nx % 64 == 0 && nz >= kTLRing && (ls * int64_t(sizeof(T))) % 16 == 0;
+    for (int i = 0; i < NL_NUM_IN && ring; ++i)
+        ring = reinterpret_cast<uintptr_t>(in[i]) % 16 == 0 && reinterpret_cast<uintptr_t>(in_i[i]) % 16 == 0;
+    const size_t rsmem = ring_lds_bytes<TLRingGeom<T>, T>(nz, kTLRing);
+    ring = ring && rsmem <= size_t(160) * 1024;   // LDS of a CU; very tall columns take the register path
+    int dev = 0;
+    if (ring)
+        if (const int rc = current_device(dev)) return rc;
+    if (ring && sizeof(T) == 8) {
+        // fp64 (two slots per wave = the register path's one level ahead): the ring wins wherever part of the chip is
+        // latency-bound - 8 192 .. 49 152 columns -3.5 .. -6 %, 98 304 (1.5 workgroups per CU) -3.7 % - and loses
+        // 1.5-2 % when every CU holds the same number of workgroups for the whole launch and HBM is saturated
+        // (65 536: 720 vs 710 us, 131 072: 1 518 vs 1 488 us; profiles/r02/ab_tl_ring.txt).  Rule: register path when
+        // at least 3/4 of the launch's workgroup rounds are full.  fp32 (8 KB slots): the ring wins at every size
+        // measured (65 536: 337 vs 389 us; 524 288: 2 986 vs 3 049 us).
+        const int64_t c = device_cus(dev), gx = grid.x;
+        const int64_t full = gx / c, rounds = (gx + c - 1) / c;
+        ring = 4 * full < 3 * rounds;
     }
-#define CS2_TL_LAUNCH(REG, EVAP, INCV)                                                                                 \
-    hipLaunchKernelGGL((tl_kernel<T, REG, EVAP, INCV>), grid, block, smem, stream, e, kc, xk, nx, nz, ls, ci, cii, eta, \
-                       co, coi, tdt, tinc, zsi)
-#define CS2_TL_LAUNCH_I(REG, EVAP)                                               \
-    do {                                                                         \
-        if (inc) CS2_TL_LAUNCH(REG, EVAP, true); else CS2_TL_LAUNCH(REG, EVAP, false); \
-    } while (0)
-    if (p.LREGCL) {
-        if (evap) CS2_TL_LAUNCH_I(true, true); else CS2_TL_LAUNCH_I(true, false);
-    } else {
-        if (evap) CS2_TL_LAUNCH_I(false, true); else CS2_TL_LAUNCH_I(false, false);
+    if (ring) {
+        const int rc = with_flags(
+            [&](auto REG, auto EVAP) {
+                constexpr auto kern = tl_ring_kernel<T, REG, EVAP, kTLRing>;
+                if (!lds_opt_in<kern>(dev, rsmem)) return -1;
+                hipLaunchKernelGGL(kern, grid, block, rsmem, stream, e, kc, xk, nx, nz, ls, ci, cii, eta, co, coi, tdt);
+                return 0;
+            },
+            p.LREGCL != 0, evap);
+        if (rc) return rc;
+        note_kernel("cs2::tl_ring_kernel");
+        return hipGetLastError() == hipSuccess ? 0 : -1;
     }
-#undef CS2_TL_LAUNCH_I
-#undef CS2_TL_LAUNCH
+    with_flags([&](auto REG, auto EVAP, auto INC) { return launch(tl_kernel<T, REG, EVAP, INC>); }, p.LREGCL != 0, evap, inc);
     note_kernel(inc ? "cs2::tl_kernel<inc>" : "cs2::tl_kernel");
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""A/B of `cloudsc2_nl_taylor_multi` builds (step sizes per launch: -DCS2_NL_MULTI_NF=...) in ONE process, interleaved:
+"""A/B of `cloudsc2_nl_taylor_multi` builds (step sizes per launch: kNLMultiNF in cloudsc2_nl.hip) in ONE process, interleaved:
   python profiles/ab_taylor_multi.py nf5=gt4py_dwarf_p_cloudsc2_tl_ad_amd/libcloudsc2_hip.so nf3=build/variants/lib_nf3.so ...
 Times the ten step sizes of the Taylor test (2 launches at NF = 5) and, for reference, ten launches of the one-step kernel."""
 import ctypes
