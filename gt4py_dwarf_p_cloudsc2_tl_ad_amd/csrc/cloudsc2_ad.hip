@@ -197,10 +197,9 @@ __device__ __forceinline__ void ad_forward(const Ext<T>& e, const NLK<T>& kc, co
     r.t2_cold = t < e.RTT;
     T z3es, r4;
     if (r.t2_cold) {
-        const T ex = fexp<T>(xk, -kc.fw2 * (r.t2 - e.RLPTRC));
-        const T rr = frcp<T>(T(1.0) + ex);
-        r.fwat = T(1.09) * rr;
-        r.sech2 = T(4.0) * ex * rr * rr;
+        T ex, rr;
+        r.fwat = logistic_fwat<T>(xk, kc.fw2, e.RLPTRC, r.t2, ex, rr);
+        r.sech2 = logistic_sech2<T>(ex, rr);
         z3es = e.R3IES;
         r4 = r.ri;
     } else {

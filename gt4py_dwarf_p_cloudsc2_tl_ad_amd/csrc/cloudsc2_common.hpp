@@ -55,10 +55,22 @@ template <> __device__ __forceinline__ float rsqrt_<float>(float x) { return sqr
 template <typename T> __device__ __forceinline__ T rpow(T x, T y);
 template <> __device__ __forceinline__ double rpow<double>(double x, double y) { return pow(x, y); }
 template <> __device__ __forceinline__ float rpow<float>(float x, float y) { return powf(x, y); }
-// Reciprocal by hardware seed + Newton steps (v_rcp_f64 + 4 fma; v_rcp_f32 + 2 fma): <= ~1 ulp, about
+// Reciprocal by hardware seed + Newton steps (v_rcp_f64 + 4 fma; v_rcp_f32 + 2 fma), about
 // half the instructions of the IEEE-correct division sequence hipcc emits for `a / b`.  The column
 // kernels are VALU-issue-bound in fp64 (profiles/), so divisions are expressed as x * frcp(y) and
 // reciprocals shared between the expressions that divide by the same quantity.
+// Accuracy, for normal x with normal 1/x: at most 1 ulp (faithful; the last step rounds r (2 - x r) =
+// 1/x (1 - d^2) once, d the relative error before it); measured: worst 0.50 ulp over 5 M arguments per precision
+// (tests/test_math_primitives.py).  Outside that range the Newton step meets inf * 0 and frcp is NOT the IEEE
+// quotient (measured on gfx950; v_rcp_f32 takes a subnormal for 0 and flushes a subnormal result):
+//         x                      1 / x (IEEE)         frcp(x)
+//         +-0                    +-inf                NaN
+//         +-inf                  +-0                  NaN
+//         subnormal              finite or +-inf      fp64: NaN where 1/x overflows, else <= 1 ulp;  fp32: NaN
+//         2^1022 < |x| <= max    subnormal            fp64: <= 1 ulp (subnormal spacing);  fp32: +-0
+//         NaN                    NaN                  NaN
+// No level loop may use frcp of a divisor that can be 0 or inf for finite inputs without a guard: the call
+// sites are listed with their guards in docs/TUNING_LOG.md 3.14.
 template <typename T> __device__ __forceinline__ T frcp(T x);
 template <> __device__ __forceinline__ double frcp<double>(double x) {
     double r = __builtin_amdgcn_rcp(x);
@@ -74,10 +86,15 @@ template <> __device__ __forceinline__ float frcp<float>(float x) {
 // exp() for the level loops.  ocml's exp re-materialises its 11 polynomial coefficients into VGPRs
 // on every call (destructive v_fmac form: 2 v_mov per coefficient, ~42 VALU per call); here the
 // coefficients travel as kernel arguments (`ExpK`), stay in registers across the loop and the
-// evaluation is 19 VALU: n = rint(x log2 e), r = x - n ln2 (two-term Cody-Waite), degree-12 Taylor
-// polynomial in Horner form on |r| <= ln2/2 (truncation 3e-17 relative), ldexp.  The argument is
+// evaluation is 19 VALU: n = rint(x log2 e), r = x - n ln2 (two-term Cody-Waite), degree-12 polynomial
+// in Horner form on |r| <= ln2/2, ldexp.  The polynomial is 1 + r + r^2/2 + r^3 g(r) with g fitted, not
+// truncated: the Taylor coefficients 1/3! .. 1/12! leave r^13/13! = 2.4e-16 of exp(r) at the interval
+// ends and measured 2.32 ulp; the fit's own error is 1e-18, so what remains is the rounding of the last
+// Horner steps.  Measured against a 50-digit reference (tests/test_math_primitives.py, table in
+// docs/TUNING_LOG.md 3.14): worst 0.86 ulp, ocml's exp 0.87 ulp on the same arguments.  The argument is
 // clamped to [-746, 710] first (exp(-746) = 0, exp(710) = inf in double): the autoconversion terms
 // exp(-(cld/crit)^2) reach arguments of -1e20, where the Cody-Waite reduction would lose all bits.
+// NaN stays NaN, -inf gives 0, +inf gives inf, results below 2^-1022 are subnormal (ldexp rounds them).
 template <typename T>
 struct ExpK {
     T l2e, ln2h, ln2l, c12, c11, c10, c9, c8, c7, c6, c5, c4, c3;
@@ -88,9 +105,17 @@ inline ExpK<T> make_expk() {
     k.l2e = T(1.4426950408889634);
     k.ln2h = T(6.93147180369123816490e-01);
     k.ln2l = T(1.90821492927058770002e-10);
-    k.c12 = T(1.0 / 479001600.0); k.c11 = T(1.0 / 39916800.0); k.c10 = T(1.0 / 3628800.0);
-    k.c9 = T(1.0 / 362880.0); k.c8 = T(1.0 / 40320.0); k.c7 = T(1.0 / 5040.0); k.c6 = T(1.0 / 720.0);
-    k.c5 = T(1.0 / 120.0); k.c4 = T(1.0 / 24.0); k.c3 = T(1.0 / 6.0);
+    // c3 .. c12: profiles/fit_exp_poly.py (Chebyshev fit of (exp(r) - 1 - r - r^2/2) / r^3 on |r| <= ln2/2)
+    k.c3 = T(1.66666666666666685e-01);
+    k.c4 = T(4.16666666666666644e-02);
+    k.c5 = T(8.33333333333006500e-03);
+    k.c6 = T(1.38888888888865540e-03);
+    k.c7 = T(1.98412698630405450e-04);
+    k.c8 = T(2.48015873171351639e-05);
+    k.c9 = T(2.75572684803100238e-06);
+    k.c10 = T(2.75572829840558774e-07);
+    k.c11 = T(2.51003758325613201e-08);
+    k.c12 = T(2.09112297297586281e-09);
     return k;
 }
 template <typename T> __device__ __forceinline__ T fexp(const ExpK<T>& k, T x);
@@ -133,6 +158,44 @@ template <typename T> __device__ __forceinline__ T rmin(T a, T b) { return a < b
 template <typename T> __device__ __forceinline__ T rmax(T a, T b) { return a > b ? a : b; }
 template <typename T> __device__ __forceinline__ T sq(T x) { return x * x; }
 template <typename T> __device__ __forceinline__ T cube(T x) { return x * x * x; }
+
+// The logistic forms of the mixed-phase weight (nonlinear/_stencils/cloudsc2.py:147, and its derivative in the TL / AD
+// stencils).  With u = 0.17 (t - RLPTRC), ex = exp(-2u) and rr = 1 / (1 + ex) - `fw2` is 2 * 0.17 (make_nlk):
+//     0.545 (tanh u + 1) = 1.09 rr          1 / cosh(u)^2 = 4 ex rr^2
+// one exponential and one reciprocal instead of tanh and cosh, and no cancellation in tanh(u) + 1 for cold t (u << 0,
+// where tanh u -> -1).  ex overflows to inf for t < RLPTRC - 2 088 K only; rr is then 0 and sech2 inf * 0 = NaN, far outside
+// any temperature.  cloudsc2_nl needs the weight alone; cloudsc2_tl and the forward sweep of cloudsc2_ad keep ex and rr for
+// sech2.  tests/primitives_probe.hip calls these two, so the accuracy test measures the code the level loops run.
+template <typename T>
+__device__ __forceinline__ T logistic_fwat(const ExpK<T>& xk, T fw2, T rlptrc, T t, T& ex, T& rr) {
+    ex = fexp<T>(xk, -fw2 * (t - rlptrc));
+    rr = frcp<T>(T(1.0) + ex);
+    return T(1.09) * rr;
+}
+template <typename T>
+__device__ __forceinline__ T logistic_fwat(const ExpK<T>& xk, T fw2, T rlptrc, T t) {
+    T ex, rr;
+    return logistic_fwat<T>(xk, fw2, rlptrc, t, ex, rr);
+}
+template <typename T>
+__device__ __forceinline__ T logistic_sech2(T ex, T rr) {
+    return T(4.0) * ex * rr * rr;
+}
+
+// Tangent-linear perturbation of the part of a precipitation flux f that evaporates, dpr f / prtot
+// (tangent_linear/_stencils/cloudsc2.py, the evaporation block): (dpr_i f + dpr f_i) / prtot - dpr f prtot_i / prtot^2, with
+// rpr = frcp(prtot).  When everything evaporates (dpr == prtot) the part is the flux itself and what is left of its
+// perturbation, f_i - evaporated_i, is 0; the reference's spelling gives exactly 0 there for 82 % of all operands,
+// this one with x * rpr for 46 %, and otherwise an ulp of perturbations that reach 1e12 at dt = 3600 s, which swamps
+// the levels below (docs/TUNING_LOG.md 3.14: which of the two happened depended on the last bit of an exp).  For that
+// case the same derivative is arranged as f_i + f / prtot (dpr_i - prtot_i): its second term is exactly 0 when the
+// capped dpr_i equals prtot_i, so the perturbation left is exactly 0.  The trajectory keeps the reference's dpr f / prtot.
+template <typename T>
+__device__ __forceinline__ T evaporated_i(T dpr, T dpr_i, T f, T f_i, T prtot, T prtot_i, T rpr) {
+    const T all = f_i + f * rpr * (dpr_i - prtot_i);
+    const T part = (dpr_i * f + dpr * f_i) * rpr - dpr * f * prtot_i * rpr * rpr;
+    return dpr == prtot ? all : part;
+}
 
 // ---- externals in the working precision -----------------------------------------------------
 template <typename T>

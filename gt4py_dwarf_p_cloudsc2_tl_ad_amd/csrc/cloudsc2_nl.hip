@@ -106,7 +106,7 @@ __device__ __forceinline__ NLOut<T> nl_level(const Ext<T>& e, const NLK<T>& kc, 
     if constexpr (LIN) {
         T z3es, r4;
         if (t < e.RTT) {
-            fwat = T(1.09) * frcp<T>(T(1.0) + fexp<T>(xk, -kc.fw2 * (t - e.RLPTRC)));
+            fwat = logistic_fwat<T>(xk, kc.fw2, e.RLPTRC, t);
             z3es = e.R3IES;
             r4 = ri;
         } else {

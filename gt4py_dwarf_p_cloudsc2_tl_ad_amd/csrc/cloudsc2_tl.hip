@@ -108,10 +108,9 @@ __device__ __forceinline__ TLOut<T> tl_level(const Ext<T>& e, const NLK<T>& kc, 
     const T rap = frcp<T>(x.ap);
     T fwat, fwat_i, z3es, z4es, r4;
     if (t < e.RTT) {
-        const T ex = fexp<T>(xk, -kc.fw2 * (t - e.RLPTRC));
-        const T rr = frcp<T>(T(1.0) + ex);
-        fwat = T(1.09) * rr;
-        fwat_i = T(0.545) * T(0.17) * t_i * (T(4.0) * ex * rr * rr);
+        T ex, rr;
+        fwat = logistic_fwat<T>(xk, kc.fw2, e.RLPTRC, t, ex, rr);
+        fwat_i = T(0.545) * T(0.17) * t_i * logistic_sech2<T>(ex, rr);
         z3es = e.R3IES;
         z4es = e.R4IES;
         r4 = ri;
@@ -400,11 +399,11 @@ __device__ __forceinline__ TLOut<T> tl_level(const Ext<T>& e, const NLK<T>& kc, 
             o.covptot_i = c.covptot_i;
             const T rpr = frcp<T>(prtot);
             evapr = dpr * rfln / prtot;
-            evapr_i = (dpr_i * rfln + dpr * rfln_i) * rpr - dpr * rfln * prtot_i * rpr * rpr;
+            evapr_i = evaporated_i<T>(dpr, dpr_i, rfln, rfln_i, prtot, prtot_i, rpr);
             rfln -= evapr;
             rfln_i -= evapr_i;
             evaps = dpr * sfln / prtot;
-            evaps_i = (dpr_i * sfln + dpr * sfln_i) * rpr - dpr * sfln * prtot_i * rpr * rpr;
+            evaps_i = evaporated_i<T>(dpr, dpr_i, sfln, sfln_i, prtot, prtot_i, rpr);
             sfln -= evaps;
             sfln_i -= evaps_i;
         }
