@@ -8,8 +8,8 @@ from __future__ import annotations
 
 import ctypes
 import os
-from ctypes import POINTER, c_char_p, c_double, c_float, c_int32, c_int64, c_void_p
-from typing import Optional
+from ctypes import POINTER, c_char_p, c_double, c_int32, c_int64, c_void_p
+from typing import Any, Dict, NamedTuple, Optional, Sequence, Tuple
 
 from .params import ABI_VERSION, Cloudsc2Params
 
@@ -17,28 +17,118 @@ LIB_NAME = "libcloudsc2_hip.so"
 #: CLOUDSC2_HIP_LIB overrides the library file (dev / A-B builds made by profiles/build_variants.sh); same checks apply
 LIB_PATH = os.environ.get("CLOUDSC2_HIP_LIB") or os.path.join(os.path.dirname(os.path.abspath(__file__)), LIB_NAME)
 
-NL_NUM_IN = 16
-NL_NUM_OUT = 10
-INC_NUM = 16
+# gtscript parameter names in C-ABI order (include/cloudsc2_hip.h enums)
+NL_IN = ("ap", "aph", "lu", "lude", "mfd", "mfu", "q", "qi", "ql", "qsat", "supsat", "t",
+         "tnd_cml_q", "tnd_cml_qi", "tnd_cml_ql", "tnd_cml_t")
+NL_OUT = ("clc", "covptot", "fhpsl", "fhpsn", "fplsl", "fplsn", "tnd_q", "tnd_qi", "tnd_ql", "tnd_t")
+INC = ("aph", "ap", "q", "qsat", "t", "ql", "qi", "lude", "lu", "mfu", "mfd",
+       "tnd_cml_t", "tnd_cml_q", "tnd_cml_ql", "tnd_cml_qi", "supsat")
 
+
+class Arg(NamedTuple):
+    """One argument of a stencil's C prototype after `(params, nx, nz, lev_stride)`; `stencils.HipStencil` builds the call
+    from these and `SIGNATURES` the ctypes `argtypes`.  Kinds:
+      ptrs      array of field pointers; `key`: the call keyword of every slot (None: a NULL slot; empty: the whole array is
+                NULL); `unless`: the scalar keyword whose presence replaces the array (it is then NULL and its keywords
+                are not accepted)
+      field     one field pointer; `key`: its keyword (None: NULL)
+      eta       the `in_eta` level vector
+      scalar    a double; `key`: its keyword (None: always `default`); `default`: the value when the keyword is absent
+                (None: the keyword is required)
+      partials  `out_partials`: float64 device buffer of taylor_blocks(nx) x [len(fs) x] len(NL_OUT) elements
+      fs        the step sizes: `(int32 count, const double* values)` - TWO C arguments
+      stream    the HIP stream"""
+    kind: str
+    key: Any = None
+    unless: Optional[str] = None
+    default: Optional[float] = None
+
+
+def _ptrs(fmt: str, base: Sequence[str], null: Optional[str] = None, unless: Optional[str] = None) -> Arg:
+    return Arg("ptrs", tuple(None if n == null else fmt.format(n) for n in base), unless)
+
+
+class Layout(NamedTuple):
+    entry: str                    # C entry points cloudsc2_<entry>_{f64,f32}
+    args: Tuple[Arg, ...]
+    nlev_offset: int = 1          # domain[2] = nz + nlev_offset
+    sets_nlev: bool = False       # external NLEV is checked against / taken from the storages (TL, AD)
+
+
+_IN, _IN_I = _ptrs("in_{}", NL_IN), _ptrs("in_{}_i", NL_IN)
+_OUT, _OUT_I, _REF = _ptrs("out_{}", NL_OUT), _ptrs("out_{}_i", NL_OUT), _ptrs("ref_{}", NL_OUT)
+_NO_PTRS, _ETA, _DT, _F, _STREAM = Arg("ptrs", key=()), Arg("eta"), Arg("scalar", "dt"), Arg("scalar", "f"), Arg("stream")
+
+#: THE description of every registered stencil: the argument order of its prototype in include/cloudsc2_hip.h.  Keyword
+#: set, pointer arrays, argtypes, exported symbols, "needs in_eta" and "sets NLEV" all follow from an entry here.
+#: Keyed by the names the reference registers with `@stencil_collection(name)`; the others are BUILD EXTENSIONS.
+LAYOUTS: Dict[str, Layout] = {
+    # nonlinear/_stencils/cloudsc2.py:24-60 (signature), :93-399 (body)
+    "cloudsc2_nl": Layout("nl", (_IN, _ETA, _OUT, _DT, _STREAM)),
+    # `saturation` + `cloudsc2_nl` in one launch: arguments of `cloudsc2_nl` minus `in_qsat`, plus `out_qsat`
+    "cloudsc2_nl_saturation": Layout("nl_fused", (_ptrs("in_{}", NL_IN, null="qsat"), _NO_PTRS, Arg("scalar", default=0.0),
+                                                  Arg("field", "out_qsat"), _ETA, _OUT, _DT, _STREAM)),
+    # `perturbed_state` + `cloudsc2_nl` in one launch (inputs read as in_X + f * in_X_i): plus the 16 `in_*_i` and `f`
+    "cloudsc2_nl_perturbed": Layout("nl_fused", (_IN, _IN_I, _F, Arg("field", key=None), _ETA, _OUT, _DT, _STREAM)),
+    # perturbed NL run + the Taylor test's reduction in one launch: `ref_*` are the 10 unperturbed outputs (read-only);
+    # `out_partials` receives, per workgroup, sum(NL(in + f in_i) - ref) in NL_OUT order.  Nothing else is written.
+    "cloudsc2_nl_taylor": Layout("nl_taylor", (_IN, _IN_I, _F, _ETA, _REF, Arg("partials"), _DT, _STREAM)),
+    # the same for ALL step sizes `fs` (up to 5 share one pass over the 42 words of a level); `out_partials` is
+    # (taylor_blocks(nx), len(fs), 10).  With `f_inc=<factor>` instead of the 16 `in_*_i` fields, `state_increment` is fused in
+    # as well: the increments are formed in the kernel as f_inc * in (external IGNORE_SUPSAT zeroes the supsat increment).
+    "cloudsc2_nl_taylor_multi": Layout("nl_taylor_multi", (_IN, _ptrs("in_{}_i", NL_IN, unless="f_inc"),
+                                                           Arg("scalar", "f_inc", default=0.0), Arg("fs"), _ETA, _REF,
+                                                           Arg("partials"), _DT, _STREAM)),
+    # tangent_linear/_stencils/cloudsc2.py:23-90 (signature), :124-774 (body)
+    "cloudsc2_tl": Layout("tl", (_IN, _IN_I, _ETA, _OUT, _OUT_I, _DT, _STREAM), sets_nlev=True),
+    # `state_increment` + `cloudsc2_tl` in one launch: the perturbations are f * in_X, formed in the kernel (external
+    # IGNORE_SUPSAT: the supsat perturbation is 0): arguments of `cloudsc2_tl` minus the 16 `in_*_i`, plus `f`
+    "cloudsc2_tl_incremented": Layout("tl_incremented", (_IN, _F, _ETA, _OUT, _OUT_I, _DT, _STREAM), sets_nlev=True),
+    # adjoint/_stencils/cloudsc2.py:24-90 (signature), :124-996 (body)
+    "cloudsc2_ad": Layout("ad", (_IN, _ptrs("in_{}_i", NL_OUT), _ETA, _OUT, _ptrs("out_{}_i", NL_IN), _DT, _STREAM),
+                          sets_nlev=True),
+    # `cloudsc2_ad` without its forward sweep: minus the ten `out_*` NL outputs, plus `traj_fplsl` / `traj_fplsn`, the flux
+    # outputs of a cloudsc2_nl / cloudsc2_tl call on the same state (read-only).  Only the 16 `out_*_i` adjoints are written.
+    # Driver switches only (no evaporation block).
+    "cloudsc2_ad_from_trajectory": Layout("ad_from_trajectory", (
+        _IN, _ptrs("in_{}_i", NL_OUT), _ETA, Arg("field", "traj_fplsl"), Arg("field", "traj_fplsn"),
+        _ptrs("out_{}_i", NL_IN), _DT, _STREAM), sets_nlev=True),
+    # common/_stencils/saturation.py:23-42; domain (nx, 1, nz)
+    "saturation": Layout("saturation", (Arg("field", "in_ap"), Arg("field", "in_t"), Arg("field", "out_qsat"), _STREAM),
+                         nlev_offset=0),
+    # common/_stencils/state_increment.py:22-80
+    "state_increment": Layout("state_increment", (_ptrs("in_{}", INC), _ptrs("out_{}_i", INC), _F, _STREAM)),
+    # common/_stencils/perturbed_state.py:22-91
+    "perturbed_state": Layout("perturbed_state", (_ptrs("in_{}", INC), _ptrs("in_{}_i", INC), _ptrs("out_{}", INC), _F,
+                                                  _STREAM)),
+}
+
+_PARR = POINTER(c_void_p)      # device pointers travel as integers (void*), never dereferenced on the host
+_CTYPES = {"ptrs": (_PARR,), "field": (c_void_p,), "eta": (c_void_p,), "scalar": (c_double,), "partials": (c_void_p,),
+           "fs": (c_int32, POINTER(c_double)), "stream": (c_void_p,)}
+
+
+def _signatures() -> Dict[str, Tuple[Any, Tuple[Any, ...]]]:
+    """symbol -> (restype, argtypes) of every entry point include/cloudsc2_hip.h declares"""
+    sig: Dict[str, Tuple[Any, Tuple[Any, ...]]] = {
+        "cloudsc2_abi_version": (c_int32, ()), "cloudsc2_params_sizeof": (c_int32, ()),
+        "cloudsc2_last_error": (c_char_p, ()), "cloudsc2_last_kernel": (c_char_p, ()),
+        "cloudsc2_device_count": (c_int32, ()), "cloudsc2_nl_taylor_blocks": (c_int32, (c_int32,)),
+        "cloudsc2_field_sums_blocks": (c_int32, (c_int32, c_int32)), "cloudsc2_column_dots_chunks": (c_int32, (c_int32,)),
+    }
+    reduction = (c_int32, c_int32, c_int64, c_int32, _PARR, _PARR, c_void_p)
+    for sfx in ("f64", "f32"):
+        sig[f"cloudsc2_field_sums_{sfx}"] = (c_int32, reduction + (c_void_p,))
+        sig[f"cloudsc2_column_dots_{sfx}"] = (c_int32, reduction + (c_int32, c_void_p))
+        for lay in LAYOUTS.values():
+            sig[f"cloudsc2_{lay.entry}_{sfx}"] = (c_int32, (POINTER(Cloudsc2Params), c_int32, c_int32, c_int64)
+                                                  + tuple(t for a in lay.args for t in _CTYPES[a.kind]))
+    return sig
+
+
+SIGNATURES = _signatures()
 #: every symbol include/cloudsc2_hip.h declares (tests check the library exports all of them)
-EXPORTED_SYMBOLS = (
-    "cloudsc2_abi_version", "cloudsc2_params_sizeof", "cloudsc2_last_error", "cloudsc2_last_kernel",
-    "cloudsc2_device_count",
-    "cloudsc2_nl_f64", "cloudsc2_nl_f32",
-    "cloudsc2_nl_fused_f64", "cloudsc2_nl_fused_f32",
-    "cloudsc2_nl_taylor_blocks", "cloudsc2_nl_taylor_f64", "cloudsc2_nl_taylor_f32",
-    "cloudsc2_nl_taylor_multi_f64", "cloudsc2_nl_taylor_multi_f32",
-    "cloudsc2_field_sums_blocks", "cloudsc2_field_sums_f64", "cloudsc2_field_sums_f32",
-    "cloudsc2_column_dots_chunks", "cloudsc2_column_dots_f64", "cloudsc2_column_dots_f32",
-    "cloudsc2_tl_f64", "cloudsc2_tl_f32",
-    "cloudsc2_tl_incremented_f64", "cloudsc2_tl_incremented_f32",
-    "cloudsc2_ad_f64", "cloudsc2_ad_f32",
-    "cloudsc2_ad_from_trajectory_f64", "cloudsc2_ad_from_trajectory_f32",
-    "cloudsc2_saturation_f64", "cloudsc2_saturation_f32",
-    "cloudsc2_state_increment_f64", "cloudsc2_state_increment_f32",
-    "cloudsc2_perturbed_state_f64", "cloudsc2_perturbed_state_f32",
-)
+EXPORTED_SYMBOLS = tuple(SIGNATURES)
 
 _lib: Optional[ctypes.CDLL] = None
 
@@ -48,64 +138,9 @@ class Cloudsc2LibraryError(RuntimeError):
 
 
 def _declare(lib: ctypes.CDLL) -> None:
-    PP = POINTER(Cloudsc2Params)
-    lib.cloudsc2_abi_version.restype = c_int32
-    lib.cloudsc2_abi_version.argtypes = []
-    lib.cloudsc2_params_sizeof.restype = c_int32
-    lib.cloudsc2_params_sizeof.argtypes = []
-    lib.cloudsc2_last_error.restype = c_char_p
-    lib.cloudsc2_last_error.argtypes = []
-    lib.cloudsc2_last_kernel.restype = c_char_p
-    lib.cloudsc2_last_kernel.argtypes = []
-    lib.cloudsc2_device_count.restype = c_int32
-    lib.cloudsc2_device_count.argtypes = []
-    lib.cloudsc2_nl_taylor_blocks.restype = c_int32
-    lib.cloudsc2_nl_taylor_blocks.argtypes = [c_int32]
-    lib.cloudsc2_field_sums_blocks.restype = c_int32
-    lib.cloudsc2_field_sums_blocks.argtypes = [c_int32, c_int32]
-    lib.cloudsc2_column_dots_chunks.restype = c_int32
-    lib.cloudsc2_column_dots_chunks.argtypes = [c_int32]
-    for sfx, real in (("f64", c_double), ("f32", c_float)):
-        del real  # device pointers travel as integers (void*), never dereferenced on the host
-        parr = POINTER(c_void_p)
-        common = [PP, c_int32, c_int32, c_int64]
-        f = getattr(lib, f"cloudsc2_nl_{sfx}")
-        f.restype = c_int32
-        f.argtypes = common + [parr, c_void_p, parr, c_double, c_void_p]
-        f = getattr(lib, f"cloudsc2_nl_fused_{sfx}")
-        f.restype = c_int32
-        f.argtypes = common + [parr, parr, c_double, c_void_p, c_void_p, parr, c_double, c_void_p]
-        f = getattr(lib, f"cloudsc2_nl_taylor_{sfx}")
-        f.restype = c_int32
-        f.argtypes = common + [parr, parr, c_double, c_void_p, parr, c_void_p, c_double, c_void_p]
-        f = getattr(lib, f"cloudsc2_nl_taylor_multi_{sfx}")
-        f.restype = c_int32
-        f.argtypes = common + [parr, parr, c_double, c_int32, POINTER(c_double), c_void_p, parr, c_void_p, c_double, c_void_p]
-        f = getattr(lib, f"cloudsc2_field_sums_{sfx}")
-        f.restype = c_int32
-        f.argtypes = [c_int32, c_int32, c_int64, c_int32, parr, parr, c_void_p, c_void_p]
-        f = getattr(lib, f"cloudsc2_column_dots_{sfx}")
-        f.restype = c_int32
-        f.argtypes = [c_int32, c_int32, c_int64, c_int32, parr, parr, c_void_p, c_int32, c_void_p]
-        f = getattr(lib, f"cloudsc2_tl_incremented_{sfx}")
-        f.restype = c_int32
-        f.argtypes = common + [parr, c_double, c_void_p, parr, parr, c_double, c_void_p]
-        for name in ("tl", "ad"):
-            f = getattr(lib, f"cloudsc2_{name}_{sfx}")
-            f.restype = c_int32
-            f.argtypes = common + [parr, parr, c_void_p, parr, parr, c_double, c_void_p]
-        f = getattr(lib, f"cloudsc2_ad_from_trajectory_{sfx}")
-        f.restype = c_int32
-        f.argtypes = common + [parr, parr, c_void_p, c_void_p, c_void_p, parr, c_double, c_void_p]
-        f = getattr(lib, f"cloudsc2_saturation_{sfx}")
-        f.restype = c_int32
-        f.argtypes = common + [c_void_p, c_void_p, c_void_p, c_void_p]
-        f = getattr(lib, f"cloudsc2_state_increment_{sfx}")
-        f.restype = c_int32
-        f.argtypes = common + [parr, parr, c_double, c_void_p]
-        f = getattr(lib, f"cloudsc2_perturbed_state_{sfx}")
-        f.restype = c_int32
-        f.argtypes = common + [parr, parr, parr, c_double, c_void_p]
+    for symbol, (restype, argtypes) in SIGNATURES.items():
+        fn = getattr(lib, symbol)
+        fn.restype, fn.argtypes = restype, list(argtypes)
 
 
 def load() -> ctypes.CDLL:
@@ -164,7 +199,4 @@ def check(rc: int, what: str) -> None:
 
 
 def ptr_array(ptrs) -> ctypes.Array:
-    arr = (c_void_p * len(ptrs))()
-    for i, p in enumerate(ptrs):
-        arr[i] = p
-    return arr
+    return (c_void_p * len(ptrs))(*ptrs)

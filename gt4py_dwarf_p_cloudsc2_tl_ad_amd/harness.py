@@ -42,7 +42,9 @@ import torch
 from .framework.timing import timing
 from .reductions import column_dots, field_sums
 from .physics import (Cloudsc2AD, Cloudsc2ADFromTrajectory, Cloudsc2NL, Cloudsc2NLPerturbed, Cloudsc2TL,
-                      Cloudsc2TLIncremented, PerturbedState, Saturation, StateIncrement, _as_dict)
+                      Cloudsc2TLIncremented, PerturbedState, Saturation, StateIncrement, _as_dict, _microphysics_externals,
+                      nl_input_keywords, nl_output_keywords, nl_output_position)
+from .stencils import NL_OUT, compile_stencil, taylor_blocks
 
 _TENDS = ("f_t", "f_q", "f_ql", "f_qi")
 _DIAGS = ("f_clc", "f_fhpsl", "f_fhpsn", "f_fplsl", "f_fplsn", "f_covptot")
@@ -107,6 +109,16 @@ def taylor_verdict(norms: Sequence[float]) -> Tuple[bool, str]:
     return True, f"The test passed with penalty {test}. HOORAY!"
 
 
+def taylor_mode(fused: bool, fused_norms: bool, fused_all: bool, store_perturbed: bool) -> str:
+    """What evaluates NL(x + f2 x_i) - NL(x) for the step sizes: "reference" (perturbed_state + cloudsc2_nl + a sum launch
+    per step size) or the build-extension stencil that replaces them."""
+    if fused_all:
+        return "cloudsc2_nl_taylor_multi"
+    if fused_norms or (fused and not store_perturbed):
+        return "cloudsc2_nl_taylor"
+    return "cloudsc2_nl_perturbed" if fused else "reference"
+
+
 class TaylorTest:
     def __init__(self, computational_grid, factor1: float, factor2s: Tuple[float, ...], kflag: int, lphylin: bool,
                  ldrain1d: bool, yoethf_params, yomcst_params, yrecldp_params, yrephli_params, yrncl_params,
@@ -114,43 +126,29 @@ class TaylorTest:
                  fused_norms: bool = False, fused_all: bool = False, graph: bool = False,
                  store_perturbed: bool = False) -> None:
         self.f1, self.f2s = factor1, tuple(factor2s)
-        self.fused_all = fused_all
-        self.fused_norms = fused_norms or fused_all or (fused and not store_perturbed)
-        self.fused = fused or self.fused_norms
+        self.mode = mode = taylor_mode(fused, fused_norms, fused_all, store_perturbed)
+        self.fused_all = mode == "cloudsc2_nl_taylor_multi"
+        self.fused_norms = mode in ("cloudsc2_nl_taylor", "cloudsc2_nl_taylor_multi")
+        self.fused = mode != "reference"
         self.graph = graph
         self._graphed: Optional[_GraphedRun] = None
         self._gt4py_config = gt4py_config
-        self._taylor = None
-        if self.fused_norms:
-            from .physics import _externals
-            from .stencils import compile_stencil
-
-            self._taylor = compile_stencil("cloudsc2_nl_taylor_multi" if fused_all else "cloudsc2_nl_taylor", _externals(
-                yoethf_params, yomcst_params, yrecldp_params, yrephli_params, yrphnc_params, ICALL=0, LPHYLIN=lphylin,
-                LDRAIN1D=ldrain1d, ZEPS1=1e-12, ZEPS2=1e-10, ZQMAX=0.5, ZSCAL=0.9))
         # no regularization in the Taylor test (validation.py:84-85)
-        yrncl = dict(yrncl_params.dict() if hasattr(yrncl_params, "dict") else yrncl_params)
-        yrncl["LREGCL"] = False
+        yrncl = dict(_as_dict(yrncl_params), LREGCL=False)
         kw = dict(enable_checks=enable_checks, gt4py_config=gt4py_config)
+        nl_args = (lphylin, ldrain1d, yoethf_params, yomcst_params, yrecldp_params, yrephli_params, yrphnc_params)
+        tl_args = (lphylin, ldrain1d, yoethf_params, yomcst_params, yrecldp_params, yrephli_params, yrncl, yrphnc_params)
         self.saturation = Saturation(computational_grid, kflag, lphylin, yoethf_params, yomcst_params, **kw)
-        self.cloudsc2_nl = Cloudsc2NL(computational_grid, lphylin, ldrain1d, yoethf_params, yomcst_params,
-                                      yrecldp_params, yrephli_params, yrphnc_params, **kw)
-        if fused_all:
-            self.cloudsc2_tl = Cloudsc2TLIncremented(computational_grid, factor1, False, lphylin, ldrain1d, yoethf_params,
-                                                     yomcst_params, yrecldp_params, yrephli_params, yrncl, yrphnc_params, **kw)
-        else:
-            self.cloudsc2_tl = Cloudsc2TL(computational_grid, lphylin, ldrain1d, yoethf_params, yomcst_params,
-                                          yrecldp_params, yrephli_params, yrncl, yrphnc_params, **kw)
+        self.cloudsc2_nl = Cloudsc2NL(computational_grid, *nl_args, **kw)
+        self.cloudsc2_tl = (Cloudsc2TLIncremented(computational_grid, factor1, False, *tl_args, **kw) if self.fused_all
+                            else Cloudsc2TL(computational_grid, *tl_args, **kw))
         self.state_increment = StateIncrement(computational_grid, factor1, **kw)
-        if self.fused_norms:
-            self.perturbed_states = [None] * len(self.f2s)
-        elif self.fused:
+        self._taylor = compile_stencil(mode, _microphysics_externals(*nl_args)) if self.fused_norms else None
+        self.perturbed_states = [None] * len(self.f2s)
+        if mode == "cloudsc2_nl_perturbed":
             # build extension: perturbation applied inside the NL kernel's loads (no perturbed copy of the state)
-            self.perturbed_nls = [Cloudsc2NLPerturbed(computational_grid, f2, lphylin, ldrain1d, yoethf_params,
-                                                      yomcst_params, yrecldp_params, yrephli_params, yrphnc_params,
-                                                      **kw) for f2 in self.f2s]
-            self.perturbed_states = [None] * len(self.f2s)
-        else:
+            self.perturbed_nls = [Cloudsc2NLPerturbed(computational_grid, f2, *nl_args, **kw) for f2 in self.f2s]
+        elif mode == "reference":
             self.perturbed_states = [PerturbedState(computational_grid, f2, **kw) for f2 in self.f2s]
         self.diags_sat: Dict[str, Any] = {}
         self.state_i: Dict[str, Any] = {}
@@ -196,17 +194,16 @@ class TaylorTest:
         with timing("norms"):
             # denominators: sum of each TL perturbation field (one launch, one small device vector)
             rows = [field_sums([getattr(self, k + "_tl")[n + "_i"].data for k, n in names])]
-        if self.fused_all:
+        if self.mode == "cloudsc2_nl_taylor_multi":
             with timing("run"):
                 rows.append(self._fused_diffs_all(state, timestep, names))
             return torch.cat([rows[0].reshape(1, -1), rows[1]])
         for i, perturbed_state in enumerate(self.perturbed_states):
-            if self.fused_norms:
-                with timing("run"):
-                    rows.append(self._fused_diffs(state, timestep, self.f2s[i], names))
-                continue
             with timing("run"):
-                if self.fused:
+                if self.mode == "cloudsc2_nl_taylor":
+                    rows.append(self._fused_diffs(state, timestep, self.f2s[i], names))
+                    continue
+                if self.mode == "cloudsc2_nl_perturbed":
                     self.tends_nl_p, self.diags_nl_p = self.perturbed_nls[i](
                         state, timestep, out_tendencies=self.tends_nl_p, out_diagnostics=self.diags_nl_p)
                 else:
@@ -220,6 +217,14 @@ class TaylorTest:
                                        [getattr(self, k + "_nl")[n].data for k, n in names]))
         return torch.stack(rows)
 
+    def stencil_sequence(self) -> List[str]:
+        """the stencils one run launches, in order (the reductions of the norms aside)"""
+        head = ["saturation", "cloudsc2_nl"]
+        if self.mode == "cloudsc2_nl_taylor_multi":
+            return head + ["cloudsc2_tl_incremented", self.mode]
+        per_step = ["perturbed_state", "cloudsc2_nl"] if self.mode == "reference" else [self.mode]
+        return head + ["state_increment", "cloudsc2_tl"] + per_step * len(self.f2s)
+
     def _finish(self, sums: torch.Tensor) -> np.ndarray:
         """The host side of a run: ONE all-reduce over the column shards, ONE copy to the host, then get_norm per step
         size (validation.py:219-237)."""
@@ -227,54 +232,37 @@ class TaylorTest:
             host = _allreduce(sums.clone() if self.graph else sums, "sum").cpu().numpy()
             return np.array([self._norm(f2, host[1 + i], host[0]) for i, f2 in enumerate(self.f2s)])
 
-    def _nl_fields(self, state, increments: bool = True):
-        from .stencils import NL_IN, NL_OUT
-
-        kw = {}
-        for n in NL_IN:
-            kw["in_" + n] = state["f_" + n].data
-            if increments:
-                kw["in_" + n + "_i"] = state["f_" + n + "_i"].data
-        for n in NL_OUT:   # unperturbed outputs: tendencies are published as f_q / f_qi / f_ql / f_t
-            kw["ref_" + n] = (self.tends_nl["f_" + n[len("tnd_"):]] if n.startswith("tnd_") else self.diags_nl["f_" + n]).data
-        any_f = state["f_ap"].data
-        kw["in_eta"] = state["f_eta"].data if hasattr(state["f_eta"], "data") else state["f_eta"]
-        return kw, any_f.shape[0], any_f.shape[2] - 1, any_f.device
-
     def _out_index(self, names, device) -> torch.Tensor:
         """positions of `names` in NL_OUT order, as a DEVICE index (made once: a host list would be copied to the device
         on every use, which a HIP-graph capture does not allow)"""
-        from .stencils import NL_OUT
-
         idx = self.__dict__.get("_idx")
         if idx is None or idx.device != device:
-            idx = torch.tensor([NL_OUT.index(("tnd_" + n[2:]) if k == "tends" else n[2:]) for k, n in names],
-                               dtype=torch.long, device=device)
+            idx = torch.tensor([nl_output_position(n, k == "tends") for k, n in names], dtype=torch.long, device=device)
             self._idx = idx
         return idx
 
+    def _launch_taylor(self, state, timestep: timedelta, increments: bool, partials_shape, **scalars) -> torch.Tensor:
+        """one launch of the fused Taylor stencil on the state and the unperturbed outputs; returns its `out_partials`"""
+        kw = nl_input_keywords(state, increments)
+        kw.update(nl_output_keywords("ref_", self.tends_nl, self.diags_nl))
+        nx, _, nlev = kw["in_ap"].shape
+        cfg = self._gt4py_config
+        part = torch.empty((taylor_blocks(nx),) + partials_shape, dtype=torch.float64, device=kw["in_ap"].device)
+        self._taylor(**kw, **scalars, out_partials=part, dt=float(timestep.total_seconds()), origin=(0, 0, 0),
+                     domain=(nx, 1, nlev), validate_args=cfg.validate_args, exec_info=cfg.exec_info)
+        return part
+
     def _fused_diffs(self, state, timestep: timedelta, f2: float, names) -> torch.Tensor:
         """sum(NL(x + f2 x_i) - NL(x)) per output field, formed in the epilogue of ONE kernel launch."""
-        from .stencils import NL_OUT, taylor_blocks
-
-        kw, nx, nz, device = self._nl_fields(state)
-        part = torch.empty((taylor_blocks(nx), len(NL_OUT)), dtype=torch.float64, device=device)
-        cfg = self._gt4py_config
-        self._taylor(**kw, out_partials=part, f=f2, dt=float(timestep.total_seconds()), origin=(0, 0, 0),
-                     domain=(nx, 1, nz + 1), validate_args=cfg.validate_args, exec_info=cfg.exec_info)
-        return part.sum(dim=0).index_select(0, self._out_index(names, device))      # fixed block order: deterministic
+        part = self._launch_taylor(state, timestep, True, (len(NL_OUT),), f=f2)
+        return part.sum(dim=0).index_select(0, self._out_index(names, part.device))      # fixed block order: deterministic
 
     def _fused_diffs_all(self, state, timestep: timedelta, names) -> torch.Tensor:
-        """(number of step sizes, 10): the sums of every step size from ceil(n / 5) launches that share their loads."""
-        from .stencils import NL_OUT, taylor_blocks
-
-        kw, nx, nz, device = self._nl_fields(state, increments=False)
-        part = torch.empty((taylor_blocks(nx), len(self.f2s), len(NL_OUT)), dtype=torch.float64, device=device)
-        cfg = self._gt4py_config
-        self._taylor(**kw, out_partials=part, fs=self.f2s, f_inc=float(cfg.dtypes.float(self.f1)),
-                     dt=float(timestep.total_seconds()), origin=(0, 0, 0),
-                     domain=(nx, 1, nz + 1), validate_args=cfg.validate_args, exec_info=cfg.exec_info)
-        return part.sum(dim=0).index_select(1, self._out_index(names, device))
+        """(number of step sizes, 10): the sums of every step size from ceil(n / 5) launches that share their loads and
+        form the increments f1 * x themselves."""
+        f_inc = float(self._gt4py_config.dtypes.float(self.f1))
+        part = self._launch_taylor(state, timestep, False, (len(self.f2s), len(NL_OUT)), fs=self.f2s, f_inc=f_inc)
+        return part.sum(dim=0).index_select(1, self._out_index(names, part.device))
 
     @staticmethod
     def _norm(f2: float, diffs: np.ndarray, sums_tl: np.ndarray) -> float:

@@ -10,16 +10,16 @@ for use where the reference checkout is not available (the GPU box) and as the i
   Cloudsc2AD       .../physics/adjoint/microphysics.py:46-238
 
 Same class names, constructor arguments, state / tendency / diagnostic field names, units and call
-protocol (`component(state, timestep, out_tendencies=..., out_diagnostics=...)`); the bodies are
-table-driven: the field lists of include/cloudsc2_hip.h generate the property dicts and the keyword
-arguments of the stencil calls.  Parameter groups may be the reference's pydantic models or plain
-mappings (anything with `.dict()` or `.items()`).
+protocol (`component(state, timestep, out_tendencies=..., out_diagnostics=...)`).  Every component is ONE field map
+(`_FIELD_MAP`): the property dicts and the keyword arguments of the stencil call are generated from it, and a build
+extension states only its difference from the component it extends.  Parameter groups may be the reference's pydantic
+models or plain mappings (anything with `.dict()` or `.items()`).
 """
 from __future__ import annotations
 
 from datetime import timedelta
 from functools import cached_property
-from typing import Any, Dict
+from typing import Any, Dict, NamedTuple, Optional, Sequence, Tuple
 
 from .framework.components import DiagnosticComponent, ImplicitTendencyComponent
 from .framework.grid import I, J, K
@@ -38,7 +38,9 @@ _DIAG_OUT = ("clc", "covptot", "fhpsl", "fhpsn", "fplsl", "fplsn")      # NL out
 _TEND_OUT = ("tnd_q", "tnd_qi", "tnd_ql", "tnd_t")                       # NL outputs kept as tendencies
 
 
-def _prop(stencil_name: str) -> Dict[str, Any]:
+def _prop(stencil_name: Optional[str]) -> Dict[str, Any]:
+    if stencil_name is None:                      # the eta level vector
+        return {"grid_dims": (K,), "units": ""}
     kdim = K - 1 / 2 if stencil_name in _HALF else K
     return {"grid_dims": (I, J, kdim), "units": _UNITS[stencil_name]}
 
@@ -59,131 +61,145 @@ def _externals(*groups: Any, **literals: Any) -> Dict[str, Any]:
     return ext
 
 
-def _stencil_common(component) -> Dict[str, Any]:
-    cfg = component.gt4py_config
-    return dict(origin=(0, 0, 0), validate_args=cfg.validate_args, exec_info=cfg.exec_info)
+def _microphysics_externals(lphylin: bool, ldrain1d: bool, *groups: Any, **more: Any) -> Dict[str, Any]:
+    """externals of the cloudsc2_* stencils (nonlinear/microphysics.py:64-78 and its TL / AD counterparts)"""
+    return _externals(*groups, ICALL=0, LPHYLIN=lphylin, LDRAIN1D=ldrain1d, ZEPS1=1e-12, ZEPS2=1e-10, ZQMAX=0.5, ZSCAL=0.9,
+                      **more)
 
 
-# ---------------------------------------------------------------------------------- small components
-class EtaLevels(DiagnosticComponent):
-    """eta[k] = ap[column 0, k] / aph[column 0, nz] - one device slice operation instead of the
-    reference's nz-step Python loop (diagnostics.py:42-45)."""
+def _tend_name(stencil_name: str) -> str:
+    """NL tendency outputs are published as f_q / f_qi / f_ql / f_t (nonlinear/microphysics.py:103-108)."""
+    return "f_" + stencil_name[len("tnd_"):]
+
+
+class _Row(NamedTuple):
+    name: str                 # key in the state / output dict
+    where: str                # the dict it lives in: "state", "tend" or "diag"
+    keyword: Optional[str]    # stencil keyword (None: published, but not an argument of the stencil)
+    field: Optional[str]      # stencil field name that gives units and half-level-ness (None: the eta vector)
+
+
+def _state(base: Sequence[str], sfx: str = "") -> Tuple[_Row, ...]:
+    return tuple(_Row(f"f_{n}{sfx}", "state", f"in_{n}{sfx}", n) for n in base)
+
+
+def _diags(base: Sequence[str], sfx: str = "") -> Tuple[_Row, ...]:
+    return tuple(_Row(f"f_{n}{sfx}", "diag", f"out_{n}{sfx}", n) for n in base)
+
+
+def _nl_outputs(*sfxs: str) -> Tuple[_Row, ...]:
+    """the ten NL outputs: six diagnostics, four tendencies - per field, once per suffix ("" and "_i" for TL)"""
+    return (tuple(r for n in _DIAG_OUT for sfx in sfxs for r in _diags((n,), sfx))
+            + tuple(_Row(_tend_name(n) + sfx, "tend", f"out_{n}{sfx}", n) for n in _TEND_OUT for sfx in sfxs))
+
+
+_ETA = (_Row("f_eta", "state", "in_eta", None),)
+
+
+class _FieldMapped:
+    """property dicts and stencil keywords of a component, from its `_FIELD_MAP`"""
+
+    _FIELD_MAP: Tuple[_Row, ...] = ()
+
+    def _props(self, where: str) -> Dict[str, Dict[str, Any]]:
+        return {r.name: _prop(r.field) for r in self._FIELD_MAP if r.where == where}
 
     @cached_property
     def input_grid_properties(self):
-        return {"f_ap": _prop("ap"), "f_aph": _prop("aph")}
+        return self._props("state")
 
     @cached_property
     def diagnostic_grid_properties(self):
-        return {"f_eta": {"grid_dims": (K,), "units": ""}}
+        return self._props("diag")
+
+    def _call_stencil(self, stencil, nlev_offset: int, dicts: Dict[str, Any], **scalars: Any) -> None:
+        g, cfg = self.computational_grid, self.gt4py_config
+        kw = {r.keyword: dicts[r.where][r.name] for r in self._FIELD_MAP if r.keyword}
+        stencil(**kw, **scalars, domain=(g.nx, 1, g.nz + nlev_offset), origin=(0, 0, 0),
+                validate_args=cfg.validate_args, exec_info=cfg.exec_info)
+
+
+# ---------------------------------------------------------------------------------- small components
+class EtaLevels(_FieldMapped, DiagnosticComponent):
+    """eta[k] = ap[column 0, k] / aph[column 0, nz] - one device slice operation instead of the
+    reference's nz-step Python loop (diagnostics.py:42-45)."""
+
+    _FIELD_MAP = (_Row("f_ap", "state", None, "ap"), _Row("f_aph", "state", None, "aph"), _Row("f_eta", "diag", None, None))
 
     def array_call(self, state, out) -> None:
         nz = self.computational_grid.nz
         out["f_eta"][:nz] = state["f_ap"][0, 0, :nz] / state["f_aph"][0, 0, nz]
 
 
-class Saturation(DiagnosticComponent):
+class Saturation(_FieldMapped, DiagnosticComponent):
+    _FIELD_MAP = _state(("ap", "t")) + _diags(("qsat",))
+
     def __init__(self, computational_grid, kflag: int, lphylin: bool, yoethf_params, yomcst_params, *,
                  enable_checks: bool = True, gt4py_config) -> None:
         super().__init__(computational_grid, enable_checks=enable_checks, gt4py_config=gt4py_config)
         ext = _externals(yoethf_params, yomcst_params, KFLAG=kflag, LPHYLIN=lphylin, QMAX=0.5)
         self.saturation = self.compile_stencil("saturation", ext)
 
-    @cached_property
-    def input_grid_properties(self):
-        return {"f_ap": _prop("ap"), "f_t": _prop("t")}
-
-    @cached_property
-    def diagnostic_grid_properties(self):
-        return {"f_qsat": _prop("qsat")}
-
     def array_call(self, state, out) -> None:
-        g = self.computational_grid
-        self.saturation(in_ap=state["f_ap"], in_t=state["f_t"], out_qsat=out["f_qsat"],
-                        domain=(g.nx, 1, g.nz), **_stencil_common(self))
+        self._call_stencil(self.saturation, 0, {"state": state, "diag": out})
 
 
-class StateIncrement(DiagnosticComponent):
+class StateIncrement(_FieldMapped, DiagnosticComponent):
+    _FIELD_MAP = _state(INC) + _diags(INC, "_i")
+
     def __init__(self, computational_grid, factor: float, ignore_supsat: bool = False, *,
                  enable_checks: bool = True, gt4py_config) -> None:
         super().__init__(computational_grid, enable_checks=enable_checks, gt4py_config=gt4py_config)
         self.f = gt4py_config.dtypes.float(factor)
         self.increment = self.compile_stencil("state_increment", {"IGNORE_SUPSAT": ignore_supsat})
 
-    @cached_property
-    def input_grid_properties(self):
-        return {"f_" + n: _prop(n) for n in INC}
-
-    @cached_property
-    def diagnostic_grid_properties(self):
-        return {"f_" + n + "_i": _prop(n) for n in INC}
-
     def array_call(self, state, out) -> None:
-        g = self.computational_grid
-        kw = {"in_" + n: state["f_" + n] for n in INC}
-        kw.update({"out_" + n + "_i": out["f_" + n + "_i"] for n in INC})
-        self.increment(**kw, f=self.f, domain=(g.nx, 1, g.nz + 1), **_stencil_common(self))
+        self._call_stencil(self.increment, 1, {"state": state, "diag": out}, f=self.f)
 
 
-class PerturbedState(DiagnosticComponent):
+class PerturbedState(_FieldMapped, DiagnosticComponent):
+    _FIELD_MAP = _state(INC) + _state(INC, "_i") + _diags(INC)
+
     def __init__(self, computational_grid, factor: float, *, enable_checks: bool = True, gt4py_config) -> None:
         super().__init__(computational_grid, enable_checks=enable_checks, gt4py_config=gt4py_config)
         self.f = gt4py_config.dtypes.float(factor)
         self.perturbed_state = self.compile_stencil("perturbed_state", {})
 
-    @cached_property
-    def input_grid_properties(self):
-        props = {"f_" + n: _prop(n) for n in INC}
-        props.update({"f_" + n + "_i": _prop(n) for n in INC})
-        return props
-
-    @cached_property
-    def diagnostic_grid_properties(self):
-        return {"f_" + n: _prop(n) for n in INC}
-
     def array_call(self, state, out) -> None:
-        g = self.computational_grid
-        kw = {"in_" + n: state["f_" + n] for n in INC}
-        kw.update({"in_" + n + "_i": state["f_" + n + "_i"] for n in INC})
-        kw.update({"out_" + n: out["f_" + n] for n in INC})
-        self.perturbed_state(**kw, f=self.f, domain=(g.nx, 1, g.nz + 1), **_stencil_common(self))
+        self._call_stencil(self.perturbed_state, 1, {"state": state, "diag": out}, f=self.f)
 
 
 # ---------------------------------------------------------------------------------- microphysics
-def _tend_name(stencil_name: str) -> str:
-    """NL tendency outputs are published as f_q / f_qi / f_ql / f_t (nonlinear/microphysics.py:103-108)."""
-    return "f_" + stencil_name[len("tnd_"):]
+class _Microphysics(_FieldMapped, ImplicitTendencyComponent):
+    """the call every cloudsc2_* component makes: its field map, `dt`, and `f` where the component carries a factor"""
 
-
-class Cloudsc2NL(ImplicitTendencyComponent):
-    def __init__(self, computational_grid, lphylin: bool, ldrain1d: bool, yoethf_params, yomcst_params,
-                 yrecldp_params, yrephli_params, yrphnc_params, *, enable_checks: bool = True, gt4py_config) -> None:
-        super().__init__(computational_grid, enable_checks=enable_checks, gt4py_config=gt4py_config)
-        ext = _externals(yoethf_params, yomcst_params, yrecldp_params, yrephli_params, yrphnc_params,
-                         ICALL=0, LPHYLIN=lphylin, LDRAIN1D=ldrain1d, ZEPS1=1e-12, ZEPS2=1e-10, ZQMAX=0.5, ZSCAL=0.9)
-        self.cloudsc2 = self.compile_stencil("cloudsc2_nl", ext)
-
-    @cached_property
-    def input_grid_properties(self):
-        props = {"f_" + n: _prop(n) for n in NL_IN}
-        props["f_eta"] = {"grid_dims": (K,), "units": ""}
-        return props
+    f: Optional[Any] = None
+    _stencil_name = ""
+    _more_externals: Dict[str, Any] = {}       # what a build extension adds to the externals of the component it extends
 
     @cached_property
     def tendency_grid_properties(self):
-        return {_tend_name(n): _prop(n) for n in _TEND_OUT}
+        return self._props("tend")
 
-    @cached_property
-    def diagnostic_grid_properties(self):
-        return {"f_" + n: _prop(n) for n in _DIAG_OUT}
+    def _compile(self, lphylin: bool, ldrain1d: bool, *groups: Any, **more: Any) -> None:
+        ext = _microphysics_externals(lphylin, ldrain1d, *groups, **more, **self._more_externals)
+        self.cloudsc2 = self.compile_stencil(self._stencil_name, ext)
 
     def array_call(self, state, timestep: timedelta, out_tendencies, out_diagnostics, overwrite_tendencies) -> None:
-        g = self.computational_grid
-        kw = {"in_" + n: state["f_" + n] for n in NL_IN}
-        kw.update({"out_" + n: out_diagnostics["f_" + n] for n in _DIAG_OUT})
-        kw.update({"out_" + n: out_tendencies[_tend_name(n)] for n in _TEND_OUT})
-        self.cloudsc2(**kw, in_eta=state["f_eta"], dt=self.gt4py_config.dtypes.float(timestep.total_seconds()),
-                      domain=(g.nx, 1, g.nz + 1), **_stencil_common(self))
+        scalars = {"dt": self.gt4py_config.dtypes.float(timestep.total_seconds())}
+        if self.f is not None:
+            scalars["f"] = self.f
+        self._call_stencil(self.cloudsc2, 1, {"state": state, "tend": out_tendencies, "diag": out_diagnostics}, **scalars)
+
+
+class Cloudsc2NL(_Microphysics):
+    _FIELD_MAP = _state(NL_IN) + _ETA + _nl_outputs("")
+    _stencil_name = "cloudsc2_nl"
+
+    def __init__(self, computational_grid, lphylin: bool, ldrain1d: bool, yoethf_params, yomcst_params,
+                 yrecldp_params, yrephli_params, yrphnc_params, *, enable_checks: bool = True, gt4py_config) -> None:
+        super().__init__(computational_grid, enable_checks=enable_checks, gt4py_config=gt4py_config)
+        self._compile(lphylin, ldrain1d, yoethf_params, yomcst_params, yrecldp_params, yrephli_params, yrphnc_params)
 
 
 class Cloudsc2NLSaturation(Cloudsc2NL):
@@ -191,119 +207,35 @@ class Cloudsc2NLSaturation(Cloudsc2NL):
     Same inputs as `Cloudsc2NL` minus `f_qsat`, which becomes an additional diagnostic output; the result is
     bit-identical to calling the two components in sequence (tests/test_hip_nl.py)."""
 
-    def __init__(self, computational_grid, lphylin: bool, ldrain1d: bool, yoethf_params, yomcst_params,
-                 yrecldp_params, yrephli_params, yrphnc_params, *, enable_checks: bool = True, gt4py_config) -> None:
-        ImplicitTendencyComponent.__init__(self, computational_grid, enable_checks=enable_checks,
-                                           gt4py_config=gt4py_config)
-        ext = _externals(yoethf_params, yomcst_params, yrecldp_params, yrephli_params, yrphnc_params,
-                         ICALL=0, LPHYLIN=lphylin, LDRAIN1D=ldrain1d, ZEPS1=1e-12, ZEPS2=1e-10, ZQMAX=0.5, ZSCAL=0.9,
-                         KFLAG=1, QMAX=0.5)
-        self.cloudsc2 = self.compile_stencil("cloudsc2_nl_saturation", ext)
-
-    @cached_property
-    def input_grid_properties(self):
-        props = {"f_" + n: _prop(n) for n in NL_IN if n != "qsat"}
-        props["f_eta"] = {"grid_dims": (K,), "units": ""}
-        return props
-
-    @cached_property
-    def diagnostic_grid_properties(self):
-        props = {"f_" + n: _prop(n) for n in _DIAG_OUT}
-        props["f_qsat"] = _prop("qsat")
-        return props
-
-    def array_call(self, state, timestep: timedelta, out_tendencies, out_diagnostics, overwrite_tendencies) -> None:
-        g = self.computational_grid
-        kw = {"in_" + n: state["f_" + n] for n in NL_IN if n != "qsat"}
-        kw["out_qsat"] = out_diagnostics["f_qsat"]
-        kw.update({"out_" + n: out_diagnostics["f_" + n] for n in _DIAG_OUT})
-        kw.update({"out_" + n: out_tendencies[_tend_name(n)] for n in _TEND_OUT})
-        self.cloudsc2(**kw, in_eta=state["f_eta"], dt=self.gt4py_config.dtypes.float(timestep.total_seconds()),
-                      domain=(g.nx, 1, g.nz + 1), **_stencil_common(self))
+    _FIELD_MAP = tuple(r for r in Cloudsc2NL._FIELD_MAP if r.name != "f_qsat") + _diags(("qsat",))
+    _stencil_name = "cloudsc2_nl_saturation"
+    _more_externals = {"KFLAG": 1, "QMAX": 0.5}
 
 
 class Cloudsc2NLPerturbed(Cloudsc2NL):
     """BUILD EXTENSION: `PerturbedState(factor)` + `Cloudsc2NL` as ONE kernel launch (stencil
     `cloudsc2_nl_perturbed`): the state fields are read as x + factor * x_i on the fly."""
 
+    _FIELD_MAP = Cloudsc2NL._FIELD_MAP + _state(NL_IN, "_i")
+    _stencil_name = "cloudsc2_nl_perturbed"
+
     def __init__(self, computational_grid, factor: float, lphylin: bool, ldrain1d: bool, yoethf_params, yomcst_params,
                  yrecldp_params, yrephli_params, yrphnc_params, *, enable_checks: bool = True, gt4py_config) -> None:
-        ImplicitTendencyComponent.__init__(self, computational_grid, enable_checks=enable_checks,
-                                           gt4py_config=gt4py_config)
         self.f = gt4py_config.dtypes.float(factor)
-        ext = _externals(yoethf_params, yomcst_params, yrecldp_params, yrephli_params, yrphnc_params,
-                         ICALL=0, LPHYLIN=lphylin, LDRAIN1D=ldrain1d, ZEPS1=1e-12, ZEPS2=1e-10, ZQMAX=0.5, ZSCAL=0.9)
-        self.cloudsc2 = self.compile_stencil("cloudsc2_nl_perturbed", ext)
-
-    @cached_property
-    def input_grid_properties(self):
-        props = {"f_eta": {"grid_dims": (K,), "units": ""}}
-        for n in NL_IN:
-            props["f_" + n] = _prop(n)
-            props["f_" + n + "_i"] = _prop(n)
-        return props
-
-    def array_call(self, state, timestep: timedelta, out_tendencies, out_diagnostics, overwrite_tendencies) -> None:
-        g = self.computational_grid
-        kw = {}
-        for n in NL_IN:
-            kw["in_" + n] = state["f_" + n]
-            kw["in_" + n + "_i"] = state["f_" + n + "_i"]
-        kw.update({"out_" + n: out_diagnostics["f_" + n] for n in _DIAG_OUT})
-        kw.update({"out_" + n: out_tendencies[_tend_name(n)] for n in _TEND_OUT})
-        self.cloudsc2(**kw, in_eta=state["f_eta"], f=self.f,
-                      dt=self.gt4py_config.dtypes.float(timestep.total_seconds()),
-                      domain=(g.nx, 1, g.nz + 1), **_stencil_common(self))
+        super().__init__(computational_grid, lphylin, ldrain1d, yoethf_params, yomcst_params, yrecldp_params,
+                         yrephli_params, yrphnc_params, enable_checks=enable_checks, gt4py_config=gt4py_config)
 
 
-class Cloudsc2TL(ImplicitTendencyComponent):
+class Cloudsc2TL(_Microphysics):
+    _FIELD_MAP = _state(NL_IN) + _state(NL_IN, "_i") + _ETA + _nl_outputs("", "_i")
+    _stencil_name = "cloudsc2_tl"
+
     def __init__(self, computational_grid, lphylin: bool, ldrain1d: bool, yoethf_params, yomcst_params,
                  yrecldp_params, yrephli_params, yrncl_params, yrphnc_params, *, enable_checks: bool = True,
                  gt4py_config) -> None:
         super().__init__(computational_grid, enable_checks=enable_checks, gt4py_config=gt4py_config)
-        ext = _externals(yoethf_params, yomcst_params, yrecldp_params, yrephli_params, yrncl_params, yrphnc_params,
-                         ICALL=0, LPHYLIN=lphylin, LDRAIN1D=ldrain1d, NLEV=computational_grid.nz,
-                         ZEPS1=1e-12, ZEPS2=1e-10, ZQMAX=0.5, ZSCAL=0.9)
-        self.cloudsc2 = self.compile_stencil("cloudsc2_tl", ext)
-
-    @cached_property
-    def input_grid_properties(self):
-        props = {"f_eta": {"grid_dims": (K,), "units": ""}}
-        for n in NL_IN:
-            props["f_" + n] = _prop(n)
-            props["f_" + n + "_i"] = _prop(n)
-        return props
-
-    @cached_property
-    def tendency_grid_properties(self):
-        props = {}
-        for n in _TEND_OUT:
-            props[_tend_name(n)] = _prop(n)
-            props[_tend_name(n) + "_i"] = _prop(n)
-        return props
-
-    @cached_property
-    def diagnostic_grid_properties(self):
-        props = {}
-        for n in _DIAG_OUT:
-            props["f_" + n] = _prop(n)
-            props["f_" + n + "_i"] = _prop(n)
-        return props
-
-    def array_call(self, state, timestep: timedelta, out_tendencies, out_diagnostics, overwrite_tendencies) -> None:
-        g = self.computational_grid
-        kw = {}
-        for n in NL_IN:
-            kw["in_" + n] = state["f_" + n]
-            kw["in_" + n + "_i"] = state["f_" + n + "_i"]
-        for n in _DIAG_OUT:
-            kw["out_" + n] = out_diagnostics["f_" + n]
-            kw["out_" + n + "_i"] = out_diagnostics["f_" + n + "_i"]
-        for n in _TEND_OUT:
-            kw["out_" + n] = out_tendencies[_tend_name(n)]
-            kw["out_" + n + "_i"] = out_tendencies[_tend_name(n) + "_i"]
-        self.cloudsc2(**kw, in_eta=state["f_eta"], dt=self.gt4py_config.dtypes.float(timestep.total_seconds()),
-                      domain=(g.nx, 1, g.nz + 1), **_stencil_common(self))
+        self._compile(lphylin, ldrain1d, yoethf_params, yomcst_params, yrecldp_params, yrephli_params, yrncl_params,
+                      yrphnc_params, NLEV=computational_grid.nz)
 
 
 class Cloudsc2TLIncremented(Cloudsc2TL):
@@ -312,84 +244,34 @@ class Cloudsc2TLIncremented(Cloudsc2TL):
     kernel.  Outputs are those of the two components called one after the other (up to the compiler's fma contraction of
     the shared level function: ulps)."""
 
+    _FIELD_MAP = tuple(r for r in Cloudsc2TL._FIELD_MAP if r not in _state(NL_IN, "_i"))
+    _stencil_name = "cloudsc2_tl_incremented"
+
     def __init__(self, computational_grid, factor: float, ignore_supsat: bool, lphylin: bool, ldrain1d: bool,
                  yoethf_params, yomcst_params, yrecldp_params, yrephli_params, yrncl_params, yrphnc_params, *,
                  enable_checks: bool = True, gt4py_config) -> None:
-        ImplicitTendencyComponent.__init__(self, computational_grid, enable_checks=enable_checks, gt4py_config=gt4py_config)
-        ext = _externals(yoethf_params, yomcst_params, yrecldp_params, yrephli_params, yrncl_params, yrphnc_params,
-                         ICALL=0, LPHYLIN=lphylin, LDRAIN1D=ldrain1d, NLEV=computational_grid.nz,
-                         ZEPS1=1e-12, ZEPS2=1e-10, ZQMAX=0.5, ZSCAL=0.9, IGNORE_SUPSAT=ignore_supsat)
         self.f = gt4py_config.dtypes.float(factor)
-        self.cloudsc2 = self.compile_stencil("cloudsc2_tl_incremented", ext)
-
-    @cached_property
-    def input_grid_properties(self):
-        props = {"f_eta": {"grid_dims": (K,), "units": ""}}
-        for n in NL_IN:
-            props["f_" + n] = _prop(n)
-        return props
-
-    def array_call(self, state, timestep: timedelta, out_tendencies, out_diagnostics, overwrite_tendencies) -> None:
-        g = self.computational_grid
-        kw = {"in_" + n: state["f_" + n] for n in NL_IN}
-        for n in _DIAG_OUT:
-            kw["out_" + n] = out_diagnostics["f_" + n]
-            kw["out_" + n + "_i"] = out_diagnostics["f_" + n + "_i"]
-        for n in _TEND_OUT:
-            kw["out_" + n] = out_tendencies[_tend_name(n)]
-            kw["out_" + n + "_i"] = out_tendencies[_tend_name(n) + "_i"]
-        self.cloudsc2(**kw, in_eta=state["f_eta"], f=self.f, dt=self.gt4py_config.dtypes.float(timestep.total_seconds()),
-                      domain=(g.nx, 1, g.nz + 1), **_stencil_common(self))
+        self._more_externals = {"IGNORE_SUPSAT": ignore_supsat}
+        super().__init__(computational_grid, lphylin, ldrain1d, yoethf_params, yomcst_params, yrecldp_params,
+                         yrephli_params, yrncl_params, yrphnc_params, enable_checks=enable_checks, gt4py_config=gt4py_config)
 
 
-class Cloudsc2AD(ImplicitTendencyComponent):
+class Cloudsc2AD(_Microphysics):
     """State in: the 16 trajectory fields + the adjoint forcings `f_{clc,...}_i`, `f_tnd_{t,q,ql,qi}_i`
     (adjoint/microphysics.py:91-121).  Out: NL tendencies/diagnostics + `f_cml_{t,q,ql,qi}_i` (tendency
     dict) and the 12 adjoint state fields (diagnostic dict), :123-157."""
+
+    _ADJ_STATE = ("ap", "aph", "lu", "lude", "mfd", "mfu", "q", "qi", "ql", "qsat", "supsat", "t")
+    _FIELD_MAP = (_state(NL_IN) + _state(NL_OUT, "_i") + _ETA + _nl_outputs("") + _diags(_ADJ_STATE, "_i")
+                  + tuple(_Row(f"f_cml_{n}_i", "tend", f"out_tnd_cml_{n}_i", "tnd_" + n) for n in ("q", "qi", "ql", "t")))
+    _stencil_name = "cloudsc2_ad"
 
     def __init__(self, computational_grid, lphylin: bool, ldrain1d: bool, yoethf_params, yomcst_params,
                  yrecldp_params, yrephli_params, yrncl_params, yrphnc_params, *, enable_checks: bool = True,
                  gt4py_config, ad_traj_fix: bool = False) -> None:
         super().__init__(computational_grid, enable_checks=enable_checks, gt4py_config=gt4py_config)
-        ext = _externals(yoethf_params, yomcst_params, yrecldp_params, yrephli_params, yrncl_params, yrphnc_params,
-                         ICALL=0, LPHYLIN=lphylin, LDRAIN1D=ldrain1d, NLEV=computational_grid.nz,
-                         ZEPS1=1e-12, ZEPS2=1e-10, ZQMAX=0.5, ZSCAL=0.9, AD_TRAJ_FIX=int(ad_traj_fix))
-        self.cloudsc2 = self.compile_stencil(self._stencil_name, ext)
-
-    _stencil_name = "cloudsc2_ad"
-    _ADJ_STATE = ("ap", "aph", "lu", "lude", "mfd", "mfu", "q", "qi", "ql", "qsat", "supsat", "t")
-
-    @cached_property
-    def input_grid_properties(self):
-        props = {"f_eta": {"grid_dims": (K,), "units": ""}}
-        props.update({"f_" + n: _prop(n) for n in NL_IN})
-        props.update({"f_" + n + "_i": _prop(n) for n in _DIAG_OUT})
-        props.update({"f_" + n + "_i": _prop(n) for n in _TEND_OUT})   # f_tnd_t_i, ...
-        return props
-
-    @cached_property
-    def tendency_grid_properties(self):
-        props = {_tend_name(n): _prop(n) for n in _TEND_OUT}
-        props.update({"f_cml_" + n[len("tnd_"):] + "_i": _prop(n) for n in _TEND_OUT})
-        return props
-
-    @cached_property
-    def diagnostic_grid_properties(self):
-        props = {"f_" + n: _prop(n) for n in _DIAG_OUT}
-        props.update({"f_" + n + "_i": _prop(n) for n in self._ADJ_STATE})
-        return props
-
-    def array_call(self, state, timestep: timedelta, out_tendencies, out_diagnostics, overwrite_tendencies) -> None:
-        g = self.computational_grid
-        kw = {"in_" + n: state["f_" + n] for n in NL_IN}
-        kw.update({"in_" + n + "_i": state["f_" + n + "_i"] for n in NL_OUT})
-        kw.update({"out_" + n: out_diagnostics["f_" + n] for n in _DIAG_OUT})
-        kw.update({"out_" + n: out_tendencies[_tend_name(n)] for n in _TEND_OUT})
-        kw.update({"out_" + n + "_i": out_diagnostics["f_" + n + "_i"] for n in self._ADJ_STATE})
-        for n in ("q", "qi", "ql", "t"):
-            kw["out_tnd_cml_" + n + "_i"] = out_tendencies["f_cml_" + n + "_i"]
-        self.cloudsc2(**kw, in_eta=state["f_eta"], dt=self.gt4py_config.dtypes.float(timestep.total_seconds()),
-                      domain=(g.nx, 1, g.nz + 1), **_stencil_common(self))
+        self._compile(lphylin, ldrain1d, yoethf_params, yomcst_params, yrecldp_params, yrephli_params, yrncl_params,
+                      yrphnc_params, NLEV=computational_grid.nz, AD_TRAJ_FIX=int(ad_traj_fix))
 
 
 class Cloudsc2ADFromTrajectory(Cloudsc2AD):
@@ -401,21 +283,25 @@ class Cloudsc2ADFromTrajectory(Cloudsc2AD):
     rounding only with `ad_traj_fix=True` or where no column's saturation adjustment crosses RTT: without the fix (quirk
     Q4) the TL fluxes differ from the ones Cloudsc2AD recomputes in such columns."""
 
+    _FIELD_MAP = (tuple(r._replace(keyword=None) if r in _nl_outputs("") else r for r in Cloudsc2AD._FIELD_MAP)
+                  + tuple(_Row(f"f_{n}", "state", f"traj_{n}", n) for n in ("fplsl", "fplsn")))
     _stencil_name = "cloudsc2_ad_from_trajectory"
 
-    @cached_property
-    def input_grid_properties(self):
-        props = dict(super().input_grid_properties)
-        props.update({"f_fplsl": _prop("fplsl"), "f_fplsn": _prop("fplsn")})
-        return props
 
-    def array_call(self, state, timestep: timedelta, out_tendencies, out_diagnostics, overwrite_tendencies) -> None:
-        g = self.computational_grid
-        kw = {"in_" + n: state["f_" + n] for n in NL_IN}
-        kw.update({"in_" + n + "_i": state["f_" + n + "_i"] for n in NL_OUT})
-        kw.update({"out_" + n + "_i": out_diagnostics["f_" + n + "_i"] for n in self._ADJ_STATE})
-        for n in ("q", "qi", "ql", "t"):
-            kw["out_tnd_cml_" + n + "_i"] = out_tendencies["f_cml_" + n + "_i"]
-        self.cloudsc2(**kw, traj_fplsl=state["f_fplsl"], traj_fplsn=state["f_fplsn"], in_eta=state["f_eta"],
-                      dt=self.gt4py_config.dtypes.float(timestep.total_seconds()), domain=(g.nx, 1, g.nz + 1),
-                      **_stencil_common(self))
+# ---------------------------------------------------------------------------------- the NL field map, for the harness
+def nl_input_keywords(state, increments: bool = False) -> Dict[str, Any]:
+    """the `in_*` (with `increments`: and `in_*_i`) and `in_eta` keywords of an NL stencil, from a state of DataArrays"""
+    rows = (Cloudsc2NLPerturbed if increments else Cloudsc2NL)._FIELD_MAP
+    return {r.keyword: state[r.name].data for r in rows if r.where == "state"}
+
+
+def nl_output_keywords(prefix: str, tends, diags) -> Dict[str, Any]:
+    """the ten outputs of a `Cloudsc2NL` call under the keywords `<prefix><NL_OUT name>` (e.g. `ref_tnd_t` = tends["f_t"])"""
+    dicts = {"tend": tends, "diag": diags}
+    return {prefix + r.field: dicts[r.where][r.name].data for r in Cloudsc2NL._FIELD_MAP if r.where != "state"}
+
+
+def nl_output_position(name: str, tendency: bool) -> int:
+    """position in NL_OUT of the output `Cloudsc2NL` publishes as `name` in its tendency / diagnostic dict"""
+    where = "tend" if tendency else "diag"
+    return NL_OUT.index(next(r.field for r in Cloudsc2NL._FIELD_MAP if r.where == where and r.name == name))

@@ -15,20 +15,14 @@ Error behaviour mirrors GT4Py's: argument problems found with ``validate_args=Tr
 from __future__ import annotations
 
 import ctypes
-from typing import Any, Callable, Dict, Mapping, Optional, Sequence
+from typing import Any, Dict, Mapping, Optional
 
 import torch
 
 from . import _lib
+from ._lib import INC, LAYOUTS, NL_IN, NL_OUT, Layout  # noqa: F401 - the field lists are part of this module's API
 from .params import make_params
 from .storage import field_geometry
-
-# gtscript parameter names in C-ABI order (include/cloudsc2_hip.h enums)
-NL_IN = ("ap", "aph", "lu", "lude", "mfd", "mfu", "q", "qi", "ql", "qsat", "supsat", "t",
-         "tnd_cml_q", "tnd_cml_qi", "tnd_cml_ql", "tnd_cml_t")
-NL_OUT = ("clc", "covptot", "fhpsl", "fhpsn", "fplsl", "fplsn", "tnd_q", "tnd_qi", "tnd_ql", "tnd_t")
-INC = ("aph", "ap", "q", "qsat", "t", "ql", "qi", "lude", "lu", "mfu", "mfd",
-       "tnd_cml_t", "tnd_cml_q", "tnd_cml_ql", "tnd_cml_qi", "supsat")
 
 _SFX = {torch.float64: "f64", torch.float32: "f32"}
 
@@ -53,22 +47,36 @@ def _current_stream_ptr(device: torch.device) -> int:
     return int(torch.cuda.current_stream(device).cuda_stream)
 
 
+def checked_nlev(name: str, externals: Mapping[str, Any], nz: int, validate: bool) -> int:
+    """`NLEV` is an external of the TL / AD stencils (tangent_linear/microphysics.py:85: the grid's nz).  When the
+    caller supplied one it must agree with the storages (checked with validate_args=True; otherwise the storages
+    win, as they must for the kernels' bounds); when it did not, it is derived from them."""
+    given = externals.get("NLEV")
+    if given is not None and int(given) != nz and validate:
+        raise ValueError(f"{name}: external NLEV={int(given)} does not match the storages (nz={nz})")
+    return nz
+
+
 class HipStencil:
-    """Base of the callable stencil objects."""
+    """The callable stencil object: a function of its externals and of its entry in `_lib.LAYOUTS` (one subclass per
+    entry, made by `_stencil_class`).  Nothing of a call is kept on the object but the memo of the disjointness check."""
 
     name: str = ""
-    scalar_name: str = "dt"
-    nlev_offset: int = 1  # domain[2] = nz + nlev_offset
+    layout: Layout = Layout("", ())
+    scalar_name: str = "dt"   # the stencil's own scalar: the last keyword scalar of the layout ("" if there is none)
+    nlev_offset: int = 1      # domain[2] = nz + nlev_offset
+    # derived from the layout, once per stencil (`_stencil_class`)
+    _kinds: frozenset = frozenset()
+    _scalars: tuple = ()        # the keyword scalars
+    _field_groups: tuple = ()   # (scalar keyword that replaces the group or None, field keywords), in layout order
 
     def __init__(self, externals: Mapping[str, Any]):
         self.externals = dict(externals)
         self.params = make_params(self.externals)
         self._lib = _lib.load()  # raises if the HIP library is missing: no fallback
+        self._entry = {dtype: getattr(self._lib, f"cloudsc2_{self.layout.entry}_{sfx}") for dtype, sfx in _SFX.items()}
 
     # -- argument handling ---------------------------------------------------------------
-    def _field_names(self) -> Sequence[str]:
-        raise NotImplementedError
-
     def _geometry(self, fields: Mapping[str, torch.Tensor], domain, origin, validate: bool):
         first = next(iter(fields.values()))
         nx, nlev, ls = field_geometry(first)
@@ -136,17 +144,6 @@ class HipStencil:
             seen.clear()
         seen.add(key)
 
-    def _collect(self, kwargs: Dict[str, Any]) -> Dict[str, torch.Tensor]:
-        fields = {}
-        for n in self._field_names():
-            if n not in kwargs:
-                raise TypeError(f"{self.name}: missing field argument '{n}'")
-            fields[n] = kwargs.pop(n)
-        for n in list(kwargs):
-            if n.startswith(_IGNORED_PREFIX):
-                kwargs.pop(n)
-        return fields
-
     def _kvec(self, v: Any, nz: int, dtype, device, validate: bool) -> torch.Tensor:
         if validate:
             if not isinstance(v, torch.Tensor) or v.dim() != 1 or v.shape[0] < nz + 1:
@@ -160,25 +157,71 @@ class HipStencil:
         domain = kwargs.pop("domain", None)
         validate = bool(kwargs.pop("validate_args", True))
         exec_info: Optional[dict] = kwargs.pop("exec_info", None)
-        self._validate = validate
-        scalar = 0.0
-        if self.scalar_name:
-            if self.scalar_name not in kwargs:
-                raise TypeError(f"{self.name}: missing scalar argument '{self.scalar_name}'")
-            scalar = float(kwargs.pop(self.scalar_name))
+        scalars: Dict[str, Optional[float]] = {}
+        for a in self._scalars:
+            v = kwargs.pop(a.key, None)
+            if v is None and a.default is None:
+                raise TypeError(f"{self.name}: missing scalar argument '{a.key}'")
+            scalars[a.key] = None if v is None else float(v)
+        fs = part = None
+        if "fs" in self._kinds:
+            if "fs" not in kwargs:
+                raise TypeError(f"{self.name}: missing argument 'fs'")
+            fs = [float(x) for x in kwargs.pop("fs")]
+        if "partials" in self._kinds:
+            if "out_partials" not in kwargs:
+                raise TypeError(f"{self.name}: missing argument 'out_partials'")
+            part = kwargs.pop("out_partials")
         eta = kwargs.pop("in_eta", None)
-        fields = self._collect(kwargs)
+        fields: Dict[str, torch.Tensor] = {}
+        try:
+            for unless, names in self._field_groups:
+                if unless is None or scalars[unless] is None:
+                    for n in names:
+                        fields[n] = kwargs.pop(n)
+        except KeyError:
+            raise TypeError(f"{self.name}: missing field argument '{n}'") from None
         if kwargs:
-            raise TypeError(f"{self.name}: unexpected arguments {sorted(kwargs)}")
+            unexpected = sorted(n for n in kwargs if not n.startswith(_IGNORED_PREFIX))
+            if unexpected:
+                raise TypeError(f"{self.name}: unexpected arguments {unexpected}")
         nx, nz, ls, dtype, device = self._geometry(fields, domain, origin, validate)
-        if eta is not None:
+        if "eta" in self._kinds:
+            if eta is None:
+                raise TypeError(f"{self.name}: missing field argument 'in_eta'")
             eta = self._kvec(eta, nz, dtype, device, validate)
+        if part is not None:
+            need = taylor_blocks(nx) * (1 if fs is None else len(fs)) * len(NL_OUT)
+            if (not isinstance(part, torch.Tensor) or part.dtype != torch.float64 or not part.is_contiguous()
+                    or part.device != device or part.numel() < need):
+                raise ValueError(f"{self.name}: out_partials must be a contiguous float64 device tensor with >= {need} "
+                                 f"elements (taylor_blocks(nx) x [len(fs) x] {len(NL_OUT)})")
+        if self.layout.sets_nlev:
+            self.params.NLEV = checked_nlev(self.name, self.externals, nz, validate)
         ev = None
         if exec_info is not None:
             ev = (torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True))
             ev[0].record()
         with torch.cuda.device(device):
-            rc = self._launch(fields, eta, scalar, nx, nz, ls, _SFX[dtype], _current_stream_ptr(device))
+            c_args: list = [ctypes.byref(self.params), nx, nz, ls]
+            for kind, key, unless, default in self.layout.args:
+                if kind == "ptrs":
+                    absent = not key or (unless is not None and scalars[unless] is not None)
+                    c_args.append(None if absent else _lib.ptr_array([fields[n].data_ptr() if n else 0 for n in key]))
+                elif kind == "field":
+                    c_args.append(fields[key].data_ptr() if key else None)
+                elif kind == "scalar":
+                    v = scalars[key] if key else None
+                    c_args.append(default if v is None else v)
+                elif kind == "eta":
+                    c_args.append(eta.data_ptr())
+                elif kind == "partials":
+                    c_args.append(part.data_ptr())
+                elif kind == "fs":
+                    c_args += [len(fs), (ctypes.c_double * max(len(fs), 1))(*fs)]
+                else:
+                    c_args.append(_current_stream_ptr(device))
+            rc = self._entry[dtype](*c_args)
         _lib.check(rc, self.name)
         if ev is not None:
             ev[1].record()
@@ -186,321 +229,31 @@ class HipStencil:
             rec["ncalls"] += 1
             rec["events"].append(ev)
 
-    def _launch(self, fields, eta, scalar, nx, nz, ls, sfx, stream) -> int:
-        raise NotImplementedError
-
-    def _set_nlev(self, nz: int) -> None:
-        """`NLEV` is an external of the TL / AD stencils (tangent_linear/microphysics.py:85: the grid's nz).  When the
-        caller supplied one it must agree with the storages (checked with validate_args=True; otherwise the storages
-        win, as they must for the kernels' bounds); when it did not, it is derived from them."""
-        given = self.externals.get("NLEV")
-        if given is not None and int(given) != nz and getattr(self, "_validate", True):
-            raise ValueError(f"{self.name}: external NLEV={int(given)} does not match the storages (nz={nz})")
-        self.params.NLEV = nz
-
-    def _fn(self, base: str, sfx: str) -> Callable:
-        return getattr(self._lib, f"cloudsc2_{base}_{sfx}")
-
-
-def _ptrs(fields: Mapping[str, torch.Tensor], names: Sequence[str]):
-    return _lib.ptr_array([fields[n].data_ptr() for n in names])
-
-
-class Cloudsc2NLStencil(HipStencil):
-    """`cloudsc2_nl` - nonlinear/_stencils/cloudsc2.py:24-60 (signature), :93-399 (body)."""
-
-    name = "cloudsc2_nl"
-
-    def _field_names(self):
-        return tuple("in_" + n for n in NL_IN) + tuple("out_" + n for n in NL_OUT)
-
-    def _launch(self, fields, eta, scalar, nx, nz, ls, sfx, stream):
-        if eta is None:
-            raise TypeError("cloudsc2_nl: missing field argument 'in_eta'")
-        return self._fn("nl", sfx)(
-            ctypes.byref(self.params), nx, nz, ls,
-            _ptrs(fields, ["in_" + n for n in NL_IN]), eta.data_ptr(),
-            _ptrs(fields, ["out_" + n for n in NL_OUT]), scalar, stream)
-
-
-class Cloudsc2NLSaturationStencil(HipStencil):
-    """BUILD EXTENSION `cloudsc2_nl_saturation`: `saturation` + `cloudsc2_nl` in one launch (C ABI
-    `cloudsc2_nl_fused_*` with `qsat_out`).  Arguments of `cloudsc2_nl` minus `in_qsat`, plus `out_qsat`."""
-
-    name = "cloudsc2_nl_saturation"
-
-    def _field_names(self):
-        return (tuple("in_" + n for n in NL_IN if n != "qsat") + ("out_qsat",)
-                + tuple("out_" + n for n in NL_OUT))
-
-    def _launch(self, fields, eta, scalar, nx, nz, ls, sfx, stream):
-        if eta is None:
-            raise TypeError(f"{self.name}: missing field argument 'in_eta'")
-        ins = _lib.ptr_array([0 if n == "qsat" else fields["in_" + n].data_ptr() for n in NL_IN])
-        return self._fn("nl_fused", sfx)(
-            ctypes.byref(self.params), nx, nz, ls, ins, None, 0.0, fields["out_qsat"].data_ptr(), eta.data_ptr(),
-            _ptrs(fields, ["out_" + n for n in NL_OUT]), scalar, stream)
-
-
-class Cloudsc2NLPerturbedStencil(HipStencil):
-    """BUILD EXTENSION `cloudsc2_nl_perturbed`: `perturbed_state` + `cloudsc2_nl` in one launch: the inputs are
-    read as in_X + f * in_X_i.  Arguments of `cloudsc2_nl` plus the 16 `in_*_i` fields and the scalar `f`."""
-
-    name = "cloudsc2_nl_perturbed"
-
-    def __call__(self, **kwargs: Any) -> None:
-        if "f" not in kwargs:
-            raise TypeError(f"{self.name}: missing scalar argument 'f'")
-        self._pf = float(kwargs.pop("f"))
-        super().__call__(**kwargs)
-
-    def _field_names(self):
-        return (tuple("in_" + n for n in NL_IN) + tuple("in_" + n + "_i" for n in NL_IN)
-                + tuple("out_" + n for n in NL_OUT))
-
-    def _launch(self, fields, eta, scalar, nx, nz, ls, sfx, stream):
-        if eta is None:
-            raise TypeError(f"{self.name}: missing field argument 'in_eta'")
-        return self._fn("nl_fused", sfx)(
-            ctypes.byref(self.params), nx, nz, ls, _ptrs(fields, ["in_" + n for n in NL_IN]),
-            _ptrs(fields, ["in_" + n + "_i" for n in NL_IN]), self._pf, None, eta.data_ptr(),
-            _ptrs(fields, ["out_" + n for n in NL_OUT]), scalar, stream)
-
-
-class Cloudsc2NLTaylorStencil(HipStencil):
-    """BUILD EXTENSION `cloudsc2_nl_taylor`: perturbed NL run + the Taylor test's reduction in one launch (C ABI
-    `cloudsc2_nl_taylor_*`).  Fields: the 16 `in_*`, the 16 `in_*_i`, the 10 unperturbed outputs `ref_*` (read-only);
-    scalar `f`; `out_partials`: contiguous float64 tensor of shape (taylor_blocks(nx), 10) that receives, per
-    workgroup, sum(NL(in + f in_i) - ref) for the 10 outputs in NL_OUT order.  Nothing else is written."""
-
-    name = "cloudsc2_nl_taylor"
-
-    def __call__(self, **kwargs: Any) -> None:
-        if "f" not in kwargs or "out_partials" not in kwargs:
-            raise TypeError(f"{self.name}: missing argument 'f' / 'out_partials'")
-        self._pf = float(kwargs.pop("f"))
-        self._partials = kwargs.pop("out_partials")
-        super().__call__(**kwargs)
-
-    def _field_names(self):
-        return (tuple("in_" + n for n in NL_IN) + tuple("in_" + n + "_i" for n in NL_IN)
-                + tuple("ref_" + n for n in NL_OUT))
-
-    def _launch(self, fields, eta, scalar, nx, nz, ls, sfx, stream):
-        if eta is None:
-            raise TypeError(f"{self.name}: missing field argument 'in_eta'")
-        part = self._partials
-        need = taylor_blocks(nx)
-        if (not isinstance(part, torch.Tensor) or part.dtype != torch.float64 or not part.is_contiguous()
-                or part.device != fields["in_ap"].device or part.numel() < need * len(NL_OUT)):
-            raise ValueError(f"{self.name}: out_partials must be a contiguous float64 device tensor with >= "
-                             f"{need} x {len(NL_OUT)} elements")
-        return self._fn("nl_taylor", sfx)(
-            ctypes.byref(self.params), nx, nz, ls, _ptrs(fields, ["in_" + n for n in NL_IN]),
-            _ptrs(fields, ["in_" + n + "_i" for n in NL_IN]), self._pf, eta.data_ptr(),
-            _ptrs(fields, ["ref_" + n for n in NL_OUT]), part.data_ptr(), scalar, stream)
-
-
-class Cloudsc2NLTaylorMultiStencil(HipStencil):
-    """BUILD EXTENSION `cloudsc2_nl_taylor_multi`: the Taylor test's perturbed NL runs for ALL step sizes (C ABI
-    `cloudsc2_nl_taylor_multi_*`: up to 5 step sizes share one pass over the 42 words of a level).  Fields as
-    `cloudsc2_nl_taylor`; `fs`: the step sizes; `out_partials`: contiguous float64 tensor of shape
-    (taylor_blocks(nx), len(fs), 10) receiving, per workgroup and step size, sum(NL(in + f in_i) - ref) in NL_OUT order.
-    With `f_inc=<factor>` instead of the 16 `in_*_i` fields, `state_increment` is fused in as well: the increments are formed
-    in the kernel as f_inc * in (external IGNORE_SUPSAT zeroes the supsat increment)."""
-
-    name = "cloudsc2_nl_taylor_multi"
-
-    def __call__(self, **kwargs: Any) -> None:
-        if "fs" not in kwargs or "out_partials" not in kwargs:
-            raise TypeError(f"{self.name}: missing argument 'fs' / 'out_partials'")
-        self._fs = [float(x) for x in kwargs.pop("fs")]
-        self._partials = kwargs.pop("out_partials")
-        self._f_inc = kwargs.pop("f_inc", None)
-        super().__call__(**kwargs)
-
-    def _field_names(self):
-        incs = () if getattr(self, "_f_inc", None) is not None else tuple("in_" + n + "_i" for n in NL_IN)
-        return tuple("in_" + n for n in NL_IN) + incs + tuple("ref_" + n for n in NL_OUT)
-
-    def _launch(self, fields, eta, scalar, nx, nz, ls, sfx, stream):
-        if eta is None:
-            raise TypeError(f"{self.name}: missing field argument 'in_eta'")
-        part, nf = self._partials, len(self._fs)
-        need = taylor_blocks(nx) * nf * len(NL_OUT)
-        if (not isinstance(part, torch.Tensor) or part.dtype != torch.float64 or not part.is_contiguous()
-                or part.device != fields["in_ap"].device or part.numel() < need):
-            raise ValueError(f"{self.name}: out_partials must be a contiguous float64 device tensor with >= {need} elements")
-        pf = (ctypes.c_double * max(nf, 1))(*self._fs)
-        fused_inc = self._f_inc is not None
-        return self._fn("nl_taylor_multi", sfx)(
-            ctypes.byref(self.params), nx, nz, ls, _ptrs(fields, ["in_" + n for n in NL_IN]),
-            None if fused_inc else _ptrs(fields, ["in_" + n + "_i" for n in NL_IN]),
-            float(self._f_inc) if fused_inc else 0.0, nf, pf, eta.data_ptr(),
-            _ptrs(fields, ["ref_" + n for n in NL_OUT]), part.data_ptr(), scalar, stream)
-
 
 def taylor_blocks(nx: int) -> int:
     """Number of per-workgroup partial rows `cloudsc2_nl_taylor` writes for nx columns."""
     return int(_lib.load().cloudsc2_nl_taylor_blocks(int(nx)))
 
 
-class Cloudsc2TLStencil(HipStencil):
-    """`cloudsc2_tl` - tangent_linear/_stencils/cloudsc2.py:23-90 (signature), :124-774 (body)."""
-
-    name = "cloudsc2_tl"
-
-    def _field_names(self):
-        return (tuple("in_" + n for n in NL_IN) + tuple("in_" + n + "_i" for n in NL_IN)
-                + tuple("out_" + n for n in NL_OUT) + tuple("out_" + n + "_i" for n in NL_OUT))
-
-    def _launch(self, fields, eta, scalar, nx, nz, ls, sfx, stream):
-        if eta is None:
-            raise TypeError("cloudsc2_tl: missing field argument 'in_eta'")
-        self._set_nlev(nz)
-        return self._fn("tl", sfx)(
-            ctypes.byref(self.params), nx, nz, ls,
-            _ptrs(fields, ["in_" + n for n in NL_IN]), _ptrs(fields, ["in_" + n + "_i" for n in NL_IN]),
-            eta.data_ptr(),
-            _ptrs(fields, ["out_" + n for n in NL_OUT]), _ptrs(fields, ["out_" + n + "_i" for n in NL_OUT]),
-            scalar, stream)
+def _stencil_class(name: str, layout: Layout) -> type:
+    scalars = tuple(a for a in layout.args if a.kind == "scalar" and a.key)
+    groups: list = []           # runs of field keywords that are present or absent together
+    for a in layout.args:
+        if a.kind in ("ptrs", "field"):
+            names = tuple(n for n in (a.key if a.kind == "ptrs" else (a.key,)) if n)
+            if groups and groups[-1][0] == a.unless:
+                groups[-1] = (a.unless, groups[-1][1] + names)
+            elif names:
+                groups.append((a.unless, names))
+    return type("".join(w.capitalize() for w in name.split("_")) + "Stencil", (HipStencil,), {
+        "name": name, "layout": layout, "nlev_offset": layout.nlev_offset,
+        "scalar_name": scalars[-1].key if scalars else "", "_kinds": frozenset(a.kind for a in layout.args),
+        "_scalars": scalars, "_field_groups": tuple(groups),
+        "__doc__": f"`{name}`: see its entry in `_lib.LAYOUTS`."})
 
 
-class Cloudsc2TLIncrementedStencil(HipStencil):
-    """BUILD EXTENSION `cloudsc2_tl_incremented`: `state_increment` + `cloudsc2_tl` in one launch (C ABI
-    `cloudsc2_tl_incremented_*`): the perturbations are formed in the kernel as f * in_X (external IGNORE_SUPSAT: the
-    supsat perturbation is 0).  Arguments of `cloudsc2_tl` minus the 16 `in_*_i` fields, plus the scalar `f`."""
-
-    name = "cloudsc2_tl_incremented"
-
-    def __call__(self, **kwargs: Any) -> None:
-        if "f" not in kwargs:
-            raise TypeError(f"{self.name}: missing scalar argument 'f'")
-        self._f = float(kwargs.pop("f"))
-        super().__call__(**kwargs)
-
-    def _field_names(self):
-        return (tuple("in_" + n for n in NL_IN) + tuple("out_" + n for n in NL_OUT)
-                + tuple("out_" + n + "_i" for n in NL_OUT))
-
-    def _launch(self, fields, eta, scalar, nx, nz, ls, sfx, stream):
-        if eta is None:
-            raise TypeError(f"{self.name}: missing field argument 'in_eta'")
-        self._set_nlev(nz)
-        return self._fn("tl_incremented", sfx)(
-            ctypes.byref(self.params), nx, nz, ls, _ptrs(fields, ["in_" + n for n in NL_IN]), self._f, eta.data_ptr(),
-            _ptrs(fields, ["out_" + n for n in NL_OUT]), _ptrs(fields, ["out_" + n + "_i" for n in NL_OUT]),
-            scalar, stream)
-
-
-class Cloudsc2ADStencil(HipStencil):
-    """`cloudsc2_ad` - adjoint/_stencils/cloudsc2.py:24-90 (signature), :124-996 (body)."""
-
-    name = "cloudsc2_ad"
-
-    def _field_names(self):
-        return (tuple("in_" + n for n in NL_IN) + tuple("in_" + n + "_i" for n in NL_OUT)
-                + tuple("out_" + n for n in NL_OUT) + tuple("out_" + n + "_i" for n in NL_IN))
-
-    def _launch(self, fields, eta, scalar, nx, nz, ls, sfx, stream):
-        if eta is None:
-            raise TypeError("cloudsc2_ad: missing field argument 'in_eta'")
-        self._set_nlev(nz)
-        return self._fn("ad", sfx)(
-            ctypes.byref(self.params), nx, nz, ls,
-            _ptrs(fields, ["in_" + n for n in NL_IN]), _ptrs(fields, ["in_" + n + "_i" for n in NL_OUT]),
-            eta.data_ptr(),
-            _ptrs(fields, ["out_" + n for n in NL_OUT]), _ptrs(fields, ["out_" + n + "_i" for n in NL_IN]),
-            scalar, stream)
-
-
-class Cloudsc2ADFromTrajectoryStencil(HipStencil):
-    """BUILD EXTENSION `cloudsc2_ad_from_trajectory`: `cloudsc2_ad` without its forward sweep (C ABI
-    `cloudsc2_ad_from_trajectory_*`).  Fields of `cloudsc2_ad` minus the ten `out_*` NL outputs, plus `traj_fplsl` /
-    `traj_fplsn`: the flux outputs of a cloudsc2_nl / cloudsc2_tl call on the same state (read-only).  Only the 16
-    `out_*_i` adjoints are written.  Driver switches only (no evaporation block)."""
-
-    name = "cloudsc2_ad_from_trajectory"
-
-    def _field_names(self):
-        return (tuple("in_" + n for n in NL_IN) + tuple("in_" + n + "_i" for n in NL_OUT) + ("traj_fplsl", "traj_fplsn")
-                + tuple("out_" + n + "_i" for n in NL_IN))
-
-    def _launch(self, fields, eta, scalar, nx, nz, ls, sfx, stream):
-        if eta is None:
-            raise TypeError(f"{self.name}: missing field argument 'in_eta'")
-        self._set_nlev(nz)
-        return self._fn("ad_from_trajectory", sfx)(
-            ctypes.byref(self.params), nx, nz, ls,
-            _ptrs(fields, ["in_" + n for n in NL_IN]), _ptrs(fields, ["in_" + n + "_i" for n in NL_OUT]),
-            eta.data_ptr(), fields["traj_fplsl"].data_ptr(), fields["traj_fplsn"].data_ptr(),
-            _ptrs(fields, ["out_" + n + "_i" for n in NL_IN]), scalar, stream)
-
-
-class SaturationStencil(HipStencil):
-    """`saturation` - common/_stencils/saturation.py:23-42; domain (nx, 1, nz)."""
-
-    name = "saturation"
-    scalar_name = ""
-    nlev_offset = 0
-
-    def _field_names(self):
-        return ("in_ap", "in_t", "out_qsat")
-
-    def _launch(self, fields, eta, scalar, nx, nz, ls, sfx, stream):
-        return self._fn("saturation", sfx)(
-            ctypes.byref(self.params), nx, nz, ls,
-            fields["in_ap"].data_ptr(), fields["in_t"].data_ptr(), fields["out_qsat"].data_ptr(), stream)
-
-
-class StateIncrementStencil(HipStencil):
-    """`state_increment` - common/_stencils/state_increment.py:22-80."""
-
-    name = "state_increment"
-    scalar_name = "f"
-
-    def _field_names(self):
-        return tuple("in_" + n for n in INC) + tuple("out_" + n + "_i" for n in INC)
-
-    def _launch(self, fields, eta, scalar, nx, nz, ls, sfx, stream):
-        return self._fn("state_increment", sfx)(
-            ctypes.byref(self.params), nx, nz, ls,
-            _ptrs(fields, ["in_" + n for n in INC]), _ptrs(fields, ["out_" + n + "_i" for n in INC]),
-            scalar, stream)
-
-
-class PerturbedStateStencil(HipStencil):
-    """`perturbed_state` - common/_stencils/perturbed_state.py:22-91."""
-
-    name = "perturbed_state"
-    scalar_name = "f"
-
-    def _field_names(self):
-        return (tuple("in_" + n for n in INC) + tuple("in_" + n + "_i" for n in INC)
-                + tuple("out_" + n for n in INC))
-
-    def _launch(self, fields, eta, scalar, nx, nz, ls, sfx, stream):
-        return self._fn("perturbed_state", sfx)(
-            ctypes.byref(self.params), nx, nz, ls,
-            _ptrs(fields, ["in_" + n for n in INC]), _ptrs(fields, ["in_" + n + "_i" for n in INC]),
-            _ptrs(fields, ["out_" + n for n in INC]), scalar, stream)
-
-
-#: registry keyed by the names the reference registers with `@stencil_collection(name)`
-STENCILS: Dict[str, type] = {
-    "cloudsc2_nl": Cloudsc2NLStencil,
-    "cloudsc2_nl_saturation": Cloudsc2NLSaturationStencil,   # build extension (fused)
-    "cloudsc2_nl_perturbed": Cloudsc2NLPerturbedStencil,     # build extension (fused)
-    "cloudsc2_nl_taylor": Cloudsc2NLTaylorStencil,           # build extension (fused + reduction)
-    "cloudsc2_nl_taylor_multi": Cloudsc2NLTaylorMultiStencil,   # build extension (all step sizes, fused + reduction)
-    "cloudsc2_tl": Cloudsc2TLStencil,
-    "cloudsc2_tl_incremented": Cloudsc2TLIncrementedStencil,    # build extension (state_increment fused in)
-    "cloudsc2_ad": Cloudsc2ADStencil,
-    "cloudsc2_ad_from_trajectory": Cloudsc2ADFromTrajectoryStencil,   # build extension (no forward sweep)
-    "saturation": SaturationStencil,
-    "state_increment": StateIncrementStencil,
-    "perturbed_state": PerturbedStateStencil,
-}
+#: registry keyed by the names the reference registers with `@stencil_collection(name)` (+ the build extensions)
+STENCILS: Dict[str, type] = {name: _stencil_class(name, layout) for name, layout in LAYOUTS.items()}
 
 
 def compile_stencil(name: str, externals: Optional[Mapping[str, Any]] = None) -> HipStencil:

@@ -3,7 +3,7 @@ container, against a RECORDING FAKE of libcloudsc2_hip.so.
 
 What is real: the reference's drivers, its component classes (Cloudsc2NL / Cloudsc2TL / Cloudsc2AD, Saturation,
 StateIncrement, PerturbedState, the Taylor / symmetry harnesses), this build's `ifs_physics_common` shim, its backend
-registry, and the product's stencil objects (`stencils.HipStencil.__call__` and every `_launch`).
+registry, and the product's stencil objects (`stencils.HipStencil.__call__`, driven by `_lib.LAYOUTS`).
 What is fake, FOR THIS TEST ONLY: the C-ABI entry points (they record their arguments and return 0 - nothing is computed,
 outputs stay zero), the device of backend "hip" (host tensors), the HIP stream and `torch.cuda.device`.
 
@@ -30,6 +30,8 @@ ABI_CALLS = []          # what reached the C ABI
 def _plain(a):
     """a ctypes argument as JSON data"""
     if isinstance(a, ctypes.Array):
+        if a._type_ is ctypes.c_double:                      # the step sizes `fs` of cloudsc2_nl_taylor_multi
+            return [float(x) for x in a]
         return [int(x or 0) for x in a]
     if hasattr(a, "_obj"):                                   # ctypes.byref(Cloudsc2Params)
         p = a._obj
@@ -47,6 +49,16 @@ class RecordingLib:
 
     def cloudsc2_last_kernel(self):
         return b"recording fake"
+
+    # size queries of the in-repo harness (tests/test_abi_trace.py): answered with an integer, not recorded
+    def cloudsc2_nl_taylor_blocks(self, nx):
+        return 1
+
+    def cloudsc2_field_sums_blocks(self, nx, nlev):
+        return 1
+
+    def cloudsc2_column_dots_chunks(self, nlev):
+        return 1
 
     def __getattr__(self, name):
         if not name.startswith("cloudsc2_"):
@@ -87,26 +99,40 @@ def install_fakes():
     torch.cuda.Event = NoEvent
     torch.cuda.synchronize = lambda device=None: None
 
-    real_call = stencils.HipStencil.__call__
+    def recording(real_call):
+        def recording_call(self, **kwargs):
+            if depth:                                       # a class's own __call__ handing on to its base: one call
+                return real_call(self, **kwargs)
+            rec = {"stencil": self.name,
+                   "externals": {k: v for k, v in self.externals.items() if isinstance(v, (bool, int))},
+                   "kwargs": sorted(kwargs), "fields": {}, "scalars": {}, "abi_first": len(ABI_CALLS)}
+            for k, v in kwargs.items():
+                if isinstance(v, torch.Tensor):
+                    rec["fields"][k] = {"ptr": v.data_ptr(), "shape": list(v.shape), "strides": list(v.stride()),
+                                        "dtype": str(v.dtype)}
+                elif k in ("dt", "f", "f_inc"):
+                    rec["scalars"][k] = {"value": float(v), "type": type(v).__name__}
+                elif k in ("origin", "domain"):
+                    rec[k] = [int(x) for x in v]
+                elif k == "validate_args":
+                    rec[k] = bool(v)
+            depth.append(1)
+            try:
+                real_call(self, **kwargs)
+            finally:
+                depth.pop()
+            rec["abi_last"] = len(ABI_CALLS)
+            STENCIL_CALLS.append(rec)
 
-    def recording_call(self, **kwargs):
-        rec = {"stencil": self.name, "externals": {k: v for k, v in self.externals.items() if isinstance(v, (bool, int))},
-               "kwargs": sorted(kwargs), "fields": {}, "scalars": {}, "abi_first": len(ABI_CALLS)}
-        for k, v in kwargs.items():
-            if isinstance(v, torch.Tensor):
-                rec["fields"][k] = {"ptr": v.data_ptr(), "shape": list(v.shape), "strides": list(v.stride()),
-                                    "dtype": str(v.dtype)}
-            elif k in ("dt", "f"):
-                rec["scalars"][k] = {"value": float(v), "type": type(v).__name__}
-            elif k in ("origin", "domain"):
-                rec[k] = [int(x) for x in v]
-            elif k == "validate_args":
-                rec[k] = bool(v)
-        real_call(self, **kwargs)
-        rec["abi_last"] = len(ABI_CALLS)
-        STENCIL_CALLS.append(rec)
+        return recording_call
 
-    stencils.HipStencil.__call__ = recording_call
+    depth = []
+    # the call is recorded where the caller makes it: at `HipStencil.__call__` and at any class that defines its own
+    # (no stencil class does today; the classes the trace fixture of tests/test_abi_trace.py was generated on did, and popped
+    # `f` / `fs` / `out_partials` before handing on - the loop and the depth guard keep that fixture regenerable there)
+    for cls in {stencils.HipStencil, *stencils.STENCILS.values()}:
+        if "__call__" in vars(cls):
+            cls.__call__ = recording(cls.__call__)
 
 
 def main() -> None:

@@ -19,6 +19,43 @@ def test_header_symbols_are_exported(hip_lib):
         assert hasattr(hip_lib, s), s
 
 
+def test_header_prototypes_match_the_declared_argtypes(hip_lib):
+    """Argument types AND their order: every `int32_t cloudsc2_*_f64(...)` prototype of the header, read as text, against
+    the `argtypes` the loaded library carries (derived from `_lib.LAYOUTS`), for both suffixes.  The header's types alone
+    do not tell a host array (`pf`) from a device array (`eta`), so "a pointer" is satisfied by `c_void_p` or
+    `POINTER(c_double)`; everything else must match exactly."""
+    from ctypes import POINTER, c_double, c_int32, c_int64, c_void_p
+
+    from gt4py_dwarf_p_cloudsc2_tl_ad_amd.params import Cloudsc2Params
+
+    header = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "cloudsc2_hip.h")).read(), flags=re.S)
+    protos = re.findall(r"int32_t\s+(cloudsc2_\w+)_f64\s*\(([^)]*)\)\s*;", header)
+    assert len(protos) >= 12, protos
+    any_pointer = (c_void_p, POINTER(c_double))
+
+    def kind(param):
+        ctype = " ".join(param.split()[:-1]) if not param.strip().endswith("*") else " ".join(param.split())
+        ctype = re.sub(r"\s*\*\s*", "* ", ctype).strip()          # "const double* const*", "void*", "double"
+        if ctype == "const Cloudsc2Params*":
+            return (POINTER(Cloudsc2Params),)
+        if ctype in ("int32_t", "int64_t", "double"):
+            return ({"int32_t": c_int32, "int64_t": c_int64, "double": c_double}[ctype],)
+        if re.fullmatch(r"(const )?(double|float)\* const\*", ctype):
+            return (POINTER(c_void_p),)
+        assert ctype.endswith("*") and "* " not in ctype[:-1], f"unrecognised parameter type {ctype!r}"
+        return any_pointer
+
+    for base, params in protos:
+        want = [kind(x) for x in params.split(",")]
+        for sfx in ("f64", "f32"):
+            fn = getattr(hip_lib, f"{base}_{sfx}")
+            assert fn.restype is c_int32
+            got = list(fn.argtypes)
+            assert len(got) == len(want), (base, sfx, got)
+            for i, (g, w) in enumerate(zip(got, want)):
+                assert g in w, f"{base}_{sfx}: argument {i} is declared {g}, the header says {params.split(',')[i].strip()!r}"
+
+
 def test_params_struct_matches(hip_lib):
     from gt4py_dwarf_p_cloudsc2_tl_ad_amd.params import ABI_VERSION, Cloudsc2Params
 
@@ -191,20 +228,49 @@ def test_outputs_must_not_alias_other_fields(hip_lib):
 
 
 def test_nlev_external_must_match_the_storages(hip_lib):
-    from gt4py_dwarf_p_cloudsc2_tl_ad_amd.stencils import compile_stencil
+    from gt4py_dwarf_p_cloudsc2_tl_ad_amd.stencils import STENCILS, checked_nlev, compile_stencil
 
+    assert [n for n, c in STENCILS.items() if c.layout.sets_nlev] == [
+        "cloudsc2_tl", "cloudsc2_tl_incremented", "cloudsc2_ad", "cloudsc2_ad_from_trajectory"]
     tl = compile_stencil("cloudsc2_tl", {"NLEV": 137})
-    tl._validate = True
-    tl._set_nlev(137)
+    assert checked_nlev(tl.name, tl.externals, 137, True) == 137
     with pytest.raises(ValueError, match="NLEV=137 does not match"):
-        tl._set_nlev(90)
-    tl._validate = False            # validate_args=False: the storages decide (the kernels' bounds depend on it)
-    tl._set_nlev(90)
-    assert tl.params.NLEV == 90
+        checked_nlev(tl.name, tl.externals, 90, True)
+    # validate_args=False: the storages decide (the kernels' bounds depend on it)
+    assert checked_nlev(tl.name, tl.externals, 90, False) == 90
     ad = compile_stencil("cloudsc2_ad", {})     # no NLEV given: derived from the storages
-    ad._validate = True
-    ad._set_nlev(60)
-    assert ad.params.NLEV == 60
+    assert checked_nlev(ad.name, ad.externals, 60, True) == 60
+
+
+def test_nlev_reaches_the_params_struct(hip_lib, monkeypatch):
+    """what `checked_nlev` returns is what the kernel is given: a call (host storages, the entry point replaced by a
+    function that returns 0) leaves it in `params.NLEV`, whether the external was absent or disagreed"""
+    import contextlib
+
+    import torch
+
+    from gt4py_dwarf_p_cloudsc2_tl_ad_amd import stencils, storage
+    from gt4py_dwarf_p_cloudsc2_tl_ad_amd.stencils import NL_IN, NL_OUT, compile_stencil
+
+    monkeypatch.setattr(stencils, "_current_stream_ptr", lambda device: 0)
+    monkeypatch.setattr(torch.cuda, "device", lambda device: contextlib.nullcontext())
+
+    def call(st, nz, names):
+        seen = []
+        st._entry = {dt: (lambda *a: seen.append(a[0]._obj.NLEV) or 0) for dt in st._entry}
+        st(**{n: storage.zeros(8, nz, torch.float64, "cpu") for n in names}, in_eta=torch.zeros(nz + 1, dtype=torch.float64),
+           dt=3600.0, origin=(0, 0, 0), domain=(8, 1, nz + 1), validate_args=False, exec_info=None)
+        return seen
+
+    ad = compile_stencil("cloudsc2_ad", {})     # no NLEV given: derived from the storages
+    ad_names = (["in_" + n for n in NL_IN] + ["in_" + n + "_i" for n in NL_OUT] + ["out_" + n for n in NL_OUT]
+                + ["out_" + n + "_i" for n in NL_IN])
+    assert call(ad, 60, ad_names) == [60] and ad.params.NLEV == 60
+    tl = compile_stencil("cloudsc2_tl", {"NLEV": 137})
+    tl_names = (["in_" + n for n in NL_IN] + ["in_" + n + "_i" for n in NL_IN] + ["out_" + n for n in NL_OUT]
+                + ["out_" + n + "_i" for n in NL_OUT])
+    assert tl.params.NLEV == 137
+    assert call(tl, 90, tl_names) == [90] and tl.params.NLEV == 90      # validate_args=False: the storages decide
 
 
 def test_level_limit_is_an_argument_error_not_a_launch_failure(hip_lib):
