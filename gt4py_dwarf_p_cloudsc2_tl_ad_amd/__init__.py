@@ -1,0 +1,13 @@
+"""CLOUDSC2 (NL / TL / AD) on the MI355X.  `cloudsc2`, `tl_masked` and `ad_masked` (the differentiable step and the masked
+linearisations underneath, see `autodiff`) are resolved on first use, so importing the package stays free of torch."""
+
+_AUTODIFF = ("cloudsc2", "tl_masked", "ad_masked")
+__all__ = list(_AUTODIFF)
+
+
+def __getattr__(name):
+    if name in _AUTODIFF:
+        from . import autodiff
+
+        return getattr(autodiff, name)
+    raise AttributeError(f"module {__name__!r} has no attribute {name!r}")

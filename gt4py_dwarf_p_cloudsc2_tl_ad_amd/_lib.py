@@ -117,7 +117,13 @@ def _signatures() -> Dict[str, Tuple[Any, Tuple[Any, ...]]]:
         "cloudsc2_field_sums_blocks": (c_int32, (c_int32, c_int32)), "cloudsc2_column_dots_chunks": (c_int32, (c_int32,)),
     }
     reduction = (c_int32, c_int32, c_int64, c_int32, _PARR, _PARR, c_void_p)
+    # the masked TL / AD entries (autodiff.py calls them directly: NULL entries are not something a stencil call has)
+    head = (POINTER(Cloudsc2Params), c_int32, c_int32, c_int64)
+    tl_masked = head + (_PARR, _PARR, c_void_p, c_void_p, _PARR, _PARR, c_double, c_void_p)
+    ad_masked = head + (_PARR, _PARR, c_void_p, c_void_p, c_void_p, c_void_p, _PARR, c_double, c_void_p)
     for sfx in ("f64", "f32"):
+        sig[f"cloudsc2_tl_masked_{sfx}"] = (c_int32, tl_masked)
+        sig[f"cloudsc2_ad_masked_{sfx}"] = (c_int32, ad_masked)
         sig[f"cloudsc2_field_sums_{sfx}"] = (c_int32, reduction + (c_void_p,))
         sig[f"cloudsc2_column_dots_{sfx}"] = (c_int32, reduction + (c_int32, c_void_p))
         for lay in LAYOUTS.values():

@@ -1,0 +1,257 @@
+"""CLOUDSC2 as a differentiable PyTorch operation (C ABI `cloudsc2_tl_masked_*`, `cloudsc2_ad_masked_*`).
+
+`cloudsc2(state, eta, dt)` is one `cloudsc2_nl` step whose gradients PyTorch can take: reverse mode (`backward`,
+`torch.autograd.grad`) runs the adjoint kernel, forward mode (`torch.autograd.forward_ad`) the tangent-linear kernel.  A
+derivative rule has perturbations / forcing on a few fields only and wants a few results only, so both go through the
+MASKED kernels: fields a call does not have are NULL entries that move no HBM words (include/cloudsc2_hip.h).
+
+`tl_masked` / `ad_masked` are the thin calls underneath, usable on their own (a variational cost, a sensitivity study).
+GPU tensors only - there is no host path."""
+from __future__ import annotations
+
+import ctypes
+from typing import Any, Dict, Iterable, Mapping, Optional, Tuple
+
+import torch
+
+from . import _lib
+from ._lib import NL_IN, NL_OUT
+from .params import default_externals, make_params
+from .storage import field_geometry, zeros
+
+_SFX = {torch.float64: "f64", torch.float32: "f32"}
+_ZERO_LINE_BYTES = 512
+_zero_lines: Dict[Tuple[torch.device, torch.dtype], torch.Tensor] = {}
+
+
+def _zero_line(device: torch.device, dtype: torch.dtype) -> torch.Tensor:
+    """the 512 zero bytes an absent input is read from: one per device and dtype, kept for the life of the process"""
+    if device.index is None:
+        device = torch.device("cuda", torch.cuda.current_device())
+    key = (device, dtype)
+    line = _zero_lines.get(key)
+    if line is None:
+        line = _zero_lines[key] = torch.zeros(_ZERO_LINE_BYTES // torch.empty((), dtype=dtype).element_size(),
+                                              dtype=dtype, device=device)
+        # its memset ran on the stream current now; later calls read it from any stream: complete it once, here
+        torch.cuda.current_stream(device).synchronize()
+    return line
+
+
+def _plain(t: torch.Tensor) -> torch.Tensor:
+    return t.detach().as_subclass(torch.Tensor)
+
+
+def _checked(what: str, groups: Iterable[Tuple[Mapping[str, torch.Tensor], Tuple[str, ...], bool]]):
+    """geometry, dtype and device shared by every field of a call; `groups`: (fields, allowed names, all required)"""
+    first, geo = None, None
+    for fields, names, required in groups:
+        unknown = sorted(set(fields) - set(names))
+        if unknown:
+            raise ValueError(f"{what}: unknown field names {unknown}")
+        if required and set(fields) != set(names):
+            raise ValueError(f"{what}: missing fields {sorted(set(names) - set(fields))}")
+        for n, f in fields.items():
+            if not isinstance(f, torch.Tensor):
+                raise TypeError(f"{what}: {n} is not a torch.Tensor")
+            if not f.is_cuda:
+                raise ValueError(f"{what}: {n} lives on {f.device}; fields must live on the GPU (there is no host path)")
+            g = field_geometry(f)
+            if first is None:
+                first, geo = f, g
+            elif g != geo or f.dtype != first.dtype or f.device != first.device:
+                raise ValueError(f"{what}: {n} has (nx, nlev, lev_stride) / dtype / device {g} / {f.dtype} / {f.device}, "
+                                 f"the call's are {geo} / {first.dtype} / {first.device}")
+    if first.dtype not in _SFX:
+        raise TypeError(f"{what}: unsupported dtype {first.dtype}")
+    return geo, first.dtype, first.device
+
+
+def _eta(what: str, eta: torch.Tensor, nz: int, dtype, device) -> torch.Tensor:
+    if (not isinstance(eta, torch.Tensor) or eta.dim() != 1 or eta.shape[0] < nz + 1 or eta.dtype != dtype
+            or eta.device != device or not eta.is_contiguous()):
+        raise ValueError(f"{what}: eta must be a contiguous 1-D {dtype} tensor on {device} with >= {nz + 1} entries")
+    return eta
+
+
+def _params(externals: Optional[Mapping[str, Any]], nz: int, **over):
+    ext = dict(default_externals() if externals is None else externals)
+    ext.update(over)
+    p = make_params(ext)
+    p.NLEV = nz
+    return p
+
+
+def _ptrs(fields: Mapping[str, torch.Tensor], names) -> ctypes.Array:
+    return _lib.ptr_array([fields[n].data_ptr() if n in fields else 0 for n in names])
+
+
+def _new_like(ref: torch.Tensor, nx: int, nz: int, ls: int) -> torch.Tensor:
+    out = zeros(nx, nz, ref.dtype, ref.device)
+    if nx > 0 and field_geometry(out)[2] != ls:      # the call's fields are windows of wider allocations: match their pitch
+        out = torch.zeros((nz + 1, ls), dtype=ref.dtype, device=ref.device)[:, :nx].unsqueeze(1).permute(2, 1, 0)
+    return out
+
+
+def tl_masked(state: Mapping[str, torch.Tensor], perturbations: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+              externals: Optional[Mapping[str, Any]] = None, *, want: Iterable[str], write_nl: bool = False):
+    """Tangent-linear CLOUDSC2 with absent fields: `perturbations` holds the perturbed inputs (`NL_IN` names; a missing
+    name is a zero perturbation), `want` names the perturbed outputs (`NL_OUT` names) to produce.  Returns
+    `(nl_outputs or None, {name: perturbed output})`; results are new `storage.zeros` fields."""
+    what = "tl_masked"
+    want = tuple(want)
+    if not want or set(want) - set(NL_OUT):
+        raise ValueError(f"{what}: `want` must name at least one of {NL_OUT}, got {want}")
+    state = {n: _plain(f) for n, f in state.items()}
+    pert = {n: _plain(f) for n, f in perturbations.items()}
+    (nx, nlev, ls), dtype, device = _checked(what, ((state, NL_IN, True), (pert, NL_IN, False)))
+    nz = nlev - 1
+    eta = _eta(what, eta, nz, dtype, device)
+    ref = state[NL_IN[0]]
+    out = {n: _new_like(ref, nx, nz, ls) for n in NL_OUT} if write_nl else None
+    out_i = {n: _new_like(ref, nx, nz, ls) for n in want}
+    p = _params(externals, nz)
+    with torch.cuda.device(device):
+        rc = getattr(_lib.load(), "cloudsc2_tl_masked_" + _SFX[dtype])(
+            ctypes.byref(p), nx, nz, ls, _ptrs(state, NL_IN), _ptrs(pert, NL_IN), _zero_line(device, dtype).data_ptr(),
+            eta.data_ptr(), None if out is None else _ptrs(out, NL_OUT), _ptrs(out_i, NL_OUT), float(dt),
+            int(torch.cuda.current_stream(device).cuda_stream))
+    _lib.check(rc, what)
+    return out, out_i
+
+
+def ad_masked(state: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+              externals: Optional[Mapping[str, Any]] = None, *, traj: Mapping[str, torch.Tensor], want: Iterable[str]):
+    """Adjoint CLOUDSC2 with absent fields: `forcing` holds the adjoint forcing (`NL_OUT` names; a missing name is zero
+    forcing), `traj` the `fplsl` / `fplsn` outputs of a `cloudsc2_nl` / `cloudsc2_tl` call on `state`, `want` names the
+    inputs (`NL_IN` names) whose adjoints to produce.  Returns `{name: adjoint}` as new `storage.zeros` fields.
+    LEVAPLS2 / LDRAIN1D are refused (`ValueError`), as by `cloudsc2_ad_from_trajectory`."""
+    what = "ad_masked"
+    want = tuple(want)
+    if not want or set(want) - set(NL_IN):
+        raise ValueError(f"{what}: `want` must name at least one of {NL_IN}, got {want}")
+    state = {n: _plain(f) for n, f in state.items()}
+    forcing = {n: _plain(f) for n, f in forcing.items()}
+    traj = {n: _plain(f) for n, f in traj.items()}
+    (nx, nlev, ls), dtype, device = _checked(what, ((state, NL_IN, True), (forcing, NL_OUT, False),
+                                                    (traj, ("fplsl", "fplsn"), True)))
+    nz = nlev - 1
+    eta = _eta(what, eta, nz, dtype, device)
+    ref = state[NL_IN[0]]
+    out_adj = {n: _new_like(ref, nx, nz, ls) for n in want}
+    p = _params(externals, nz)
+    with torch.cuda.device(device):
+        rc = getattr(_lib.load(), "cloudsc2_ad_masked_" + _SFX[dtype])(
+            ctypes.byref(p), nx, nz, ls, _ptrs(state, NL_IN), _ptrs(forcing, NL_OUT), _zero_line(device, dtype).data_ptr(),
+            eta.data_ptr(), traj["fplsl"].data_ptr(), traj["fplsn"].data_ptr(), _ptrs(out_adj, NL_IN), float(dt),
+            int(torch.cuda.current_stream(device).cuda_stream))
+    _lib.check(rc, what)
+    return out_adj
+
+
+def _in_layout(g: torch.Tensor, ref: torch.Tensor, geo) -> torch.Tensor:
+    """`g` as a field of the call's geometry: itself, or a copy into a `storage.zeros` field (autograd hands over whatever
+    layout the consumer produced, e.g. the stride-0 expansion of `.sum().backward()`)"""
+    g = _plain(g)
+    nx, nlev, ls = geo
+    if g.dtype == ref.dtype and g.device == ref.device and tuple(g.shape) == (nx, 1, nlev):
+        try:
+            if field_geometry(g) == geo:
+                return g
+        except ValueError:
+            pass
+    f = _new_like(ref, nx, nlev - 1, ls)
+    f.copy_(g)
+    return f
+
+
+class _Cloudsc2(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, eta, dt, externals, *inputs):
+        from .stencils import compile_stencil
+
+        ctx.set_materialize_grads(False)
+        state = {n: _plain(f) for n, f in zip(NL_IN, inputs)}
+        (nx, nlev, ls), dtype, device = _checked("cloudsc2", ((state, NL_IN, True),))
+        nz = nlev - 1
+        ref = state[NL_IN[0]]
+        out = {n: _new_like(ref, nx, nz, ls) for n in NL_OUT}
+        ext = dict(default_externals() if externals is None else externals)
+        compile_stencil("cloudsc2_nl", ext)(**{"in_" + n: f for n, f in state.items()}, **{"out_" + n: f for n, f in out.items()},
+                                             in_eta=eta, dt=dt, origin=(0, 0, 0), domain=(nx, 1, nlev), validate_args=False,
+                                             exec_info=None)
+        ctx.eta, ctx.dt, ctx.ext, ctx.geo = eta, float(dt), ext, (nx, nlev, ls)
+        ctx.save_for_backward(*inputs, out["fplsl"], out["fplsn"])
+        ctx.save_for_forward(*inputs)
+        return tuple(out[n] for n in NL_OUT)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        need = ctx.needs_input_grad[3:]
+        none = (None,) * (3 + len(NL_IN))
+        if all(g is None for g in grads) or not any(need):
+            return none
+        saved = ctx.saved_tensors
+        state = dict(zip(NL_IN, saved[:len(NL_IN)]))
+        ref = _plain(saved[0])
+        forcing = {n: _in_layout(g, ref, ctx.geo) for n, g in zip(NL_OUT, grads) if g is not None}
+        want = tuple(n for n, w in zip(NL_IN, need) if w)
+        ext = dict(ctx.ext, AD_TRAJ_FIX=1)
+        if ext.get("LEVAPLS2") or ext.get("LDRAIN1D"):
+            adj = _dense_ad(state, forcing, ctx.eta, ctx.dt, ext, ctx.geo, want)
+        else:
+            adj = ad_masked(state, forcing, ctx.eta, ctx.dt, ext, traj={"fplsl": saved[-2], "fplsn": saved[-1]}, want=want)
+        return (None, None, None) + tuple(adj.get(n) for n in NL_IN)
+
+    @staticmethod
+    def jvp(ctx, _eta_t, _dt_t, _ext_t, *tangents):
+        state = dict(zip(NL_IN, ctx.saved_tensors))      # in jvp: what save_for_forward kept
+        ref = _plain(state[NL_IN[0]])
+        pert = {n: _in_layout(t, ref, ctx.geo) for n, t in zip(NL_IN, tangents) if t is not None}
+        if not pert:
+            return (None,) * len(NL_OUT)
+        _, out_i = tl_masked(state, pert, ctx.eta, ctx.dt, ctx.ext, want=NL_OUT, write_nl=False)
+        return tuple(out_i[n] for n in NL_OUT)
+
+
+def _dense_ad(state, forcing, eta, dt, ext, geo, want):
+    """the evaporation switches: `cloudsc2_ad` with zero fields for the absent forcing; unwanted adjoints are dropped"""
+    from .stencils import compile_stencil
+
+    nx, nlev, ls = geo
+    ref = _plain(state[NL_IN[0]])
+    new = lambda: _new_like(ref, nx, nlev - 1, ls)  # noqa: E731
+    args = {"in_" + n: _plain(f) for n, f in state.items()}
+    args.update({"in_" + n + "_i": forcing[n] if n in forcing else new() for n in NL_OUT})
+    args.update({"out_" + n: new() for n in NL_OUT})
+    adj = {n: new() for n in NL_IN}
+    args.update({"out_" + n + "_i": f for n, f in adj.items()})
+    compile_stencil("cloudsc2_ad", ext)(**args, in_eta=eta, dt=dt, origin=(0, 0, 0), domain=(nx, 1, nlev), validate_args=False,
+                                         exec_info=None)
+    return {n: adj[n] for n in want}
+
+
+def cloudsc2(state: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+             externals: Optional[Mapping[str, Any]] = None) -> Dict[str, torch.Tensor]:
+    """One differentiable CLOUDSC2 step: the 16 inputs (`NL_IN` names, storage layout `(nx, 1, nz+1)`, column-fastest) ->
+    the 10 NL outputs (`NL_OUT` names), computed by `cloudsc2_nl`.
+
+    Derivatives are the reference's tangent-linear model and its exact transpose.  They are the reference's REGULARISED
+    TL / AD (LREGCL damps the derivatives of the cloud-fraction and autoconversion terms), not finite differences of the
+    NL step: a Taylor test of NL against them converges to the regularised slope.  `AD_TRAJ_FIX=1` is forced for the
+    adjoint call, so the VJP is the transpose of the JVP in every column (the reference's own AD differs from it where the
+    saturation adjustment crosses the freezing point), and the trajectory fluxes are the NL kernel's own.
+
+    `backward` is ONE masked adjoint launch: forcing = the gradients that arrived, results = the inputs that require one;
+    `jvp` is one masked tangent-linear launch.  With LEVAPLS2 / LDRAIN1D the backward falls back to the dense
+    `cloudsc2_ad` (which recomputes the trajectory: 70 words per level and column plus ten zero-filled forcing fields and
+    26 scratch results) - same gradients, at that cost.  Second derivatives are not available (`once_differentiable`)."""
+    missing = [n for n in NL_IN if n not in state]
+    if missing or len(state) != len(NL_IN):
+        raise ValueError(f"cloudsc2: state must hold exactly the fields {NL_IN}; missing {missing}")
+    for n in NL_IN:
+        if isinstance(state[n], torch.Tensor) and not state[n].is_cuda:
+            raise ValueError(f"cloudsc2: {n} lives on {state[n].device}; fields must live on the GPU")
+    outs = _Cloudsc2.apply(eta, dt, externals, *(state[n] for n in NL_IN))
+    return dict(zip(NL_OUT, outs))

@@ -1088,4 +1088,230 @@ template int launch_ad<double>(const Cloudsc2Params&, int, int, int64_t, const d
 template int launch_ad<float>(const Cloudsc2Params&, int, int, int64_t, const float* const*, const float* const*,
                               const float*, float* const*, float* const*, double, hipStream_t, const float*, const float*);
 
+// ------------------------------------------------------------------------------------------------------------------
+// Masked adjoint (BUILD EXTENSION, C ABI cloudsc2_ad_masked_*): the vector-Jacobian product as an automatic-differentiation
+// framework asks for it - forcing on a few NL outputs, adjoints of a few inputs.  Sweep 2 of ad_kernel<TRAJ> (same
+// ad_forward / ad_backward, same prefetch of one level, same parking) in which
+//   * an ABSENT FORCING is still loaded - every load of a level is issued unconditionally, so hipcc's wait-count insertion
+//     keeps an exact count of the loads in flight and the wait for level k-1's words never reaches the prefetch of level
+//     k-2 just issued (a wave-uniform branch around a load - `p ? ldg(p, o) : 0` - loses that count, and with it the only
+//     memory-level parallelism one wave per SIMD has).  What differs is WHERE it reads: the launcher has replaced the
+//     field's pointer by the caller's zero line and the lane's offset becomes lane * sizeof(T) (one v_cndmask on a
+//     wave-uniform bit of `have`).  Every wave reads the same 512 B, which stay in cache: no HBM word moves;
+//   * an UNWANTED ADJOINT is not stored: a wave-uniform branch on a bit of `want` around the store.  The store count of a
+//     level is then unknown to hipcc, so the wait for the next level's words also covers the stores issued since those
+//     words were requested; the kernel therefore issues a level's stores one iteration late (see the loop), where they
+//     have a whole level's arithmetic to complete before that wait.
+// The words the level functions see are those of the dense call with zero fields, so the adjoints that are written are
+// the trajectory variant's bit for bit.  Driver switches and 32-bit offsets only, as ad_kernel<TRAJ>.
+template <typename T>
+struct ADMaskedArgs {
+    Ext<T> e;
+    NLK<T> kc;
+    ExpK<T> xk;
+    int nx, nz;
+    int64_t ls;
+    CPtrs<T, NL_NUM_IN> in;
+    CPtrs<T, NL_NUM_OUT> adj;    // an absent forcing: the zero line
+    const T* eta;
+    MPtrs<T, NL_NUM_IN> oadj;    // an unwanted adjoint: nullptr, never used (its bit of `want` is 0)
+    T dt;
+    const T* traj_l;
+    const T* traj_n;
+    uint32_t have;               // bit f: forcing f (NL_OUT_*) is a field of the call
+    uint32_t want;               // bit f: adjoint f (NL_IN_*) is written
+};
+template <typename T>
+struct ADMaskedFields : KernArgs<ADMaskedArgs<T>> {
+    __device__ __forceinline__ const T* in(int i) const { return this->ka->in.p[i]; }
+    __device__ __forceinline__ const T* adj(int i) const { return this->ka->adj.p[i]; }
+    __device__ __forceinline__ T* oadj(int i) const { return this->ka->oadj.p[i]; }
+    __device__ __forceinline__ const T* traj_l() const { return this->ka->traj_l; }
+    __device__ __forceinline__ const T* traj_n() const { return this->ka->traj_n; }
+};
+
+// ad_load_force with a per-field offset: the field's own `o`, or `zo` into the zero line (raw words, as there)
+template <typename T, typename FP>
+__device__ __forceinline__ ADForce<T> ad_load_force_masked(const FP& F, uint32_t have, uint32_t lsb, uint32_t o, uint32_t zo) {
+    const auto at = [&](int f, uint32_t x) { return (have >> f & 1u) ? x : zo; };
+    ADForce<T> f;
+    f.clc = ldg(F.adj(NL_OUT_CLC), at(NL_OUT_CLC, o));
+    f.tnd_q = ldg(F.adj(NL_OUT_TND_Q), at(NL_OUT_TND_Q, o));
+    f.tnd_qi = ldg(F.adj(NL_OUT_TND_QI), at(NL_OUT_TND_QI, o));
+    f.tnd_ql = ldg(F.adj(NL_OUT_TND_QL), at(NL_OUT_TND_QL, o));
+    f.tnd_t = ldg(F.adj(NL_OUT_TND_T), at(NL_OUT_TND_T, o));
+    f.fplsl1 = ldg(F.adj(NL_OUT_FPLSL), at(NL_OUT_FPLSL, o + lsb));
+    f.fhpsl1 = ldg(F.adj(NL_OUT_FHPSL), at(NL_OUT_FHPSL, o + lsb));
+    f.fplsn1 = ldg(F.adj(NL_OUT_FPLSN), at(NL_OUT_FPLSN, o + lsb));
+    f.fhpsn1 = ldg(F.adj(NL_OUT_FHPSN), at(NL_OUT_FHPSN, o + lsb));
+    f.covptot = T(0.0);   // read by the evaporation block only
+    return f;
+}
+
+// The sixteen stores of one level of sweep 2 (ad_kernel's, :992-996 included), each under its bit of `want`.
+template <typename T, typename FP>
+__device__ __forceinline__ void ad_store_masked(const FP& F, uint32_t want, uint32_t lsb, uint32_t o, T dt, const ADOut<T>& a) {
+#define CS2_WANT(f) (want >> (f) & 1u)
+    if (CS2_WANT(NL_IN_AP)) stg(F.oadj(NL_IN_AP), o, a.ap);
+    if (CS2_WANT(NL_IN_T)) stg(F.oadj(NL_IN_T), o, a.t);
+    if (CS2_WANT(NL_IN_Q)) stg(F.oadj(NL_IN_Q), o, a.q);
+    if (CS2_WANT(NL_IN_QL)) stg(F.oadj(NL_IN_QL), o, a.ql);
+    if (CS2_WANT(NL_IN_QI)) stg(F.oadj(NL_IN_QI), o, a.qi);
+    if (CS2_WANT(NL_IN_QSAT)) stg(F.oadj(NL_IN_QSAT), o, a.qsat);
+    if (CS2_WANT(NL_IN_LUDE)) stg(F.oadj(NL_IN_LUDE), o, a.lude);
+    if (CS2_WANT(NL_IN_MFD)) stg(F.oadj(NL_IN_MFD), o, a.mfd);
+    if (CS2_WANT(NL_IN_MFU)) stg(F.oadj(NL_IN_MFU), o, a.mfu);
+    if (CS2_WANT(NL_IN_SUPSAT)) stg(F.oadj(NL_IN_SUPSAT), o, dt * a.q);           // :992 (Q7, literal)
+    if (CS2_WANT(NL_IN_TND_CML_T)) stg(F.oadj(NL_IN_TND_CML_T), o, dt * a.t);     // :993-996
+    if (CS2_WANT(NL_IN_TND_CML_Q)) stg(F.oadj(NL_IN_TND_CML_Q), o, dt * a.q);
+    if (CS2_WANT(NL_IN_TND_CML_QL)) stg(F.oadj(NL_IN_TND_CML_QL), o, dt * a.ql);
+    if (CS2_WANT(NL_IN_TND_CML_QI)) stg(F.oadj(NL_IN_TND_CML_QI), o, dt * a.qi);
+    if (CS2_WANT(NL_IN_APH)) stg(F.oadj(NL_IN_APH), o + lsb, a.aph1);
+    if (CS2_WANT(NL_IN_LU)) stg(F.oadj(NL_IN_LU), o + lsb, a.lu1);
+#undef CS2_WANT
+}
+
+template <typename T, bool REG, bool FIX>
+__global__ void __launch_bounds__(kColBlock, sizeof(T) == 4 ? 3 : 1)
+ad_masked_kernel(const ADMaskedArgs<T> A) {
+    Ext<T> e = A.e;
+    NLK<T> kc = A.kc;
+    ExpK<T> xk = A.xk;
+    const int nx = A.nx, nz = A.nz;
+    const int64_t ls = A.ls;
+    const T* __restrict__ eta = A.eta;
+    T dt = A.dt;
+    const uint32_t have = A.have, want = A.want;
+    ADMaskedFields<T> F;
+    const auto F_in = [&](int i) { return F.in(i); };
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    T* s_eta = reinterpret_cast<T*>(smem_raw);
+    T* s_scalm = s_eta + (nz + 1);
+    int klo, khi;
+    build_level_table<T>(eta, nz, e, s_eta, s_scalm, klo, khi);
+    if constexpr (sizeof(T) == 8) {
+        pin_vgprs(e.RCPD, e.RLSTT, e.RLVTT, e.R4LES, e.R4IES, e.RTT, e.R3IES, e.R3LES, e.R2ES, e.ZQMAX, e.RETV, e.R5LES,
+                  e.R5IES, e.RG, e.RD, kc.rdt, kc.cons2, kc.rRD, kc.rRCPD, dt);
+        pin_expk(xk);
+    }
+
+    const int gcol = xcd_block() * kColBlock + threadIdx.x;
+    T* const park_lds = s_scalm + (nz + 1) + threadIdx.x;
+    (void)park_lds;
+    if (gcol >= nx) return;  // no later workgroup barrier: whole lanes may retire
+    using O = uint32_t;
+    const O lsb = O(ls) * O(sizeof(T));
+    const O colb = O(gcol) * O(sizeof(T));
+    const O zo = O(threadIdx.x & (kWave - 1)) * O(sizeof(T));   // this lane's word of the zero line
+
+    const T trpaus = trpaus_prescan<T, false, O>(F.in(NL_IN_T), F.in(NL_IN_TND_CML_T), lsb, colb, dt, s_eta, klo, khi);
+    const CrhCol<T> crh = crh_setup<T>(trpaus);
+
+    ADBack<T> b;
+    b.tmp_rfln_i = b.tmp_sfln_i = b.rfl_i = b.sfl_i = b.daph_i = b.dp_i = T(0.0);
+    b.covptot_i = b.aph_s_i = T(0.0);
+    b.aph_s = T(1.0);
+    // ONE loop, k = nz .. -1, and nothing of a level outside it: iteration k requests level k-1's words, stores level k+1's
+    // adjoints and computes level k (the first iteration only requests, the last only stores).
+    //   * A level's adjoints are stored ONE ITERATION LATE, right behind the next prefetch: with the store count unknown,
+    //     the wait for level k-1's words (requested before level k is computed, first read after it) covers every
+    //     operation issued since - stores included.  Stores issued behind level k's arithmetic would be waited for at
+    //     their full latency on every level; stores issued before it have long completed by then.
+    //   * No prologue batch and no epilogue stores: hipcc lays such blocks out around the loop as it pleases, and
+    //     check_ring_isa.check_prefetch_distance reads every backward branch as a loop.
+    O o = O(nz) * lsb + colb, po = o;
+    ADOut<T> pa;
+    pa.ap = pa.t = pa.q = pa.ql = pa.qi = pa.qsat = pa.lude = pa.mfd = pa.mfu = pa.aph1 = pa.lu1 = T(0.0);
+    LevelIn<T> xa;
+    xa.ap = xa.aph1 = xa.lu1 = xa.lude = xa.mfd = xa.mfu = xa.q = xa.qi = xa.ql = xa.qsat = xa.supsat = xa.t = xa.tq = xa.tqi =
+        xa.tql = xa.tt = T(0.0);
+    ADForce<T> fa;
+    fa.clc = fa.tnd_q = fa.tnd_qi = fa.tnd_ql = fa.tnd_t = fa.fplsl1 = fa.fplsn1 = fa.fhpsl1 = fa.fhpsn1 = fa.covptot = T(0.0);
+    T aph_k = ldg(F.in(NL_IN_APH), o), sfl = T(0.0), rfl = T(0.0);   // aph[nz]: level nz-1's lower half level
+    for (int k = nz; k >= -1; --k) {
+        F.fresh();
+        LevelIn<T> xn = xa;
+        ADForce<T> fn = fa;
+        T aph_n = aph_k, sfl_n = sfl, rfl_n = rfl;
+        if (k > 0) {
+            const O om = o - lsb;
+            xn = load_level<T>(F_in, lsb, om);
+            xn.aph1 = aph_k;   // aph[k]: already here as this level's upper half level
+            fn = ad_load_force_masked<T>(F, have, lsb, om, zo);
+            aph_n = ldg(F.in(NL_IN_APH), om);
+            sfl_n = ldg(F.traj_n(), om);
+            rfl_n = ldg(F.traj_l(), om);
+        }
+        if (k < nz - 1) ad_store_masked<T>(F, want, lsb, po, dt, pa);
+        if (k >= 0 && k < nz) {
+            ADTraj<T> r;
+            ad_forward<T, FIX, false>(e, kc, xk, xa, aph_k, k, s_eta[k], s_scalm[k], crh, dt, rfl, sfl, T(0.0), T(1.0), r);
+            if constexpr (kADPark<T>) ad_park<T>(park_lds, r);
+            pa = ad_backward<T, REG, FIX, false>(e, kc, xa, k, s_scalm[k], dt, sfl, r, fa, b, park_lds);
+            po = o;
+        }
+        xa = xn;
+        fa = fn;
+        aph_k = aph_n;
+        sfl = sfl_n;
+        rfl = rfl_n;
+        o -= lsb;
+    }
+    // :982-986 top half level
+    if (want >> NL_IN_APH & 1u) stg(F.oadj(NL_IN_APH), colb, b.daph_i - b.dp_i);
+    if (want >> NL_IN_LU & 1u) stg(F.oadj(NL_IN_LU), colb, T(0.0));
+}
+
+// in_adj[f] == nullptr: forcing f is zero everywhere (read from `zero`); out_adj[f] == nullptr: adjoint f is not written.
+// The caller (cloudsc2_capi.hip) has refused the evaporation switches and fields of 4 GiB and more.
+template <typename T>
+int launch_ad_masked(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* const* in, const T* const* in_adj,
+                     const T* zero, const T* eta, const T* traj_l, const T* traj_n, T* const* out_adj, double dt,
+                     hipStream_t stream) {
+    if (p.LEVAPLS2 || p.LDRAIN1D || !fits_u32_offsets<T>(nz, ls)) return -2;
+    ADMaskedArgs<T> args;
+    args.e = make_ext<T>(p);
+    args.kc = make_nlk<T>(p, dt, false);
+    args.xk = make_expk<T>();
+    args.nx = nx; args.nz = nz; args.ls = ls;
+    args.have = args.want = 0;
+    for (int i = 0; i < NL_NUM_IN; ++i) {
+        args.in.p[i] = in[i];
+        args.oadj.p[i] = out_adj[i];
+        if (out_adj[i]) args.want |= 1u << i;
+    }
+    for (int i = 0; i < NL_NUM_OUT; ++i) {
+        args.adj.p[i] = in_adj[i] ? in_adj[i] : zero;
+        if (in_adj[i]) args.have |= 1u << i;
+    }
+    args.eta = eta;
+    args.dt = static_cast<T>(dt);
+    args.traj_l = traj_l;
+    args.traj_n = traj_n;
+    const dim3 grid((nx + kColBlock - 1) / kColBlock), block(kColBlock);
+    const size_t smem = 2 * size_t(nz + 1) * sizeof(T) + (kADPark<T> ? size_t(CS2_AD_PARK_COUNT) * kColBlock * sizeof(T) : 0);
+    if (smem > size_t(160) * 1024) return -2;
+    int dev = 0;
+    if (smem > size_t(64) * 1024)
+        if (const int rc = current_device(dev)) return rc;
+    const int rc = with_flags(
+        [&](auto REG, auto FIX) {
+            constexpr auto kern = ad_masked_kernel<T, REG, FIX>;
+            if (smem > size_t(64) * 1024 && !lds_opt_in<kern>(dev, smem)) return -1;
+            hipLaunchKernelGGL(kern, grid, block, smem, stream, args);
+            return 0;
+        },
+        p.LREGCL != 0, p.AD_TRAJ_FIX != 0);
+    if (rc) return rc;
+    note_kernel("cs2::ad_masked_kernel");
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+template int launch_ad_masked<double>(const Cloudsc2Params&, int, int, int64_t, const double* const*, const double* const*,
+                                      const double*, const double*, const double*, const double*, double* const*, double,
+                                      hipStream_t);
+template int launch_ad_masked<float>(const Cloudsc2Params&, int, int, int64_t, const float* const*, const float* const*,
+                                     const float*, const float*, const float*, const float*, float* const*, double,
+                                     hipStream_t);
+
 }  // namespace cs2

@@ -26,6 +26,12 @@ template <typename T>
 int launch_ad(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T* const*, const T*, T* const*,
               T* const*, double, hipStream_t, const T* traj_l = nullptr, const T* traj_n = nullptr);
 template <typename T>
+int launch_tl_masked(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T* const*, const T*, const T*,
+                     T* const*, T* const*, double, hipStream_t);
+template <typename T>
+int launch_ad_masked(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T* const*, const T*, const T*,
+                     const T*, const T*, T* const*, double, hipStream_t);
+template <typename T>
 int launch_saturation(const Cloudsc2Params&, int, int, int64_t, const T*, const T*, T*, hipStream_t);
 template <typename T>
 int launch_increment(const Cloudsc2Params&, int, int, int64_t, const T* const*, T* const*, double, hipStream_t);
@@ -36,7 +42,9 @@ int launch_perturb(int, int, int64_t, const T* const*, const T* const*, T* const
 namespace {
 
 thread_local char g_err[512] = "";
-thread_local const char* g_kernel = "";
+// process-wide, not thread-local: torch.autograd runs a backward on a thread of its own, and the caller asks from another.
+// The names are string literals, so a reader sees a whole name, the last one stored.
+std::atomic<const char*> g_kernel{""};
 
 int fail(int code, const char* fmt, ...) {
     va_list ap;
@@ -235,6 +243,79 @@ int ad_traj_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t nz
                                           static_cast<hipStream_t>(stream), traj_fplsl, traj_fplsn));
 }
 
+// ---- the masked TL / AD entries: NULL entries of in_i / in_adj are zero fields, NULL entries of out_i / out_adj are not
+// written (include/cloudsc2_hip.h).  `what` names the array in messages.
+template <typename T>
+int check_masked_inputs(const char* fn, const char* what, const T* const* arr, int n, const T* zero_line) {
+    if (!arr) return fail(CLOUDSC2_E_ARG, "%s: %s is NULL (the array itself; its entries may be)", fn, what);
+    for (int i = 0; i < n; ++i)
+        if (!arr[i] && !zero_line)
+            return fail(CLOUDSC2_E_ARG, "%s: %s[%d] is NULL (a zero field) but zero_line is NULL too", fn, what, i);
+    if (reinterpret_cast<uintptr_t>(zero_line) % 16)
+        return fail(CLOUDSC2_E_ARG, "%s: zero_line is not 16-byte aligned", fn);
+    return 0;
+}
+
+template <typename T>
+int check_masked_outputs(const char* fn, const char* what, T* const* arr, int n) {
+    if (!arr) return fail(CLOUDSC2_E_ARG, "%s: %s is NULL (the array itself; its entries may be)", fn, what);
+    for (int i = 0; i < n; ++i)
+        if (arr[i]) return 0;
+    return fail(CLOUDSC2_E_ARG, "%s: every entry of %s is NULL: nothing would be written", fn, what);
+}
+
+template <typename T>
+int check_masked_size(const char* fn, int32_t nz, int64_t ls) {
+    if (cs2::fits_u32_offsets<T>(nz, ls)) return 0;
+    return fail(CLOUDSC2_E_UNSUPPORTED,
+                "%s: fields of 4 GiB or more ((nz+1) * lev_stride * sizeof(element) = %llu bytes >= 2^32): the masked "
+                "kernels keep 32-bit byte offsets - use the dense stencil, or narrower allocations", fn,
+                (unsigned long long)(nz + 1) * (unsigned long long)ls * sizeof(T));
+}
+
+template <typename T>
+int tl_masked_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,
+                   const T* const* in_i, const T* zero_line, const T* eta, T* const* out, T* const* out_i, double dt,
+                   void* stream) {
+    if (int rc = check_common(fn, p, nx, nz, ls)) return rc;
+    if (nx == 0) return CLOUDSC2_OK;
+    if (int rc = check_ptrs(fn, "in", in, NL_NUM_IN)) return rc;
+    if (int rc = check_masked_inputs(fn, "in_i", in_i, NL_NUM_IN, zero_line)) return rc;
+    if (out)
+        if (int rc = check_ptrs(fn, "out (all ten entries, or the array itself NULL)", const_cast<const T* const*>(out), NL_NUM_OUT))
+            return rc;
+    if (int rc = check_masked_outputs(fn, "out_i", out_i, NL_NUM_OUT)) return rc;
+    if (!eta) return fail(CLOUDSC2_E_ARG, "%s: eta is NULL", fn);
+    if (p->ICALL != 0) return fail(CLOUDSC2_E_UNSUPPORTED, "%s: ICALL=%d unsupported", fn, p->ICALL);
+    if (!(dt > 0.0)) return fail(CLOUDSC2_E_ARG, "%s: dt=%g must be > 0", fn, dt);
+    if (p->NLEV != nz) return fail(CLOUDSC2_E_ARG, "%s: NLEV=%d != nz=%d", fn, p->NLEV, nz);
+    if (int rc = check_masked_size<T>(fn, nz, ls)) return rc;
+    return launched(fn, cs2::launch_tl_masked<T>(*p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt,
+                                                 static_cast<hipStream_t>(stream)));
+}
+
+template <typename T>
+int ad_masked_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,
+                   const T* const* in_adj, const T* zero_line, const T* eta, const T* traj_fplsl, const T* traj_fplsn,
+                   T* const* out_adj, double dt, void* stream) {
+    if (int rc = check_common(fn, p, nx, nz, ls)) return rc;
+    if (nx == 0) return CLOUDSC2_OK;
+    if (int rc = check_ptrs(fn, "in", in, NL_NUM_IN)) return rc;
+    if (int rc = check_masked_inputs(fn, "in_adj", in_adj, NL_NUM_OUT, zero_line)) return rc;
+    if (int rc = check_masked_outputs(fn, "out_adj", out_adj, NL_NUM_IN)) return rc;
+    if (!eta || !traj_fplsl || !traj_fplsn) return fail(CLOUDSC2_E_ARG, "%s: eta / traj_fplsl / traj_fplsn is NULL", fn);
+    if (p->ICALL != 0) return fail(CLOUDSC2_E_UNSUPPORTED, "%s: ICALL=%d unsupported", fn, p->ICALL);
+    if (p->LEVAPLS2 || p->LDRAIN1D)
+        return fail(CLOUDSC2_E_UNSUPPORTED, "%s: LEVAPLS2 / LDRAIN1D: the masked adjoint reads its trajectory like "
+                    "cloudsc2_ad_from_trajectory and covers the driver switches only (the evaporation block's parked "
+                    "precipitation cover has no counterpart among the NL outputs) - use cloudsc2_ad", fn);
+    if (!(dt > 0.0)) return fail(CLOUDSC2_E_ARG, "%s: dt=%g must be > 0", fn, dt);
+    if (p->NLEV != nz) return fail(CLOUDSC2_E_ARG, "%s: NLEV=%d != nz=%d", fn, p->NLEV, nz);
+    if (int rc = check_masked_size<T>(fn, nz, ls)) return rc;
+    return launched(fn, cs2::launch_ad_masked<T>(*p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn,
+                                                 out_adj, dt, static_cast<hipStream_t>(stream)));
+}
+
 template <typename T>
 int sat_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* ap, const T* t,
              T* qsat, void* stream) {
@@ -268,7 +349,7 @@ int per_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t nz, in
 }  // namespace
 
 namespace cs2 {
-void note_kernel(const char* name) { g_kernel = name; }
+void note_kernel(const char* name) { g_kernel.store(name, std::memory_order_relaxed); }
 }  // namespace cs2
 
 extern "C" {
@@ -276,7 +357,7 @@ extern "C" {
 int32_t cloudsc2_abi_version(void) { return CLOUDSC2_ABI_VERSION; }
 int32_t cloudsc2_params_sizeof(void) { return (int32_t)sizeof(Cloudsc2Params); }
 const char* cloudsc2_last_error(void) { return g_err; }
-const char* cloudsc2_last_kernel(void) { return g_kernel; }
+const char* cloudsc2_last_kernel(void) { return g_kernel.load(std::memory_order_relaxed); }
 int32_t cloudsc2_device_count(void) {
     int n = 0;
     if (hipGetDeviceCount(&n) != hipSuccess) {
@@ -386,6 +467,30 @@ int32_t cloudsc2_ad_from_trajectory_f32(const Cloudsc2Params* p, int32_t nx, int
                                         const float* traj_fplsn, float* const* out_adj, double dt, void* stream) {
     return ad_traj_impl<float>("cloudsc2_ad_from_trajectory_f32", p, nx, nz, ls, in, in_adj, eta, traj_fplsl, traj_fplsn,
                                out_adj, dt, stream);
+}
+int32_t cloudsc2_tl_masked_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const double* const* in,
+                               const double* const* in_i, const double* zero_line, const double* eta, double* const* out,
+                               double* const* out_i, double dt, void* stream) {
+    return tl_masked_impl<double>("cloudsc2_tl_masked_f64", p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt, stream);
+}
+int32_t cloudsc2_tl_masked_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const float* const* in,
+                               const float* const* in_i, const float* zero_line, const float* eta, float* const* out,
+                               float* const* out_i, double dt, void* stream) {
+    return tl_masked_impl<float>("cloudsc2_tl_masked_f32", p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt, stream);
+}
+int32_t cloudsc2_ad_masked_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const double* const* in,
+                               const double* const* in_adj, const double* zero_line, const double* eta,
+                               const double* traj_fplsl, const double* traj_fplsn, double* const* out_adj, double dt,
+                               void* stream) {
+    return ad_masked_impl<double>("cloudsc2_ad_masked_f64", p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl,
+                                  traj_fplsn, out_adj, dt, stream);
+}
+int32_t cloudsc2_ad_masked_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const float* const* in,
+                               const float* const* in_adj, const float* zero_line, const float* eta,
+                               const float* traj_fplsl, const float* traj_fplsn, float* const* out_adj, double dt,
+                               void* stream) {
+    return ad_masked_impl<float>("cloudsc2_ad_masked_f32", p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl,
+                                 traj_fplsn, out_adj, dt, stream);
 }
 int32_t cloudsc2_saturation_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const double* ap,
                                 const double* t, double* qsat, void* stream) {

@@ -488,7 +488,7 @@ struct KernArgs {
     __device__ __forceinline__ KA* operator->() const { return ka; }
 };
 
-// diagnostics: the launchers record the name of the kernel they enqueued (cloudsc2_last_kernel(), thread-local)
+// diagnostics: the launchers record the name of the kernel they enqueued (cloudsc2_last_kernel(), process-wide)
 void note_kernel(const char* name);
 
 // ---- per-device facts the launchers cache (host side) ---------------------------------------------------------

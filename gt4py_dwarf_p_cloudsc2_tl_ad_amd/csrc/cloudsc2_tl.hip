@@ -844,4 +844,204 @@ template int launch_tl<double>(const Cloudsc2Params&, int, int, int64_t, const d
 template int launch_tl<float>(const Cloudsc2Params&, int, int, int64_t, const float* const*, const float* const*,
                               const float*, float* const*, float* const*, double, hipStream_t, double);
 
+// ------------------------------------------------------------------------------------------------------------------
+// Masked tangent-linear (BUILD EXTENSION, C ABI cloudsc2_tl_masked_*): the Jacobian-vector product as an
+// automatic-differentiation framework asks for it - perturbations on a few inputs, a few perturbed outputs, the NL outputs
+// only on request.  The register-path sweep of tl_kernel (same tl_level, one level of prefetch, stores drained per level)
+// with the mechanism of ad_masked_kernel (cloudsc2_ad.hip): every load is issued, an absent perturbation reads this lane's
+// word of the caller's zero line (the launcher has put the line in place of the field's pointer; one v_cndmask on a
+// wave-uniform bit of `have` picks the offset), an unwanted output is skipped by a wave-uniform branch around its store.
+// The field pointers are read from the kernarg segment (KernArgs): 52 of them do not fit the SGPRs beside the constants.
+template <typename T>
+struct TLMaskedArgs {
+    Ext<T> e;
+    NLK<T> kc;
+    ExpK<T> xk;
+    int nx, nz;
+    int64_t ls;
+    CPtrs<T, NL_NUM_IN> in;
+    CPtrs<T, NL_NUM_IN> in_i;     // an absent perturbation: the zero line
+    const T* eta;
+    MPtrs<T, NL_NUM_OUT> out;     // all or none (kTLWantNL)
+    MPtrs<T, NL_NUM_OUT> out_i;   // an unwanted field: nullptr, never used (its bit of `want` is 0)
+    T dt;
+    uint32_t have;                // bit f: perturbation f (NL_IN_*) is a field of the call
+    uint32_t want;                // bit f: out_i[f] (NL_OUT_*) is written; kTLWantNL: the ten NL outputs are
+};
+constexpr uint32_t kTLWantNL = 1u << 31;
+template <typename T>
+struct TLMaskedFields : KernArgs<TLMaskedArgs<T>> {
+    __device__ __forceinline__ const T* in(int i) const { return this->ka->in.p[i]; }
+    __device__ __forceinline__ const T* in_i(int i) const { return this->ka->in_i.p[i]; }
+    __device__ __forceinline__ T* out(int i) const { return this->ka->out.p[i]; }
+    __device__ __forceinline__ T* out_i(int i) const { return this->ka->out_i.p[i]; }
+};
+
+// load_level with a per-field offset: the field's own, or `zo` into the zero line
+template <typename T, typename P>
+__device__ __forceinline__ LevelIn<T> load_level_masked(const P& ptr, uint32_t have, uint32_t lsb, uint32_t o, uint32_t zo) {
+    const auto at = [&](int f, uint32_t x) { return (have >> f & 1u) ? x : zo; };
+    LevelIn<T> x;
+    x.ap = ldg(ptr(NL_IN_AP), at(NL_IN_AP, o));
+    x.aph1 = ldg(ptr(NL_IN_APH), at(NL_IN_APH, o + lsb));
+    x.lu1 = ldg(ptr(NL_IN_LU), at(NL_IN_LU, o + lsb));
+    x.lude = ldg(ptr(NL_IN_LUDE), at(NL_IN_LUDE, o));
+    x.mfd = ldg(ptr(NL_IN_MFD), at(NL_IN_MFD, o));
+    x.mfu = ldg(ptr(NL_IN_MFU), at(NL_IN_MFU, o));
+    x.q = ldg(ptr(NL_IN_Q), at(NL_IN_Q, o));
+    x.qi = ldg(ptr(NL_IN_QI), at(NL_IN_QI, o));
+    x.ql = ldg(ptr(NL_IN_QL), at(NL_IN_QL, o));
+    x.qsat = ldg(ptr(NL_IN_QSAT), at(NL_IN_QSAT, o));
+    x.supsat = ldg(ptr(NL_IN_SUPSAT), at(NL_IN_SUPSAT, o));
+    x.t = ldg(ptr(NL_IN_T), at(NL_IN_T, o));
+    x.tq = ldg(ptr(NL_IN_TND_CML_Q), at(NL_IN_TND_CML_Q, o));
+    x.tqi = ldg(ptr(NL_IN_TND_CML_QI), at(NL_IN_TND_CML_QI, o));
+    x.tql = ldg(ptr(NL_IN_TND_CML_QL), at(NL_IN_TND_CML_QL, o));
+    x.tt = ldg(ptr(NL_IN_TND_CML_T), at(NL_IN_TND_CML_T, o));
+    return x;
+}
+
+// tl_store, each field under its bit of `want`
+template <typename T, typename FP>
+__device__ __forceinline__ void tl_store_masked(const FP& F, uint32_t want, const Ext<T>& e, uint32_t lsb, uint32_t i,
+                                                const TLOut<T>& o) {
+#define CS2_WANT(f) (want >> (f) & 1u)
+    if (want & kTLWantNL) {
+        stg(F.out(NL_OUT_CLC), i, o.clc);
+        stg(F.out(NL_OUT_COVPTOT), i, o.covptot);
+        stg(F.out(NL_OUT_TND_Q), i, o.tnd_q);
+        stg(F.out(NL_OUT_TND_T), i, o.tnd_t);
+        stg(F.out(NL_OUT_TND_QL), i, o.tnd_ql);
+        stg(F.out(NL_OUT_TND_QI), i, o.tnd_qi);
+        stg(F.out(NL_OUT_FPLSL), i + lsb, o.rfln);
+        stg(F.out(NL_OUT_FPLSN), i + lsb, o.sfln);
+        stg(F.out(NL_OUT_FHPSL), i + lsb, -o.rfln * e.RLVTT);
+        stg(F.out(NL_OUT_FHPSN), i + lsb, -o.sfln * e.RLSTT);
+    }
+    if (CS2_WANT(NL_OUT_CLC)) stg(F.out_i(NL_OUT_CLC), i, o.clc_i);
+    if (CS2_WANT(NL_OUT_COVPTOT)) stg(F.out_i(NL_OUT_COVPTOT), i, o.covptot_i);
+    if (CS2_WANT(NL_OUT_TND_Q)) stg(F.out_i(NL_OUT_TND_Q), i, o.tnd_q_i);
+    if (CS2_WANT(NL_OUT_TND_T)) stg(F.out_i(NL_OUT_TND_T), i, o.tnd_t_i);
+    if (CS2_WANT(NL_OUT_TND_QL)) stg(F.out_i(NL_OUT_TND_QL), i, o.tnd_ql_i);
+    if (CS2_WANT(NL_OUT_TND_QI)) stg(F.out_i(NL_OUT_TND_QI), i, o.tnd_qi_i);
+    if (CS2_WANT(NL_OUT_FPLSL)) stg(F.out_i(NL_OUT_FPLSL), i + lsb, o.rfln_i);
+    if (CS2_WANT(NL_OUT_FPLSN)) stg(F.out_i(NL_OUT_FPLSN), i + lsb, o.sfln_i);
+    if (CS2_WANT(NL_OUT_FHPSL)) stg(F.out_i(NL_OUT_FHPSL), i + lsb, -o.rfln_i * e.RLVTT);
+    if (CS2_WANT(NL_OUT_FHPSN)) stg(F.out_i(NL_OUT_FHPSN), i + lsb, -o.sfln_i * e.RLSTT);
+#undef CS2_WANT
+}
+
+template <typename T, bool REG, bool EVAP>
+__global__ void __launch_bounds__(kColBlock)
+tl_masked_kernel(const TLMaskedArgs<T> A) {
+    Ext<T> e = A.e;
+    NLK<T> kc = A.kc;
+    ExpK<T> xk = A.xk;
+    const int nx = A.nx, nz = A.nz;
+    const int64_t ls = A.ls;
+    const T* __restrict__ eta = A.eta;
+    T dt = A.dt;
+    const uint32_t have = A.have, want = A.want;
+    TLMaskedFields<T> F;
+    const auto F_in = [&](int i) { return F.in(i); };
+    const auto F_in_i = [&](int i) { return F.in_i(i); };
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    T* s_eta = reinterpret_cast<T*>(smem_raw);
+    T* s_scalm = s_eta + (nz + 1);
+    int klo, khi;
+    build_level_table<T>(eta, nz, e, s_eta, s_scalm, klo, khi);
+    if constexpr (sizeof(T) == 8) pin_tl_constants(e, kc, xk, dt);
+
+    const int gcol = xcd_block() * kColBlock + threadIdx.x;
+    if (gcol >= nx) return;   // see tl_kernel
+    using O = uint32_t;
+    const O lsb = O(ls) * O(sizeof(T));
+    const O colb = O(gcol) * O(sizeof(T));
+    const O zo = O(threadIdx.x & (kWave - 1)) * O(sizeof(T));   // this lane's word of the zero line
+    const auto at_aph = [&](O x) { return (have >> NL_IN_APH & 1u) ? x : zo; };
+
+    const T trpaus = trpaus_prescan<T, false, O>(F.in(NL_IN_T), F.in(NL_IN_TND_CML_T), lsb, colb, dt, s_eta, klo, khi);
+    const CrhCol<T> crh = crh_setup<T>(trpaus);
+
+    // :124-135
+    TLCarry<T> c;
+    c.rfl = c.rfl_i = c.sfl = c.sfl_i = c.covptot = c.covptot_i = T(0.0);
+    c.aph_k = ldg(F.in(NL_IN_APH), colb);
+    c.aph_s = EVAP ? ldg(F.in(NL_IN_APH), O(nz) * lsb + colb) : T(1.0);
+    c.aph_k_i = ldg(F.in_i(NL_IN_APH), at_aph(colb));
+    c.aph_s_i = EVAP ? ldg(F.in_i(NL_IN_APH), at_aph(O(nz) * lsb + colb)) : T(0.0);
+
+    // :757-765
+    if (want & kTLWantNL) {
+        stg(F.out(NL_OUT_FPLSL), colb, T(0.0));
+        stg(F.out(NL_OUT_FPLSN), colb, T(0.0));
+        stg(F.out(NL_OUT_FHPSL), colb, T(0.0));
+        stg(F.out(NL_OUT_FHPSN), colb, T(0.0));
+    }
+    if (want >> NL_OUT_FPLSL & 1u) stg(F.out_i(NL_OUT_FPLSL), colb, T(0.0));
+    if (want >> NL_OUT_FPLSN & 1u) stg(F.out_i(NL_OUT_FPLSN), colb, T(0.0));
+    if (want >> NL_OUT_FHPSL & 1u) stg(F.out_i(NL_OUT_FHPSL), colb, T(0.0));
+    if (want >> NL_OUT_FHPSN & 1u) stg(F.out_i(NL_OUT_FHPSN), colb, T(0.0));
+
+    O o = colb;
+    LevelIn<T> xa = load_level<T, O>(F_in, lsb, o), ya = load_level_masked<T>(F_in_i, have, lsb, o, zo);
+    for (int k = 0; k < nz; ++k) {
+        F.fresh();
+        LevelIn<T> xn = xa, yn = ya;
+        if (k + 1 < nz) {
+            xn = load_level<T, O>(F_in, lsb, o + lsb);
+            yn = load_level_masked<T>(F_in_i, have, lsb, o + lsb, zo);
+        }
+        const TLOut<T> r = tl_level<T, REG, EVAP>(e, kc, xk, xa, ya, k, s_eta[k], s_scalm[k], crh, dt, c);
+        tl_store_masked<T>(F, want, e, lsb, o, r);
+        drain_vmem();   // see drain_vmem
+        xa = xn;
+        ya = yn;
+        o += lsb;
+    }
+}
+
+// in_i[f] == nullptr: perturbation f is zero everywhere (read from `zero`); out == nullptr: no NL outputs;
+// out_i[f] == nullptr: not written.  Always the register path; 32-bit offsets only.
+template <typename T>
+int launch_tl_masked(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* const* in, const T* const* in_i,
+                     const T* zero, const T* eta, T* const* out, T* const* out_i, double dt, hipStream_t stream) {
+    if (!fits_u32_offsets<T>(nz, ls)) return -2;
+    const bool evap = p.LEVAPLS2 || p.LDRAIN1D;
+    TLMaskedArgs<T> args;
+    args.e = make_ext<T>(p);
+    args.kc = make_nlk<T>(p, dt, evap);
+    args.xk = make_expk<T>();
+    args.nx = nx; args.nz = nz; args.ls = ls;
+    args.have = 0;
+    args.want = out ? kTLWantNL : 0u;
+    for (int i = 0; i < NL_NUM_IN; ++i) {
+        args.in.p[i] = in[i];
+        args.in_i.p[i] = in_i[i] ? in_i[i] : zero;
+        if (in_i[i]) args.have |= 1u << i;
+    }
+    for (int i = 0; i < NL_NUM_OUT; ++i) {
+        args.out.p[i] = out ? out[i] : nullptr;
+        args.out_i.p[i] = out_i[i];
+        if (out_i[i]) args.want |= 1u << i;
+    }
+    args.eta = eta;
+    args.dt = static_cast<T>(dt);
+    const dim3 grid((nx + kColBlock - 1) / kColBlock), block(kColBlock);
+    const size_t smem = 2 * size_t(nz + 1) * sizeof(T);
+    with_flags(
+        [&](auto REG, auto EVAP) {
+            hipLaunchKernelGGL((tl_masked_kernel<T, REG, EVAP>), grid, block, smem, stream, args);
+            return 0;
+        },
+        p.LREGCL != 0, evap);
+    note_kernel("cs2::tl_masked_kernel");
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+template int launch_tl_masked<double>(const Cloudsc2Params&, int, int, int64_t, const double* const*, const double* const*,
+                                      const double*, const double*, double* const*, double* const*, double, hipStream_t);
+template int launch_tl_masked<float>(const Cloudsc2Params&, int, int, int64_t, const float* const*, const float* const*,
+                                     const float*, const float*, float* const*, float* const*, double, hipStream_t);
+
 }  // namespace cs2

@@ -24,7 +24,7 @@
  *   - return value: 0 on success, <0 on error (CLOUDSC2_E_*); `cloudsc2_last_error()` returns a
  *     thread-local message.  Kernels are launched asynchronously on `stream`;
  *   - threading: the library is written for ONE host thread per process and device (the one-process-per-GPU
- *     model of the drivers).  Error text and kernel-name diagnostics are thread-local; the per-device facts the
+ *     model of the drivers).  Error text is thread-local, the kernel-name diagnostic process-wide (an atomic pointer to a literal); the per-device facts the
  *     launchers cache (CU count, the >64 KiB LDS opt-in of the ring kernels) are relaxed atomics whose only race
  *     is a repeated, idempotent query, so a second thread launching on the same device is safe.  Device ordinals
  *     >= 64 are refused (CLOUDSC2_E_UNSUPPORTED);
@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-#define CLOUDSC2_ABI_VERSION 3
+#define CLOUDSC2_ABI_VERSION 4
 
 #define CLOUDSC2_OK 0
 #define CLOUDSC2_E_ARG (-1)      /* bad argument (null pointer, nx/nz/stride out of range)      */
@@ -74,7 +74,8 @@ typedef struct Cloudsc2Params {
 int32_t cloudsc2_abi_version(void);
 int32_t cloudsc2_params_sizeof(void);
 const char* cloudsc2_last_error(void);
-/* diagnostics: name of the kernel the calling thread's last successful entry-point call enqueued, e.g.
+/* diagnostics: name of the kernel the process's last successful entry-point call enqueued, whichever thread made it
+ * (torch.autograd runs a backward pass on a thread of its own), e.g.
  * "cs2::nl_ring_kernel" (LDS-ring load path) or "cs2::nl_kernel" (register prefetch); "" before the first launch */
 const char* cloudsc2_last_kernel(void);
 /* number of HIP devices visible to the library's runtime (0 if none / runtime unusable) */
@@ -248,6 +249,47 @@ int32_t cloudsc2_ad_from_trajectory_f32(const Cloudsc2Params* p, int32_t nx, int
                                         const float* const* in, const float* const* in_adj, const float* eta,
                                         const float* traj_fplsl, const float* traj_fplsn, float* const* out_adj, double dt,
                                         void* stream);
+
+/* ---- cloudsc2_tl / cloudsc2_ad with ABSENT fields (BUILD EXTENSIONS): the linearisation as a derivative rule.
+ * The reference calls its TL and AD stencils with all 52 fields (tangent_linear/microphysics.py:162-242,
+ * adjoint/microphysics.py:159-238).  A Jacobian-vector or vector-Jacobian product taken by an automatic-differentiation
+ * framework has perturbations / forcing on a few fields only and wants a few results only; every field it does not have
+ * or does not want is HBM traffic of the dense calls.  Here such fields are NULL entries:
+ *   in       16 entries, NL_IN_* order, all required (the trajectory);
+ *   in_i     (TL) 16 entries, NL_IN_* order;  NULL entry = that perturbation is zero everywhere;
+ *   in_adj   (AD) 10 entries, NL_OUT_* order; NULL entry = that forcing is zero everywhere;
+ *   out      (TL) NULL as a whole (the NL outputs are not written), or 10 non-NULL entries, NL_OUT_* order;
+ *   out_i    (TL) 10 entries, NL_OUT_* order, and
+ *   out_adj  (AD) 16 entries, NL_IN_* order:  NULL entry = that field is not written; at least one entry is non-NULL;
+ *   zero_line  caller-owned DEVICE memory of at least 512 zero bytes, 16-byte aligned, read-only: what the kernels read in
+ *            place of an absent input (every wave reads the same line, which therefore stays in cache; the library still
+ *            never allocates).  May be NULL when no entry of in_i / in_adj is NULL;
+ *   traj_fplsl / traj_fplsn  (AD) required: out_fplsl / out_fplsn of a cloudsc2_nl / cloudsc2_tl call on the same state, as
+ *            for cloudsc2_ad_from_trajectory_*, whose restrictions the AD entry keeps: LEVAPLS2 / LDRAIN1D are refused
+ *            (CLOUDSC2_E_UNSUPPORTED).
+ * Both entries keep 32-bit byte offsets: fields of 4 GiB and more are refused (CLOUDSC2_E_UNSUPPORTED) - use the dense
+ * stencils there.  The TL entry takes every combination of externals cloudsc2_tl takes.  Argument errors are settled on
+ * the host before any launch; nx == 0 is a successful no-op.
+ * A field that is written equals what the dense call writes for the same inputs with zero fields in place of the absent
+ * ones: for AD bit for bit (the arithmetic of cloudsc2_ad_from_trajectory_*), for TL to rounding (the compiler contracts
+ * the shared level function per kernel).
+ * Words moved per level and column: TL 16 + (present in_i) + (10 if out) + (present out_i) against 52 of cloudsc2_tl;
+ * AD 16 + 2 + (present in_adj) + (present out_adj) against 44 of cloudsc2_ad_from_trajectory and 70 of cloudsc2_ad - e.g.
+ * forcing on the four tendencies and adjoints of t, q, ql, qi: 26. */
+int32_t cloudsc2_tl_masked_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                               const double* const* in, const double* const* in_i, const double* zero_line,
+                               const double* eta, double* const* out, double* const* out_i, double dt, void* stream);
+int32_t cloudsc2_tl_masked_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                               const float* const* in, const float* const* in_i, const float* zero_line,
+                               const float* eta, float* const* out, float* const* out_i, double dt, void* stream);
+int32_t cloudsc2_ad_masked_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                               const double* const* in, const double* const* in_adj, const double* zero_line,
+                               const double* eta, const double* traj_fplsl, const double* traj_fplsn,
+                               double* const* out_adj, double dt, void* stream);
+int32_t cloudsc2_ad_masked_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                               const float* const* in, const float* const* in_adj, const float* zero_line,
+                               const float* eta, const float* traj_fplsl, const float* traj_fplsn,
+                               float* const* out_adj, double dt, void* stream);
 
 #ifdef __cplusplus
 }
