@@ -121,9 +121,16 @@ def _signatures() -> Dict[str, Tuple[Any, Tuple[Any, ...]]]:
     head = (POINTER(Cloudsc2Params), c_int32, c_int32, c_int64)
     tl_masked = head + (_PARR, _PARR, c_void_p, c_void_p, _PARR, _PARR, c_double, c_void_p)
     ad_masked = head + (_PARR, _PARR, c_void_p, c_void_p, c_void_p, c_void_p, _PARR, c_double, c_void_p)
+    # the derivative rules of `saturation` and of the whole step (autodiff.py too): NULL fields again
+    sat_tl = head + (c_void_p,) * 6 + (c_void_p,)
+    sat_ad = head + (c_void_p,) * 5 + (c_int32, c_void_p)
     for sfx in ("f64", "f32"):
         sig[f"cloudsc2_tl_masked_{sfx}"] = (c_int32, tl_masked)
         sig[f"cloudsc2_ad_masked_{sfx}"] = (c_int32, ad_masked)
+        sig[f"cloudsc2_tl_step_{sfx}"] = (c_int32, tl_masked)
+        sig[f"cloudsc2_ad_step_{sfx}"] = (c_int32, ad_masked)
+        sig[f"cloudsc2_saturation_tl_{sfx}"] = (c_int32, sat_tl)
+        sig[f"cloudsc2_saturation_ad_{sfx}"] = (c_int32, sat_ad)
         sig[f"cloudsc2_field_sums_{sfx}"] = (c_int32, reduction + (c_void_p,))
         sig[f"cloudsc2_column_dots_{sfx}"] = (c_int32, reduction + (c_int32, c_void_p))
         for lay in LAYOUTS.values():

@@ -1,12 +1,17 @@
-"""CLOUDSC2 as a differentiable PyTorch operation (C ABI `cloudsc2_tl_masked_*`, `cloudsc2_ad_masked_*`).
+"""CLOUDSC2 as a differentiable PyTorch operation (C ABI `cloudsc2_tl_masked_*`, `cloudsc2_ad_masked_*`, and for the
+whole step `cloudsc2_saturation_tl_*` / `_ad_*`, `cloudsc2_tl_step_*` / `cloudsc2_ad_step_*`).
 
 `cloudsc2(state, eta, dt)` is one `cloudsc2_nl` step whose gradients PyTorch can take: reverse mode (`backward`,
 `torch.autograd.grad`) runs the adjoint kernel, forward mode (`torch.autograd.forward_ad`) the tangent-linear kernel.  A
 derivative rule has perturbations / forcing on a few fields only and wants a few results only, so both go through the
 MASKED kernels: fields a call does not have are NULL entries that move no HBM words (include/cloudsc2_hip.h).
 
-`tl_masked` / `ad_masked` are the thin calls underneath, usable on their own (a variational cost, a sensitivity study).
-GPU tensors only - there is no host path."""
+`cloudsc2` differentiates `cloudsc2_nl` alone: `qsat` is one of its 16 independent inputs.  The step the drivers run is
+`saturation` + `cloudsc2_nl`, where `qsat` is a function of `ap` and `t`: `cloudsc2_step(state, eta, dt)` is that step with
+the TOTAL derivative (the path t, ap -> qsat -> cloudsc2 included), `saturation(ap, t)` its first half on its own.
+
+`tl_masked` / `ad_masked`, `tl_step` / `ad_step` and `saturation_tl` / `saturation_ad` are the thin calls underneath, usable
+on their own (a variational cost, a sensitivity study).  GPU tensors only - there is no host path."""
 from __future__ import annotations
 
 import ctypes
@@ -20,6 +25,8 @@ from .params import default_externals, make_params
 from .storage import field_geometry, zeros
 
 _SFX = {torch.float64: "f64", torch.float32: "f32"}
+#: the inputs of the step: those of `cloudsc2_nl` without `qsat`, which the step forms from `ap` and `t`
+STEP_IN = tuple(n for n in NL_IN if n != "qsat")
 _ZERO_LINE_BYTES = 512
 _zero_lines: Dict[Tuple[torch.device, torch.dtype], torch.Tensor] = {}
 
@@ -98,13 +105,24 @@ def tl_masked(state: Mapping[str, torch.Tensor], perturbations: Mapping[str, tor
     """Tangent-linear CLOUDSC2 with absent fields: `perturbations` holds the perturbed inputs (`NL_IN` names; a missing
     name is a zero perturbation), `want` names the perturbed outputs (`NL_OUT` names) to produce.  Returns
     `(nl_outputs or None, {name: perturbed output})`; results are new `storage.zeros` fields."""
-    what = "tl_masked"
+    return _tl_call("tl_masked", NL_IN, state, perturbations, eta, dt, externals, want, write_nl)
+
+
+def tl_step(state: Mapping[str, torch.Tensor], perturbations: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+            externals: Optional[Mapping[str, Any]] = None, *, want: Iterable[str], write_nl: bool = False):
+    """Tangent-linear of the step `saturation` + `cloudsc2_nl` in ONE launch (`cloudsc2_tl_step_*`): `tl_masked` without the
+    field `qsat` (`STEP_IN` names).  `qsat` is formed in the kernel from `ap` and `t`, and its perturbation from theirs by
+    the derivative rule of `saturation_tl`.  LPHYLIN only (`ValueError` otherwise)."""
+    return _tl_call("tl_step", STEP_IN, state, perturbations, eta, dt, externals, want, write_nl)
+
+
+def _tl_call(what, in_names, state, perturbations, eta, dt, externals, want, write_nl):
     want = tuple(want)
     if not want or set(want) - set(NL_OUT):
         raise ValueError(f"{what}: `want` must name at least one of {NL_OUT}, got {want}")
     state = {n: _plain(f) for n, f in state.items()}
     pert = {n: _plain(f) for n, f in perturbations.items()}
-    (nx, nlev, ls), dtype, device = _checked(what, ((state, NL_IN, True), (pert, NL_IN, False)))
+    (nx, nlev, ls), dtype, device = _checked(what, ((state, in_names, True), (pert, in_names, False)))
     nz = nlev - 1
     eta = _eta(what, eta, nz, dtype, device)
     ref = state[NL_IN[0]]
@@ -112,7 +130,7 @@ def tl_masked(state: Mapping[str, torch.Tensor], perturbations: Mapping[str, tor
     out_i = {n: _new_like(ref, nx, nz, ls) for n in want}
     p = _params(externals, nz)
     with torch.cuda.device(device):
-        rc = getattr(_lib.load(), "cloudsc2_tl_masked_" + _SFX[dtype])(
+        rc = getattr(_lib.load(), f"cloudsc2_{what}_{_SFX[dtype]}")(
             ctypes.byref(p), nx, nz, ls, _ptrs(state, NL_IN), _ptrs(pert, NL_IN), _zero_line(device, dtype).data_ptr(),
             eta.data_ptr(), None if out is None else _ptrs(out, NL_OUT), _ptrs(out_i, NL_OUT), float(dt),
             int(torch.cuda.current_stream(device).cuda_stream))
@@ -126,14 +144,25 @@ def ad_masked(state: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Ten
     forcing), `traj` the `fplsl` / `fplsn` outputs of a `cloudsc2_nl` / `cloudsc2_tl` call on `state`, `want` names the
     inputs (`NL_IN` names) whose adjoints to produce.  Returns `{name: adjoint}` as new `storage.zeros` fields.
     LEVAPLS2 / LDRAIN1D are refused (`ValueError`), as by `cloudsc2_ad_from_trajectory`."""
-    what = "ad_masked"
+    return _ad_call("ad_masked", NL_IN, state, forcing, eta, dt, externals, traj, want)
+
+
+def ad_step(state: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+            externals: Optional[Mapping[str, Any]] = None, *, traj: Mapping[str, torch.Tensor], want: Iterable[str]):
+    """Adjoint of the step `saturation` + `cloudsc2_nl` in ONE launch (`cloudsc2_ad_step_*`): `ad_masked` without the field
+    `qsat` (`STEP_IN` names).  The adjoint of `qsat` is not produced: it is taken through `saturation` by the rule of
+    `saturation_ad` and arrives inside the adjoints of `t` and `ap`.  LPHYLIN only, and no LEVAPLS2 / LDRAIN1D."""
+    return _ad_call("ad_step", STEP_IN, state, forcing, eta, dt, externals, traj, want)
+
+
+def _ad_call(what, in_names, state, forcing, eta, dt, externals, traj, want):
     want = tuple(want)
-    if not want or set(want) - set(NL_IN):
-        raise ValueError(f"{what}: `want` must name at least one of {NL_IN}, got {want}")
+    if not want or set(want) - set(in_names):
+        raise ValueError(f"{what}: `want` must name at least one of {in_names}, got {want}")
     state = {n: _plain(f) for n, f in state.items()}
     forcing = {n: _plain(f) for n, f in forcing.items()}
     traj = {n: _plain(f) for n, f in traj.items()}
-    (nx, nlev, ls), dtype, device = _checked(what, ((state, NL_IN, True), (forcing, NL_OUT, False),
+    (nx, nlev, ls), dtype, device = _checked(what, ((state, in_names, True), (forcing, NL_OUT, False),
                                                     (traj, ("fplsl", "fplsn"), True)))
     nz = nlev - 1
     eta = _eta(what, eta, nz, dtype, device)
@@ -141,7 +170,7 @@ def ad_masked(state: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Ten
     out_adj = {n: _new_like(ref, nx, nz, ls) for n in want}
     p = _params(externals, nz)
     with torch.cuda.device(device):
-        rc = getattr(_lib.load(), "cloudsc2_ad_masked_" + _SFX[dtype])(
+        rc = getattr(_lib.load(), f"cloudsc2_{what}_{_SFX[dtype]}")(
             ctypes.byref(p), nx, nz, ls, _ptrs(state, NL_IN), _ptrs(forcing, NL_OUT), _zero_line(device, dtype).data_ptr(),
             eta.data_ptr(), traj["fplsl"].data_ptr(), traj["fplsn"].data_ptr(), _ptrs(out_adj, NL_IN), float(dt),
             int(torch.cuda.current_stream(device).cuda_stream))
@@ -255,3 +284,217 @@ def cloudsc2(state: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
             raise ValueError(f"cloudsc2: {n} lives on {state[n].device}; fields must live on the GPU")
     outs = _Cloudsc2.apply(eta, dt, externals, *(state[n] for n in NL_IN))
     return dict(zip(NL_OUT, outs))
+
+
+# ---- the first half of the step, and the step as a whole ------------------------------------------------------------------
+def _ptr(f: Optional[torch.Tensor]):
+    return None if f is None else f.data_ptr()
+
+
+def saturation_tl(ap: torch.Tensor, t: torch.Tensor, ap_i: Optional[torch.Tensor] = None, t_i: Optional[torch.Tensor] = None,
+                  externals: Optional[Mapping[str, Any]] = None, *, write_qsat: bool = False):
+    """Tangent-linear of `saturation` (`cloudsc2_saturation_tl_*`): `qsat_i = g_t t_i + g_ap ap_i` on levels `< nz`; a
+    perturbation that is `None` is zero (at least one is given).  Returns `(qsat or None, qsat_i)` as new `storage.zeros`
+    fields.  All three forms of `saturation` (LPHYLIN; KFLAG 1 / other)."""
+    what = "saturation_tl"
+    fields = {"ap": _plain(ap), "t": _plain(t)}
+    pert = {n: _plain(f) for n, f in (("ap", ap_i), ("t", t_i)) if f is not None}
+    if not pert:
+        raise ValueError(f"{what}: ap_i and t_i are both None: there is nothing to propagate")
+    (nx, nlev, ls), dtype, device = _checked(what, ((fields, ("ap", "t"), True), (pert, ("ap", "t"), False)))
+    nz = nlev - 1
+    qsat = _new_like(fields["ap"], nx, nz, ls) if write_qsat else None
+    qsat_i = _new_like(fields["ap"], nx, nz, ls)
+    p = _params(externals, nz)
+    with torch.cuda.device(device):
+        rc = getattr(_lib.load(), "cloudsc2_saturation_tl_" + _SFX[dtype])(
+            ctypes.byref(p), nx, nz, ls, fields["ap"].data_ptr(), fields["t"].data_ptr(), _ptr(pert.get("ap")),
+            _ptr(pert.get("t")), _ptr(qsat), qsat_i.data_ptr(), int(torch.cuda.current_stream(device).cuda_stream))
+    _lib.check(rc, what)
+    return qsat, qsat_i
+
+
+def saturation_ad(ap: torch.Tensor, t: torch.Tensor, qsat_adj: torch.Tensor, externals: Optional[Mapping[str, Any]] = None,
+                  *, want: Iterable[str] = ("ap", "t"), into: Optional[Mapping[str, torch.Tensor]] = None):
+    """Adjoint of `saturation` (`cloudsc2_saturation_ad_*`): `t_adj = g_t qsat_adj`, `ap_adj = g_ap qsat_adj` on levels
+    `< nz`, for the names in `want`.  With `into` (a field per wanted name) the products are ADDED to those fields in place
+    (`accumulate = 1`) - e.g. to the `t` / `ap` adjoints `ad_masked` has just written, which completes the adjoint of
+    `saturation` + `cloudsc2_nl`.  Returns `{name: adjoint}`: new `storage.zeros` fields, or the fields of `into`."""
+    what = "saturation_ad"
+    want = tuple(want)
+    if not want or set(want) - {"ap", "t"}:
+        raise ValueError(f"{what}: `want` must name at least one of ('ap', 't'), got {want}")
+    fields = {"ap": _plain(ap), "t": _plain(t), "qsat_adj": _plain(qsat_adj)}
+    groups = [(fields, ("ap", "t", "qsat_adj"), True)]
+    if into is not None:
+        if set(into) != set(want):
+            raise ValueError(f"{what}: `into` must hold exactly the wanted fields {want}, got {sorted(into)}")
+        groups.append(({n: _plain(f) for n, f in into.items()}, ("ap", "t"), False))
+    (nx, nlev, ls), dtype, device = _checked(what, groups)
+    nz = nlev - 1
+    adj = {n: (_new_like(fields["ap"], nx, nz, ls) if into is None else _plain(into[n])) for n in want}
+    p = _params(externals, nz)
+    with torch.cuda.device(device):
+        rc = getattr(_lib.load(), "cloudsc2_saturation_ad_" + _SFX[dtype])(
+            ctypes.byref(p), nx, nz, ls, fields["ap"].data_ptr(), fields["t"].data_ptr(), fields["qsat_adj"].data_ptr(),
+            _ptr(adj.get("ap")), _ptr(adj.get("t")), 0 if into is None else 1,
+            int(torch.cuda.current_stream(device).cuda_stream))
+    _lib.check(rc, what)
+    return adj
+
+
+def _run_saturation(ap, t, ext, geo):
+    from .stencils import compile_stencil
+
+    nx, nlev, ls = geo
+    qsat = _new_like(ap, nx, nlev - 1, ls)
+    compile_stencil("saturation", ext)(in_ap=ap, in_t=t, out_qsat=qsat, origin=(0, 0, 0), domain=(nx, 1, nlev - 1),
+                                       validate_args=False, exec_info=None)
+    return qsat
+
+
+class _Saturation(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, externals, ap, t):
+        ctx.set_materialize_grads(False)
+        fields = {"ap": _plain(ap), "t": _plain(t)}
+        ctx.geo, _, _ = _checked("saturation", ((fields, ("ap", "t"), True),))
+        ctx.ext = dict(default_externals() if externals is None else externals)
+        ctx.save_for_backward(ap, t)
+        ctx.save_for_forward(ap, t)
+        return _run_saturation(fields["ap"], fields["t"], ctx.ext, ctx.geo)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, grad):
+        want = tuple(n for n, w in zip(("ap", "t"), ctx.needs_input_grad[1:]) if w)
+        if grad is None or not want:
+            return None, None, None
+        ap, t = ctx.saved_tensors
+        adj = saturation_ad(ap, t, _in_layout(grad, _plain(ap), ctx.geo), ctx.ext, want=want)
+        return None, adj.get("ap"), adj.get("t")
+
+    @staticmethod
+    def jvp(ctx, _ext_t, ap_i, t_i):
+        if ap_i is None and t_i is None:
+            return None
+        ap, t = ctx.saved_tensors
+        ref = _plain(ap)
+        lay = lambda g: None if g is None else _in_layout(g, ref, ctx.geo)  # noqa: E731
+        return saturation_tl(ap, t, lay(ap_i), lay(t_i), ctx.ext)[1]
+
+
+def saturation(ap: torch.Tensor, t: torch.Tensor, externals: Optional[Mapping[str, Any]] = None) -> torch.Tensor:
+    """Differentiable `saturation`: `qsat` of `ap` and `t` on levels `< nz` (level `nz` stays 0), computed by the
+    `saturation` stencil, all three forms (LPHYLIN; KFLAG 1 / other).  `backward` is ONE `saturation_ad` launch, `jvp` one
+    `saturation_tl` launch.  The derivative is the exact one of the formula, with every `min` / `max` taken on the branch
+    the value took (a clamped branch - `alfa` outside (RTICE, RTWAT), `qs` clipped at QMAX - has derivative 0)."""
+    for n, f in (("ap", ap), ("t", t)):
+        if isinstance(f, torch.Tensor) and not f.is_cuda:
+            raise ValueError(f"saturation: {n} lives on {f.device}; fields must live on the GPU")
+    return _Saturation.apply(externals, ap, t)
+
+
+def _evap(ext) -> bool:
+    return bool(ext.get("LEVAPLS2") or ext.get("LDRAIN1D"))
+
+
+class _Cloudsc2Step(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, eta, dt, externals, *inputs):
+        from .stencils import compile_stencil
+
+        ctx.set_materialize_grads(False)
+        state = {n: _plain(f) for n, f in zip(STEP_IN, inputs)}
+        (nx, nlev, ls), dtype, device = _checked("cloudsc2_step", ((state, STEP_IN, True),))
+        nz = nlev - 1
+        ref = state[STEP_IN[0]]
+        out = {n: _new_like(ref, nx, nz, ls) for n in NL_OUT}
+        ext = dict(default_externals() if externals is None else externals)
+        call = dict(in_eta=eta, dt=dt, origin=(0, 0, 0), domain=(nx, 1, nlev), validate_args=False, exec_info=None)
+        ins, outs = {"in_" + n: f for n, f in state.items()}, {"out_" + n: f for n, f in out.items()}
+        if ext.get("LPHYLIN"):
+            qsat = _new_like(ref, nx, nz, ls)
+            compile_stencil("cloudsc2_nl_saturation", ext)(**ins, out_qsat=qsat, **outs, **call)
+        else:
+            qsat = _run_saturation(state["ap"], state["t"], ext, (nx, nlev, ls))
+            compile_stencil("cloudsc2_nl", ext)(**ins, in_qsat=qsat, **outs, **call)
+        ctx.eta, ctx.dt, ctx.ext, ctx.geo = eta, float(dt), ext, (nx, nlev, ls)
+        ctx.save_for_backward(*inputs, qsat, out["fplsl"], out["fplsn"])
+        ctx.save_for_forward(*inputs, qsat)
+        ctx.mark_non_differentiable(qsat)
+        return tuple(out[n] for n in NL_OUT) + (qsat,)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, *grads):
+        grads = grads[:len(NL_OUT)]                      # the last one belongs to `qsat`: not differentiable
+        need = ctx.needs_input_grad[3:]
+        none = (None,) * (3 + len(STEP_IN))
+        if all(g is None for g in grads) or not any(need):
+            return none
+        saved = ctx.saved_tensors
+        state = dict(zip(STEP_IN, saved[:len(STEP_IN)]))
+        qsat, traj = saved[-3], {"fplsl": saved[-2], "fplsn": saved[-1]}
+        ref = _plain(saved[0])
+        forcing = {n: _in_layout(g, ref, ctx.geo) for n, g in zip(NL_OUT, grads) if g is not None}
+        want = tuple(n for n, w in zip(STEP_IN, need) if w)
+        ext = dict(ctx.ext, AD_TRAJ_FIX=1)
+        if ext.get("LPHYLIN") and not _evap(ext):
+            adj = ad_step(state, forcing, ctx.eta, ctx.dt, ext, traj=traj, want=want)
+        else:
+            through = tuple(n for n in ("ap", "t") if n in want)       # the adjoints the path through qsat arrives in
+            full = dict(state, qsat=qsat)
+            want16 = want + (("qsat",) if through else ())
+            if _evap(ext):
+                adj = _dense_ad(full, forcing, ctx.eta, ctx.dt, ext, ctx.geo, want16)
+            else:
+                adj = ad_masked(full, forcing, ctx.eta, ctx.dt, ext, traj=traj, want=want16)
+            if through:
+                saturation_ad(state["ap"], state["t"], adj["qsat"], ext, want=through, into={n: adj[n] for n in through})
+        return (None, None, None) + tuple(adj.get(n) for n in STEP_IN)
+
+    @staticmethod
+    def jvp(ctx, _eta_t, _dt_t, _ext_t, *tangents):
+        saved = ctx.saved_tensors                        # in jvp: what save_for_forward kept
+        state, qsat = dict(zip(STEP_IN, saved[:len(STEP_IN)])), saved[-1]
+        ref = _plain(saved[0])
+        pert = {n: _in_layout(t, ref, ctx.geo) for n, t in zip(STEP_IN, tangents) if t is not None}
+        if not pert:
+            return (None,) * (len(NL_OUT) + 1)
+        if ctx.ext.get("LPHYLIN"):
+            _, out_i = tl_step(state, pert, ctx.eta, ctx.dt, ctx.ext, want=NL_OUT, write_nl=False)
+        else:
+            if "ap" in pert or "t" in pert:
+                pert["qsat"] = saturation_tl(state["ap"], state["t"], pert.get("ap"), pert.get("t"), ctx.ext)[1]
+            _, out_i = tl_masked(dict(state, qsat=qsat), pert, ctx.eta, ctx.dt, ctx.ext, want=NL_OUT, write_nl=False)
+        return tuple(out_i[n] for n in NL_OUT) + (None,)
+
+
+def cloudsc2_step(state: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+                  externals: Optional[Mapping[str, Any]] = None) -> Dict[str, torch.Tensor]:
+    """One differentiable step as the drivers run it, `saturation` + `cloudsc2_nl`: the 15 inputs (`STEP_IN` names = `NL_IN`
+    without `qsat`) -> the 10 NL outputs (`NL_OUT` names) plus `"qsat"`, the saturation field the step formed.
+
+    Gradients are TOTAL derivatives: the path t, ap -> qsat -> cloudsc2, which `cloudsc2` on a precomputed `qsat` leaves
+    out, is part of them.  They are the reference's regularised TL / AD of `cloudsc2` (see `cloudsc2`: LREGCL damping,
+    `AD_TRAJ_FIX=1` forced for the adjoint, trajectory fluxes the NL kernel's own) chained with the EXACT derivative of
+    `saturation`, in which every `min` / `max` is differentiated on the branch the value took (`alfa` clamped outside
+    (RTICE, RTWAT) and `qs` clipped at QMAX contribute 0).  The reference has no TL / AD of `saturation`.
+
+    `"qsat"` is returned for inspection and is not differentiable; who needs gradients through it composes `saturation`
+    with `cloudsc2`.  Forward, LPHYLIN: one launch (`cloudsc2_nl_saturation`), otherwise `saturation` then `cloudsc2_nl`.
+    `backward` with LPHYLIN and without LEVAPLS2 / LDRAIN1D is ONE `cloudsc2_ad_step` launch; otherwise `ad_masked` (or the
+    dense `cloudsc2_ad` for the evaporation switches) producing the `qsat` adjoint, then `saturation_ad` adding into the
+    `t` / `ap` adjoints.  `jvp` is one `cloudsc2_tl_step` launch, or `saturation_tl` then `tl_masked`."""
+    if "qsat" in state:
+        raise ValueError("cloudsc2_step: `state` holds `qsat`, which the step forms itself from `ap` and `t`; for a qsat of "
+                         "your own use `cloudsc2` (compose it with `saturation` for the total derivative)")
+    missing = [n for n in STEP_IN if n not in state]
+    if missing or len(state) != len(STEP_IN):
+        raise ValueError(f"cloudsc2_step: state must hold exactly the fields {STEP_IN}; missing {missing}")
+    for n in STEP_IN:
+        if isinstance(state[n], torch.Tensor) and not state[n].is_cuda:
+            raise ValueError(f"cloudsc2_step: {n} lives on {state[n].device}; fields must live on the GPU")
+    outs = _Cloudsc2Step.apply(eta, dt, externals, *(state[n] for n in STEP_IN))
+    return dict(zip(NL_OUT + ("qsat",), outs))

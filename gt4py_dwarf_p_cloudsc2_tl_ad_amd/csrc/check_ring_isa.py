@@ -14,9 +14,9 @@ on the compiled gfx950 assembly (no GPU needed):
     wait other than the three hand-written ones (NFULL, NHEAD, 0).  (RAGGED instantiations: the exec-masked stores of
     a partly filled last wave are counted as issued - see `_cfg`.)
 
-  * register-path kernels (tl_kernel, nl_kernel, nl_taylor_multi_kernel, ad_kernel; `check_prefetch_distance`): in every
-    level loop the first wait that reaches into the batch of prefetch loads for the next level comes at least 60
-    instructions behind the batch - i.e. nothing consumes a prefetched word at the load site.
+  * register-path kernels (tl_kernel, nl_kernel, nl_taylor_multi_kernel, ad_kernel, tl_step_kernel, ad_step_kernel;
+    `check_prefetch_distance`): in every level loop the first wait that reaches into the batch of prefetch loads for the
+    next level comes at least 60 instructions behind the batch - i.e. nothing consumes a prefetched word at the load site.
 
 Used by tests/test_ring_isa.py (CPU suite) and by `__graft_entry__.build()` whenever it really recompiles the library, so a
 library built by a different hipcc cannot ship with a wrong count.  `python check_ring_isa.py` runs it by hand."""
@@ -367,6 +367,15 @@ def check_all(out_dir=None) -> dict:
     #  + the 8 trajectory instantiations of ad_kernel, one sweep each)
     assert pf["tl_kernel"] >= 24 and pf["nl_kernel"] >= 36 and pf["nl_taylor_multi_kernel"] >= 64 and pf["ad_kernel"] >= 72, pf
     assert check_prefetch_distance(asm_ad, "9ad_kernelIdLb1ELb0ELb0ELb0ELb1E") == 1, "cloudsc2_ad_from_trajectory fp64: sweep not seen"
+    # the step kernels (saturation's derivative fused into the masked sweeps; what autodiff.cloudsc2_step's backward / jvp
+    # launch): T x REG x EVAP and T x REG x FIX, one level loop each, held to the masked kernels' properties
+    # (tests/test_masked_isa.py, tests/test_step_isa.py) - the prefetch is not waited for at the load site, no scratch
+    pf["tl_step_kernel"] = check_prefetch_distance(asm_tl, "tl_step_kernelI")
+    pf["ad_step_kernel"] = check_prefetch_distance(asm_ad, "ad_step_kernelI")
+    assert pf["tl_step_kernel"] == 8 and pf["ad_step_kernel"] == 8, pf
+    for asm, pre in ((asm_tl, "tl_step_kernelI"), (asm_ad, "ad_step_kernelI")):
+        for name, _ in _kernels(asm, pre):
+            assert kernel_resources(asm, name)["ScratchSize"] == 0, (name, "spills to scratch")
     res = check_resources(asm_nl, asm_tl, asm_ad)
     n_asm = sum(check_inline_asm_vmem(a, f) for a, f in ((asm_nl, "cloudsc2_nl.hip"), (asm_tl, "cloudsc2_tl.hip"),
                                                          (asm_ad, "cloudsc2_ad.hip")))

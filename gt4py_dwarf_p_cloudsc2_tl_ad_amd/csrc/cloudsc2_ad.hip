@@ -1149,11 +1149,14 @@ __device__ __forceinline__ ADForce<T> ad_load_force_masked(const FP& F, uint32_t
 }
 
 // The sixteen stores of one level of sweep 2 (ad_kernel's, :992-996 included), each under its bit of `want`.
-template <typename T, typename FP>
-__device__ __forceinline__ void ad_store_masked(const FP& F, uint32_t want, uint32_t lsb, uint32_t o, T dt, const ADOut<T>& a) {
+// STEP (ad_step_kernel): `fold_ap` / `fold_t`, the level's qsat adjoint taken through `saturation`, are added into the ap
+// and the t store - and into those two only: tnd_cml_t below still gets dt * a.t, the adjoint of cloudsc2 itself.
+template <typename T, bool STEP = false, typename FP>
+__device__ __forceinline__ void ad_store_masked(const FP& F, uint32_t want, uint32_t lsb, uint32_t o, T dt, const ADOut<T>& a,
+                                                T fold_ap = T(0.0), T fold_t = T(0.0)) {
 #define CS2_WANT(f) (want >> (f) & 1u)
-    if (CS2_WANT(NL_IN_AP)) stg(F.oadj(NL_IN_AP), o, a.ap);
-    if (CS2_WANT(NL_IN_T)) stg(F.oadj(NL_IN_T), o, a.t);
+    if (CS2_WANT(NL_IN_AP)) stg(F.oadj(NL_IN_AP), o, STEP ? a.ap + fold_ap : a.ap);
+    if (CS2_WANT(NL_IN_T)) stg(F.oadj(NL_IN_T), o, STEP ? a.t + fold_t : a.t);
     if (CS2_WANT(NL_IN_Q)) stg(F.oadj(NL_IN_Q), o, a.q);
     if (CS2_WANT(NL_IN_QL)) stg(F.oadj(NL_IN_QL), o, a.ql);
     if (CS2_WANT(NL_IN_QI)) stg(F.oadj(NL_IN_QI), o, a.qi);
@@ -1171,9 +1174,15 @@ __device__ __forceinline__ void ad_store_masked(const FP& F, uint32_t want, uint
 #undef CS2_WANT
 }
 
-template <typename T, bool REG, bool FIX>
-__global__ void __launch_bounds__(kColBlock, sizeof(T) == 4 ? 3 : 1)
-ad_masked_kernel(const ADMaskedArgs<T> A) {
+// The sweep of ad_masked_kernel and of ad_step_kernel (one copy).  STEP: the adjoint of `saturation` is fused in (C ABI
+// cloudsc2_ad_step_*).  in_qsat is not read: the level's qsat is saturation_point's value of the level's t and ap words
+// (LPHYLIN form, what cloudsc2_nl_fused_* computes).  The level's qsat adjoint (ADOut::qsat) is not stored but folded into
+// the t and ap adjoints as g_t * qsat_adj and g_ap * qsat_adj.  The two exponentials of g_t / g_ap stay out of ad_backward's
+// live range (the fp64 instantiation already parks trajectory words in LDS to stay within 256 VGPRs): the level's t and ap
+// (`pt`, `pap`: two words) are kept beside its adjoints and the derivative is formed where those are stored, one iteration
+// late and before the next level's arithmetic starts.
+template <typename T, bool REG, bool FIX, bool STEP>
+__device__ __forceinline__ void ad_masked_sweep(const ADMaskedArgs<T>& A) {
     Ext<T> e = A.e;
     NLK<T> kc = A.kc;
     ExpK<T> xk = A.xk;
@@ -1228,6 +1237,7 @@ ad_masked_kernel(const ADMaskedArgs<T> A) {
     ADForce<T> fa;
     fa.clc = fa.tnd_q = fa.tnd_qi = fa.tnd_ql = fa.tnd_t = fa.fplsl1 = fa.fplsn1 = fa.fhpsl1 = fa.fhpsn1 = fa.covptot = T(0.0);
     T aph_k = ldg(F.in(NL_IN_APH), o), sfl = T(0.0), rfl = T(0.0);   // aph[nz]: level nz-1's lower half level
+    T pt = T(273.0), pap = T(1.0e5);   // STEP: t and ap of the level whose adjoints `pa` holds
     for (int k = nz; k >= -1; --k) {
         F.fresh();
         LevelIn<T> xn = xa;
@@ -1235,20 +1245,32 @@ ad_masked_kernel(const ADMaskedArgs<T> A) {
         T aph_n = aph_k, sfl_n = sfl, rfl_n = rfl;
         if (k > 0) {
             const O om = o - lsb;
-            xn = load_level<T>(F_in, lsb, om);
+            xn = load_level<T>(F_in, lsb, om, STEP);
             xn.aph1 = aph_k;   // aph[k]: already here as this level's upper half level
             fn = ad_load_force_masked<T>(F, have, lsb, om, zo);
             aph_n = ldg(F.in(NL_IN_APH), om);
             sfl_n = ldg(F.traj_n(), om);
             rfl_n = ldg(F.traj_l(), om);
         }
-        if (k < nz - 1) ad_store_masked<T>(F, want, lsb, po, dt, pa);
+        if (k < nz - 1) {
+            if constexpr (STEP) {
+                const SatD<T> s = saturation_point_d<T, 0>(e, xk, pt, pap);
+                ad_store_masked<T, true>(F, want, lsb, po, dt, pa, s.g_ap * pa.qsat, s.g_t * pa.qsat);
+            } else {
+                ad_store_masked<T>(F, want, lsb, po, dt, pa);
+            }
+        }
         if (k >= 0 && k < nz) {
+            if constexpr (STEP) xa.qsat = saturation_point<T, 0>(e, xk, xa.t, xa.ap);
             ADTraj<T> r;
             ad_forward<T, FIX, false>(e, kc, xk, xa, aph_k, k, s_eta[k], s_scalm[k], crh, dt, rfl, sfl, T(0.0), T(1.0), r);
             if constexpr (kADPark<T>) ad_park<T>(park_lds, r);
             pa = ad_backward<T, REG, FIX, false>(e, kc, xa, k, s_scalm[k], dt, sfl, r, fa, b, park_lds);
             po = o;
+            if constexpr (STEP) {
+                pt = xa.t;
+                pap = xa.ap;
+            }
         }
         xa = xn;
         fa = fn;
@@ -1262,12 +1284,27 @@ ad_masked_kernel(const ADMaskedArgs<T> A) {
     if (want >> NL_IN_LU & 1u) stg(F.oadj(NL_IN_LU), colb, T(0.0));
 }
 
+template <typename T, bool REG, bool FIX>
+__global__ void __launch_bounds__(kColBlock, sizeof(T) == 4 ? 3 : 1)
+ad_masked_kernel(const ADMaskedArgs<T> A) {
+    ad_masked_sweep<T, REG, FIX, false>(A);
+}
+
+// cloudsc2_ad_masked + the adjoint of `saturation` in one launch (BUILD EXTENSION, C ABI cloudsc2_ad_step_*): see
+// ad_masked_sweep
+template <typename T, bool REG, bool FIX>
+__global__ void __launch_bounds__(kColBlock, sizeof(T) == 4 ? 3 : 1)
+ad_step_kernel(const ADMaskedArgs<T> A) {
+    ad_masked_sweep<T, REG, FIX, true>(A);
+}
+
 // in_adj[f] == nullptr: forcing f is zero everywhere (read from `zero`); out_adj[f] == nullptr: adjoint f is not written.
-// The caller (cloudsc2_capi.hip) has refused the evaporation switches and fields of 4 GiB and more.
+// The caller (cloudsc2_capi.hip) has refused the evaporation switches and fields of 4 GiB and more.  `step`: ad_step_kernel
+// (in[NL_IN_QSAT] is not read, out_adj[NL_IN_QSAT] is NULL).
 template <typename T>
 int launch_ad_masked(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* const* in, const T* const* in_adj,
                      const T* zero, const T* eta, const T* traj_l, const T* traj_n, T* const* out_adj, double dt,
-                     hipStream_t stream) {
+                     hipStream_t stream, bool step) {
     if (p.LEVAPLS2 || p.LDRAIN1D || !fits_u32_offsets<T>(nz, ls)) return -2;
     ADMaskedArgs<T> args;
     args.e = make_ext<T>(p);
@@ -1295,23 +1332,23 @@ int launch_ad_masked(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const 
     if (smem > size_t(64) * 1024)
         if (const int rc = current_device(dev)) return rc;
     const int rc = with_flags(
-        [&](auto REG, auto FIX) {
-            constexpr auto kern = ad_masked_kernel<T, REG, FIX>;
+        [&](auto REG, auto FIX, auto STEP) {
+            constexpr auto kern = STEP ? ad_step_kernel<T, REG, FIX> : ad_masked_kernel<T, REG, FIX>;
             if (smem > size_t(64) * 1024 && !lds_opt_in<kern>(dev, smem)) return -1;
             hipLaunchKernelGGL(kern, grid, block, smem, stream, args);
             return 0;
         },
-        p.LREGCL != 0, p.AD_TRAJ_FIX != 0);
+        p.LREGCL != 0, p.AD_TRAJ_FIX != 0, step);
     if (rc) return rc;
-    note_kernel("cs2::ad_masked_kernel");
+    note_kernel(step ? "cs2::ad_step_kernel" : "cs2::ad_masked_kernel");
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 template int launch_ad_masked<double>(const Cloudsc2Params&, int, int, int64_t, const double* const*, const double* const*,
                                       const double*, const double*, const double*, const double*, double* const*, double,
-                                      hipStream_t);
+                                      hipStream_t, bool);
 template int launch_ad_masked<float>(const Cloudsc2Params&, int, int, int64_t, const float* const*, const float* const*,
                                      const float*, const float*, const float*, const float*, float* const*, double,
-                                     hipStream_t);
+                                     hipStream_t, bool);
 
 }  // namespace cs2

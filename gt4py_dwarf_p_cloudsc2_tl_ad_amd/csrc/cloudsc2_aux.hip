@@ -104,6 +104,89 @@ int launch_saturation(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
+// ---- tangent-linear and adjoint of `saturation` (BUILD EXTENSIONS behind cloudsc2_saturation_tl_* / _ad_*) ---------------
+// The reference has neither (its harnesses perturb qsat independently); the rule is saturation_point_d's.  One point per
+// lane, grid as saturation_kernel.  An absent field is never a branch around a load: the launcher puts a field of the
+// call that is always present in its place (`ap`, whose word this lane has just read: expected to be served from the
+// cache without another HBM word - an expectation, not a measurement: both loads are non-temporal and no counter was read)
+// and a wave-uniform select on a kernel argument drops what was loaded.  Unwanted results are wave-uniform branches around
+// stores.
+template <typename T, int MODE>
+__global__ void __launch_bounds__(kAuxBlock)
+saturation_tl_kernel(Ext<T> e, ExpK<T> xk, int nx, int64_t ls, const T* __restrict__ ap, const T* __restrict__ t,
+                     const T* ap_i, const T* t_i, int has_ap_i, int has_t_i, T* __restrict__ qsat, T* __restrict__ qsat_i) {
+    const int col = blockIdx.x * kAuxBlock + threadIdx.x;
+    if (col >= nx) return;
+    const int64_t i = int64_t(blockIdx.y) * ls + col;
+    const T va = ntload(ap + i), vt = ntload(t + i);
+    T va_i = ntload(ap_i + i), vt_i = ntload(t_i + i);
+    va_i = has_ap_i ? va_i : T(0.0);
+    vt_i = has_t_i ? vt_i : T(0.0);
+    const SatD<T> s = saturation_point_d<T, MODE>(e, xk, vt, va);
+    if (qsat) ntstore(qsat + i, s.qsat);
+    ntstore(qsat_i + i, s.g_t * vt_i + s.g_ap * va_i);
+}
+
+// `prev_*`: what the adjoints are added to - the output fields themselves (accumulate), or `ap` again with the loaded
+// words dropped by `acc` = 0.
+template <typename T, int MODE>
+__global__ void __launch_bounds__(kAuxBlock)
+saturation_ad_kernel(Ext<T> e, ExpK<T> xk, int nx, int64_t ls, const T* __restrict__ ap, const T* __restrict__ t,
+                     const T* __restrict__ qsat_adj, const T* prev_ap, const T* prev_t, int acc_ap, int acc_t, T* ap_adj,
+                     T* t_adj) {
+    const int col = blockIdx.x * kAuxBlock + threadIdx.x;
+    if (col >= nx) return;
+    const int64_t i = int64_t(blockIdx.y) * ls + col;
+    const T va = ntload(ap + i), vt = ntload(t + i), vq = ntload(qsat_adj + i);
+    T pa = ntload(prev_ap + i), pt = ntload(prev_t + i);
+    pa = acc_ap ? pa : T(0.0);
+    pt = acc_t ? pt : T(0.0);
+    const SatD<T> s = saturation_point_d<T, MODE>(e, xk, vt, va);
+    if (ap_adj) ntstore(ap_adj + i, pa + s.g_ap * vq);
+    if (t_adj) ntstore(t_adj + i, pt + s.g_t * vq);
+}
+
+template <typename F>
+static int with_saturation_mode(const Cloudsc2Params& p, F&& f) {
+    if (p.LPHYLIN) return f(std::integral_constant<int, 0>{});
+    if (p.KFLAG == 1) return f(std::integral_constant<int, 1>{});
+    return f(std::integral_constant<int, 2>{});
+}
+
+// ap_i / t_i: nullptr = a zero perturbation; qsat: nullptr = the value is not written (the C entry has settled the rest)
+template <typename T>
+int launch_saturation_tl(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* ap, const T* t, const T* ap_i,
+                         const T* t_i, T* qsat, T* qsat_i, hipStream_t stream) {
+    const Ext<T> e = make_ext<T>(p);
+    const ExpK<T> xk = make_expk<T>();
+    const dim3 grid((nx + kAuxBlock - 1) / kAuxBlock, nz), block(kAuxBlock);
+    with_saturation_mode(p, [&](auto MODE) {
+        hipLaunchKernelGGL((saturation_tl_kernel<T, MODE>), grid, block, 0, stream, e, xk, nx, ls, ap, t, ap_i ? ap_i : ap,
+                           t_i ? t_i : ap, ap_i ? 1 : 0, t_i ? 1 : 0, qsat, qsat_i);
+        return 0;
+    });
+    note_kernel("cs2::saturation_tl_kernel");
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// ap_adj / t_adj: nullptr = that adjoint is not wanted; accumulate: add to what the wanted ones hold
+template <typename T>
+int launch_saturation_ad(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* ap, const T* t, const T* qsat_adj,
+                         T* ap_adj, T* t_adj, int accumulate, hipStream_t stream) {
+    const Ext<T> e = make_ext<T>(p);
+    const ExpK<T> xk = make_expk<T>();
+    const dim3 grid((nx + kAuxBlock - 1) / kAuxBlock, nz), block(kAuxBlock);
+    const int acc_ap = (accumulate && ap_adj) ? 1 : 0, acc_t = (accumulate && t_adj) ? 1 : 0;
+    with_saturation_mode(p, [&](auto MODE) {
+        hipLaunchKernelGGL((saturation_ad_kernel<T, MODE>), grid, block, 0, stream, e, xk, nx, ls, ap, t, qsat_adj,
+                           acc_ap ? static_cast<const T*>(ap_adj) : ap, acc_t ? static_cast<const T*>(t_adj) : ap, acc_ap,
+                           acc_t, ap_adj, t_adj);
+        return 0;
+    });
+    note_kernel("cs2::saturation_ad_kernel");
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
 template <typename T>
 __global__ void __launch_bounds__(kAuxBlock)
 increment_kernel(int nx, int64_t ls, CPtrs<T, INC_NUM> in, MPtrs<T, INC_NUM> out, T f, int ignore_supsat) {
@@ -276,6 +359,10 @@ int launch_column_dots(int nx, int nlev, int64_t ls, int np, const T* const* a, 
 #define CS2_INST(T)                                                                                           \
     template int launch_saturation<T>(const Cloudsc2Params&, int, int, int64_t, const T*, const T*, T*,      \
                                       hipStream_t);                                                           \
+    template int launch_saturation_tl<T>(const Cloudsc2Params&, int, int, int64_t, const T*, const T*,       \
+                                         const T*, const T*, T*, T*, hipStream_t);                            \
+    template int launch_saturation_ad<T>(const Cloudsc2Params&, int, int, int64_t, const T*, const T*,       \
+                                         const T*, T*, T*, int, hipStream_t);                                 \
     template int launch_increment<T>(const Cloudsc2Params&, int, int, int64_t, const T* const*, T* const*,   \
                                      double, hipStream_t);                                                    \
     template int launch_perturb<T>(int, int, int64_t, const T* const*, const T* const*, T* const*, double,   \

@@ -27,12 +27,17 @@ int launch_ad(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T
               T* const*, double, hipStream_t, const T* traj_l = nullptr, const T* traj_n = nullptr);
 template <typename T>
 int launch_tl_masked(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T* const*, const T*, const T*,
-                     T* const*, T* const*, double, hipStream_t);
+                     T* const*, T* const*, double, hipStream_t, bool step);
 template <typename T>
 int launch_ad_masked(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T* const*, const T*, const T*,
-                     const T*, const T*, T* const*, double, hipStream_t);
+                     const T*, const T*, T* const*, double, hipStream_t, bool step);
 template <typename T>
 int launch_saturation(const Cloudsc2Params&, int, int, int64_t, const T*, const T*, T*, hipStream_t);
+template <typename T>
+int launch_saturation_tl(const Cloudsc2Params&, int, int, int64_t, const T*, const T*, const T*, const T*, T*, T*,
+                         hipStream_t);
+template <typename T>
+int launch_saturation_ad(const Cloudsc2Params&, int, int, int64_t, const T*, const T*, const T*, T*, T*, int, hipStream_t);
 template <typename T>
 int launch_increment(const Cloudsc2Params&, int, int, int64_t, const T* const*, T* const*, double, hipStream_t);
 template <typename T>
@@ -273,14 +278,41 @@ int check_masked_size(const char* fn, int32_t nz, int64_t ls) {
                 (unsigned long long)(nz + 1) * (unsigned long long)ls * sizeof(T));
 }
 
+// The step entries (cloudsc2_tl_step_* / cloudsc2_ad_step_*: `saturation` fused in): in[NL_IN_QSAT] is not read and may be
+// NULL, every other trajectory field is required.
+template <typename T>
+int check_step_trajectory(const char* fn, const T* const* in) {
+    if (!in) return fail(CLOUDSC2_E_ARG, "%s: in is NULL", fn);
+    for (int i = 0; i < NL_NUM_IN; ++i)
+        if (!in[i] && i != NL_IN_QSAT) return fail(CLOUDSC2_E_ARG, "%s: in[%d] is NULL", fn, i);
+    return 0;
+}
+
+int check_step_saturation(const char* fn, const Cloudsc2Params* p) {
+    if (p->LPHYLIN) return 0;
+    return fail(CLOUDSC2_E_UNSUPPORTED, "%s: only the LPHYLIN form of saturation is available fused (use "
+                "cloudsc2_saturation_tl / _ad with the masked entries for the other forms)", fn);
+}
+
+// `step`: the cloudsc2_tl_step_* entry (tl_step_kernel)
 template <typename T>
 int tl_masked_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,
                    const T* const* in_i, const T* zero_line, const T* eta, T* const* out, T* const* out_i, double dt,
-                   void* stream) {
+                   void* stream, bool step = false) {
     if (int rc = check_common(fn, p, nx, nz, ls)) return rc;
     if (nx == 0) return CLOUDSC2_OK;
-    if (int rc = check_ptrs(fn, "in", in, NL_NUM_IN)) return rc;
-    if (int rc = check_masked_inputs(fn, "in_i", in_i, NL_NUM_IN, zero_line)) return rc;
+    if (int rc = step ? check_step_trajectory(fn, in) : check_ptrs(fn, "in", in, NL_NUM_IN)) return rc;
+    if (step && in_i && in_i[NL_IN_QSAT])
+        return fail(CLOUDSC2_E_ARG, "%s: in_i[NL_IN_QSAT] (in_i[%d]) must be NULL: the qsat perturbation is formed in the "
+                    "kernel from in_i[NL_IN_T] and in_i[NL_IN_AP] (use cloudsc2_tl_masked for an independent one)", fn,
+                    NL_IN_QSAT);
+    if (step && in_i && !zero_line) {       // the one NULL entry that needs no zero line: it is not read at all
+        for (int i = 0; i < NL_NUM_IN; ++i)
+            if (!in_i[i] && i != NL_IN_QSAT)
+                return fail(CLOUDSC2_E_ARG, "%s: in_i[%d] is NULL (a zero field) but zero_line is NULL too", fn, i);
+    } else if (int rc = check_masked_inputs(fn, "in_i", in_i, NL_NUM_IN, zero_line)) {
+        return rc;
+    }
     if (out)
         if (int rc = check_ptrs(fn, "out (all ten entries, or the array itself NULL)", const_cast<const T* const*>(out), NL_NUM_OUT))
             return rc;
@@ -289,19 +321,24 @@ int tl_masked_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t 
     if (p->ICALL != 0) return fail(CLOUDSC2_E_UNSUPPORTED, "%s: ICALL=%d unsupported", fn, p->ICALL);
     if (!(dt > 0.0)) return fail(CLOUDSC2_E_ARG, "%s: dt=%g must be > 0", fn, dt);
     if (p->NLEV != nz) return fail(CLOUDSC2_E_ARG, "%s: NLEV=%d != nz=%d", fn, p->NLEV, nz);
+    if (step)
+        if (int rc = check_step_saturation(fn, p)) return rc;
     if (int rc = check_masked_size<T>(fn, nz, ls)) return rc;
     return launched(fn, cs2::launch_tl_masked<T>(*p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt,
-                                                 static_cast<hipStream_t>(stream)));
+                                                 static_cast<hipStream_t>(stream), step));
 }
 
 template <typename T>
 int ad_masked_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,
                    const T* const* in_adj, const T* zero_line, const T* eta, const T* traj_fplsl, const T* traj_fplsn,
-                   T* const* out_adj, double dt, void* stream) {
+                   T* const* out_adj, double dt, void* stream, bool step = false) {
     if (int rc = check_common(fn, p, nx, nz, ls)) return rc;
     if (nx == 0) return CLOUDSC2_OK;
-    if (int rc = check_ptrs(fn, "in", in, NL_NUM_IN)) return rc;
+    if (int rc = step ? check_step_trajectory(fn, in) : check_ptrs(fn, "in", in, NL_NUM_IN)) return rc;
     if (int rc = check_masked_inputs(fn, "in_adj", in_adj, NL_NUM_OUT, zero_line)) return rc;
+    if (step && out_adj && out_adj[NL_IN_QSAT])
+        return fail(CLOUDSC2_E_ARG, "%s: out_adj[NL_IN_QSAT] (out_adj[%d]) must be NULL: the qsat adjoint is folded into "
+                    "out_adj[NL_IN_T] and out_adj[NL_IN_AP] (use cloudsc2_ad_masked to have it stored)", fn, NL_IN_QSAT);
     if (int rc = check_masked_outputs(fn, "out_adj", out_adj, NL_NUM_IN)) return rc;
     if (!eta || !traj_fplsl || !traj_fplsn) return fail(CLOUDSC2_E_ARG, "%s: eta / traj_fplsl / traj_fplsn is NULL", fn);
     if (p->ICALL != 0) return fail(CLOUDSC2_E_UNSUPPORTED, "%s: ICALL=%d unsupported", fn, p->ICALL);
@@ -311,9 +348,11 @@ int ad_masked_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t 
                     "precipitation cover has no counterpart among the NL outputs) - use cloudsc2_ad", fn);
     if (!(dt > 0.0)) return fail(CLOUDSC2_E_ARG, "%s: dt=%g must be > 0", fn, dt);
     if (p->NLEV != nz) return fail(CLOUDSC2_E_ARG, "%s: NLEV=%d != nz=%d", fn, p->NLEV, nz);
+    if (step)
+        if (int rc = check_step_saturation(fn, p)) return rc;
     if (int rc = check_masked_size<T>(fn, nz, ls)) return rc;
     return launched(fn, cs2::launch_ad_masked<T>(*p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn,
-                                                 out_adj, dt, static_cast<hipStream_t>(stream)));
+                                                 out_adj, dt, static_cast<hipStream_t>(stream), step));
 }
 
 template <typename T>
@@ -323,6 +362,33 @@ int sat_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t nz, in
     if (nx == 0) return CLOUDSC2_OK;   // empty call: nothing to check or launch (zero-size tensors carry NULL pointers)
     if (!ap || !t || !qsat) return fail(CLOUDSC2_E_ARG, "%s: NULL field pointer", fn);
     return launched(fn, cs2::launch_saturation<T>(*p, nx, nz, ls, ap, t, qsat, static_cast<hipStream_t>(stream)));
+}
+
+// tangent-linear / adjoint of `saturation` (build extensions): see include/cloudsc2_hip.h
+template <typename T>
+int sat_tl_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* ap, const T* t,
+                const T* ap_i, const T* t_i, T* qsat, T* qsat_i, void* stream) {
+    if (int rc = check_common(fn, p, nx, nz, ls)) return rc;
+    if (nx == 0) return CLOUDSC2_OK;
+    if (!ap) return fail(CLOUDSC2_E_ARG, "%s: ap is NULL", fn);
+    if (!t) return fail(CLOUDSC2_E_ARG, "%s: t is NULL", fn);
+    if (!ap_i && !t_i) return fail(CLOUDSC2_E_ARG, "%s: ap_i and t_i are both NULL: there is nothing to propagate", fn);
+    if (!qsat_i) return fail(CLOUDSC2_E_ARG, "%s: qsat_i is NULL", fn);
+    return launched(fn, cs2::launch_saturation_tl<T>(*p, nx, nz, ls, ap, t, ap_i, t_i, qsat, qsat_i,
+                                                     static_cast<hipStream_t>(stream)));
+}
+
+template <typename T>
+int sat_ad_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* ap, const T* t,
+                const T* qsat_adj, T* ap_adj, T* t_adj, int32_t accumulate, void* stream) {
+    if (int rc = check_common(fn, p, nx, nz, ls)) return rc;
+    if (nx == 0) return CLOUDSC2_OK;
+    if (!ap) return fail(CLOUDSC2_E_ARG, "%s: ap is NULL", fn);
+    if (!t) return fail(CLOUDSC2_E_ARG, "%s: t is NULL", fn);
+    if (!qsat_adj) return fail(CLOUDSC2_E_ARG, "%s: qsat_adj is NULL", fn);
+    if (!ap_adj && !t_adj) return fail(CLOUDSC2_E_ARG, "%s: ap_adj and t_adj are both NULL: nothing would be written", fn);
+    return launched(fn, cs2::launch_saturation_ad<T>(*p, nx, nz, ls, ap, t, qsat_adj, ap_adj, t_adj, accumulate,
+                                                     static_cast<hipStream_t>(stream)));
 }
 
 template <typename T>
@@ -491,6 +557,46 @@ int32_t cloudsc2_ad_masked_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, 
                                void* stream) {
     return ad_masked_impl<float>("cloudsc2_ad_masked_f32", p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl,
                                  traj_fplsn, out_adj, dt, stream);
+}
+int32_t cloudsc2_tl_step_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const double* const* in,
+                             const double* const* in_i, const double* zero_line, const double* eta, double* const* out,
+                             double* const* out_i, double dt, void* stream) {
+    return tl_masked_impl<double>("cloudsc2_tl_step_f64", p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt, stream, true);
+}
+int32_t cloudsc2_ad_step_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const double* const* in,
+                             const double* const* in_adj, const double* zero_line, const double* eta, const double* traj_fplsl,
+                             const double* traj_fplsn, double* const* out_adj, double dt, void* stream) {
+    return ad_masked_impl<double>("cloudsc2_ad_step_f64", p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn,
+                               out_adj, dt, stream, true);
+}
+int32_t cloudsc2_saturation_tl_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const double* ap,
+                                   const double* t, const double* ap_i, const double* t_i, double* qsat, double* qsat_i, void* stream) {
+    return sat_tl_impl<double>("cloudsc2_saturation_tl_f64", p, nx, nz, ls, ap, t, ap_i, t_i, qsat, qsat_i, stream);
+}
+int32_t cloudsc2_saturation_ad_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const double* ap,
+                                   const double* t, const double* qsat_adj, double* ap_adj, double* t_adj, int32_t accumulate,
+                                   void* stream) {
+    return sat_ad_impl<double>("cloudsc2_saturation_ad_f64", p, nx, nz, ls, ap, t, qsat_adj, ap_adj, t_adj, accumulate, stream);
+}
+int32_t cloudsc2_tl_step_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const float* const* in,
+                             const float* const* in_i, const float* zero_line, const float* eta, float* const* out,
+                             float* const* out_i, double dt, void* stream) {
+    return tl_masked_impl<float>("cloudsc2_tl_step_f32", p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt, stream, true);
+}
+int32_t cloudsc2_ad_step_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const float* const* in,
+                             const float* const* in_adj, const float* zero_line, const float* eta, const float* traj_fplsl,
+                             const float* traj_fplsn, float* const* out_adj, double dt, void* stream) {
+    return ad_masked_impl<float>("cloudsc2_ad_step_f32", p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn,
+                               out_adj, dt, stream, true);
+}
+int32_t cloudsc2_saturation_tl_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const float* ap,
+                                   const float* t, const float* ap_i, const float* t_i, float* qsat, float* qsat_i, void* stream) {
+    return sat_tl_impl<float>("cloudsc2_saturation_tl_f32", p, nx, nz, ls, ap, t, ap_i, t_i, qsat, qsat_i, stream);
+}
+int32_t cloudsc2_saturation_ad_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const float* ap,
+                                   const float* t, const float* qsat_adj, float* ap_adj, float* t_adj, int32_t accumulate,
+                                   void* stream) {
+    return sat_ad_impl<float>("cloudsc2_saturation_ad_f32", p, nx, nz, ls, ap, t, qsat_adj, ap_adj, t_adj, accumulate, stream);
 }
 int32_t cloudsc2_saturation_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const double* ap,
                                 const double* t, double* qsat, void* stream) {

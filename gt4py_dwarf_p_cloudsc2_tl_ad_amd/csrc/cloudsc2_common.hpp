@@ -229,6 +229,9 @@ inline Ext<T> make_ext(const Cloudsc2Params& p) {
 // (cloudsc2_nl.hip).  Contraction is switched off inside: every caller then evaluates the literal sequence of
 // multiplies and adds below (frcp / fexp spell their fma's out), so the three kernels agree bit for bit whatever
 // their surrounding code looks like.  MODE 0: LPHYLIN; 1: not LPHYLIN, KFLAG == 1 (f_foeewmcu); 2: f_foeewm.
+// KEEP IN STEP: saturation_point_d below repeats this sequence for its value, and ad_step_kernel calls both for the same
+// point (the value at the head of a level, the derivative where its adjoints are stored).  Change the operations or the
+// comparisons of one and the other must follow; tests/test_saturation_grad.py holds the two values bit-equal.
 template <typename T>
 __device__ __forceinline__ T foealfa(const Ext<T>& e, T t) {
 #pragma clang fp contract(off)
@@ -261,6 +264,51 @@ __device__ __forceinline__ T saturation_point(const Ext<T>& e, const ExpK<T>& xk
     }
     const T den = T(1.0) - e.RETV * qs;
     return qs * frcp<T>(den);
+}
+
+// saturation_point with its derivative (BUILD EXTENSION: the reference has no TL / AD of `saturation`):
+// qsat, g_t = d qsat / d t and g_ap = d qsat / d ap of one point.  The value is saturation_point's own sequence (same
+// primitives, same comparisons, each exponential evaluated once), so the two agree bit for bit and the derivative is taken
+// on the branch the value took; a clamped branch has derivative 0:
+//     alfa' = 2 (t - TI) RI^2  for TI < t < RTWAT, else 0   (at t == RTWAT the inner and the outer clamp of alfa meet: 0)
+//     ew_t  = alfa' (el - ei) + alfa el R3LES (RTT - R4LES) / (t - R4LES)^2 + (1 - alfa) ei R3IES (RTT - R4IES) / (t - R4IES)^2
+//     clipped at QMAX (the value's own `ew / ap < QMAX` is false): qs_t = qs_ap = 0;  else qs_t = ew_t / ap, qs_ap = -ew / ap^2
+//     g_t = qs_t / (1 - RETV qs)^2,  g_ap = qs_ap / (1 - RETV qs)^2
+// Callers: saturation_tl_kernel / saturation_ad_kernel (cloudsc2_aux.hip), tl_step_kernel, ad_step_kernel.
+template <typename T>
+struct SatD {
+    T qsat, g_t, g_ap;
+};
+template <typename T, int MODE>
+__device__ __forceinline__ SatD<T> saturation_point_d(const Ext<T>& e, const ExpK<T>& xk, T tt, T app) {
+#pragma clang fp contract(off)
+    const T rap = frcp<T>(app);
+    const T dl = tt - e.R4LES, di = tt - e.R4IES, dtt = tt - e.RTT;
+    const T al = e.R3LES * dtt, ai = e.R3IES * dtt;
+    const T rdl = frcp<T>(dl), rdi = frcp<T>(di);
+    const T foeewl = fexp<T>(xk, al * rdl);
+    const T foeewi = fexp<T>(xk, ai * rdi);
+    const T ti = (MODE == 1) ? e.RTICECU : e.RTICE, ri = (MODE == 1) ? e.RTWAT_RTICECU_R : e.RTWAT_RTICE_R;
+    const T alfa = (MODE == 1) ? foealfcu(e, tt) : foealfa(e, tt);
+    const T el = e.R2ES * foeewl, ei = e.R2ES * foeewi;
+    T q0;
+    if constexpr (MODE == 0) {
+        q0 = (alfa * el + (T(1.0) - alfa) * ei) * rap;
+    } else {
+        q0 = e.R2ES * (alfa * foeewl + (T(1.0) - alfa) * foeewi) * rap;
+    }
+    const bool open = q0 < e.QMAX;            // rmin's own comparison
+    const T qs = open ? q0 : e.QMAX;
+    const T rden = frcp<T>(T(1.0) - e.RETV * qs);
+    const T dalfa = (ti < tt && tt < e.RTWAT) ? T(2.0) * (tt - ti) * ri * ri : T(0.0);
+    const T ew_t = dalfa * (el - ei) + alfa * el * (e.R3LES * (e.RTT - e.R4LES)) * (rdl * rdl) +
+                   (T(1.0) - alfa) * ei * (e.R3IES * (e.RTT - e.R4IES)) * (rdi * rdi);
+    const T cor2 = rden * rden;
+    SatD<T> r;
+    r.qsat = qs * rden;
+    r.g_t = open ? ew_t * rap * cor2 : T(0.0);
+    r.g_ap = open ? -(q0 * rap) * cor2 : T(0.0);
+    return r;
 }
 
 // Pin a wave-uniform value in a VGPR.  The fp64 kernels use ~45 named double constants; together with

@@ -877,8 +877,9 @@ struct TLMaskedFields : KernArgs<TLMaskedArgs<T>> {
     __device__ __forceinline__ T* out_i(int i) const { return this->ka->out_i.p[i]; }
 };
 
-// load_level with a per-field offset: the field's own, or `zo` into the zero line
-template <typename T, typename P>
+// load_level with a per-field offset: the field's own, or `zo` into the zero line.  SKIPQ: the qsat word is not read (the
+// step kernels form it from the level's t and ap words)
+template <typename T, bool SKIPQ = false, typename P>
 __device__ __forceinline__ LevelIn<T> load_level_masked(const P& ptr, uint32_t have, uint32_t lsb, uint32_t o, uint32_t zo) {
     const auto at = [&](int f, uint32_t x) { return (have >> f & 1u) ? x : zo; };
     LevelIn<T> x;
@@ -891,7 +892,8 @@ __device__ __forceinline__ LevelIn<T> load_level_masked(const P& ptr, uint32_t h
     x.q = ldg(ptr(NL_IN_Q), at(NL_IN_Q, o));
     x.qi = ldg(ptr(NL_IN_QI), at(NL_IN_QI, o));
     x.ql = ldg(ptr(NL_IN_QL), at(NL_IN_QL, o));
-    x.qsat = ldg(ptr(NL_IN_QSAT), at(NL_IN_QSAT, o));
+    if constexpr (SKIPQ) x.qsat = T(0.0);
+    else x.qsat = ldg(ptr(NL_IN_QSAT), at(NL_IN_QSAT, o));
     x.supsat = ldg(ptr(NL_IN_SUPSAT), at(NL_IN_SUPSAT, o));
     x.t = ldg(ptr(NL_IN_T), at(NL_IN_T, o));
     x.tq = ldg(ptr(NL_IN_TND_CML_Q), at(NL_IN_TND_CML_Q, o));
@@ -931,9 +933,12 @@ __device__ __forceinline__ void tl_store_masked(const FP& F, uint32_t want, cons
 #undef CS2_WANT
 }
 
-template <typename T, bool REG, bool EVAP>
-__global__ void __launch_bounds__(kColBlock)
-tl_masked_kernel(const TLMaskedArgs<T> A) {
+// The sweep of tl_masked_kernel and of tl_step_kernel (one copy).  STEP: `saturation` and its tangent-linear are fused in
+// (C ABI cloudsc2_tl_step_*): in_qsat and its perturbation are not read; the level's qsat is saturation_point_d's value of
+// the level's t and ap words (LPHYLIN form, what cloudsc2_nl_fused_* computes) and the perturbation the level function
+// sees is g_t * t_i + g_ap * ap_i - formed at the head of the level's arithmetic, behind the prefetch of the next level.
+template <typename T, bool REG, bool EVAP, bool STEP>
+__device__ __forceinline__ void tl_masked_sweep(const TLMaskedArgs<T>& A) {
     Ext<T> e = A.e;
     NLK<T> kc = A.kc;
     ExpK<T> xk = A.xk;
@@ -984,13 +989,18 @@ tl_masked_kernel(const TLMaskedArgs<T> A) {
     if (want >> NL_OUT_FHPSN & 1u) stg(F.out_i(NL_OUT_FHPSN), colb, T(0.0));
 
     O o = colb;
-    LevelIn<T> xa = load_level<T, O>(F_in, lsb, o), ya = load_level_masked<T>(F_in_i, have, lsb, o, zo);
+    LevelIn<T> xa = load_level<T, O>(F_in, lsb, o, STEP), ya = load_level_masked<T, STEP>(F_in_i, have, lsb, o, zo);
     for (int k = 0; k < nz; ++k) {
         F.fresh();
         LevelIn<T> xn = xa, yn = ya;
         if (k + 1 < nz) {
-            xn = load_level<T, O>(F_in, lsb, o + lsb);
-            yn = load_level_masked<T>(F_in_i, have, lsb, o + lsb, zo);
+            xn = load_level<T, O>(F_in, lsb, o + lsb, STEP);
+            yn = load_level_masked<T, STEP>(F_in_i, have, lsb, o + lsb, zo);
+        }
+        if constexpr (STEP) {
+            const SatD<T> s = saturation_point_d<T, 0>(e, xk, xa.t, xa.ap);
+            xa.qsat = s.qsat;
+            ya.qsat = s.g_t * ya.t + s.g_ap * ya.ap;
         }
         const TLOut<T> r = tl_level<T, REG, EVAP>(e, kc, xk, xa, ya, k, s_eta[k], s_scalm[k], crh, dt, c);
         tl_store_masked<T>(F, want, e, lsb, o, r);
@@ -1001,11 +1011,25 @@ tl_masked_kernel(const TLMaskedArgs<T> A) {
     }
 }
 
+template <typename T, bool REG, bool EVAP>
+__global__ void __launch_bounds__(kColBlock)
+tl_masked_kernel(const TLMaskedArgs<T> A) {
+    tl_masked_sweep<T, REG, EVAP, false>(A);
+}
+
+// `saturation` + cloudsc2_tl_masked in one launch (BUILD EXTENSION, C ABI cloudsc2_tl_step_*): see tl_masked_sweep
+template <typename T, bool REG, bool EVAP>
+__global__ void __launch_bounds__(kColBlock)
+tl_step_kernel(const TLMaskedArgs<T> A) {
+    tl_masked_sweep<T, REG, EVAP, true>(A);
+}
+
 // in_i[f] == nullptr: perturbation f is zero everywhere (read from `zero`); out == nullptr: no NL outputs;
-// out_i[f] == nullptr: not written.  Always the register path; 32-bit offsets only.
+// out_i[f] == nullptr: not written.  Always the register path; 32-bit offsets only.  `step`: tl_step_kernel (in[NL_IN_QSAT]
+// and in_i[NL_IN_QSAT] are not read).
 template <typename T>
 int launch_tl_masked(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* const* in, const T* const* in_i,
-                     const T* zero, const T* eta, T* const* out, T* const* out_i, double dt, hipStream_t stream) {
+                     const T* zero, const T* eta, T* const* out, T* const* out_i, double dt, hipStream_t stream, bool step) {
     if (!fits_u32_offsets<T>(nz, ls)) return -2;
     const bool evap = p.LEVAPLS2 || p.LDRAIN1D;
     TLMaskedArgs<T> args;
@@ -1030,18 +1054,19 @@ int launch_tl_masked(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const 
     const dim3 grid((nx + kColBlock - 1) / kColBlock), block(kColBlock);
     const size_t smem = 2 * size_t(nz + 1) * sizeof(T);
     with_flags(
-        [&](auto REG, auto EVAP) {
-            hipLaunchKernelGGL((tl_masked_kernel<T, REG, EVAP>), grid, block, smem, stream, args);
+        [&](auto REG, auto EVAP, auto STEP) {
+            if constexpr (STEP) hipLaunchKernelGGL((tl_step_kernel<T, REG, EVAP>), grid, block, smem, stream, args);
+            else hipLaunchKernelGGL((tl_masked_kernel<T, REG, EVAP>), grid, block, smem, stream, args);
             return 0;
         },
-        p.LREGCL != 0, evap);
-    note_kernel("cs2::tl_masked_kernel");
+        p.LREGCL != 0, evap, step);
+    note_kernel(step ? "cs2::tl_step_kernel" : "cs2::tl_masked_kernel");
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 template int launch_tl_masked<double>(const Cloudsc2Params&, int, int, int64_t, const double* const*, const double* const*,
-                                      const double*, const double*, double* const*, double* const*, double, hipStream_t);
+                                      const double*, const double*, double* const*, double* const*, double, hipStream_t, bool);
 template int launch_tl_masked<float>(const Cloudsc2Params&, int, int, int64_t, const float* const*, const float* const*,
-                                     const float*, const float*, float* const*, float* const*, double, hipStream_t);
+                                     const float*, const float*, float* const*, float* const*, double, hipStream_t, bool);
 
 }  // namespace cs2

@@ -41,6 +41,8 @@
 extern "C" {
 #endif
 
+/* Stays 4 with the cloudsc2_saturation_tl_* / _ad_* and cloudsc2_tl_step_* / _ad_step_* entries: they are purely additive
+ * (no existing prototype, enum or struct changed), so a caller built against the earlier version 4 header runs unchanged. */
 #define CLOUDSC2_ABI_VERSION 4
 
 #define CLOUDSC2_OK 0
@@ -172,6 +174,39 @@ int32_t cloudsc2_saturation_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz,
 int32_t cloudsc2_saturation_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
                                 const float* ap, const float* t, float* qsat, void* stream);
 
+/* ---- tangent-linear and adjoint of `saturation` (BUILD EXTENSIONS - the reference has no such stencil: its harnesses
+ * perturb qsat independently).  With, per point of the nx x nz domain of cloudsc2_saturation_* (level nz is never touched),
+ *     alfa = min(1, ((max(TI, min(RTWAT, t)) - TI) RI)^2),  el / ei = R2ES exp(R3xES (t - RTT) / (t - R4xES)),
+ *     ew = alfa el + (1 - alfa) ei,  qs = min(ew / ap, QMAX),  qsat = qs / (1 - RETV qs)
+ * ((TI, RI) = (RTICE, RTWAT_RTICE_R), or (RTICECU, RTWAT_RTICECU_R) when LPHYLIN == 0 and KFLAG == 1), the derivative takes
+ * every min / max on the branch the value took, with the value's own comparison; a clamped branch has derivative 0:
+ *     alfa' = 2 (t - TI) RI^2 for TI < t < RTWAT, else 0
+ *     ew_t  = alfa' (el - ei) + alfa el R3LES (RTT - R4LES) / (t - R4LES)^2 + (1 - alfa) ei R3IES (RTT - R4IES) / (t - R4IES)^2
+ *     clipped at QMAX: qs_t = qs_ap = 0;  otherwise qs_t = ew_t / ap, qs_ap = -ew / ap^2
+ *     g_t = qs_t / (1 - RETV qs)^2,  g_ap = qs_ap / (1 - RETV qs)^2
+ *   TL:  qsat_i = g_t t_i + g_ap ap_i.   ap_i or t_i may be NULL (a zero perturbation; at least one is not);
+ *        qsat may be NULL (the value is not written; when written it equals cloudsc2_saturation_*'s bit for bit).
+ *   AD:  t_adj (+)= g_t qsat_adj,  ap_adj (+)= g_ap qsat_adj.   ap_adj or t_adj may be NULL (that adjoint is not wanted; at
+ *        least one is not); accumulate != 0 adds to what they hold - e.g. the t / ap adjoints cloudsc2_ad_masked_* has just
+ *        written, which completes the adjoint of saturation + cloudsc2_nl.
+ * All three forms (LPHYLIN; KFLAG == 1 / other).  Argument errors are settled on the host before any launch, with the
+ * argument's name in cloudsc2_last_error(); nx == 0 is a successful no-op.
+ * Words moved per point: TL 2 + (present perturbations) + 1 + (1 if qsat); AD 3 + (wanted adjoints), twice those when
+ * accumulating (counted on the expectation that the word loaded in place of an absent field is served from the cache;
+ * no counter was read). */
+int32_t cloudsc2_saturation_tl_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride, const double* ap,
+                                   const double* t, const double* ap_i, const double* t_i, double* qsat, double* qsat_i,
+                                   void* stream);
+int32_t cloudsc2_saturation_tl_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride, const float* ap,
+                                   const float* t, const float* ap_i, const float* t_i, float* qsat, float* qsat_i,
+                                   void* stream);
+int32_t cloudsc2_saturation_ad_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride, const double* ap,
+                                   const double* t, const double* qsat_adj, double* ap_adj, double* t_adj,
+                                   int32_t accumulate, void* stream);
+int32_t cloudsc2_saturation_ad_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride, const float* ap,
+                                   const float* t, const float* qsat_adj, float* ap_adj, float* t_adj,
+                                   int32_t accumulate, void* stream);
+
 /* ---- state_increment : common/_stencils/state_increment.py:22-80, called at common/increment.py:93-132
  * ---- perturbed_state : common/_stencils/perturbed_state.py:22-91, called at common/increment.py:219-261
  * Field order of the 16-entry arrays (same for in / in_i / out): */
@@ -290,6 +325,42 @@ int32_t cloudsc2_ad_masked_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, 
                                const float* const* in, const float* const* in_adj, const float* zero_line,
                                const float* eta, const float* traj_fplsl, const float* traj_fplsn,
                                float* const* out_adj, double dt, void* stream);
+
+/* ---- the derivative of the whole step, saturation + cloudsc2_nl, in one launch (BUILD EXTENSIONS - no reference stencil).
+ * cloudsc2_nl_fused_* with qsat_out is the step; these are its tangent-linear and its adjoint: the masked entries above with
+ * the derivative of `saturation` (the rule documented with cloudsc2_saturation_tl_* / _ad_*) fused in, so the path
+ * t, ap -> qsat -> cloudsc2 is part of the result.  Arguments are those of cloudsc2_tl_masked_* / cloudsc2_ad_masked_*, and
+ * so are the size (fields below 4 GiB), zero-line and evaporation-switch rules (the AD entry refuses LEVAPLS2 / LDRAIN1D),
+ * with these differences:
+ *   in[NL_IN_QSAT]       is not read and may be NULL: the kernel forms qsat from in[NL_IN_AP] and in[NL_IN_T], bit for bit
+ *                        what cloudsc2_nl_fused_* / cloudsc2_saturation_* compute;
+ *   LPHYLIN              only this form of saturation is available fused, as for cloudsc2_nl_fused_*: anything else is
+ *                        CLOUDSC2_E_UNSUPPORTED (compose cloudsc2_saturation_tl_* / _ad_* with the masked entries);
+ *   in_i[NL_IN_QSAT]     (TL) must be NULL (CLOUDSC2_E_ARG): the perturbation the level sees is g_t t_i + g_ap ap_i, formed
+ *                        from that level's words.  This one NULL entry needs no zero line;
+ *   out_adj[NL_IN_QSAT]  (AD) must be NULL (CLOUDSC2_E_ARG): the level's qsat adjoint is not stored but folded, as
+ *                        g_t qsat_adj into out_adj[NL_IN_T] and as g_ap qsat_adj into out_adj[NL_IN_AP].  Only those two:
+ *                        out_adj[NL_IN_TND_CML_T] stays dt times the t adjoint of cloudsc2 itself.
+ * cloudsc2_last_kernel() reports "cs2::tl_step_kernel" / "cs2::ad_step_kernel".
+ * Words moved per level and column: TL 15 + (present in_i) + (10 if out) + (present out_i) - two words less than
+ * cloudsc2_saturation_tl + cloudsc2_tl_masked, and one launch less; AD 15 + 2 + (present in_adj) + (present out_adj), where
+ * the composition moves 16 + 2 + ... + 1 (the qsat adjoint) in cloudsc2_ad_masked and then reads 3 fields and
+ * read-modify-writes 2 in cloudsc2_saturation_ad - e.g. forcing on the four tendencies and adjoints of t, q, ql, qi: 25
+ * words in one launch against about 34 in two. */
+int32_t cloudsc2_tl_step_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                             const double* const* in, const double* const* in_i, const double* zero_line,
+                             const double* eta, double* const* out, double* const* out_i, double dt, void* stream);
+int32_t cloudsc2_tl_step_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                             const float* const* in, const float* const* in_i, const float* zero_line,
+                             const float* eta, float* const* out, float* const* out_i, double dt, void* stream);
+int32_t cloudsc2_ad_step_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                             const double* const* in, const double* const* in_adj, const double* zero_line,
+                             const double* eta, const double* traj_fplsl, const double* traj_fplsn,
+                             double* const* out_adj, double dt, void* stream);
+int32_t cloudsc2_ad_step_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                             const float* const* in, const float* const* in_adj, const float* zero_line,
+                             const float* eta, const float* traj_fplsl, const float* traj_fplsn,
+                             float* const* out_adj, double dt, void* stream);
 
 #ifdef __cplusplus
 }
