@@ -103,6 +103,13 @@ LAYOUTS: Dict[str, Layout] = {
                                                   _STREAM)),
 }
 
+#: the multi-direction TL entries (autodiff.tl_multi / tl_step_multi call them directly, like the masked entries they
+#: extend): name -> the single-direction entry whose argument list they repeat, followed by `ndir`, `in_dir_stride` and
+#: `out_dir_stride` (elements)
+MULTI_LAYOUTS: Dict[str, str] = {"tl_multi": "tl_masked", "tl_multi_step": "tl_step"}
+#: CLOUDSC2_TL_MAX_DIRS of include/cloudsc2_hip.h
+TL_MAX_DIRS = 8
+
 _PARR = POINTER(c_void_p)      # device pointers travel as integers (void*), never dereferenced on the host
 _CTYPES = {"ptrs": (_PARR,), "field": (c_void_p,), "eta": (c_void_p,), "scalar": (c_double,), "partials": (c_void_p,),
            "fs": (c_int32, POINTER(c_double)), "stream": (c_void_p,)}
@@ -129,6 +136,8 @@ def _signatures() -> Dict[str, Tuple[Any, Tuple[Any, ...]]]:
         sig[f"cloudsc2_ad_masked_{sfx}"] = (c_int32, ad_masked)
         sig[f"cloudsc2_tl_step_{sfx}"] = (c_int32, tl_masked)
         sig[f"cloudsc2_ad_step_{sfx}"] = (c_int32, ad_masked)
+        for multi, single in MULTI_LAYOUTS.items():
+            sig[f"cloudsc2_{multi}_{sfx}"] = (c_int32, sig[f"cloudsc2_{single}_{sfx}"][1] + (c_int32, c_int64, c_int64))
         sig[f"cloudsc2_saturation_tl_{sfx}"] = (c_int32, sat_tl)
         sig[f"cloudsc2_saturation_ad_{sfx}"] = (c_int32, sat_ad)
         sig[f"cloudsc2_field_sums_{sfx}"] = (c_int32, reduction + (c_void_p,))

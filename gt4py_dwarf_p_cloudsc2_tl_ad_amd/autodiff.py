@@ -11,22 +11,36 @@ MASKED kernels: fields a call does not have are NULL entries that move no HBM wo
 the TOTAL derivative (the path t, ap -> qsat -> cloudsc2 included), `saturation(ap, t)` its first half on its own.
 
 `tl_masked` / `ad_masked`, `tl_step` / `ad_step` and `saturation_tl` / `saturation_ad` are the thin calls underneath, usable
-on their own (a variational cost, a sensitivity study).  GPU tensors only - there is no host path."""
+on their own (a variational cost, a sensitivity study).  GPU tensors only - there is no host path.
+
+MANY derivatives on one trajectory.  `tl_multi` / `tl_step_multi` push `ndir` perturbations through one linearisation (C ABI
+`cloudsc2_tl_multi_*` / `cloudsc2_tl_multi_step_*`: one launch reads the state once for up to `width` directions; the default
+width per precision, `MULTI_WIDTH`, is 1 - single launches - until the kernel's gain has been measured).
+`cloudsc2`, `cloudsc2_step` and `saturation` work under `torch.func`: `jvp`, `vjp`, `grad`, `jacfwd`, `jacrev`, and `vmap`
+over TANGENTS or COTANGENTS (`vmap` of `jvp`, which is what `jacfwd` is; `vmap` of a `vjp` function, which is what `jacrev`
+is).  Batched tangents run `tl_multi` / `tl_step_multi`; batched cotangents loop over single adjoint launches (there is no
+multi-direction adjoint kernel).  Not supported: `vmap` over the STATE (`NotImplementedError`),
+`torch.autograd.grad(..., is_grads_batched=True)` (the legacy vmap, which knows no `vmap` rule of a Function), second
+derivatives."""
 from __future__ import annotations
 
 import ctypes
-from typing import Any, Dict, Iterable, Mapping, Optional, Tuple
+from typing import Any, Dict, Iterable, Mapping, NamedTuple, Optional, Tuple
 
 import torch
 
 from . import _lib
 from ._lib import NL_IN, NL_OUT
 from .params import default_externals, make_params
-from .storage import field_geometry, zeros
+from .storage import direction_stride, field_geometry, zeros, zeros_batched
 
 _SFX = {torch.float64: "f64", torch.float32: "f32"}
 #: the inputs of the step: those of `cloudsc2_nl` without `qsat`, which the step forms from `ap` and `t`
 STEP_IN = tuple(n for n in NL_IN if n != "qsat")
+#: directions per launch of the multi-direction TL, per precision: the measured width with the best time per direction.
+#: 1 = that precision loops over single `tl_masked` / `tl_step` launches.  The measurement (profiles/bench_tl_multi.py) has
+#: not been taken on an MI355X yet, so no width is enabled (docs/TUNING_LOG.md 3.18); `width=` of `tl_multi` reaches the kernel.
+MULTI_WIDTH: Dict[torch.dtype, int] = {torch.float64: 1, torch.float32: 1}
 _ZERO_LINE_BYTES = 512
 _zero_lines: Dict[Tuple[torch.device, torch.dtype], torch.Tensor] = {}
 
@@ -116,7 +130,9 @@ def tl_step(state: Mapping[str, torch.Tensor], perturbations: Mapping[str, torch
     return _tl_call("tl_step", STEP_IN, state, perturbations, eta, dt, externals, want, write_nl)
 
 
-def _tl_call(what, in_names, state, perturbations, eta, dt, externals, want, write_nl):
+def _tl_call(what, in_names, state, perturbations, eta, dt, externals, want, write_nl, into=None):
+    """`into`: the perturbed outputs are written to these fields of the call's geometry (`tl_multi`: one direction of its
+    batched results) and not to new ones"""
     want = tuple(want)
     if not want or set(want) - set(NL_OUT):
         raise ValueError(f"{what}: `want` must name at least one of {NL_OUT}, got {want}")
@@ -127,7 +143,7 @@ def _tl_call(what, in_names, state, perturbations, eta, dt, externals, want, wri
     eta = _eta(what, eta, nz, dtype, device)
     ref = state[NL_IN[0]]
     out = {n: _new_like(ref, nx, nz, ls) for n in NL_OUT} if write_nl else None
-    out_i = {n: _new_like(ref, nx, nz, ls) for n in want}
+    out_i = {n: _new_like(ref, nx, nz, ls) for n in want} if into is None else into
     p = _params(externals, nz)
     with torch.cuda.device(device):
         rc = getattr(_lib.load(), f"cloudsc2_{what}_{_SFX[dtype]}")(
@@ -135,6 +151,93 @@ def _tl_call(what, in_names, state, perturbations, eta, dt, externals, want, wri
             eta.data_ptr(), None if out is None else _ptrs(out, NL_OUT), _ptrs(out_i, NL_OUT), float(dt),
             int(torch.cuda.current_stream(device).cuda_stream))
     _lib.check(rc, what)
+    return out, out_i
+
+
+def tl_multi(state: Mapping[str, torch.Tensor], perturbations: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+             externals: Optional[Mapping[str, Any]] = None, *, want: Iterable[str], write_nl: bool = False,
+             width: Optional[int] = None):
+    """`tl_masked` for `ndir` perturbations of one state: `perturbations` maps `NL_IN` names to `(ndir, nx, 1, nz+1)`
+    tensors (a missing name is zero in every direction).  Returns `(nl_outputs or None, {name: (ndir, nx, 1, nz+1)})`; the
+    results are one `storage.zeros_batched` allocation per name, the NL outputs are written once.
+
+    Directions are served in chunks of at most `width` (default `MULTI_WIDTH` of the dtype) per `cloudsc2_tl_multi_*`
+    launch, which reads the state once per chunk; a chunk of one direction is a plain `tl_masked` launch.  Any `ndir >= 1`
+    works.  A perturbation that is not laid out as `storage.zeros_batched` gives is copied into such a field first."""
+    return _tl_multi_call("tl_multi", "tl_masked", NL_IN, state, perturbations, eta, dt, externals, want, write_nl, width)
+
+
+def tl_step_multi(state: Mapping[str, torch.Tensor], perturbations: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+                  externals: Optional[Mapping[str, Any]] = None, *, want: Iterable[str], write_nl: bool = False,
+                  width: Optional[int] = None):
+    """`tl_step` for `ndir` perturbations of one state (`cloudsc2_tl_multi_step_*`; `STEP_IN` names): see `tl_multi`.
+    `saturation` and its derivative are evaluated once per level for all directions of a chunk.  LPHYLIN only."""
+    return _tl_multi_call("tl_multi_step", "tl_step", STEP_IN, state, perturbations, eta, dt, externals, want, write_nl, width)
+
+
+def _batched_layout(g: torch.Tensor, ref: torch.Tensor, geo) -> torch.Tensor:
+    """`g` as `ndir` fields of the call's geometry, one field behind the other: itself, or a copy into a `zeros_batched`
+    allocation (what `_in_layout` is for one direction)"""
+    g = _plain(g)
+    nx, nlev, ls = geo
+    if g.dtype == ref.dtype and g.device == ref.device and g.dim() == 4 and tuple(g.shape[1:]) == (nx, 1, nlev):
+        try:
+            if field_geometry(g[0]) == geo and direction_stride(g) == nlev * ls:
+                return g
+        except ValueError:
+            pass
+    f = zeros_batched(g.shape[0], nx, nlev - 1, ref.dtype, ref.device, ls)
+    f.copy_(g)
+    return f
+
+
+def _tl_multi_call(what, single, in_names, state, perturbations, eta, dt, externals, want, write_nl, width):
+    want = tuple(want)
+    if not want or set(want) - set(NL_OUT):
+        raise ValueError(f"{what}: `want` must name at least one of {NL_OUT}, got {want}")
+    state = {n: _plain(f) for n, f in state.items()}
+    geo, dtype, device = _checked(what, ((state, in_names, True),))
+    nx, nlev, ls = geo
+    unknown = sorted(set(perturbations) - set(in_names))
+    if unknown:
+        raise ValueError(f"{what}: unknown field names {unknown}")
+    if not perturbations:
+        raise ValueError(f"{what}: no perturbation given")
+    shapes = {tuple(f.shape) for f in perturbations.values() if isinstance(f, torch.Tensor)}
+    if len(shapes) != 1 or len(next(iter(shapes))) != 4 or next(iter(shapes))[1:] != (nx, 1, nlev) or next(iter(shapes))[0] < 1:
+        raise ValueError(f"{what}: every perturbation must be a tensor of one shape (ndir, {nx}, 1, {nlev}), got "
+                         f"{ {n: tuple(getattr(f, 'shape', ())) for n, f in perturbations.items()} }")
+    ndir = next(iter(shapes))[0]
+    for n, f in perturbations.items():
+        if not f.is_cuda:
+            raise ValueError(f"{what}: {n} lives on {f.device}; fields must live on the GPU (there is no host path)")
+    nz = nlev - 1
+    eta = _eta(what, eta, nz, dtype, device)
+    ref = state[NL_IN[0]]
+    width = MULTI_WIDTH[dtype] if width is None else int(width)
+    if not 1 <= width <= _lib.TL_MAX_DIRS:
+        raise ValueError(f"{what}: width={width} outside [1, {_lib.TL_MAX_DIRS}]")
+    pert = {n: _batched_layout(f, ref, geo) for n, f in perturbations.items()}
+    out = None
+    out_i = {n: zeros_batched(ndir, nx, nz, dtype, device, ls) for n in want}
+    dstride = nlev * ls
+    p = _params(externals, nz)
+    for d0 in range(0, ndir, width):
+        n = min(width, ndir - d0)
+        nl = write_nl and d0 == 0
+        if n == 1:
+            o, _ = _tl_call(single, in_names, state, {k: f[d0] for k, f in pert.items()}, eta, dt, externals, want, nl,
+                            into={k: f[d0] for k, f in out_i.items()})
+        else:
+            o = {k: _new_like(ref, nx, nz, ls) for k in NL_OUT} if nl else None
+            with torch.cuda.device(device):
+                rc = getattr(_lib.load(), f"cloudsc2_{what}_{_SFX[dtype]}")(
+                    ctypes.byref(p), nx, nz, ls, _ptrs(state, NL_IN), _ptrs({k: f[d0] for k, f in pert.items()}, NL_IN),
+                    _zero_line(device, dtype).data_ptr(), eta.data_ptr(), None if o is None else _ptrs(o, NL_OUT),
+                    _ptrs({k: f[d0] for k, f in out_i.items()}, NL_OUT), float(dt),
+                    int(torch.cuda.current_stream(device).cuda_stream), n, dstride, dstride)
+            _lib.check(rc, what)
+        out = o if nl else out
     return out, out_i
 
 
@@ -194,25 +297,221 @@ def _in_layout(g: torch.Tensor, ref: torch.Tensor, geo) -> torch.Tensor:
     return f
 
 
+# ---- the launches behind the derivative rules, as Functions of their own ---------------------------------------------------
+# `backward` and `jvp` of the public Functions touch no storage: they hand what they were given to one of these, which holds
+# the layout normalisation and the launch - and a `vmap` rule, so that under `torch.func.vmap` (`jacfwd`, `jacrev`, `vmap` of
+# `jvp`) the rule sees all tangents / cotangents stacked, as ordinary tensors.  Outside `vmap` they are plain calls.
+_BATCHED_STATE = ("only tangents and cotangents may be batched: `vmap` over the state (a primal input of cloudsc2 / "
+                  "cloudsc2_step / saturation) is not supported - loop over the states, or put them side by side as columns")
+
+
+class _Launch(NamedTuple):
+    """what a launch needs beside its tensors; `have`: the names of the tangents / cotangents that follow the fixed tensors
+    (absent ones are `None` in autograd and are not passed); `want`: the adjoints to produce (AD)"""
+    eta: Optional[torch.Tensor]
+    dt: float
+    ext: Mapping[str, Any]
+    geo: Tuple[int, int, int]
+    have: Tuple[str, ...]
+    want: Tuple[str, ...] = ()
+
+
+def _unbatched_state(in_dims, nfixed):
+    """in_dims[0] belongs to the `_Launch` (a tuple like it: `eta` is its one tensor), the next `nfixed` to the state"""
+    if in_dims[0].eta is not None or any(d is not None for d in in_dims[1:1 + nfixed]):
+        raise NotImplementedError(_BATCHED_STATE)
+
+
+def _stacked(info, in_dims, tensors, nfixed):
+    """the tangents / cotangents behind the `nfixed` state tensors, each as (batch, nx, 1, nlev)"""
+    return [t.unsqueeze(0).expand(info.batch_size, *t.shape) if d is None else t.movedim(d, 0)
+            for t, d in zip(tensors[nfixed:], in_dims[1 + nfixed:])]
+
+
+class _InnerFunction(torch.autograd.Function):
+    """no derivative of its own (second derivatives are not available): it exists for its `vmap` rule"""
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        pass
+
+
+class _TLMasked(_InnerFunction):
+    """(call, 16 state fields, present tangents) -> the ten perturbed outputs"""
+    @staticmethod
+    def forward(call, *tensors):
+        state = dict(zip(NL_IN, tensors[:len(NL_IN)]))
+        ref = _plain(tensors[0])
+        pert = {n: _in_layout(t, ref, call.geo) for n, t in zip(call.have, tensors[len(NL_IN):])}
+        _, out_i = tl_masked(state, pert, call.eta, call.dt, call.ext, want=NL_OUT, write_nl=False)
+        return tuple(out_i[n] for n in NL_OUT)
+
+    @staticmethod
+    def vmap(info, in_dims, call, *tensors):
+        _unbatched_state(in_dims, len(NL_IN))
+        state = dict(zip(NL_IN, tensors[:len(NL_IN)]))
+        pert = dict(zip(call.have, _stacked(info, in_dims, tensors, len(NL_IN))))
+        _, out_i = tl_multi(state, pert, call.eta, call.dt, call.ext, want=NL_OUT, write_nl=False)
+        return tuple(out_i[n] for n in NL_OUT), (0,) * len(NL_OUT)
+
+
+def _saturation_tl_stacked(ap, t, pert, ext, geo):
+    """`saturation_tl` per direction (pointwise and cheap: it loops) -> the qsat perturbations as one batch"""
+    nx, nlev, ls = geo
+    ref = _plain(ap)
+    ndir = next(iter(pert.values())).shape[0]
+    lay = lambda n, d: _in_layout(pert[n][d], ref, geo) if n in pert else None  # noqa: E731
+    qsat_i = zeros_batched(ndir, nx, nlev - 1, ref.dtype, ref.device, ls)
+    for d in range(ndir):
+        qsat_i[d].copy_(saturation_tl(ap, t, lay("ap", d), lay("t", d), ext)[1])
+    return qsat_i
+
+
+class _TLStep(_InnerFunction):
+    """(call, 15 state fields, qsat, present tangents) -> the ten perturbed outputs of the step"""
+    @staticmethod
+    def forward(call, *tensors):
+        nst = len(STEP_IN)
+        state, qsat = dict(zip(STEP_IN, tensors[:nst])), tensors[nst]
+        ref = _plain(tensors[0])
+        pert = {n: _in_layout(t, ref, call.geo) for n, t in zip(call.have, tensors[nst + 1:])}
+        if call.ext.get("LPHYLIN"):
+            _, out_i = tl_step(state, pert, call.eta, call.dt, call.ext, want=NL_OUT, write_nl=False)
+        else:
+            if "ap" in pert or "t" in pert:
+                pert["qsat"] = saturation_tl(state["ap"], state["t"], pert.get("ap"), pert.get("t"), call.ext)[1]
+            _, out_i = tl_masked(dict(state, qsat=qsat), pert, call.eta, call.dt, call.ext, want=NL_OUT, write_nl=False)
+        return tuple(out_i[n] for n in NL_OUT)
+
+    @staticmethod
+    def vmap(info, in_dims, call, *tensors):
+        nst = len(STEP_IN)
+        _unbatched_state(in_dims, nst + 1)
+        state, qsat = dict(zip(STEP_IN, tensors[:nst])), tensors[nst]
+        pert = dict(zip(call.have, _stacked(info, in_dims, tensors, nst + 1)))
+        if call.ext.get("LPHYLIN"):
+            _, out_i = tl_step_multi(state, pert, call.eta, call.dt, call.ext, want=NL_OUT, write_nl=False)
+        else:
+            if "ap" in pert or "t" in pert:
+                sat = {n: pert[n] for n in ("ap", "t") if n in pert}
+                pert["qsat"] = _saturation_tl_stacked(state["ap"], state["t"], sat, call.ext, call.geo)
+            _, out_i = tl_multi(dict(state, qsat=qsat), pert, call.eta, call.dt, call.ext, want=NL_OUT, write_nl=False)
+        return tuple(out_i[n] for n in NL_OUT), (0,) * len(NL_OUT)
+
+
+class _SaturationTL(_InnerFunction):
+    """(call, ap, t, present tangents of ap / t) -> qsat_i"""
+    @staticmethod
+    def forward(call, ap, t, *tangents):
+        ref = _plain(ap)
+        pert = {n: _in_layout(g, ref, call.geo) for n, g in zip(call.have, tangents)}
+        return saturation_tl(ap, t, pert.get("ap"), pert.get("t"), call.ext)[1]
+
+    @staticmethod
+    def vmap(info, in_dims, call, ap, t, *tangents):
+        _unbatched_state(in_dims, 2)
+        pert = dict(zip(call.have, _stacked(info, in_dims, (ap, t) + tangents, 2)))
+        return _saturation_tl_stacked(ap, t, pert, call.ext, call.geo), 0
+
+
+def _ad_masked_or_dense(call, state, forcing, traj, want):
+    ext = dict(call.ext, AD_TRAJ_FIX=1)
+    if _evap(ext):
+        return _dense_ad(state, forcing, call.eta, call.dt, ext, call.geo, want)
+    return ad_masked(state, forcing, call.eta, call.dt, ext, traj=traj, want=want)
+
+
+def _looped_adjoint(one, info, in_dims, call, tensors, nfixed, nout):
+    """the `vmap` rule of the adjoint launches: one single launch per cotangent, results stacked (no multi-direction
+    adjoint kernel); `one(call, *tensors)` is the Function's own `forward`"""
+    _unbatched_state(in_dims, nfixed)
+    cot = _stacked(info, in_dims, tensors, nfixed)
+    rows = [one(call, *tensors[:nfixed], *(g[b] for g in cot)) for b in range(info.batch_size)]
+    return tuple(torch.stack([r[i] for r in rows]) for i in range(nout)), (0,) * nout
+
+
+class _ADMasked(_InnerFunction):
+    """(call, 16 state fields, traj fplsl, traj fplsn, present cotangents) -> the adjoints of `call.want`"""
+    @staticmethod
+    def forward(call, *tensors):
+        nst = len(NL_IN)
+        state = dict(zip(NL_IN, tensors[:nst]))
+        ref = _plain(tensors[0])
+        forcing = {n: _in_layout(g, ref, call.geo) for n, g in zip(call.have, tensors[nst + 2:])}
+        adj = _ad_masked_or_dense(call, state, forcing, {"fplsl": tensors[nst], "fplsn": tensors[nst + 1]}, call.want)
+        return tuple(adj[n] for n in call.want)
+
+    @staticmethod
+    def vmap(info, in_dims, call, *tensors):
+        return _looped_adjoint(_ADMasked.forward, info, in_dims, call, tensors, len(NL_IN) + 2, len(call.want))
+
+
+class _ADStep(_InnerFunction):
+    """(call, 15 state fields, qsat, traj fplsl, traj fplsn, present cotangents) -> the adjoints of `call.want`"""
+    @staticmethod
+    def forward(call, *tensors):
+        nst = len(STEP_IN)
+        state, qsat = dict(zip(STEP_IN, tensors[:nst])), tensors[nst]
+        traj = {"fplsl": tensors[nst + 1], "fplsn": tensors[nst + 2]}
+        ref = _plain(tensors[0])
+        forcing = {n: _in_layout(g, ref, call.geo) for n, g in zip(call.have, tensors[nst + 3:])}
+        want = call.want
+        ext = dict(call.ext, AD_TRAJ_FIX=1)
+        if ext.get("LPHYLIN") and not _evap(ext):
+            adj = ad_step(state, forcing, call.eta, call.dt, ext, traj=traj, want=want)
+        else:
+            through = tuple(n for n in ("ap", "t") if n in want)       # the adjoints the path through qsat arrives in
+            adj = _ad_masked_or_dense(call, dict(state, qsat=qsat), forcing, traj, want + (("qsat",) if through else ()))
+            if through:
+                saturation_ad(state["ap"], state["t"], adj["qsat"], ext, want=through, into={n: adj[n] for n in through})
+        return tuple(adj[n] for n in want)
+
+    @staticmethod
+    def vmap(info, in_dims, call, *tensors):
+        return _looped_adjoint(_ADStep.forward, info, in_dims, call, tensors, len(STEP_IN) + 3, len(call.want))
+
+
+class _SaturationAD(_InnerFunction):
+    """(call, ap, t, the cotangent of qsat) -> the adjoints of `call.want` (of ap, t)"""
+    @staticmethod
+    def forward(call, ap, t, grad):
+        adj = saturation_ad(ap, t, _in_layout(grad, _plain(ap), call.geo), call.ext, want=call.want)
+        return tuple(adj[n] for n in call.want)
+
+    @staticmethod
+    def vmap(info, in_dims, call, ap, t, grad):
+        return _looped_adjoint(_SaturationAD.forward, info, in_dims, call, (ap, t, grad), 2, len(call.want))
+
+
+def _ext_of(externals) -> Dict[str, Any]:
+    return dict(default_externals() if externals is None else externals)
+
+
+def _refuse_batched_state(info, in_dims, *args):
+    raise NotImplementedError(_BATCHED_STATE)
+
+
 class _Cloudsc2(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, eta, dt, externals, *inputs):
+    def forward(eta, dt, externals, *inputs):
         from .stencils import compile_stencil
 
-        ctx.set_materialize_grads(False)
         state = {n: _plain(f) for n, f in zip(NL_IN, inputs)}
         (nx, nlev, ls), dtype, device = _checked("cloudsc2", ((state, NL_IN, True),))
         nz = nlev - 1
         ref = state[NL_IN[0]]
         out = {n: _new_like(ref, nx, nz, ls) for n in NL_OUT}
-        ext = dict(default_externals() if externals is None else externals)
-        compile_stencil("cloudsc2_nl", ext)(**{"in_" + n: f for n, f in state.items()}, **{"out_" + n: f for n, f in out.items()},
-                                             in_eta=eta, dt=dt, origin=(0, 0, 0), domain=(nx, 1, nlev), validate_args=False,
-                                             exec_info=None)
-        ctx.eta, ctx.dt, ctx.ext, ctx.geo = eta, float(dt), ext, (nx, nlev, ls)
-        ctx.save_for_backward(*inputs, out["fplsl"], out["fplsn"])
-        ctx.save_for_forward(*inputs)
+        compile_stencil("cloudsc2_nl", _ext_of(externals))(
+            **{"in_" + n: f for n, f in state.items()}, **{"out_" + n: f for n, f in out.items()}, in_eta=eta, dt=dt,
+            origin=(0, 0, 0), domain=(nx, 1, nlev), validate_args=False, exec_info=None)
         return tuple(out[n] for n in NL_OUT)
+
+    @staticmethod
+    def setup_context(ctx, inputs, outputs):
+        eta, dt, externals, *fields = inputs
+        ctx.set_materialize_grads(False)
+        ctx.call = _Launch(eta, float(dt), _ext_of(externals), field_geometry(fields[0]), ())
+        ctx.save_for_backward(*fields, outputs[NL_OUT.index("fplsl")], outputs[NL_OUT.index("fplsn")])
+        ctx.save_for_forward(*fields)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -221,27 +520,23 @@ class _Cloudsc2(torch.autograd.Function):
         none = (None,) * (3 + len(NL_IN))
         if all(g is None for g in grads) or not any(need):
             return none
-        saved = ctx.saved_tensors
-        state = dict(zip(NL_IN, saved[:len(NL_IN)]))
-        ref = _plain(saved[0])
-        forcing = {n: _in_layout(g, ref, ctx.geo) for n, g in zip(NL_OUT, grads) if g is not None}
+        have = tuple(n for n, g in zip(NL_OUT, grads) if g is not None)
         want = tuple(n for n, w in zip(NL_IN, need) if w)
-        ext = dict(ctx.ext, AD_TRAJ_FIX=1)
-        if ext.get("LEVAPLS2") or ext.get("LDRAIN1D"):
-            adj = _dense_ad(state, forcing, ctx.eta, ctx.dt, ext, ctx.geo, want)
-        else:
-            adj = ad_masked(state, forcing, ctx.eta, ctx.dt, ext, traj={"fplsl": saved[-2], "fplsn": saved[-1]}, want=want)
+        adj = dict(zip(want, _ADMasked.apply(ctx.call._replace(have=have, want=want), *(f.detach() for f in ctx.saved_tensors),
+                                             *(g for g in grads if g is not None))))
         return (None, None, None) + tuple(adj.get(n) for n in NL_IN)
 
     @staticmethod
     def jvp(ctx, _eta_t, _dt_t, _ext_t, *tangents):
-        state = dict(zip(NL_IN, ctx.saved_tensors))      # in jvp: what save_for_forward kept
-        ref = _plain(state[NL_IN[0]])
-        pert = {n: _in_layout(t, ref, ctx.geo) for n, t in zip(NL_IN, tangents) if t is not None}
-        if not pert:
+        have = tuple(n for n, t in zip(NL_IN, tangents) if t is not None)
+        if not have:
             return (None,) * len(NL_OUT)
-        _, out_i = tl_masked(state, pert, ctx.eta, ctx.dt, ctx.ext, want=NL_OUT, write_nl=False)
-        return tuple(out_i[n] for n in NL_OUT)
+        # in jvp, ctx.saved_tensors is what save_for_forward kept
+        with torch.no_grad():
+            return _TLMasked.apply(ctx.call._replace(have=have), *(f.detach() for f in ctx.saved_tensors),
+                                   *(t for t in tangents if t is not None))
+
+    vmap = staticmethod(_refuse_batched_state)
 
 
 def _dense_ad(state, forcing, eta, dt, ext, geo, want):
@@ -355,14 +650,18 @@ def _run_saturation(ap, t, ext, geo):
 
 class _Saturation(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, externals, ap, t):
-        ctx.set_materialize_grads(False)
+    def forward(externals, ap, t):
         fields = {"ap": _plain(ap), "t": _plain(t)}
-        ctx.geo, _, _ = _checked("saturation", ((fields, ("ap", "t"), True),))
-        ctx.ext = dict(default_externals() if externals is None else externals)
+        geo, _, _ = _checked("saturation", ((fields, ("ap", "t"), True),))
+        return _run_saturation(fields["ap"], fields["t"], _ext_of(externals), geo)
+
+    @staticmethod
+    def setup_context(ctx, inputs, output):
+        externals, ap, t = inputs
+        ctx.set_materialize_grads(False)
+        ctx.call = _Launch(None, 0.0, _ext_of(externals), field_geometry(ap), ())
         ctx.save_for_backward(ap, t)
         ctx.save_for_forward(ap, t)
-        return _run_saturation(fields["ap"], fields["t"], ctx.ext, ctx.geo)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -371,17 +670,20 @@ class _Saturation(torch.autograd.Function):
         if grad is None or not want:
             return None, None, None
         ap, t = ctx.saved_tensors
-        adj = saturation_ad(ap, t, _in_layout(grad, _plain(ap), ctx.geo), ctx.ext, want=want)
+        adj = dict(zip(want, _SaturationAD.apply(ctx.call._replace(want=want), ap.detach(), t.detach(), grad)))
         return None, adj.get("ap"), adj.get("t")
 
     @staticmethod
     def jvp(ctx, _ext_t, ap_i, t_i):
-        if ap_i is None and t_i is None:
+        have = tuple(n for n, g in (("ap", ap_i), ("t", t_i)) if g is not None)
+        if not have:
             return None
         ap, t = ctx.saved_tensors
-        ref = _plain(ap)
-        lay = lambda g: None if g is None else _in_layout(g, ref, ctx.geo)  # noqa: E731
-        return saturation_tl(ap, t, lay(ap_i), lay(t_i), ctx.ext)[1]
+        with torch.no_grad():
+            return _SaturationTL.apply(ctx.call._replace(have=have), ap.detach(), t.detach(),
+                                       *(g for g in (ap_i, t_i) if g is not None))
+
+    vmap = staticmethod(_refuse_batched_state)
 
 
 def saturation(ap: torch.Tensor, t: torch.Tensor, externals: Optional[Mapping[str, Any]] = None) -> torch.Tensor:
@@ -401,16 +703,15 @@ def _evap(ext) -> bool:
 
 class _Cloudsc2Step(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, eta, dt, externals, *inputs):
+    def forward(eta, dt, externals, *inputs):
         from .stencils import compile_stencil
 
-        ctx.set_materialize_grads(False)
         state = {n: _plain(f) for n, f in zip(STEP_IN, inputs)}
         (nx, nlev, ls), dtype, device = _checked("cloudsc2_step", ((state, STEP_IN, True),))
         nz = nlev - 1
         ref = state[STEP_IN[0]]
         out = {n: _new_like(ref, nx, nz, ls) for n in NL_OUT}
-        ext = dict(default_externals() if externals is None else externals)
+        ext = _ext_of(externals)
         call = dict(in_eta=eta, dt=dt, origin=(0, 0, 0), domain=(nx, 1, nlev), validate_args=False, exec_info=None)
         ins, outs = {"in_" + n: f for n, f in state.items()}, {"out_" + n: f for n, f in out.items()}
         if ext.get("LPHYLIN"):
@@ -419,11 +720,17 @@ class _Cloudsc2Step(torch.autograd.Function):
         else:
             qsat = _run_saturation(state["ap"], state["t"], ext, (nx, nlev, ls))
             compile_stencil("cloudsc2_nl", ext)(**ins, in_qsat=qsat, **outs, **call)
-        ctx.eta, ctx.dt, ctx.ext, ctx.geo = eta, float(dt), ext, (nx, nlev, ls)
-        ctx.save_for_backward(*inputs, qsat, out["fplsl"], out["fplsn"])
-        ctx.save_for_forward(*inputs, qsat)
-        ctx.mark_non_differentiable(qsat)
         return tuple(out[n] for n in NL_OUT) + (qsat,)
+
+    @staticmethod
+    def setup_context(ctx, inputs, outputs):
+        eta, dt, externals, *fields = inputs
+        qsat = outputs[-1]
+        ctx.set_materialize_grads(False)
+        ctx.call = _Launch(eta, float(dt), _ext_of(externals), field_geometry(fields[0]), ())
+        ctx.save_for_backward(*fields, qsat, outputs[NL_OUT.index("fplsl")], outputs[NL_OUT.index("fplsn")])
+        ctx.save_for_forward(*fields, qsat)
+        ctx.mark_non_differentiable(qsat)
 
     @staticmethod
     @torch.autograd.function.once_differentiable
@@ -433,42 +740,24 @@ class _Cloudsc2Step(torch.autograd.Function):
         none = (None,) * (3 + len(STEP_IN))
         if all(g is None for g in grads) or not any(need):
             return none
-        saved = ctx.saved_tensors
-        state = dict(zip(STEP_IN, saved[:len(STEP_IN)]))
-        qsat, traj = saved[-3], {"fplsl": saved[-2], "fplsn": saved[-1]}
-        ref = _plain(saved[0])
-        forcing = {n: _in_layout(g, ref, ctx.geo) for n, g in zip(NL_OUT, grads) if g is not None}
+        have = tuple(n for n, g in zip(NL_OUT, grads) if g is not None)
         want = tuple(n for n, w in zip(STEP_IN, need) if w)
-        ext = dict(ctx.ext, AD_TRAJ_FIX=1)
-        if ext.get("LPHYLIN") and not _evap(ext):
-            adj = ad_step(state, forcing, ctx.eta, ctx.dt, ext, traj=traj, want=want)
-        else:
-            through = tuple(n for n in ("ap", "t") if n in want)       # the adjoints the path through qsat arrives in
-            full = dict(state, qsat=qsat)
-            want16 = want + (("qsat",) if through else ())
-            if _evap(ext):
-                adj = _dense_ad(full, forcing, ctx.eta, ctx.dt, ext, ctx.geo, want16)
-            else:
-                adj = ad_masked(full, forcing, ctx.eta, ctx.dt, ext, traj=traj, want=want16)
-            if through:
-                saturation_ad(state["ap"], state["t"], adj["qsat"], ext, want=through, into={n: adj[n] for n in through})
+        adj = dict(zip(want, _ADStep.apply(ctx.call._replace(have=have, want=want), *(f.detach() for f in ctx.saved_tensors),
+                                           *(g for g in grads if g is not None))))
         return (None, None, None) + tuple(adj.get(n) for n in STEP_IN)
 
     @staticmethod
     def jvp(ctx, _eta_t, _dt_t, _ext_t, *tangents):
-        saved = ctx.saved_tensors                        # in jvp: what save_for_forward kept
-        state, qsat = dict(zip(STEP_IN, saved[:len(STEP_IN)])), saved[-1]
-        ref = _plain(saved[0])
-        pert = {n: _in_layout(t, ref, ctx.geo) for n, t in zip(STEP_IN, tangents) if t is not None}
-        if not pert:
+        have = tuple(n for n, t in zip(STEP_IN, tangents) if t is not None)
+        if not have:
             return (None,) * (len(NL_OUT) + 1)
-        if ctx.ext.get("LPHYLIN"):
-            _, out_i = tl_step(state, pert, ctx.eta, ctx.dt, ctx.ext, want=NL_OUT, write_nl=False)
-        else:
-            if "ap" in pert or "t" in pert:
-                pert["qsat"] = saturation_tl(state["ap"], state["t"], pert.get("ap"), pert.get("t"), ctx.ext)[1]
-            _, out_i = tl_masked(dict(state, qsat=qsat), pert, ctx.eta, ctx.dt, ctx.ext, want=NL_OUT, write_nl=False)
-        return tuple(out_i[n] for n in NL_OUT) + (None,)
+        # in jvp, ctx.saved_tensors is what save_for_forward kept: the 15 fields and qsat
+        with torch.no_grad():
+            out_i = _TLStep.apply(ctx.call._replace(have=have), *(f.detach() for f in ctx.saved_tensors),
+                                  *(t for t in tangents if t is not None))
+        return tuple(out_i) + (None,)
+
+    vmap = staticmethod(_refuse_batched_state)
 
 
 def cloudsc2_step(state: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,

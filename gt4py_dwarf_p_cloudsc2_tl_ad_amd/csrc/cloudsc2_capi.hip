@@ -29,6 +29,9 @@ template <typename T>
 int launch_tl_masked(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T* const*, const T*, const T*,
                      T* const*, T* const*, double, hipStream_t, bool step);
 template <typename T>
+int launch_tl_dirs(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T* const*, const T*, const T*, T* const*,
+                   T* const*, double, hipStream_t, bool step, int ndir, int64_t in_ds, int64_t out_ds);
+template <typename T>
 int launch_ad_masked(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T* const*, const T*, const T*,
                      const T*, const T*, T* const*, double, hipStream_t, bool step);
 template <typename T>
@@ -294,12 +297,26 @@ int check_step_saturation(const char* fn, const Cloudsc2Params* p) {
                 "cloudsc2_saturation_tl / _ad with the masked entries for the other forms)", fn);
 }
 
-// `step`: the cloudsc2_tl_step_* entry (tl_step_kernel)
+// the direction arguments of the cloudsc2_tl_multi_* entries
+int check_dirs(const char* fn, int32_t nz, int64_t ls, int32_t ndir, int64_t in_ds, int64_t out_ds) {
+    if (ndir < 1 || ndir > CLOUDSC2_TL_MAX_DIRS)
+        return fail(CLOUDSC2_E_ARG, "%s: ndir=%d outside [1, %d] (CLOUDSC2_TL_MAX_DIRS)", fn, ndir, CLOUDSC2_TL_MAX_DIRS);
+    const int64_t field = int64_t(nz + 1) * ls;
+    if (in_ds < field || out_ds < field)
+        return fail(CLOUDSC2_E_ARG, "%s: in_dir_stride=%lld / out_dir_stride=%lld < (nz+1) * lev_stride = %lld: the "
+                    "directions of a field would overlap", fn, (long long)in_ds, (long long)out_ds, (long long)field);
+    return 0;
+}
+
+// `step`: the cloudsc2_tl_step_* entry (tl_step_kernel); `ndir` > 0: the cloudsc2_tl_multi_* entries (tl_dirs_kernel)
 template <typename T>
 int tl_masked_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,
                    const T* const* in_i, const T* zero_line, const T* eta, T* const* out, T* const* out_i, double dt,
-                   void* stream, bool step = false) {
+                   void* stream, bool step = false, bool multi = false, int32_t ndir = 0, int64_t in_ds = 0,
+                   int64_t out_ds = 0) {
     if (int rc = check_common(fn, p, nx, nz, ls)) return rc;
+    if (multi)
+        if (int rc = check_dirs(fn, nz, ls, ndir, in_ds, out_ds)) return rc;
     if (nx == 0) return CLOUDSC2_OK;
     if (int rc = step ? check_step_trajectory(fn, in) : check_ptrs(fn, "in", in, NL_NUM_IN)) return rc;
     if (step && in_i && in_i[NL_IN_QSAT])
@@ -324,6 +341,9 @@ int tl_masked_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t 
     if (step)
         if (int rc = check_step_saturation(fn, p)) return rc;
     if (int rc = check_masked_size<T>(fn, nz, ls)) return rc;
+    if (multi)
+        return launched(fn, cs2::launch_tl_dirs<T>(*p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt,
+                                                   static_cast<hipStream_t>(stream), step, ndir, in_ds, out_ds));
     return launched(fn, cs2::launch_tl_masked<T>(*p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt,
                                                  static_cast<hipStream_t>(stream), step));
 }
@@ -623,6 +643,30 @@ int32_t cloudsc2_perturbed_state_f32(const Cloudsc2Params* p, int32_t nx, int32_
                                      const float* const* in, const float* const* in_i, float* const* out,
                                      double f, void* stream) {
     return per_impl<float>("cloudsc2_perturbed_state_f32", p, nx, nz, ls, in, in_i, out, f, stream);
+}
+int32_t cloudsc2_tl_multi_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const double* const* in,
+                              const double* const* in_i, const double* zero_line, const double* eta, double* const* out,
+                              double* const* out_i, double dt, void* stream, int32_t ndir, int64_t in_ds, int64_t out_ds) {
+    return tl_masked_impl<double>("cloudsc2_tl_multi_f64", p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt, stream, false, true,
+                            ndir, in_ds, out_ds);
+}
+int32_t cloudsc2_tl_multi_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const float* const* in,
+                              const float* const* in_i, const float* zero_line, const float* eta, float* const* out,
+                              float* const* out_i, double dt, void* stream, int32_t ndir, int64_t in_ds, int64_t out_ds) {
+    return tl_masked_impl<float>("cloudsc2_tl_multi_f32", p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt, stream, false, true,
+                           ndir, in_ds, out_ds);
+}
+int32_t cloudsc2_tl_multi_step_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const double* const* in,
+                                   const double* const* in_i, const double* zero_line, const double* eta, double* const* out,
+                                   double* const* out_i, double dt, void* stream, int32_t ndir, int64_t in_ds, int64_t out_ds) {
+    return tl_masked_impl<double>("cloudsc2_tl_multi_step_f64", p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt, stream, true, true,
+                            ndir, in_ds, out_ds);
+}
+int32_t cloudsc2_tl_multi_step_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const float* const* in,
+                                   const float* const* in_i, const float* zero_line, const float* eta, float* const* out,
+                                   float* const* out_i, double dt, void* stream, int32_t ndir, int64_t in_ds, int64_t out_ds) {
+    return tl_masked_impl<float>("cloudsc2_tl_multi_step_f32", p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt, stream, true, true,
+                           ndir, in_ds, out_ds);
 }
 
 }  // extern "C"

@@ -1069,4 +1069,203 @@ template int launch_tl_masked<double>(const Cloudsc2Params&, int, int, int64_t, 
 template int launch_tl_masked<float>(const Cloudsc2Params&, int, int, int64_t, const float* const*, const float* const*,
                                      const float*, const float*, float* const*, float* const*, double, hipStream_t, bool);
 
+// ------------------------------------------------------------------------------------------------------------------
+// Masked tangent-linear over `ndir` DIRECTIONS on one trajectory (BUILD EXTENSION, C ABI cloudsc2_tl_multi_* /
+// cloudsc2_tl_multi_step_*): a Jacobian block, an ensemble of perturbations pushed through one linearisation.  Direction d
+// of a present perturbation lies d * in_ds elements behind direction 0, direction d of a wanted output d * out_ds elements.
+// Per column the pre-scan, the level table and the first `aph` words are formed once; per level the 16 (STEP: 15) state
+// words are loaded once (next level prefetched, as in tl_masked_sweep), saturation_point_d runs once, the NL outputs are
+// stored once.  Inside the level a RUNTIME loop over the directions loads one direction's perturbation words ahead (the
+// next direction of this level, or direction 0 of the next level), calls the unchanged tl_level and stores under `want`.
+//   * tl_level advances the whole carry.  Its nonlinear half is the same for every direction: it is snapshot in front of the
+//     direction loop and every direction starts from the snapshot, so it advances exactly once per level.
+//   * the `_i` half of the carry (five words per direction) lives in LDS slots [word][d][threadIdx.x] that no other lane
+//     touches: no barrier.  kTLMaxDirs * 5 * 256 words = 80 KB in fp64 (one workgroup per CU at these kernels' one wave per
+//     SIMD), 40 KB in fp32; the launcher sizes the slots by the call's ndir and opts in beyond 64 KB.
+//   * the direction base is wave-uniform: it is added to the field pointer as a 64-bit scalar (an absent field keeps the
+//     zero line's pointer), the per-lane offsets stay 32-bit.  Every load is issued; at the last direction of the last level
+//     the look-ahead re-reads direction 0 of that level.
+constexpr int kTLMaxDirs = CLOUDSC2_TL_MAX_DIRS;
+constexpr int kTLCarryWords = 5;   // rfl_i, sfl_i, covptot_i, aph_k_i, aph_s_i
+template <typename T>
+struct TLDirsArgs {
+    TLMaskedArgs<T> m;             // at kernarg offset 0: TLMaskedFields reads the pointers from there
+    int64_t in_ds, out_ds;         // direction strides, in elements
+    int ndir;
+};
+// TLMaskedFields with the output perturbations moved to one direction (what tl_store_masked is handed)
+template <typename T>
+struct TLDirFields {
+    const TLMaskedFields<T>& F;
+    int64_t ob;
+    __device__ __forceinline__ T* out(int i) const { return F.out(i); }
+    __device__ __forceinline__ T* out_i(int i) const { return F.out_i(i) + ob; }
+};
+
+template <typename T>
+inline size_t tl_dirs_lds_bytes(int nz, int ndir) {
+    return (2 * size_t(nz + 1) + size_t(kTLCarryWords) * ndir * kColBlock) * sizeof(T);
+}
+
+template <typename T, bool REG, bool EVAP, bool STEP>
+__device__ __forceinline__ void tl_dirs_sweep(const TLDirsArgs<T>& A) {
+    Ext<T> e = A.m.e;
+    NLK<T> kc = A.m.kc;
+    ExpK<T> xk = A.m.xk;
+    const int nx = A.m.nx, nz = A.m.nz, ndir = A.ndir;
+    const int64_t ls = A.m.ls, in_ds = A.in_ds, out_ds = A.out_ds;
+    const T* __restrict__ eta = A.m.eta;
+    T dt = A.m.dt;
+    const uint32_t have = A.m.have, want = A.m.want;
+    TLMaskedFields<T> F;
+    const auto F_in = [&](int i) { return F.in(i); };
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    T* s_eta = reinterpret_cast<T*>(smem_raw);
+    T* s_scalm = s_eta + (nz + 1);
+    T* s_carry = s_scalm + (nz + 1) + threadIdx.x;   // word w of direction d: s_carry[(w * ndir + d) * kColBlock]
+    int klo, khi;
+    build_level_table<T>(eta, nz, e, s_eta, s_scalm, klo, khi);
+    if constexpr (sizeof(T) == 8) pin_tl_constants(e, kc, xk, dt);
+
+    const int gcol = xcd_block() * kColBlock + threadIdx.x;
+    if (gcol >= nx) return;   // see tl_kernel
+    using O = uint32_t;
+    const O lsb = O(ls) * O(sizeof(T));
+    const O colb = O(gcol) * O(sizeof(T));
+    const O zo = O(threadIdx.x & (kWave - 1)) * O(sizeof(T));   // this lane's word of the zero line
+    const auto at_aph = [&](O x) { return (have >> NL_IN_APH & 1u) ? x : zo; };
+    const auto slot = [&](int w, int d) -> T& { return s_carry[(w * ndir + d) * kColBlock]; };
+
+    const T trpaus = trpaus_prescan<T, false, O>(F.in(NL_IN_T), F.in(NL_IN_TND_CML_T), lsb, colb, dt, s_eta, klo, khi);
+    const CrhCol<T> crh = crh_setup<T>(trpaus);
+
+    // :124-135, :757-765
+    TLCarry<T> c;
+    c.rfl = c.sfl = c.covptot = T(0.0);
+    c.aph_k = ldg(F.in(NL_IN_APH), colb);
+    c.aph_s = EVAP ? ldg(F.in(NL_IN_APH), O(nz) * lsb + colb) : T(1.0);
+    if (want & kTLWantNL) {
+        stg(F.out(NL_OUT_FPLSL), colb, T(0.0));
+        stg(F.out(NL_OUT_FPLSN), colb, T(0.0));
+        stg(F.out(NL_OUT_FHPSL), colb, T(0.0));
+        stg(F.out(NL_OUT_FHPSN), colb, T(0.0));
+    }
+    for (int d = 0; d < ndir; ++d) {
+        const T* aph_i = F.in_i(NL_IN_APH) + ((have >> NL_IN_APH & 1u) ? d * in_ds : int64_t(0));
+        slot(0, d) = T(0.0);
+        slot(1, d) = T(0.0);
+        slot(2, d) = T(0.0);
+        slot(3, d) = ldg(aph_i, at_aph(colb));
+        slot(4, d) = EVAP ? ldg(aph_i, at_aph(O(nz) * lsb + colb)) : T(0.0);
+        const int64_t ob = d * out_ds;
+        if (want >> NL_OUT_FPLSL & 1u) stg(F.out_i(NL_OUT_FPLSL) + ob, colb, T(0.0));
+        if (want >> NL_OUT_FPLSN & 1u) stg(F.out_i(NL_OUT_FPLSN) + ob, colb, T(0.0));
+        if (want >> NL_OUT_FHPSL & 1u) stg(F.out_i(NL_OUT_FHPSL) + ob, colb, T(0.0));
+        if (want >> NL_OUT_FHPSN & 1u) stg(F.out_i(NL_OUT_FHPSN) + ob, colb, T(0.0));
+    }
+
+    // perturbation words of direction d at byte offset o
+    const auto load_dir = [&](int d, O o) {
+        const int64_t ib = d * in_ds;
+        const auto ptr = [&](int f) { return F.in_i(f) + ((have >> f & 1u) ? ib : int64_t(0)); };
+        return load_level_masked<T, STEP>(ptr, have, lsb, o, zo);
+    };
+    O o = colb;
+    LevelIn<T> xa = load_level<T, O>(F_in, lsb, o, STEP), ya = load_dir(0, o);
+    for (int k = 0; k < nz; ++k) {
+        const bool more = k + 1 < nz;
+        LevelIn<T> xn = xa;
+        if (more) xn = load_level<T, O>(F_in, lsb, o + lsb, STEP);
+        T g_t = T(0.0), g_ap = T(0.0);
+        if constexpr (STEP) {
+            const SatD<T> s = saturation_point_d<T, 0>(e, xk, xa.t, xa.ap);
+            xa.qsat = s.qsat;
+            g_t = s.g_t;
+            g_ap = s.g_ap;
+        }
+        const T rfl0 = c.rfl, sfl0 = c.sfl, covptot0 = c.covptot, aph_k0 = c.aph_k;
+        for (int d = 0; d < ndir; ++d) {
+            F.fresh();
+            const bool last = d + 1 == ndir;
+            const LevelIn<T> yn = load_dir(last ? 0 : d + 1, last && more ? o + lsb : o);
+            if constexpr (STEP) ya.qsat = g_t * ya.t + g_ap * ya.ap;
+            c.rfl = rfl0; c.sfl = sfl0; c.covptot = covptot0; c.aph_k = aph_k0;
+            c.rfl_i = slot(0, d); c.sfl_i = slot(1, d); c.covptot_i = slot(2, d); c.aph_k_i = slot(3, d); c.aph_s_i = slot(4, d);
+            const TLOut<T> r = tl_level<T, REG, EVAP>(e, kc, xk, xa, ya, k, s_eta[k], s_scalm[k], crh, dt, c);
+            slot(0, d) = c.rfl_i; slot(1, d) = c.sfl_i; slot(2, d) = c.covptot_i; slot(3, d) = c.aph_k_i;
+            const TLDirFields<T> Fd{F, d * out_ds};
+            tl_store_masked<T>(Fd, d == 0 ? want : want & ~kTLWantNL, e, lsb, o, r);
+            drain_vmem();   // see drain_vmem
+            ya = yn;
+        }
+        xa = xn;
+        o += lsb;
+    }
+}
+
+template <typename T, bool REG, bool EVAP>
+__global__ void __launch_bounds__(kColBlock)
+tl_dirs_kernel(const TLDirsArgs<T> A) {
+    tl_dirs_sweep<T, REG, EVAP, false>(A);
+}
+
+template <typename T, bool REG, bool EVAP>
+__global__ void __launch_bounds__(kColBlock)
+tl_dirs_step_kernel(const TLDirsArgs<T> A) {
+    tl_dirs_sweep<T, REG, EVAP, true>(A);
+}
+
+// launch_tl_masked for `ndir` directions (1 <= ndir <= kTLMaxDirs, checked by the caller): in_i[f] / out_i[f] point at
+// direction 0; the strides are in elements
+template <typename T>
+int launch_tl_dirs(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* const* in, const T* const* in_i,
+                   const T* zero, const T* eta, T* const* out, T* const* out_i, double dt, hipStream_t stream, bool step,
+                   int ndir, int64_t in_ds, int64_t out_ds) {
+    if (!fits_u32_offsets<T>(nz, ls)) return -2;
+    const bool evap = p.LEVAPLS2 || p.LDRAIN1D;
+    TLDirsArgs<T> args;
+    args.m.e = make_ext<T>(p);
+    args.m.kc = make_nlk<T>(p, dt, evap);
+    args.m.xk = make_expk<T>();
+    args.m.nx = nx; args.m.nz = nz; args.m.ls = ls;
+    args.m.have = 0;
+    args.m.want = out ? kTLWantNL : 0u;
+    for (int i = 0; i < NL_NUM_IN; ++i) {
+        args.m.in.p[i] = in[i];
+        args.m.in_i.p[i] = in_i[i] ? in_i[i] : zero;
+        if (in_i[i]) args.m.have |= 1u << i;
+    }
+    for (int i = 0; i < NL_NUM_OUT; ++i) {
+        args.m.out.p[i] = out ? out[i] : nullptr;
+        args.m.out_i.p[i] = out_i[i];
+        if (out_i[i]) args.m.want |= 1u << i;
+    }
+    args.m.eta = eta;
+    args.m.dt = static_cast<T>(dt);
+    args.in_ds = in_ds; args.out_ds = out_ds; args.ndir = ndir;
+    const dim3 grid((nx + kColBlock - 1) / kColBlock), block(kColBlock);
+    const size_t smem = tl_dirs_lds_bytes<T>(nz, ndir);
+    if (smem > size_t(160) * 1024) return -2;
+    int dev = 0;
+    if (const int rc = current_device(dev)) return rc;
+    const int rc = with_flags(
+        [&](auto REG, auto EVAP, auto STEP) {
+            constexpr auto kern = STEP ? tl_dirs_step_kernel<T, REG, EVAP> : tl_dirs_kernel<T, REG, EVAP>;
+            if (smem > size_t(64) * 1024 && !lds_opt_in<kern>(dev, smem)) return -1;
+            hipLaunchKernelGGL(kern, grid, block, smem, stream, args);
+            return 0;
+        },
+        p.LREGCL != 0, evap, step);
+    if (rc) return rc;
+    note_kernel(step ? "cs2::tl_dirs_step_kernel" : "cs2::tl_dirs_kernel");
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+template int launch_tl_dirs<double>(const Cloudsc2Params&, int, int, int64_t, const double* const*, const double* const*,
+                                    const double*, const double*, double* const*, double* const*, double, hipStream_t, bool,
+                                    int, int64_t, int64_t);
+template int launch_tl_dirs<float>(const Cloudsc2Params&, int, int, int64_t, const float* const*, const float* const*,
+                                   const float*, const float*, float* const*, float* const*, double, hipStream_t, bool, int,
+                                   int64_t, int64_t);
+
 }  // namespace cs2

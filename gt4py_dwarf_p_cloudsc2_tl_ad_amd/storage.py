@@ -382,6 +382,30 @@ def zeros(nx: int, nz: int, dtype: Any, device: Any) -> torch.Tensor:
     return logical_view(torch.zeros((nz + 1, nx), dtype=dt, device=dev))
 
 
+def zeros_batched(ndir: int, nx: int, nz: int, dtype: Any, device: Any, lev_stride: Optional[int] = None) -> torch.Tensor:
+    """`ndir` zero-initialised fields in ONE allocation, as the view (ndir, nx, 1, nz+1): entry d is a field of the
+    geometry `zeros` gives (level pitch `level_pitch(nx, dtype)`, or `lev_stride` to match windows of wider allocations),
+    direction d + 1 starts `direction_stride` elements behind direction d.  What the multi-direction tangent-linear
+    (`autodiff.tl_multi`) reads its perturbations from and writes its results to."""
+    dt, dev = torch_dtype(dtype), torch.device(device)
+    ls = level_pitch(nx, dt) if lev_stride is None else int(lev_stride)
+    if ndir < 1 or ls < nx:
+        raise ValueError(f"zeros_batched: ndir={ndir} < 1 or lev_stride={ls} < nx={nx}")
+    return torch.zeros((int(ndir), nz + 1, ls), dtype=dt, device=dev)[:, :, :nx].unsqueeze(2).permute(0, 3, 2, 1)
+
+
+def direction_stride(batched: torch.Tensor) -> int:
+    """elements from one direction to the next of a (ndir, nx, 1, nz+1) batch of column-fastest fields that share one
+    geometry (`zeros_batched`); raises `ValueError` for anything else, overlapping directions included"""
+    if batched.dim() != 4 or batched.shape[0] < 1:
+        raise ValueError(f"expected a (ndir, nx, 1, nz+1) batch of fields, got shape {tuple(batched.shape)}")
+    nx, nlev, ls = field_geometry(batched[0])
+    stride = batched.stride(0) if batched.shape[0] > 1 else nlev * ls
+    if stride < nlev * ls:
+        raise ValueError(f"directions overlap: stride {stride} < nlev * lev_stride = {nlev * ls}")
+    return stride
+
+
 def zeros_k(nz: int, dtype: Any, device: Any) -> torch.Tensor:
     """Zero-initialised K-vector with nz+1 entries."""
     return torch.zeros((nz + 1,), dtype=torch_dtype(dtype), device=device)

@@ -362,6 +362,39 @@ int32_t cloudsc2_ad_step_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, in
                              const float* eta, const float* traj_fplsl, const float* traj_fplsn,
                              float* const* out_adj, double dt, void* stream);
 
+/* ---- cloudsc2_tl_masked / cloudsc2_tl_step for SEVERAL DIRECTIONS on one trajectory (BUILD EXTENSIONS): a Jacobian block,
+ * an ensemble of perturbations pushed through one linearisation.  Arguments are those of cloudsc2_tl_masked_* (multi) and
+ * of cloudsc2_tl_step_* (multi_step), and so are their rules (NULL entries, zero line, LPHYLIN for the step, fields below
+ * 4 GiB PER DIRECTION), plus:
+ *   ndir            number of directions, 1 .. CLOUDSC2_TL_MAX_DIRS (CLOUDSC2_E_ARG otherwise);
+ *   in_dir_stride   in ELEMENTS: in_i[f] points at direction 0 of a batched field, direction d of every present
+ *                   perturbation starts d * in_dir_stride elements later;
+ *   out_dir_stride  in ELEMENTS: the same for every wanted out_i[f].
+ * Both strides must be at least (nz+1) * lev_stride (CLOUDSC2_E_ARG): the directions of a field do not overlap.  A field is
+ * present or absent for all directions alike.  `out` (the NL outputs) is not batched: it is written once.
+ * One launch reads the trajectory once: the kernel keeps the five perturbation words of each direction's carried state in
+ * LDS (5 * ndir * 256 elements per workgroup beside the level table) and loops over the directions inside each level.  Every
+ * direction of every written field equals what the single-direction entry writes for that direction alone.
+ * cloudsc2_last_kernel() reports "cs2::tl_dirs_kernel" / "cs2::tl_dirs_step_kernel".
+ * Words moved per level and column: 16 (step: 15) + ndir * ((present in_i) + (present out_i)) + (10 if out). */
+#define CLOUDSC2_TL_MAX_DIRS 8
+int32_t cloudsc2_tl_multi_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                              const double* const* in, const double* const* in_i, const double* zero_line,
+                              const double* eta, double* const* out, double* const* out_i, double dt, void* stream,
+                              int32_t ndir, int64_t in_dir_stride, int64_t out_dir_stride);
+int32_t cloudsc2_tl_multi_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                              const float* const* in, const float* const* in_i, const float* zero_line,
+                              const float* eta, float* const* out, float* const* out_i, double dt, void* stream,
+                              int32_t ndir, int64_t in_dir_stride, int64_t out_dir_stride);
+int32_t cloudsc2_tl_multi_step_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                   const double* const* in, const double* const* in_i, const double* zero_line,
+                                   const double* eta, double* const* out, double* const* out_i, double dt, void* stream,
+                                   int32_t ndir, int64_t in_dir_stride, int64_t out_dir_stride);
+int32_t cloudsc2_tl_multi_step_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                   const float* const* in, const float* const* in_i, const float* zero_line,
+                                   const float* eta, float* const* out, float* const* out_i, double dt, void* stream,
+                                   int32_t ndir, int64_t in_dir_stride, int64_t out_dir_stride);
+
 #ifdef __cplusplus
 }
 #endif
