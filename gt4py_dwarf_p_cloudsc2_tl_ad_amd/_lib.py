@@ -103,12 +103,15 @@ LAYOUTS: Dict[str, Layout] = {
                                                   _STREAM)),
 }
 
-#: the multi-direction TL entries (autodiff.tl_multi / tl_step_multi call them directly, like the masked entries they
-#: extend): name -> the single-direction entry whose argument list they repeat, followed by `ndir`, `in_dir_stride` and
-#: `out_dir_stride` (elements)
-MULTI_LAYOUTS: Dict[str, str] = {"tl_multi": "tl_masked", "tl_multi_step": "tl_step"}
+#: the multi-direction TL / AD entries (autodiff.tl_multi / tl_step_multi / ad_multi / ad_step_multi call them directly, like
+#: the masked entries they extend): name -> the single-direction entry whose argument list they repeat, followed by `ndir`,
+#: `in_dir_stride` and `out_dir_stride` (elements)
+MULTI_LAYOUTS: Dict[str, str] = {"tl_multi": "tl_masked", "tl_multi_step": "tl_step",
+                                 "ad_multi": "ad_masked", "ad_multi_step": "ad_step"}
 #: CLOUDSC2_TL_MAX_DIRS of include/cloudsc2_hip.h
 TL_MAX_DIRS = 8
+#: CLOUDSC2_AD_MAX_DIRS of include/cloudsc2_hip.h
+AD_MAX_DIRS = 8
 
 _PARR = POINTER(c_void_p)      # device pointers travel as integers (void*), never dereferenced on the host
 _CTYPES = {"ptrs": (_PARR,), "field": (c_void_p,), "eta": (c_void_p,), "scalar": (c_double,), "partials": (c_void_p,),

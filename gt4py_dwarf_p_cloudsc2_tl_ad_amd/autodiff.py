@@ -15,11 +15,15 @@ on their own (a variational cost, a sensitivity study).  GPU tensors only - ther
 
 MANY derivatives on one trajectory.  `tl_multi` / `tl_step_multi` push `ndir` perturbations through one linearisation (C ABI
 `cloudsc2_tl_multi_*` / `cloudsc2_tl_multi_step_*`: one launch reads the state once for up to `width` directions; the default
-width per precision, `MULTI_WIDTH`, is 1 - single launches - until the kernel's gain has been measured).
+width per precision, `MULTI_WIDTH`, is 1 - single launches; docs/TUNING_LOG.md 3.18 has the measurement).  `ad_multi` /
+`ad_step_multi` pull `ndir` cotangents back through it (C ABI `cloudsc2_ad_multi_*` / `cloudsc2_ad_multi_step_*`: one
+launch reads the state and recomputes each level's nonlinear trajectory once for up to `width` cotangents; the default
+width per precision is `AD_MULTI_WIDTH`, set from the measurement of docs/TUNING_LOG.md 3.19).
 `cloudsc2`, `cloudsc2_step` and `saturation` work under `torch.func`: `jvp`, `vjp`, `grad`, `jacfwd`, `jacrev`, and `vmap`
 over TANGENTS or COTANGENTS (`vmap` of `jvp`, which is what `jacfwd` is; `vmap` of a `vjp` function, which is what `jacrev`
-is).  Batched tangents run `tl_multi` / `tl_step_multi`; batched cotangents loop over single adjoint launches (there is no
-multi-direction adjoint kernel).  Not supported: `vmap` over the STATE (`NotImplementedError`),
+is).  Batched tangents run `tl_multi` / `tl_step_multi`; batched cotangents run `ad_multi` / `ad_step_multi` (the
+evaporation switches and the non-LPHYLIN step, which have no multi-direction kernel, loop over their single-cotangent
+fallbacks, and so does `saturation`, which is pointwise).  Not supported: `vmap` over the STATE (`NotImplementedError`),
 `torch.autograd.grad(..., is_grads_batched=True)` (the legacy vmap, which knows no `vmap` rule of a Function), second
 derivatives."""
 from __future__ import annotations
@@ -38,9 +42,18 @@ _SFX = {torch.float64: "f64", torch.float32: "f32"}
 #: the inputs of the step: those of `cloudsc2_nl` without `qsat`, which the step forms from `ap` and `t`
 STEP_IN = tuple(n for n in NL_IN if n != "qsat")
 #: directions per launch of the multi-direction TL, per precision: the measured width with the best time per direction.
-#: 1 = that precision loops over single `tl_masked` / `tl_step` launches.  The measurement (profiles/bench_tl_multi.py) has
-#: not been taken on an MI355X yet, so no width is enabled (docs/TUNING_LOG.md 3.18); `width=` of `tl_multi` reaches the kernel.
+#: 1 = that precision loops over single `tl_masked` / `tl_step` launches.  The measurement (profiles/bench_tl_multi.py,
+#: docs/TUNING_LOG.md 3.18) has been taken; no width has been enabled from it yet; `width=` of `tl_multi` reaches the kernel.
 MULTI_WIDTH: Dict[torch.dtype, int] = {torch.float64: 1, torch.float32: 1}
+#: cotangents per launch of the multi-direction AD, per precision, by the rule of docs/TUNING_LOG.md 3.19: the measured
+#: width with the best median time per direction, if that beats the looped single launches by more than the looped case's
+#: own min-max spread in the same run; otherwise 1 = that precision loops over single `ad_masked` / `ad_step` launches.
+#: `width=` of `ad_multi` / `ad_step_multi` reaches the kernel in any case.  Measured on an MI355X (profiles/bench_ad_multi.py,
+#: 4D-Var mask of the step family, microseconds per direction, looped singles -> one launch; looped min-max spread):
+#:   fp64  65 536 columns   D=2 547 -> 458   D=4 538 -> 350   D=8 528 -> 301   (8 launches 4 221 us +- 76, one 2 406 us)
+#:   fp32 524 288 columns   D=2 1 896 -> 1 889   D=4 1 865 -> 1 441   D=8 1 823 -> 2 086   (4 launches 7 458 us +- 273, one 5 765 us)
+#: fp32 loses at 8: its 83 KB of LDS leave one workgroup per CU where 4 directions (59 KB) leave two.
+AD_MULTI_WIDTH: Dict[torch.dtype, int] = {torch.float64: 8, torch.float32: 4}
 _ZERO_LINE_BYTES = 512
 _zero_lines: Dict[Tuple[torch.device, torch.dtype], torch.Tensor] = {}
 
@@ -258,7 +271,9 @@ def ad_step(state: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tenso
     return _ad_call("ad_step", STEP_IN, state, forcing, eta, dt, externals, traj, want)
 
 
-def _ad_call(what, in_names, state, forcing, eta, dt, externals, traj, want):
+def _ad_call(what, in_names, state, forcing, eta, dt, externals, traj, want, into=None):
+    """`into`: the adjoints are written to these fields of the call's geometry (`ad_multi`: one direction of its batched
+    results) and not to new ones"""
     want = tuple(want)
     if not want or set(want) - set(in_names):
         raise ValueError(f"{what}: `want` must name at least one of {in_names}, got {want}")
@@ -270,7 +285,7 @@ def _ad_call(what, in_names, state, forcing, eta, dt, externals, traj, want):
     nz = nlev - 1
     eta = _eta(what, eta, nz, dtype, device)
     ref = state[NL_IN[0]]
-    out_adj = {n: _new_like(ref, nx, nz, ls) for n in want}
+    out_adj = {n: _new_like(ref, nx, nz, ls) for n in want} if into is None else into
     p = _params(externals, nz)
     with torch.cuda.device(device):
         rc = getattr(_lib.load(), f"cloudsc2_{what}_{_SFX[dtype]}")(
@@ -278,6 +293,76 @@ def _ad_call(what, in_names, state, forcing, eta, dt, externals, traj, want):
             eta.data_ptr(), traj["fplsl"].data_ptr(), traj["fplsn"].data_ptr(), _ptrs(out_adj, NL_IN), float(dt),
             int(torch.cuda.current_stream(device).cuda_stream))
     _lib.check(rc, what)
+    return out_adj
+
+
+def ad_multi(state: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+             externals: Optional[Mapping[str, Any]] = None, *, traj: Mapping[str, torch.Tensor], want: Iterable[str],
+             width: Optional[int] = None):
+    """`ad_masked` for `ndir` cotangents of one state: `forcing` maps `NL_OUT` names to `(ndir, nx, 1, nz+1)` tensors (a
+    missing name is zero forcing in every direction); `traj` is not batched.  Returns `{name: (ndir, nx, 1, nz+1)}`, one
+    `storage.zeros_batched` allocation per wanted name.
+
+    Directions are served in chunks of at most `width` (default `AD_MULTI_WIDTH` of the dtype) per `cloudsc2_ad_multi_*`
+    launch, which reads the state and recomputes the nonlinear trajectory once per chunk; a chunk of one direction is a
+    plain `ad_masked` launch.  Any `ndir >= 1` works.  A forcing that is not laid out as `storage.zeros_batched` gives is
+    copied into such a field first.  LEVAPLS2 / LDRAIN1D are refused (`ValueError`)."""
+    return _ad_multi_call("ad_multi", "ad_masked", NL_IN, state, forcing, eta, dt, externals, traj, want, width)
+
+
+def ad_step_multi(state: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+                  externals: Optional[Mapping[str, Any]] = None, *, traj: Mapping[str, torch.Tensor], want: Iterable[str],
+                  width: Optional[int] = None):
+    """`ad_step` for `ndir` cotangents of one state (`cloudsc2_ad_multi_step_*`; `STEP_IN` names): see `ad_multi`.
+    `saturation` and its derivative are evaluated once per level for all directions of a chunk.  LPHYLIN only, and no
+    LEVAPLS2 / LDRAIN1D."""
+    return _ad_multi_call("ad_multi_step", "ad_step", STEP_IN, state, forcing, eta, dt, externals, traj, want, width)
+
+
+def _ad_multi_call(what, single, in_names, state, forcing, eta, dt, externals, traj, want, width):
+    want = tuple(want)
+    if not want or set(want) - set(in_names):
+        raise ValueError(f"{what}: `want` must name at least one of {in_names}, got {want}")
+    state = {n: _plain(f) for n, f in state.items()}
+    traj = {n: _plain(f) for n, f in traj.items()}
+    geo, dtype, device = _checked(what, ((state, in_names, True), (traj, ("fplsl", "fplsn"), True)))
+    nx, nlev, ls = geo
+    unknown = sorted(set(forcing) - set(NL_OUT))
+    if unknown:
+        raise ValueError(f"{what}: unknown field names {unknown}")
+    if not forcing:
+        raise ValueError(f"{what}: no forcing given")
+    shapes = {tuple(f.shape) for f in forcing.values() if isinstance(f, torch.Tensor)}
+    if len(shapes) != 1 or len(next(iter(shapes))) != 4 or next(iter(shapes))[1:] != (nx, 1, nlev) or next(iter(shapes))[0] < 1:
+        raise ValueError(f"{what}: every forcing must be a tensor of one shape (ndir, {nx}, 1, {nlev}), got "
+                         f"{ {n: tuple(getattr(f, 'shape', ())) for n, f in forcing.items()} }")
+    ndir = next(iter(shapes))[0]
+    for n, f in forcing.items():
+        if not f.is_cuda:
+            raise ValueError(f"{what}: {n} lives on {f.device}; fields must live on the GPU (there is no host path)")
+    nz = nlev - 1
+    eta = _eta(what, eta, nz, dtype, device)
+    ref = state[NL_IN[0]]
+    width = AD_MULTI_WIDTH[dtype] if width is None else int(width)
+    if not 1 <= width <= _lib.AD_MAX_DIRS:
+        raise ValueError(f"{what}: width={width} outside [1, {_lib.AD_MAX_DIRS}]")
+    forc = {n: _batched_layout(f, ref, geo) for n, f in forcing.items()}
+    out_adj = {n: zeros_batched(ndir, nx, nz, dtype, device, ls) for n in want}
+    dstride = nlev * ls
+    p = _params(externals, nz)
+    for d0 in range(0, ndir, width):
+        n = min(width, ndir - d0)
+        if n == 1:
+            _ad_call(single, in_names, state, {k: f[d0] for k, f in forc.items()}, eta, dt, externals, traj, want,
+                     into={k: f[d0] for k, f in out_adj.items()})
+        else:
+            with torch.cuda.device(device):
+                rc = getattr(_lib.load(), f"cloudsc2_{what}_{_SFX[dtype]}")(
+                    ctypes.byref(p), nx, nz, ls, _ptrs(state, NL_IN), _ptrs({k: f[d0] for k, f in forc.items()}, NL_OUT),
+                    _zero_line(device, dtype).data_ptr(), eta.data_ptr(), traj["fplsl"].data_ptr(), traj["fplsn"].data_ptr(),
+                    _ptrs({k: f[d0] for k, f in out_adj.items()}, NL_IN), float(dt),
+                    int(torch.cuda.current_stream(device).cuda_stream), n, dstride, dstride)
+            _lib.check(rc, what)
     return out_adj
 
 
@@ -421,8 +506,9 @@ def _ad_masked_or_dense(call, state, forcing, traj, want):
 
 
 def _looped_adjoint(one, info, in_dims, call, tensors, nfixed, nout):
-    """the `vmap` rule of the adjoint launches: one single launch per cotangent, results stacked (no multi-direction
-    adjoint kernel); `one(call, *tensors)` is the Function's own `forward`"""
+    """the `vmap` rule of the adjoint launches that have no multi-direction kernel (the evaporation switches, the
+    non-LPHYLIN step, `saturation`): one single launch per cotangent, results stacked; `one(call, *tensors)` is the
+    Function's own `forward`"""
     _unbatched_state(in_dims, nfixed)
     cot = _stacked(info, in_dims, tensors, nfixed)
     rows = [one(call, *tensors[:nfixed], *(g[b] for g in cot)) for b in range(info.batch_size)]
@@ -442,7 +528,15 @@ class _ADMasked(_InnerFunction):
 
     @staticmethod
     def vmap(info, in_dims, call, *tensors):
-        return _looped_adjoint(_ADMasked.forward, info, in_dims, call, tensors, len(NL_IN) + 2, len(call.want))
+        nst = len(NL_IN)
+        ext = dict(call.ext, AD_TRAJ_FIX=1)
+        if _evap(ext):
+            return _looped_adjoint(_ADMasked.forward, info, in_dims, call, tensors, nst + 2, len(call.want))
+        _unbatched_state(in_dims, nst + 2)
+        forcing = dict(zip(call.have, _stacked(info, in_dims, tensors, nst + 2)))
+        adj = ad_multi(dict(zip(NL_IN, tensors[:nst])), forcing, call.eta, call.dt, ext,
+                       traj={"fplsl": tensors[nst], "fplsn": tensors[nst + 1]}, want=call.want)
+        return tuple(adj[n] for n in call.want), (0,) * len(call.want)
 
 
 class _ADStep(_InnerFunction):
@@ -467,7 +561,15 @@ class _ADStep(_InnerFunction):
 
     @staticmethod
     def vmap(info, in_dims, call, *tensors):
-        return _looped_adjoint(_ADStep.forward, info, in_dims, call, tensors, len(STEP_IN) + 3, len(call.want))
+        nst = len(STEP_IN)
+        ext = dict(call.ext, AD_TRAJ_FIX=1)
+        if not ext.get("LPHYLIN") or _evap(ext):
+            return _looped_adjoint(_ADStep.forward, info, in_dims, call, tensors, nst + 3, len(call.want))
+        _unbatched_state(in_dims, nst + 3)
+        forcing = dict(zip(call.have, _stacked(info, in_dims, tensors, nst + 3)))
+        adj = ad_step_multi(dict(zip(STEP_IN, tensors[:nst])), forcing, call.eta, call.dt, ext,
+                            traj={"fplsl": tensors[nst + 1], "fplsn": tensors[nst + 2]}, want=call.want)
+        return tuple(adj[n] for n in call.want), (0,) * len(call.want)
 
 
 class _SaturationAD(_InnerFunction):

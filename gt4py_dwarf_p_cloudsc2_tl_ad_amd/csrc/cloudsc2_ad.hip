@@ -1351,4 +1351,230 @@ template int launch_ad_masked<float>(const Cloudsc2Params&, int, int, int64_t, c
                                      const float*, const float*, const float*, const float*, float* const*, double,
                                      hipStream_t, bool);
 
+// ------------------------------------------------------------------------------------------------------------------
+// Masked adjoint over `ndir` DIRECTIONS on one trajectory (BUILD EXTENSION, C ABI cloudsc2_ad_multi_* /
+// cloudsc2_ad_multi_step_*): a block of rows of the Jacobian (`jacrev`), several cost functionals on one trajectory.
+// Direction d of a present forcing lies d * in_ds elements behind direction 0, direction d of a wanted adjoint d * out_ds
+// elements.  A sibling of ad_masked_sweep (same ad_forward / ad_backward, same parking, same zero line).  Only ad_backward
+// depends on the cotangent, so
+//   * per column the level table, the pre-scan and crh_setup are formed once; per level the 16 (STEP: 15) state words, `aph`
+//     and the two trajectory flux words are loaded once (next level prefetched), ad_forward - the nonlinear recomputation
+//     with all its exponentials - runs once, and with STEP saturation_point_d runs once (its value is saturation_point's
+//     bit for bit, see there);
+//   * inside the level a RUNTIME loop over the directions loads one direction's nine forcing words ahead (the next
+//     direction of this level, or direction 0 of the level above), calls the unchanged ad_backward on the level's ADTraj
+//     and stores under `want`.  ad_backward writes nothing into the ADTraj but what ad_unpark reloads from LDS (fp32) - the
+//     very words ad_park stored once in front of the direction loop - so every direction sees the single launch's words;
+//   * the backward carry (ADBack without the evaporation members: six words per direction) lives in LDS slots
+//     [word][d][threadIdx.x] that no other lane touches: no barrier.  The launcher sizes the slots by the call's ndir;
+//   * the direction base is wave-uniform: it is added to the field pointer as a 64-bit scalar (an absent forcing keeps the
+//     zero line's pointer), the per-lane offsets stay 32-bit.  Every load is issued; at the last direction of level 0 the
+//     look-ahead re-reads direction 0 of that level;
+//   * STORES: ad_masked_sweep holds a level's eleven results one iteration late; eleven per direction do not fit 256 VGPRs
+//     beside an ADTraj that has to survive the direction loop.  A direction's results are stored in plain order, behind
+//     its ad_backward, followed by drain_vmem (as tl_dirs_sweep): with the store count unknown hipcc's next wait would
+//     cover them anyway, and the explicit drain sits behind a whole ad_backward, where the look-ahead words (issued in
+//     front of it) have arrived.
+constexpr int kADMaxDirs = CLOUDSC2_AD_MAX_DIRS;
+constexpr int kADCarryWords = 6;   // tmp_rfln_i, tmp_sfln_i, rfl_i, sfl_i, daph_i, dp_i
+template <typename T>
+struct ADDirsArgs {
+    ADMaskedArgs<T> m;             // at kernarg offset 0: ADMaskedFields reads the pointers from there
+    int64_t in_ds, out_ds;         // direction strides, in elements
+    int ndir;
+};
+// ADMaskedFields moved to one direction (what ad_load_force_masked / ad_store_masked are handed)
+template <typename T>
+struct ADDirFields {
+    const ADMaskedFields<T>& F;
+    uint32_t have;
+    int64_t ib, ob;
+    __device__ __forceinline__ const T* adj(int i) const { return F.adj(i) + ((have >> i & 1u) ? ib : int64_t(0)); }
+    __device__ __forceinline__ T* oadj(int i) const { return F.oadj(i) + ob; }
+};
+
+template <typename T>
+inline size_t ad_dirs_lds_bytes(int nz, int ndir) {
+    return (2 * size_t(nz + 1) + (kADPark<T> ? size_t(CS2_AD_PARK_COUNT) * kColBlock : 0) +
+            size_t(kADCarryWords) * ndir * kColBlock) * sizeof(T);
+}
+
+template <typename T, bool REG, bool FIX, bool STEP>
+__device__ __forceinline__ void ad_dirs_sweep(const ADDirsArgs<T>& A) {
+    Ext<T> e = A.m.e;
+    NLK<T> kc = A.m.kc;
+    ExpK<T> xk = A.m.xk;
+    const int nx = A.m.nx, nz = A.m.nz, ndir = A.ndir;
+    const int64_t ls = A.m.ls, in_ds = A.in_ds, out_ds = A.out_ds;
+    const T* __restrict__ eta = A.m.eta;
+    T dt = A.m.dt;
+    const uint32_t have = A.m.have, want = A.m.want;
+    ADMaskedFields<T> F;
+    const auto F_in = [&](int i) { return F.in(i); };
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    T* s_eta = reinterpret_cast<T*>(smem_raw);
+    T* s_scalm = s_eta + (nz + 1);
+    int klo, khi;
+    build_level_table<T>(eta, nz, e, s_eta, s_scalm, klo, khi);
+    if constexpr (sizeof(T) == 8) {
+        pin_vgprs(e.RCPD, e.RLSTT, e.RLVTT, e.R4LES, e.R4IES, e.RTT, e.R3IES, e.R3LES, e.R2ES, e.ZQMAX, e.RETV, e.R5LES,
+                  e.R5IES, e.RG, e.RD, kc.rdt, kc.cons2, kc.rRD, kc.rRCPD, dt);
+        pin_expk(xk);
+    }
+
+    const int gcol = xcd_block() * kColBlock + threadIdx.x;
+    T* const park_lds = s_scalm + (nz + 1) + threadIdx.x;
+    // word w of direction d: s_carry[(w * ndir + d) * kColBlock], behind the parking slots
+    T* const s_carry = park_lds + (kADPark<T> ? CS2_AD_PARK_COUNT * kColBlock : 0);
+    if (gcol >= nx) return;  // no later workgroup barrier: whole lanes may retire
+    using O = uint32_t;
+    const O lsb = O(ls) * O(sizeof(T));
+    const O colb = O(gcol) * O(sizeof(T));
+    const O zo = O(threadIdx.x & (kWave - 1)) * O(sizeof(T));   // this lane's word of the zero line
+    const auto slot = [&](int w, int d) -> T& { return s_carry[(w * ndir + d) * kColBlock]; };
+
+    const T trpaus = trpaus_prescan<T, false, O>(F.in(NL_IN_T), F.in(NL_IN_TND_CML_T), lsb, colb, dt, s_eta, klo, khi);
+    const CrhCol<T> crh = crh_setup<T>(trpaus);
+
+    for (int d = 0; d < ndir; ++d)
+        for (int w = 0; w < kADCarryWords; ++w) slot(w, d) = T(0.0);
+
+    // forcing words of direction d for the level at byte offset o
+    const auto load_dir = [&](int d, O o) {
+        const ADDirFields<T> Fd{F, have, d * in_ds, int64_t(0)};
+        return ad_load_force_masked<T>(Fd, have, lsb, o, zo);
+    };
+    // ONE loop, k = nz .. 0, and no batch of loads outside it (see ad_masked_sweep: hipcc lays a prologue out around the loop
+    // as it pleases, and check_ring_isa.check_prefetch_distance reads every backward branch as a loop): iteration k requests
+    // level k-1's state words and computes level k; the first iteration only requests - its direction loop runs the last
+    // direction's look-ahead alone, which is direction 0 of level nz-1.
+    O o = O(nz) * lsb + colb;
+    LevelIn<T> xa;
+    xa.ap = xa.aph1 = xa.lu1 = xa.lude = xa.mfd = xa.mfu = xa.q = xa.qi = xa.ql = xa.qsat = xa.supsat = xa.t = xa.tq = xa.tqi =
+        xa.tql = xa.tt = T(0.0);
+    ADForce<T> fa;
+    fa.clc = fa.tnd_q = fa.tnd_qi = fa.tnd_ql = fa.tnd_t = fa.fplsl1 = fa.fplsn1 = fa.fhpsl1 = fa.fhpsn1 = fa.covptot = T(0.0);
+    T aph_k = ldg(F.in(NL_IN_APH), o), sfl = T(0.0), rfl = T(0.0);   // aph[nz]: level nz-1's lower half level
+    for (int k = nz; k >= 0; --k) {
+        const bool more = k > 0, live = k < nz;
+        LevelIn<T> xn = xa;
+        T aph_n = aph_k, sfl_n = sfl, rfl_n = rfl;
+        if (more) {
+            const O om = o - lsb;
+            xn = load_level<T>(F_in, lsb, om, STEP);
+            xn.aph1 = aph_k;   // aph[k]: already here as this level's upper half level
+            aph_n = ldg(F.in(NL_IN_APH), om);
+            sfl_n = ldg(F.traj_n(), om);
+            rfl_n = ldg(F.traj_l(), om);
+        }
+        T g_t = T(0.0), g_ap = T(0.0);
+        ADTraj<T> r;
+        if (live) {
+            if constexpr (STEP) {
+                const SatD<T> s = saturation_point_d<T, 0>(e, xk, xa.t, xa.ap);
+                xa.qsat = s.qsat;
+                g_t = s.g_t;
+                g_ap = s.g_ap;
+            }
+            ad_forward<T, FIX, false>(e, kc, xk, xa, aph_k, k, s_eta[k], s_scalm[k], crh, dt, rfl, sfl, T(0.0), T(1.0), r);
+            if constexpr (kADPark<T>) ad_park<T>(park_lds, r);
+        }
+        for (int d = live ? 0 : ndir - 1; d < ndir; ++d) {
+            F.fresh();
+            const bool last = d + 1 == ndir;
+            const ADForce<T> fn = load_dir(last ? 0 : d + 1, last && more ? o - lsb : o);
+            if (live) {
+                ADBack<T> b;
+                b.tmp_rfln_i = slot(0, d); b.tmp_sfln_i = slot(1, d); b.rfl_i = slot(2, d); b.sfl_i = slot(3, d);
+                b.daph_i = slot(4, d); b.dp_i = slot(5, d);
+                b.covptot_i = b.aph_s_i = T(0.0);
+                b.aph_s = T(1.0);
+                const ADOut<T> a = ad_backward<T, REG, FIX, false>(e, kc, xa, k, s_scalm[k], dt, sfl, r, fa, b, park_lds);
+                slot(0, d) = b.tmp_rfln_i; slot(1, d) = b.tmp_sfln_i; slot(2, d) = b.rfl_i; slot(3, d) = b.sfl_i;
+                slot(4, d) = b.daph_i; slot(5, d) = b.dp_i;
+                const ADDirFields<T> Fd{F, have, int64_t(0), d * out_ds};
+                ad_store_masked<T, STEP>(Fd, want, lsb, o, dt, a, g_ap * a.qsat, g_t * a.qsat);
+                drain_vmem();   // see drain_vmem
+            }
+            fa = fn;
+        }
+        xa = xn;
+        aph_k = aph_n;
+        sfl = sfl_n;
+        rfl = rfl_n;
+        o -= lsb;
+    }
+    // :982-986 top half level, per direction
+    for (int d = 0; d < ndir; ++d) {
+        const int64_t ob = d * out_ds;
+        if (want >> NL_IN_APH & 1u) stg(F.oadj(NL_IN_APH) + ob, colb, slot(4, d) - slot(5, d));
+        if (want >> NL_IN_LU & 1u) stg(F.oadj(NL_IN_LU) + ob, colb, T(0.0));
+    }
+}
+
+template <typename T, bool REG, bool FIX>
+__global__ void __launch_bounds__(kColBlock)
+ad_dirs_kernel(const ADDirsArgs<T> A) {
+    ad_dirs_sweep<T, REG, FIX, false>(A);
+}
+
+template <typename T, bool REG, bool FIX>
+__global__ void __launch_bounds__(kColBlock)
+ad_dirs_step_kernel(const ADDirsArgs<T> A) {
+    ad_dirs_sweep<T, REG, FIX, true>(A);
+}
+
+// launch_ad_masked for `ndir` directions (1 <= ndir <= kADMaxDirs, checked by the caller): in_adj[f] / out_adj[f] point at
+// direction 0; the strides are in elements
+template <typename T>
+int launch_ad_dirs(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* const* in, const T* const* in_adj,
+                   const T* zero, const T* eta, const T* traj_l, const T* traj_n, T* const* out_adj, double dt,
+                   hipStream_t stream, bool step, int ndir, int64_t in_ds, int64_t out_ds) {
+    if (p.LEVAPLS2 || p.LDRAIN1D || !fits_u32_offsets<T>(nz, ls)) return -2;
+    if (ndir < 1 || ndir > kADMaxDirs) return -1;
+    ADDirsArgs<T> args;
+    args.m.e = make_ext<T>(p);
+    args.m.kc = make_nlk<T>(p, dt, false);
+    args.m.xk = make_expk<T>();
+    args.m.nx = nx; args.m.nz = nz; args.m.ls = ls;
+    args.m.have = args.m.want = 0;
+    for (int i = 0; i < NL_NUM_IN; ++i) {
+        args.m.in.p[i] = in[i];
+        args.m.oadj.p[i] = out_adj[i];
+        if (out_adj[i]) args.m.want |= 1u << i;
+    }
+    for (int i = 0; i < NL_NUM_OUT; ++i) {
+        args.m.adj.p[i] = in_adj[i] ? in_adj[i] : zero;
+        if (in_adj[i]) args.m.have |= 1u << i;
+    }
+    args.m.eta = eta;
+    args.m.dt = static_cast<T>(dt);
+    args.m.traj_l = traj_l;
+    args.m.traj_n = traj_n;
+    args.in_ds = in_ds; args.out_ds = out_ds; args.ndir = ndir;
+    const dim3 grid((nx + kColBlock - 1) / kColBlock), block(kColBlock);
+    const size_t smem = ad_dirs_lds_bytes<T>(nz, ndir);
+    if (smem > size_t(160) * 1024) return -2;
+    int dev = 0;
+    if (const int rc = current_device(dev)) return rc;
+    const int rc = with_flags(
+        [&](auto REG, auto FIX, auto STEP) {
+            constexpr auto kern = STEP ? ad_dirs_step_kernel<T, REG, FIX> : ad_dirs_kernel<T, REG, FIX>;
+            if (smem > size_t(64) * 1024 && !lds_opt_in<kern>(dev, smem)) return -1;
+            hipLaunchKernelGGL(kern, grid, block, smem, stream, args);
+            return 0;
+        },
+        p.LREGCL != 0, p.AD_TRAJ_FIX != 0, step);
+    if (rc) return rc;
+    note_kernel(step ? "cs2::ad_dirs_step_kernel" : "cs2::ad_dirs_kernel");
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+template int launch_ad_dirs<double>(const Cloudsc2Params&, int, int, int64_t, const double* const*, const double* const*,
+                                    const double*, const double*, const double*, const double*, double* const*, double,
+                                    hipStream_t, bool, int, int64_t, int64_t);
+template int launch_ad_dirs<float>(const Cloudsc2Params&, int, int, int64_t, const float* const*, const float* const*,
+                                   const float*, const float*, const float*, const float*, float* const*, double,
+                                   hipStream_t, bool, int, int64_t, int64_t);
+
 }  // namespace cs2

@@ -35,6 +35,9 @@ template <typename T>
 int launch_ad_masked(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T* const*, const T*, const T*,
                      const T*, const T*, T* const*, double, hipStream_t, bool step);
 template <typename T>
+int launch_ad_dirs(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T* const*, const T*, const T*, const T*,
+                   const T*, T* const*, double, hipStream_t, bool step, int ndir, int64_t in_ds, int64_t out_ds);
+template <typename T>
 int launch_saturation(const Cloudsc2Params&, int, int, int64_t, const T*, const T*, T*, hipStream_t);
 template <typename T>
 int launch_saturation_tl(const Cloudsc2Params&, int, int, int64_t, const T*, const T*, const T*, const T*, T*, T*,
@@ -297,10 +300,11 @@ int check_step_saturation(const char* fn, const Cloudsc2Params* p) {
                 "cloudsc2_saturation_tl / _ad with the masked entries for the other forms)", fn);
 }
 
-// the direction arguments of the cloudsc2_tl_multi_* entries
-int check_dirs(const char* fn, int32_t nz, int64_t ls, int32_t ndir, int64_t in_ds, int64_t out_ds) {
-    if (ndir < 1 || ndir > CLOUDSC2_TL_MAX_DIRS)
-        return fail(CLOUDSC2_E_ARG, "%s: ndir=%d outside [1, %d] (CLOUDSC2_TL_MAX_DIRS)", fn, ndir, CLOUDSC2_TL_MAX_DIRS);
+// the direction arguments of the cloudsc2_tl_multi_* / cloudsc2_ad_multi_* entries
+int check_dirs(const char* fn, int32_t nz, int64_t ls, int32_t ndir, int64_t in_ds, int64_t out_ds,
+               int max_dirs = CLOUDSC2_TL_MAX_DIRS, const char* max_name = "CLOUDSC2_TL_MAX_DIRS") {
+    if (ndir < 1 || ndir > max_dirs)
+        return fail(CLOUDSC2_E_ARG, "%s: ndir=%d outside [1, %d] (%s)", fn, ndir, max_dirs, max_name);
     const int64_t field = int64_t(nz + 1) * ls;
     if (in_ds < field || out_ds < field)
         return fail(CLOUDSC2_E_ARG, "%s: in_dir_stride=%lld / out_dir_stride=%lld < (nz+1) * lev_stride = %lld: the "
@@ -348,11 +352,15 @@ int tl_masked_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t 
                                                  static_cast<hipStream_t>(stream), step));
 }
 
+// `step`: the cloudsc2_ad_step_* entry (ad_step_kernel); `multi`: the cloudsc2_ad_multi_* entries (ad_dirs_kernel)
 template <typename T>
 int ad_masked_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,
                    const T* const* in_adj, const T* zero_line, const T* eta, const T* traj_fplsl, const T* traj_fplsn,
-                   T* const* out_adj, double dt, void* stream, bool step = false) {
+                   T* const* out_adj, double dt, void* stream, bool step = false, bool multi = false, int32_t ndir = 0,
+                   int64_t in_ds = 0, int64_t out_ds = 0) {
     if (int rc = check_common(fn, p, nx, nz, ls)) return rc;
+    if (multi)
+        if (int rc = check_dirs(fn, nz, ls, ndir, in_ds, out_ds, CLOUDSC2_AD_MAX_DIRS, "CLOUDSC2_AD_MAX_DIRS")) return rc;
     if (nx == 0) return CLOUDSC2_OK;
     if (int rc = step ? check_step_trajectory(fn, in) : check_ptrs(fn, "in", in, NL_NUM_IN)) return rc;
     if (int rc = check_masked_inputs(fn, "in_adj", in_adj, NL_NUM_OUT, zero_line)) return rc;
@@ -371,6 +379,9 @@ int ad_masked_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t 
     if (step)
         if (int rc = check_step_saturation(fn, p)) return rc;
     if (int rc = check_masked_size<T>(fn, nz, ls)) return rc;
+    if (multi)
+        return launched(fn, cs2::launch_ad_dirs<T>(*p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn, out_adj,
+                                                   dt, static_cast<hipStream_t>(stream), step, ndir, in_ds, out_ds));
     return launched(fn, cs2::launch_ad_masked<T>(*p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn,
                                                  out_adj, dt, static_cast<hipStream_t>(stream), step));
 }
@@ -667,6 +678,30 @@ int32_t cloudsc2_tl_multi_step_f32(const Cloudsc2Params* p, int32_t nx, int32_t 
                                    float* const* out_i, double dt, void* stream, int32_t ndir, int64_t in_ds, int64_t out_ds) {
     return tl_masked_impl<float>("cloudsc2_tl_multi_step_f32", p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt, stream, true, true,
                            ndir, in_ds, out_ds);
+}
+int32_t cloudsc2_ad_multi_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const double* const* in,
+        const double* const* in_adj, const double* zero_line, const double* eta, const double* traj_fplsl, const double* traj_fplsn,
+        double* const* out_adj, double dt, void* stream, int32_t ndir, int64_t in_ds, int64_t out_ds) {
+    return ad_masked_impl<double>("cloudsc2_ad_multi_f64", p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn, out_adj, dt,
+                           stream, false, true, ndir, in_ds, out_ds);
+}
+int32_t cloudsc2_ad_multi_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const float* const* in,
+        const float* const* in_adj, const float* zero_line, const float* eta, const float* traj_fplsl, const float* traj_fplsn,
+        float* const* out_adj, double dt, void* stream, int32_t ndir, int64_t in_ds, int64_t out_ds) {
+    return ad_masked_impl<float>("cloudsc2_ad_multi_f32", p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn, out_adj, dt,
+                           stream, false, true, ndir, in_ds, out_ds);
+}
+int32_t cloudsc2_ad_multi_step_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const double* const* in,
+        const double* const* in_adj, const double* zero_line, const double* eta, const double* traj_fplsl, const double* traj_fplsn,
+        double* const* out_adj, double dt, void* stream, int32_t ndir, int64_t in_ds, int64_t out_ds) {
+    return ad_masked_impl<double>("cloudsc2_ad_multi_step_f64", p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn, out_adj, dt,
+                           stream, true, true, ndir, in_ds, out_ds);
+}
+int32_t cloudsc2_ad_multi_step_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const float* const* in,
+        const float* const* in_adj, const float* zero_line, const float* eta, const float* traj_fplsl, const float* traj_fplsn,
+        float* const* out_adj, double dt, void* stream, int32_t ndir, int64_t in_ds, int64_t out_ds) {
+    return ad_masked_impl<float>("cloudsc2_ad_multi_step_f32", p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn, out_adj, dt,
+                           stream, true, true, ndir, in_ds, out_ds);
 }
 
 }  // extern "C"

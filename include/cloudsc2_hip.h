@@ -395,6 +395,50 @@ int32_t cloudsc2_tl_multi_step_f32(const Cloudsc2Params* p, int32_t nx, int32_t 
                                    const float* eta, float* const* out, float* const* out_i, double dt, void* stream,
                                    int32_t ndir, int64_t in_dir_stride, int64_t out_dir_stride);
 
+/* ---- cloudsc2_ad_masked / cloudsc2_ad_step for SEVERAL DIRECTIONS on one trajectory (BUILD EXTENSIONS): a block of rows
+ * of the Jacobian, several cost functionals or observation sensitivities on one trajectory.  Arguments are those of
+ * cloudsc2_ad_masked_* (multi) and of cloudsc2_ad_step_* (multi_step), and so are their rules, all settled on the host
+ * before any launch (NULL entries, zero line, at least one wanted adjoint, LEVAPLS2 / LDRAIN1D refused with
+ * CLOUDSC2_E_UNSUPPORTED, LPHYLIN and out_adj[NL_IN_QSAT] == NULL for the step, fields below 4 GiB PER DIRECTION;
+ * nx == 0 is a successful no-op), plus:
+ *   ndir            number of directions, 1 .. CLOUDSC2_AD_MAX_DIRS (CLOUDSC2_E_ARG otherwise);
+ *   in_dir_stride   in ELEMENTS: in_adj[f] points at direction 0 of a batched field, direction d of every present forcing
+ *                   starts d * in_dir_stride elements later;
+ *   out_dir_stride  in ELEMENTS: the same for every wanted out_adj[f].
+ * Both strides must be at least (nz+1) * lev_stride (CLOUDSC2_E_ARG): the directions of a field do not overlap.  A field is
+ * present or absent for all directions alike.  `traj_fplsl` / `traj_fplsn` (the trajectory) are not batched.
+ * One launch reads the trajectory once and recomputes each level's nonlinear state (all its exponentials; for the step,
+ * saturation and its derivative too) once: only the backward statements run per direction, in a loop inside each level.
+ * LDS per workgroup: the level table, 2 * (nz+1) elements; in fp32 the 34 * 256 parked trajectory elements of the single
+ * entries; and the six words of each direction's backward carry, 6 * ndir * 256 elements (ndir = 8, nz = 137: about 98 KB
+ * in fp64, 83 KB in fp32).  A call whose demand exceeds 160 KB is refused (CLOUDSC2_E_UNSUPPORTED).
+ * Every direction of every written field equals what the single-direction entry writes for that direction alone (the same
+ * ad_forward / ad_backward on the same words; to rounding, since the compiler contracts them per kernel).
+ * cloudsc2_last_kernel() reports "cs2::ad_dirs_kernel" / "cs2::ad_dirs_step_kernel".
+ * Words moved per level and column: 16 (step: 15) + 2 + ndir * ((present in_adj) + (present out_adj)) - e.g. forcing on the
+ * four tendencies and adjoints of t, q, ql, qi with the step entry: 17 + 8 ndir against 25 ndir of ndir single launches. */
+#define CLOUDSC2_AD_MAX_DIRS 8
+int32_t cloudsc2_ad_multi_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                              const double* const* in, const double* const* in_adj, const double* zero_line,
+                              const double* eta, const double* traj_fplsl, const double* traj_fplsn,
+                              double* const* out_adj, double dt, void* stream,
+                              int32_t ndir, int64_t in_dir_stride, int64_t out_dir_stride);
+int32_t cloudsc2_ad_multi_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                              const float* const* in, const float* const* in_adj, const float* zero_line,
+                              const float* eta, const float* traj_fplsl, const float* traj_fplsn,
+                              float* const* out_adj, double dt, void* stream,
+                              int32_t ndir, int64_t in_dir_stride, int64_t out_dir_stride);
+int32_t cloudsc2_ad_multi_step_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                   const double* const* in, const double* const* in_adj, const double* zero_line,
+                                   const double* eta, const double* traj_fplsl, const double* traj_fplsn,
+                                   double* const* out_adj, double dt, void* stream,
+                                   int32_t ndir, int64_t in_dir_stride, int64_t out_dir_stride);
+int32_t cloudsc2_ad_multi_step_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                   const float* const* in, const float* const* in_adj, const float* zero_line,
+                                   const float* eta, const float* traj_fplsl, const float* traj_fplsn,
+                                   float* const* out_adj, double dt, void* stream,
+                                   int32_t ndir, int64_t in_dir_stride, int64_t out_dir_stride);
+
 #ifdef __cplusplus
 }
 #endif
