@@ -54,6 +54,22 @@ MULTI_WIDTH: Dict[torch.dtype, int] = {torch.float64: 1, torch.float32: 1}
 #:   fp32 524 288 columns   D=2 1 896 -> 1 889   D=4 1 865 -> 1 441   D=8 1 823 -> 2 086   (4 launches 7 458 us +- 273, one 5 765 us)
 #: fp32 loses at 8: its 83 KB of LDS leave one workgroup per CU where 4 directions (59 KB) leave two.
 AD_MULTI_WIDTH: Dict[torch.dtype, int] = {torch.float64: 8, torch.float32: 4}
+
+
+class _Family(NamedTuple):
+    """one of the four kernel families behind the eight thin calls"""
+    single: str                      # the C entry `cloudsc2_<single>_{f64,f32}`: one direction per launch
+    multi: str                       # its multi-direction form (`_lib.MULTI_LAYOUTS`): the same arguments + (ndir, strides)
+    names: Tuple[str, ...]           # the fields of the state
+    width: Dict[torch.dtype, int]    # directions per launch by default, per precision
+    max_dirs: int                    # the most one launch takes
+    adjoint: bool = False            # forcing (`NL_OUT` names) and `traj` in, adjoints of `names` out; else the tangent-linear
+
+
+_TL_MASKED = _Family("tl_masked", "tl_multi", NL_IN, MULTI_WIDTH, _lib.TL_MAX_DIRS)
+_TL_STEP = _Family("tl_step", "tl_multi_step", STEP_IN, MULTI_WIDTH, _lib.TL_MAX_DIRS)
+_AD_MASKED = _Family("ad_masked", "ad_multi", NL_IN, AD_MULTI_WIDTH, _lib.AD_MAX_DIRS, adjoint=True)
+_AD_STEP = _Family("ad_step", "ad_multi_step", STEP_IN, AD_MULTI_WIDTH, _lib.AD_MAX_DIRS, adjoint=True)
 _ZERO_LINE_BYTES = 512
 _zero_lines: Dict[Tuple[torch.device, torch.dtype], torch.Tensor] = {}
 
@@ -132,7 +148,7 @@ def tl_masked(state: Mapping[str, torch.Tensor], perturbations: Mapping[str, tor
     """Tangent-linear CLOUDSC2 with absent fields: `perturbations` holds the perturbed inputs (`NL_IN` names; a missing
     name is a zero perturbation), `want` names the perturbed outputs (`NL_OUT` names) to produce.  Returns
     `(nl_outputs or None, {name: perturbed output})`; results are new `storage.zeros` fields."""
-    return _tl_call("tl_masked", NL_IN, state, perturbations, eta, dt, externals, want, write_nl)
+    return _call(_TL_MASKED, False, state, perturbations, eta, dt, externals, want, write_nl=write_nl)
 
 
 def tl_step(state: Mapping[str, torch.Tensor], perturbations: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
@@ -140,31 +156,7 @@ def tl_step(state: Mapping[str, torch.Tensor], perturbations: Mapping[str, torch
     """Tangent-linear of the step `saturation` + `cloudsc2_nl` in ONE launch (`cloudsc2_tl_step_*`): `tl_masked` without the
     field `qsat` (`STEP_IN` names).  `qsat` is formed in the kernel from `ap` and `t`, and its perturbation from theirs by
     the derivative rule of `saturation_tl`.  LPHYLIN only (`ValueError` otherwise)."""
-    return _tl_call("tl_step", STEP_IN, state, perturbations, eta, dt, externals, want, write_nl)
-
-
-def _tl_call(what, in_names, state, perturbations, eta, dt, externals, want, write_nl, into=None):
-    """`into`: the perturbed outputs are written to these fields of the call's geometry (`tl_multi`: one direction of its
-    batched results) and not to new ones"""
-    want = tuple(want)
-    if not want or set(want) - set(NL_OUT):
-        raise ValueError(f"{what}: `want` must name at least one of {NL_OUT}, got {want}")
-    state = {n: _plain(f) for n, f in state.items()}
-    pert = {n: _plain(f) for n, f in perturbations.items()}
-    (nx, nlev, ls), dtype, device = _checked(what, ((state, in_names, True), (pert, in_names, False)))
-    nz = nlev - 1
-    eta = _eta(what, eta, nz, dtype, device)
-    ref = state[NL_IN[0]]
-    out = {n: _new_like(ref, nx, nz, ls) for n in NL_OUT} if write_nl else None
-    out_i = {n: _new_like(ref, nx, nz, ls) for n in want} if into is None else into
-    p = _params(externals, nz)
-    with torch.cuda.device(device):
-        rc = getattr(_lib.load(), f"cloudsc2_{what}_{_SFX[dtype]}")(
-            ctypes.byref(p), nx, nz, ls, _ptrs(state, NL_IN), _ptrs(pert, NL_IN), _zero_line(device, dtype).data_ptr(),
-            eta.data_ptr(), None if out is None else _ptrs(out, NL_OUT), _ptrs(out_i, NL_OUT), float(dt),
-            int(torch.cuda.current_stream(device).cuda_stream))
-    _lib.check(rc, what)
-    return out, out_i
+    return _call(_TL_STEP, False, state, perturbations, eta, dt, externals, want, write_nl=write_nl)
 
 
 def tl_multi(state: Mapping[str, torch.Tensor], perturbations: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
@@ -177,7 +169,7 @@ def tl_multi(state: Mapping[str, torch.Tensor], perturbations: Mapping[str, torc
     Directions are served in chunks of at most `width` (default `MULTI_WIDTH` of the dtype) per `cloudsc2_tl_multi_*`
     launch, which reads the state once per chunk; a chunk of one direction is a plain `tl_masked` launch.  Any `ndir >= 1`
     works.  A perturbation that is not laid out as `storage.zeros_batched` gives is copied into such a field first."""
-    return _tl_multi_call("tl_multi", "tl_masked", NL_IN, state, perturbations, eta, dt, externals, want, write_nl, width)
+    return _call(_TL_MASKED, True, state, perturbations, eta, dt, externals, want, write_nl=write_nl, width=width)
 
 
 def tl_step_multi(state: Mapping[str, torch.Tensor], perturbations: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
@@ -185,7 +177,47 @@ def tl_step_multi(state: Mapping[str, torch.Tensor], perturbations: Mapping[str,
                   width: Optional[int] = None):
     """`tl_step` for `ndir` perturbations of one state (`cloudsc2_tl_multi_step_*`; `STEP_IN` names): see `tl_multi`.
     `saturation` and its derivative are evaluated once per level for all directions of a chunk.  LPHYLIN only."""
-    return _tl_multi_call("tl_multi_step", "tl_step", STEP_IN, state, perturbations, eta, dt, externals, want, write_nl, width)
+    return _call(_TL_STEP, True, state, perturbations, eta, dt, externals, want, write_nl=write_nl, width=width)
+
+
+def ad_masked(state: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+              externals: Optional[Mapping[str, Any]] = None, *, traj: Mapping[str, torch.Tensor], want: Iterable[str]):
+    """Adjoint CLOUDSC2 with absent fields: `forcing` holds the adjoint forcing (`NL_OUT` names; a missing name is zero
+    forcing), `traj` the `fplsl` / `fplsn` outputs of a `cloudsc2_nl` / `cloudsc2_tl` call on `state`, `want` names the
+    inputs (`NL_IN` names) whose adjoints to produce.  Returns `{name: adjoint}` as new `storage.zeros` fields.
+    LEVAPLS2 / LDRAIN1D are refused (`ValueError`), as by `cloudsc2_ad_from_trajectory`."""
+    return _call(_AD_MASKED, False, state, forcing, eta, dt, externals, want, traj=traj)
+
+
+def ad_step(state: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+            externals: Optional[Mapping[str, Any]] = None, *, traj: Mapping[str, torch.Tensor], want: Iterable[str]):
+    """Adjoint of the step `saturation` + `cloudsc2_nl` in ONE launch (`cloudsc2_ad_step_*`): `ad_masked` without the field
+    `qsat` (`STEP_IN` names).  The adjoint of `qsat` is not produced: it is taken through `saturation` by the rule of
+    `saturation_ad` and arrives inside the adjoints of `t` and `ap`.  LPHYLIN only, and no LEVAPLS2 / LDRAIN1D."""
+    return _call(_AD_STEP, False, state, forcing, eta, dt, externals, want, traj=traj)
+
+
+def ad_multi(state: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+             externals: Optional[Mapping[str, Any]] = None, *, traj: Mapping[str, torch.Tensor], want: Iterable[str],
+             width: Optional[int] = None):
+    """`ad_masked` for `ndir` cotangents of one state: `forcing` maps `NL_OUT` names to `(ndir, nx, 1, nz+1)` tensors (a
+    missing name is zero forcing in every direction); `traj` is not batched.  Returns `{name: (ndir, nx, 1, nz+1)}`, one
+    `storage.zeros_batched` allocation per wanted name.
+
+    Directions are served in chunks of at most `width` (default `AD_MULTI_WIDTH` of the dtype) per `cloudsc2_ad_multi_*`
+    launch, which reads the state and recomputes the nonlinear trajectory once per chunk; a chunk of one direction is a
+    plain `ad_masked` launch.  Any `ndir >= 1` works.  A forcing that is not laid out as `storage.zeros_batched` gives is
+    copied into such a field first.  LEVAPLS2 / LDRAIN1D are refused (`ValueError`)."""
+    return _call(_AD_MASKED, True, state, forcing, eta, dt, externals, want, traj=traj, width=width)
+
+
+def ad_step_multi(state: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+                  externals: Optional[Mapping[str, Any]] = None, *, traj: Mapping[str, torch.Tensor], want: Iterable[str],
+                  width: Optional[int] = None):
+    """`ad_step` for `ndir` cotangents of one state (`cloudsc2_ad_multi_step_*`; `STEP_IN` names): see `ad_multi`.
+    `saturation` and its derivative are evaluated once per level for all directions of a chunk.  LPHYLIN only, and no
+    LEVAPLS2 / LDRAIN1D."""
+    return _call(_AD_STEP, True, state, forcing, eta, dt, externals, want, traj=traj, width=width)
 
 
 def _batched_layout(g: torch.Tensor, ref: torch.Tensor, geo) -> torch.Tensor:
@@ -204,166 +236,93 @@ def _batched_layout(g: torch.Tensor, ref: torch.Tensor, geo) -> torch.Tensor:
     return f
 
 
-def _tl_multi_call(what, single, in_names, state, perturbations, eta, dt, externals, want, write_nl, width):
-    want = tuple(want)
-    if not want or set(want) - set(NL_OUT):
-        raise ValueError(f"{what}: `want` must name at least one of {NL_OUT}, got {want}")
-    state = {n: _plain(f) for n, f in state.items()}
-    geo, dtype, device = _checked(what, ((state, in_names, True),))
-    nx, nlev, ls = geo
-    unknown = sorted(set(perturbations) - set(in_names))
+def _batch_size(what, noun, dirs, names, geo) -> int:
+    """`dirs`, the `ndir` perturbations / forcings of a multi call: known names, at least one, all GPU tensors of the one
+    shape (ndir, nx, 1, nlev) -> ndir"""
+    nx, nlev, _ = geo
+    unknown = sorted(set(dirs) - set(names))
     if unknown:
         raise ValueError(f"{what}: unknown field names {unknown}")
-    if not perturbations:
-        raise ValueError(f"{what}: no perturbation given")
-    shapes = {tuple(f.shape) for f in perturbations.values() if isinstance(f, torch.Tensor)}
-    if len(shapes) != 1 or len(next(iter(shapes))) != 4 or next(iter(shapes))[1:] != (nx, 1, nlev) or next(iter(shapes))[0] < 1:
-        raise ValueError(f"{what}: every perturbation must be a tensor of one shape (ndir, {nx}, 1, {nlev}), got "
-                         f"{ {n: tuple(getattr(f, 'shape', ())) for n, f in perturbations.items()} }")
-    ndir = next(iter(shapes))[0]
-    for n, f in perturbations.items():
+    if not dirs:
+        raise ValueError(f"{what}: no {noun} given")
+    shapes = {tuple(f.shape) for f in dirs.values() if isinstance(f, torch.Tensor)}
+    shape = next(iter(shapes)) if len(shapes) == 1 else ()
+    if len(shape) != 4 or shape[1:] != (nx, 1, nlev) or shape[0] < 1:
+        raise ValueError(f"{what}: every {noun} must be a tensor of one shape (ndir, {nx}, 1, {nlev}), got "
+                         f"{ {n: tuple(getattr(f, 'shape', ())) for n, f in dirs.items()} }")
+    for n, f in dirs.items():
         if not f.is_cuda:
             raise ValueError(f"{what}: {n} lives on {f.device}; fields must live on the GPU (there is no host path)")
-    nz = nlev - 1
-    eta = _eta(what, eta, nz, dtype, device)
-    ref = state[NL_IN[0]]
-    width = MULTI_WIDTH[dtype] if width is None else int(width)
-    if not 1 <= width <= _lib.TL_MAX_DIRS:
-        raise ValueError(f"{what}: width={width} outside [1, {_lib.TL_MAX_DIRS}]")
-    pert = {n: _batched_layout(f, ref, geo) for n, f in perturbations.items()}
-    out = None
-    out_i = {n: zeros_batched(ndir, nx, nz, dtype, device, ls) for n in want}
-    dstride = nlev * ls
-    p = _params(externals, nz)
-    for d0 in range(0, ndir, width):
-        n = min(width, ndir - d0)
-        nl = write_nl and d0 == 0
-        if n == 1:
-            o, _ = _tl_call(single, in_names, state, {k: f[d0] for k, f in pert.items()}, eta, dt, externals, want, nl,
-                            into={k: f[d0] for k, f in out_i.items()})
-        else:
-            o = {k: _new_like(ref, nx, nz, ls) for k in NL_OUT} if nl else None
-            with torch.cuda.device(device):
-                rc = getattr(_lib.load(), f"cloudsc2_{what}_{_SFX[dtype]}")(
-                    ctypes.byref(p), nx, nz, ls, _ptrs(state, NL_IN), _ptrs({k: f[d0] for k, f in pert.items()}, NL_IN),
-                    _zero_line(device, dtype).data_ptr(), eta.data_ptr(), None if o is None else _ptrs(o, NL_OUT),
-                    _ptrs({k: f[d0] for k, f in out_i.items()}, NL_OUT), float(dt),
-                    int(torch.cuda.current_stream(device).cuda_stream), n, dstride, dstride)
-            _lib.check(rc, what)
-        out = o if nl else out
-    return out, out_i
+    return shape[0]
 
 
-def ad_masked(state: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
-              externals: Optional[Mapping[str, Any]] = None, *, traj: Mapping[str, torch.Tensor], want: Iterable[str]):
-    """Adjoint CLOUDSC2 with absent fields: `forcing` holds the adjoint forcing (`NL_OUT` names; a missing name is zero
-    forcing), `traj` the `fplsl` / `fplsn` outputs of a `cloudsc2_nl` / `cloudsc2_tl` call on `state`, `want` names the
-    inputs (`NL_IN` names) whose adjoints to produce.  Returns `{name: adjoint}` as new `storage.zeros` fields.
-    LEVAPLS2 / LDRAIN1D are refused (`ValueError`), as by `cloudsc2_ad_from_trajectory`."""
-    return _ad_call("ad_masked", NL_IN, state, forcing, eta, dt, externals, traj, want)
+def _tl_args(p, geo, state, pert, zero_line, eta, out, out_i, dt, stream, tail=()):
+    """the arguments of `cloudsc2_tl_masked_*` / `_tl_step_*`; with `tail` = (ndir, in_dir_stride, out_dir_stride) those of
+    their multi-direction forms (`_lib.MULTI_LAYOUTS`)"""
+    nx, nlev, ls = geo
+    return (ctypes.byref(p), nx, nlev - 1, ls, _ptrs(state, NL_IN), _ptrs(pert, NL_IN), zero_line.data_ptr(), eta.data_ptr(),
+            None if out is None else _ptrs(out, NL_OUT), _ptrs(out_i, NL_OUT), float(dt), stream) + tail
 
 
-def ad_step(state: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
-            externals: Optional[Mapping[str, Any]] = None, *, traj: Mapping[str, torch.Tensor], want: Iterable[str]):
-    """Adjoint of the step `saturation` + `cloudsc2_nl` in ONE launch (`cloudsc2_ad_step_*`): `ad_masked` without the field
-    `qsat` (`STEP_IN` names).  The adjoint of `qsat` is not produced: it is taken through `saturation` by the rule of
-    `saturation_ad` and arrives inside the adjoints of `t` and `ap`.  LPHYLIN only, and no LEVAPLS2 / LDRAIN1D."""
-    return _ad_call("ad_step", STEP_IN, state, forcing, eta, dt, externals, traj, want)
-
-
-def _ad_call(what, in_names, state, forcing, eta, dt, externals, traj, want, into=None):
-    """`into`: the adjoints are written to these fields of the call's geometry (`ad_multi`: one direction of its batched
-    results) and not to new ones"""
-    want = tuple(want)
-    if not want or set(want) - set(in_names):
-        raise ValueError(f"{what}: `want` must name at least one of {in_names}, got {want}")
-    state = {n: _plain(f) for n, f in state.items()}
-    forcing = {n: _plain(f) for n, f in forcing.items()}
-    traj = {n: _plain(f) for n, f in traj.items()}
-    (nx, nlev, ls), dtype, device = _checked(what, ((state, in_names, True), (forcing, NL_OUT, False),
-                                                    (traj, ("fplsl", "fplsn"), True)))
-    nz = nlev - 1
-    eta = _eta(what, eta, nz, dtype, device)
-    ref = state[NL_IN[0]]
-    out_adj = {n: _new_like(ref, nx, nz, ls) for n in want} if into is None else into
-    p = _params(externals, nz)
-    with torch.cuda.device(device):
-        rc = getattr(_lib.load(), f"cloudsc2_{what}_{_SFX[dtype]}")(
-            ctypes.byref(p), nx, nz, ls, _ptrs(state, NL_IN), _ptrs(forcing, NL_OUT), _zero_line(device, dtype).data_ptr(),
+def _ad_args(p, geo, state, forcing, zero_line, eta, traj, out_adj, dt, stream, tail=()):
+    """the arguments of `cloudsc2_ad_masked_*` / `_ad_step_*`; `tail` as for `_tl_args`"""
+    nx, nlev, ls = geo
+    return (ctypes.byref(p), nx, nlev - 1, ls, _ptrs(state, NL_IN), _ptrs(forcing, NL_OUT), zero_line.data_ptr(),
             eta.data_ptr(), traj["fplsl"].data_ptr(), traj["fplsn"].data_ptr(), _ptrs(out_adj, NL_IN), float(dt),
-            int(torch.cuda.current_stream(device).cuda_stream))
-    _lib.check(rc, what)
-    return out_adj
+            stream) + tail
 
 
-def ad_multi(state: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
-             externals: Optional[Mapping[str, Any]] = None, *, traj: Mapping[str, torch.Tensor], want: Iterable[str],
-             width: Optional[int] = None):
-    """`ad_masked` for `ndir` cotangents of one state: `forcing` maps `NL_OUT` names to `(ndir, nx, 1, nz+1)` tensors (a
-    missing name is zero forcing in every direction); `traj` is not batched.  Returns `{name: (ndir, nx, 1, nz+1)}`, one
-    `storage.zeros_batched` allocation per wanted name.
-
-    Directions are served in chunks of at most `width` (default `AD_MULTI_WIDTH` of the dtype) per `cloudsc2_ad_multi_*`
-    launch, which reads the state and recomputes the nonlinear trajectory once per chunk; a chunk of one direction is a
-    plain `ad_masked` launch.  Any `ndir >= 1` works.  A forcing that is not laid out as `storage.zeros_batched` gives is
-    copied into such a field first.  LEVAPLS2 / LDRAIN1D are refused (`ValueError`)."""
-    return _ad_multi_call("ad_multi", "ad_masked", NL_IN, state, forcing, eta, dt, externals, traj, want, width)
-
-
-def ad_step_multi(state: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
-                  externals: Optional[Mapping[str, Any]] = None, *, traj: Mapping[str, torch.Tensor], want: Iterable[str],
-                  width: Optional[int] = None):
-    """`ad_step` for `ndir` cotangents of one state (`cloudsc2_ad_multi_step_*`; `STEP_IN` names): see `ad_multi`.
-    `saturation` and its derivative are evaluated once per level for all directions of a chunk.  LPHYLIN only, and no
-    LEVAPLS2 / LDRAIN1D."""
-    return _ad_multi_call("ad_multi_step", "ad_step", STEP_IN, state, forcing, eta, dt, externals, traj, want, width)
-
-
-def _ad_multi_call(what, single, in_names, state, forcing, eta, dt, externals, traj, want, width):
+def _call(fam: _Family, batched: bool, state, dirs, eta, dt, externals, want, *, traj=None, write_nl=False, width=None):
+    """The launch path of the eight thin calls.  Everything is checked ONCE, up front; then the directions are served in
+    chunks of at most `width`: a chunk of one direction by the single-direction entry, a wider one by the multi-direction
+    entry.  `batched`: `dirs` maps names to (ndir, nx, 1, nlev) batches and so do the results, which are one `zeros_batched`
+    allocation per wanted name that every chunk writes through the views `f[d0]`; otherwise `dirs` and the results are
+    single fields and there is one launch.  The NL outputs of `write_nl` are new fields, written by the first launch."""
+    what = fam.multi if batched else fam.single
+    noun, dir_names, res_names = ("forcing", NL_OUT, fam.names) if fam.adjoint else ("perturbation", fam.names, NL_OUT)
     want = tuple(want)
-    if not want or set(want) - set(in_names):
-        raise ValueError(f"{what}: `want` must name at least one of {in_names}, got {want}")
+    if not want or set(want) - set(res_names):
+        raise ValueError(f"{what}: `want` must name at least one of {res_names}, got {want}")
     state = {n: _plain(f) for n, f in state.items()}
-    traj = {n: _plain(f) for n, f in traj.items()}
-    geo, dtype, device = _checked(what, ((state, in_names, True), (traj, ("fplsl", "fplsn"), True)))
+    groups = [(state, fam.names, True)]
+    if not batched:
+        dirs = {n: _plain(f) for n, f in dirs.items()}
+        groups.append((dirs, dir_names, False))
+    if fam.adjoint:
+        traj = {n: _plain(f) for n, f in traj.items()}
+        groups.append((traj, ("fplsl", "fplsn"), True))
+    geo, dtype, device = _checked(what, groups)
     nx, nlev, ls = geo
-    unknown = sorted(set(forcing) - set(NL_OUT))
-    if unknown:
-        raise ValueError(f"{what}: unknown field names {unknown}")
-    if not forcing:
-        raise ValueError(f"{what}: no forcing given")
-    shapes = {tuple(f.shape) for f in forcing.values() if isinstance(f, torch.Tensor)}
-    if len(shapes) != 1 or len(next(iter(shapes))) != 4 or next(iter(shapes))[1:] != (nx, 1, nlev) or next(iter(shapes))[0] < 1:
-        raise ValueError(f"{what}: every forcing must be a tensor of one shape (ndir, {nx}, 1, {nlev}), got "
-                         f"{ {n: tuple(getattr(f, 'shape', ())) for n, f in forcing.items()} }")
-    ndir = next(iter(shapes))[0]
-    for n, f in forcing.items():
-        if not f.is_cuda:
-            raise ValueError(f"{what}: {n} lives on {f.device}; fields must live on the GPU (there is no host path)")
     nz = nlev - 1
+    ndir = _batch_size(what, noun, dirs, dir_names, geo) if batched else 1
     eta = _eta(what, eta, nz, dtype, device)
     ref = state[NL_IN[0]]
-    width = AD_MULTI_WIDTH[dtype] if width is None else int(width)
-    if not 1 <= width <= _lib.AD_MAX_DIRS:
-        raise ValueError(f"{what}: width={width} outside [1, {_lib.AD_MAX_DIRS}]")
-    forc = {n: _batched_layout(f, ref, geo) for n, f in forcing.items()}
-    out_adj = {n: zeros_batched(ndir, nx, nz, dtype, device, ls) for n in want}
-    dstride = nlev * ls
+    if batched:
+        width = fam.width[dtype] if width is None else int(width)
+        if not 1 <= width <= fam.max_dirs:
+            raise ValueError(f"{what}: width={width} outside [1, {fam.max_dirs}]")
+        dirs = {n: _batched_layout(f, ref, geo) for n, f in dirs.items()}
+        res = {n: zeros_batched(ndir, nx, nz, dtype, device, ls) for n in want}
+    else:
+        width = 1
+        res = {n: _new_like(ref, nx, nz, ls) for n in want}
+    out = {n: _new_like(ref, nx, nz, ls) for n in NL_OUT} if write_nl else None
     p = _params(externals, nz)
-    for d0 in range(0, ndir, width):
-        n = min(width, ndir - d0)
-        if n == 1:
-            _ad_call(single, in_names, state, {k: f[d0] for k, f in forc.items()}, eta, dt, externals, traj, want,
-                     into={k: f[d0] for k, f in out_adj.items()})
-        else:
-            with torch.cuda.device(device):
-                rc = getattr(_lib.load(), f"cloudsc2_{what}_{_SFX[dtype]}")(
-                    ctypes.byref(p), nx, nz, ls, _ptrs(state, NL_IN), _ptrs({k: f[d0] for k, f in forc.items()}, NL_OUT),
-                    _zero_line(device, dtype).data_ptr(), eta.data_ptr(), traj["fplsl"].data_ptr(), traj["fplsn"].data_ptr(),
-                    _ptrs({k: f[d0] for k, f in out_adj.items()}, NL_IN), float(dt),
-                    int(torch.cuda.current_stream(device).cuda_stream), n, dstride, dstride)
-            _lib.check(rc, what)
-    return out_adj
+    lib, zero, dstride = _lib.load(), _zero_line(device, dtype), nlev * ls
+    stream = int(torch.cuda.current_stream(device).cuda_stream)
+    with torch.cuda.device(device):
+        for d0 in range(0, ndir, width):
+            n = min(width, ndir - d0)
+            entry = fam.single if n == 1 else fam.multi
+            tail = () if n == 1 else (n, dstride, dstride)
+            d = {k: f[d0] for k, f in dirs.items()} if batched else dirs
+            r = {k: f[d0] for k, f in res.items()} if batched else res
+            if fam.adjoint:
+                args = _ad_args(p, geo, state, d, zero, eta, traj, r, dt, stream, tail)
+            else:
+                args = _tl_args(p, geo, state, d, zero, eta, out if d0 == 0 else None, r, dt, stream, tail)
+            _lib.check(getattr(lib, f"cloudsc2_{entry}_{_SFX[dtype]}")(*args), entry)
+    return res if fam.adjoint else (out, res)
 
 
 def _in_layout(g: torch.Tensor, ref: torch.Tensor, geo) -> torch.Tensor:
@@ -420,23 +379,22 @@ class _InnerFunction(torch.autograd.Function):
         pass
 
 
-class _TLMasked(_InnerFunction):
-    """(call, 16 state fields, present tangents) -> the ten perturbed outputs"""
-    @staticmethod
-    def forward(call, *tensors):
-        state = dict(zip(NL_IN, tensors[:len(NL_IN)]))
+def _unpacked(names, step, adjoint, call, tensors, info=None, in_dims=None):
+    """`(call, *tensors)` of an inner Function -> state, `qsat` or None, `traj` or None, present tangents / cotangents by name.
+    The fixed tensors come first: the `names` of the state, for a `step` its `qsat`, for an `adjoint` the two trajectory
+    fluxes.  `forward`: every tangent / cotangent becomes a field of the call's geometry; `vmap` (`info`, `in_dims` given):
+    they are stacked as (batch, nx, 1, nlev), and a batched state is refused."""
+    nst = len(names)
+    nfixed = nst + step + 2 * adjoint
+    if info is None:
         ref = _plain(tensors[0])
-        pert = {n: _in_layout(t, ref, call.geo) for n, t in zip(call.have, tensors[len(NL_IN):])}
-        _, out_i = tl_masked(state, pert, call.eta, call.dt, call.ext, want=NL_OUT, write_nl=False)
-        return tuple(out_i[n] for n in NL_OUT)
-
-    @staticmethod
-    def vmap(info, in_dims, call, *tensors):
-        _unbatched_state(in_dims, len(NL_IN))
-        state = dict(zip(NL_IN, tensors[:len(NL_IN)]))
-        pert = dict(zip(call.have, _stacked(info, in_dims, tensors, len(NL_IN))))
-        _, out_i = tl_multi(state, pert, call.eta, call.dt, call.ext, want=NL_OUT, write_nl=False)
-        return tuple(out_i[n] for n in NL_OUT), (0,) * len(NL_OUT)
+        rest = [_in_layout(t, ref, call.geo) for t in tensors[nfixed:]]
+    else:
+        _unbatched_state(in_dims, nfixed)
+        rest = _stacked(info, in_dims, tensors, nfixed)
+    qsat = tensors[nst] if step else None
+    traj = {"fplsl": tensors[nfixed - 2], "fplsn": tensors[nfixed - 1]} if adjoint else None
+    return dict(zip(names, tensors)), qsat, traj, dict(zip(call.have, rest))
 
 
 def _saturation_tl_stacked(ap, t, pert, ext, geo):
@@ -451,36 +409,44 @@ def _saturation_tl_stacked(ap, t, pert, ext, geo):
     return qsat_i
 
 
+def _tl_rule(fam, call, tensors, info=None, in_dims=None):
+    """`forward` and, with `info` and `in_dims`, `vmap` of `_TLMasked` / `_TLStep`: batched tangents take the family's
+    multi-direction launches.  The step without LPHYLIN has no kernel of its own: the qsat perturbation comes from
+    `saturation_tl`, then the masked family runs on the step's `qsat`."""
+    batched, step = info is not None, fam is _TL_STEP
+    state, qsat, _, pert = _unpacked(fam.names, step, False, call, tensors, info, in_dims)
+    if step and not call.ext.get("LPHYLIN"):
+        if batched and ("ap" in pert or "t" in pert):
+            sat = {n: pert[n] for n in ("ap", "t") if n in pert}
+            pert["qsat"] = _saturation_tl_stacked(state["ap"], state["t"], sat, call.ext, call.geo)
+        elif "ap" in pert or "t" in pert:
+            pert["qsat"] = saturation_tl(state["ap"], state["t"], pert.get("ap"), pert.get("t"), call.ext)[1]
+        fam, state = _TL_MASKED, dict(state, qsat=qsat)
+    out_i = _call(fam, batched, state, pert, call.eta, call.dt, call.ext, NL_OUT)[1]
+    outs = tuple(out_i[n] for n in NL_OUT)
+    return (outs, (0,) * len(outs)) if batched else outs
+
+
+class _TLMasked(_InnerFunction):
+    """(call, 16 state fields, present tangents) -> the ten perturbed outputs"""
+    @staticmethod
+    def forward(call, *tensors):
+        return _tl_rule(_TL_MASKED, call, tensors)
+
+    @staticmethod
+    def vmap(info, in_dims, call, *tensors):
+        return _tl_rule(_TL_MASKED, call, tensors, info, in_dims)
+
+
 class _TLStep(_InnerFunction):
     """(call, 15 state fields, qsat, present tangents) -> the ten perturbed outputs of the step"""
     @staticmethod
     def forward(call, *tensors):
-        nst = len(STEP_IN)
-        state, qsat = dict(zip(STEP_IN, tensors[:nst])), tensors[nst]
-        ref = _plain(tensors[0])
-        pert = {n: _in_layout(t, ref, call.geo) for n, t in zip(call.have, tensors[nst + 1:])}
-        if call.ext.get("LPHYLIN"):
-            _, out_i = tl_step(state, pert, call.eta, call.dt, call.ext, want=NL_OUT, write_nl=False)
-        else:
-            if "ap" in pert or "t" in pert:
-                pert["qsat"] = saturation_tl(state["ap"], state["t"], pert.get("ap"), pert.get("t"), call.ext)[1]
-            _, out_i = tl_masked(dict(state, qsat=qsat), pert, call.eta, call.dt, call.ext, want=NL_OUT, write_nl=False)
-        return tuple(out_i[n] for n in NL_OUT)
+        return _tl_rule(_TL_STEP, call, tensors)
 
     @staticmethod
     def vmap(info, in_dims, call, *tensors):
-        nst = len(STEP_IN)
-        _unbatched_state(in_dims, nst + 1)
-        state, qsat = dict(zip(STEP_IN, tensors[:nst])), tensors[nst]
-        pert = dict(zip(call.have, _stacked(info, in_dims, tensors, nst + 1)))
-        if call.ext.get("LPHYLIN"):
-            _, out_i = tl_step_multi(state, pert, call.eta, call.dt, call.ext, want=NL_OUT, write_nl=False)
-        else:
-            if "ap" in pert or "t" in pert:
-                sat = {n: pert[n] for n in ("ap", "t") if n in pert}
-                pert["qsat"] = _saturation_tl_stacked(state["ap"], state["t"], sat, call.ext, call.geo)
-            _, out_i = tl_multi(dict(state, qsat=qsat), pert, call.eta, call.dt, call.ext, want=NL_OUT, write_nl=False)
-        return tuple(out_i[n] for n in NL_OUT), (0,) * len(NL_OUT)
+        return _tl_rule(_TL_STEP, call, tensors, info, in_dims)
 
 
 class _SaturationTL(_InnerFunction):
@@ -498,13 +464,6 @@ class _SaturationTL(_InnerFunction):
         return _saturation_tl_stacked(ap, t, pert, call.ext, call.geo), 0
 
 
-def _ad_masked_or_dense(call, state, forcing, traj, want):
-    ext = dict(call.ext, AD_TRAJ_FIX=1)
-    if _evap(ext):
-        return _dense_ad(state, forcing, call.eta, call.dt, ext, call.geo, want)
-    return ad_masked(state, forcing, call.eta, call.dt, ext, traj=traj, want=want)
-
-
 def _looped_adjoint(one, info, in_dims, call, tensors, nfixed, nout):
     """the `vmap` rule of the adjoint launches that have no multi-direction kernel (the evaporation switches, the
     non-LPHYLIN step, `saturation`): one single launch per cotangent, results stacked; `one(call, *tensors)` is the
@@ -515,61 +474,54 @@ def _looped_adjoint(one, info, in_dims, call, tensors, nfixed, nout):
     return tuple(torch.stack([r[i] for r in rows]) for i in range(nout)), (0,) * nout
 
 
+def _ad_rule(fam, call, tensors, info=None, in_dims=None):
+    """`forward` and, with `info` and `in_dims`, `vmap` of `_ADMasked` / `_ADStep`.  Where the adjoint is ONE launch of the
+    family - not with the evaporation switches, and the step with LPHYLIN only - batched cotangents take its multi-direction
+    launches.  Elsewhere they loop over this rule for one cotangent: the dense `cloudsc2_ad` (evaporation) or `ad_masked`,
+    for the step producing the adjoint of its `qsat`, which `saturation_ad` adds into those of `ap` and `t`."""
+    batched, step, want = info is not None, fam is _AD_STEP, call.want
+    ext = dict(call.ext, AD_TRAJ_FIX=1)
+    one_launch = not _evap(ext) and (not step or bool(ext.get("LPHYLIN")))
+    if batched and not one_launch:
+        return _looped_adjoint(lambda c, *t: _ad_rule(fam, c, t), info, in_dims, call, tensors, len(fam.names) + step + 2,
+                               len(want))
+    state, qsat, traj, forcing = _unpacked(fam.names, step, True, call, tensors, info, in_dims)
+    if one_launch:
+        adj = _call(fam, batched, state, forcing, call.eta, call.dt, ext, want, traj=traj)
+    else:
+        through = tuple(n for n in ("ap", "t") if step and n in want)    # the adjoints the path through qsat arrives in
+        if step:
+            state, want = dict(state, qsat=qsat), want + (("qsat",) if through else ())
+        if _evap(ext):
+            adj = _dense_ad(state, forcing, call.eta, call.dt, ext, call.geo, want)
+        else:
+            adj = ad_masked(state, forcing, call.eta, call.dt, ext, traj=traj, want=want)
+        if through:
+            saturation_ad(state["ap"], state["t"], adj["qsat"], ext, want=through, into={n: adj[n] for n in through})
+    outs = tuple(adj[n] for n in call.want)
+    return (outs, (0,) * len(outs)) if batched else outs
+
+
 class _ADMasked(_InnerFunction):
     """(call, 16 state fields, traj fplsl, traj fplsn, present cotangents) -> the adjoints of `call.want`"""
     @staticmethod
     def forward(call, *tensors):
-        nst = len(NL_IN)
-        state = dict(zip(NL_IN, tensors[:nst]))
-        ref = _plain(tensors[0])
-        forcing = {n: _in_layout(g, ref, call.geo) for n, g in zip(call.have, tensors[nst + 2:])}
-        adj = _ad_masked_or_dense(call, state, forcing, {"fplsl": tensors[nst], "fplsn": tensors[nst + 1]}, call.want)
-        return tuple(adj[n] for n in call.want)
+        return _ad_rule(_AD_MASKED, call, tensors)
 
     @staticmethod
     def vmap(info, in_dims, call, *tensors):
-        nst = len(NL_IN)
-        ext = dict(call.ext, AD_TRAJ_FIX=1)
-        if _evap(ext):
-            return _looped_adjoint(_ADMasked.forward, info, in_dims, call, tensors, nst + 2, len(call.want))
-        _unbatched_state(in_dims, nst + 2)
-        forcing = dict(zip(call.have, _stacked(info, in_dims, tensors, nst + 2)))
-        adj = ad_multi(dict(zip(NL_IN, tensors[:nst])), forcing, call.eta, call.dt, ext,
-                       traj={"fplsl": tensors[nst], "fplsn": tensors[nst + 1]}, want=call.want)
-        return tuple(adj[n] for n in call.want), (0,) * len(call.want)
+        return _ad_rule(_AD_MASKED, call, tensors, info, in_dims)
 
 
 class _ADStep(_InnerFunction):
     """(call, 15 state fields, qsat, traj fplsl, traj fplsn, present cotangents) -> the adjoints of `call.want`"""
     @staticmethod
     def forward(call, *tensors):
-        nst = len(STEP_IN)
-        state, qsat = dict(zip(STEP_IN, tensors[:nst])), tensors[nst]
-        traj = {"fplsl": tensors[nst + 1], "fplsn": tensors[nst + 2]}
-        ref = _plain(tensors[0])
-        forcing = {n: _in_layout(g, ref, call.geo) for n, g in zip(call.have, tensors[nst + 3:])}
-        want = call.want
-        ext = dict(call.ext, AD_TRAJ_FIX=1)
-        if ext.get("LPHYLIN") and not _evap(ext):
-            adj = ad_step(state, forcing, call.eta, call.dt, ext, traj=traj, want=want)
-        else:
-            through = tuple(n for n in ("ap", "t") if n in want)       # the adjoints the path through qsat arrives in
-            adj = _ad_masked_or_dense(call, dict(state, qsat=qsat), forcing, traj, want + (("qsat",) if through else ()))
-            if through:
-                saturation_ad(state["ap"], state["t"], adj["qsat"], ext, want=through, into={n: adj[n] for n in through})
-        return tuple(adj[n] for n in want)
+        return _ad_rule(_AD_STEP, call, tensors)
 
     @staticmethod
     def vmap(info, in_dims, call, *tensors):
-        nst = len(STEP_IN)
-        ext = dict(call.ext, AD_TRAJ_FIX=1)
-        if not ext.get("LPHYLIN") or _evap(ext):
-            return _looped_adjoint(_ADStep.forward, info, in_dims, call, tensors, nst + 3, len(call.want))
-        _unbatched_state(in_dims, nst + 3)
-        forcing = dict(zip(call.have, _stacked(info, in_dims, tensors, nst + 3)))
-        adj = ad_step_multi(dict(zip(STEP_IN, tensors[:nst])), forcing, call.eta, call.dt, ext,
-                            traj={"fplsl": tensors[nst + 1], "fplsn": tensors[nst + 2]}, want=call.want)
-        return tuple(adj[n] for n in call.want), (0,) * len(call.want)
+        return _ad_rule(_AD_STEP, call, tensors, info, in_dims)
 
 
 class _SaturationAD(_InnerFunction):
@@ -592,7 +544,67 @@ def _refuse_batched_state(info, in_dims, *args):
     raise NotImplementedError(_BATCHED_STATE)
 
 
-class _Cloudsc2(torch.autograd.Function):
+class _NLFunction(torch.autograd.Function):
+    """What `_Cloudsc2` and `_Cloudsc2Step` share: everything but `forward`.  A subclass names its inputs behind (eta, dt,
+    externals) in `names`, the inner Functions that launch its `jvp` / `backward` in `tl` / `ad`, and says `with_qsat` if its
+    last output is `qsat`: not differentiable, and saved behind the inputs for both modes.  The rules are classmethods -
+    torch reaches them through the class in every mode (autograd, forward AD, `torch.func`)."""
+    names: Tuple[str, ...] = ()
+    tl = ad = None
+    with_qsat = False
+
+    @classmethod
+    def setup_context(cls, ctx, inputs, outputs):
+        eta, dt, externals, *fields = inputs
+        qsat = outputs[len(NL_OUT):] if cls.with_qsat else ()
+        ctx.set_materialize_grads(False)
+        ctx.call = _Launch(eta, float(dt), _ext_of(externals), field_geometry(fields[0]), ())
+        ctx.save_for_backward(*fields, *qsat, outputs[NL_OUT.index("fplsl")], outputs[NL_OUT.index("fplsn")])
+        ctx.save_for_forward(*fields, *qsat)
+        if qsat:
+            ctx.mark_non_differentiable(*qsat)
+
+    @classmethod
+    @torch.autograd.function.once_differentiable     # it hands its arguments through: here (cls, ctx, *grads)
+    def backward(cls, ctx, *grads):
+        grads = grads[:len(NL_OUT)]                      # one behind them belongs to `qsat`
+        need = ctx.needs_input_grad[3:]
+        if all(g is None for g in grads) or not any(need):
+            return (None,) * (3 + len(cls.names))
+        have = tuple(n for n, g in zip(NL_OUT, grads) if g is not None)
+        want = tuple(n for n, w in zip(cls.names, need) if w)
+        adj = dict(zip(want, cls.ad.apply(ctx.call._replace(have=have, want=want), *(f.detach() for f in ctx.saved_tensors),
+                                          *(g for g in grads if g is not None))))
+        return (None, None, None) + tuple(adj.get(n) for n in cls.names)
+
+    @classmethod
+    def jvp(cls, ctx, _eta_t, _dt_t, _ext_t, *tangents):
+        have = tuple(n for n, t in zip(cls.names, tangents) if t is not None)
+        if not have:
+            return (None,) * (len(NL_OUT) + cls.with_qsat)
+        # in jvp, ctx.saved_tensors is what save_for_forward kept: the fields, and `qsat`
+        with torch.no_grad():
+            out_i = cls.tl.apply(ctx.call._replace(have=have), *(f.detach() for f in ctx.saved_tensors),
+                                 *(t for t in tangents if t is not None))
+        return tuple(out_i) + (None,) * cls.with_qsat
+
+    vmap = staticmethod(_refuse_batched_state)
+
+
+def _state_fields(what, state, names):
+    """the public calls' check of `state` -> its fields in the order of `names`"""
+    missing = [n for n in names if n not in state]
+    if missing or len(state) != len(names):
+        raise ValueError(f"{what}: state must hold exactly the fields {names}; missing {missing}")
+    for n in names:
+        if isinstance(state[n], torch.Tensor) and not state[n].is_cuda:
+            raise ValueError(f"{what}: {n} lives on {state[n].device}; fields must live on the GPU")
+    return tuple(state[n] for n in names)
+
+
+class _Cloudsc2(_NLFunction):
+    names, tl, ad = NL_IN, _TLMasked, _ADMasked
+
     @staticmethod
     def forward(eta, dt, externals, *inputs):
         from .stencils import compile_stencil
@@ -606,39 +618,6 @@ class _Cloudsc2(torch.autograd.Function):
             **{"in_" + n: f for n, f in state.items()}, **{"out_" + n: f for n, f in out.items()}, in_eta=eta, dt=dt,
             origin=(0, 0, 0), domain=(nx, 1, nlev), validate_args=False, exec_info=None)
         return tuple(out[n] for n in NL_OUT)
-
-    @staticmethod
-    def setup_context(ctx, inputs, outputs):
-        eta, dt, externals, *fields = inputs
-        ctx.set_materialize_grads(False)
-        ctx.call = _Launch(eta, float(dt), _ext_of(externals), field_geometry(fields[0]), ())
-        ctx.save_for_backward(*fields, outputs[NL_OUT.index("fplsl")], outputs[NL_OUT.index("fplsn")])
-        ctx.save_for_forward(*fields)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, *grads):
-        need = ctx.needs_input_grad[3:]
-        none = (None,) * (3 + len(NL_IN))
-        if all(g is None for g in grads) or not any(need):
-            return none
-        have = tuple(n for n, g in zip(NL_OUT, grads) if g is not None)
-        want = tuple(n for n, w in zip(NL_IN, need) if w)
-        adj = dict(zip(want, _ADMasked.apply(ctx.call._replace(have=have, want=want), *(f.detach() for f in ctx.saved_tensors),
-                                             *(g for g in grads if g is not None))))
-        return (None, None, None) + tuple(adj.get(n) for n in NL_IN)
-
-    @staticmethod
-    def jvp(ctx, _eta_t, _dt_t, _ext_t, *tangents):
-        have = tuple(n for n, t in zip(NL_IN, tangents) if t is not None)
-        if not have:
-            return (None,) * len(NL_OUT)
-        # in jvp, ctx.saved_tensors is what save_for_forward kept
-        with torch.no_grad():
-            return _TLMasked.apply(ctx.call._replace(have=have), *(f.detach() for f in ctx.saved_tensors),
-                                   *(t for t in tangents if t is not None))
-
-    vmap = staticmethod(_refuse_batched_state)
 
 
 def _dense_ad(state, forcing, eta, dt, ext, geo, want):
@@ -673,13 +652,7 @@ def cloudsc2(state: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
     `jvp` is one masked tangent-linear launch.  With LEVAPLS2 / LDRAIN1D the backward falls back to the dense
     `cloudsc2_ad` (which recomputes the trajectory: 70 words per level and column plus ten zero-filled forcing fields and
     26 scratch results) - same gradients, at that cost.  Second derivatives are not available (`once_differentiable`)."""
-    missing = [n for n in NL_IN if n not in state]
-    if missing or len(state) != len(NL_IN):
-        raise ValueError(f"cloudsc2: state must hold exactly the fields {NL_IN}; missing {missing}")
-    for n in NL_IN:
-        if isinstance(state[n], torch.Tensor) and not state[n].is_cuda:
-            raise ValueError(f"cloudsc2: {n} lives on {state[n].device}; fields must live on the GPU")
-    outs = _Cloudsc2.apply(eta, dt, externals, *(state[n] for n in NL_IN))
+    outs = _Cloudsc2.apply(eta, dt, externals, *_state_fields("cloudsc2", state, NL_IN))
     return dict(zip(NL_OUT, outs))
 
 
@@ -803,7 +776,9 @@ def _evap(ext) -> bool:
     return bool(ext.get("LEVAPLS2") or ext.get("LDRAIN1D"))
 
 
-class _Cloudsc2Step(torch.autograd.Function):
+class _Cloudsc2Step(_NLFunction):
+    names, tl, ad, with_qsat = STEP_IN, _TLStep, _ADStep, True
+
     @staticmethod
     def forward(eta, dt, externals, *inputs):
         from .stencils import compile_stencil
@@ -823,43 +798,6 @@ class _Cloudsc2Step(torch.autograd.Function):
             qsat = _run_saturation(state["ap"], state["t"], ext, (nx, nlev, ls))
             compile_stencil("cloudsc2_nl", ext)(**ins, in_qsat=qsat, **outs, **call)
         return tuple(out[n] for n in NL_OUT) + (qsat,)
-
-    @staticmethod
-    def setup_context(ctx, inputs, outputs):
-        eta, dt, externals, *fields = inputs
-        qsat = outputs[-1]
-        ctx.set_materialize_grads(False)
-        ctx.call = _Launch(eta, float(dt), _ext_of(externals), field_geometry(fields[0]), ())
-        ctx.save_for_backward(*fields, qsat, outputs[NL_OUT.index("fplsl")], outputs[NL_OUT.index("fplsn")])
-        ctx.save_for_forward(*fields, qsat)
-        ctx.mark_non_differentiable(qsat)
-
-    @staticmethod
-    @torch.autograd.function.once_differentiable
-    def backward(ctx, *grads):
-        grads = grads[:len(NL_OUT)]                      # the last one belongs to `qsat`: not differentiable
-        need = ctx.needs_input_grad[3:]
-        none = (None,) * (3 + len(STEP_IN))
-        if all(g is None for g in grads) or not any(need):
-            return none
-        have = tuple(n for n, g in zip(NL_OUT, grads) if g is not None)
-        want = tuple(n for n, w in zip(STEP_IN, need) if w)
-        adj = dict(zip(want, _ADStep.apply(ctx.call._replace(have=have, want=want), *(f.detach() for f in ctx.saved_tensors),
-                                           *(g for g in grads if g is not None))))
-        return (None, None, None) + tuple(adj.get(n) for n in STEP_IN)
-
-    @staticmethod
-    def jvp(ctx, _eta_t, _dt_t, _ext_t, *tangents):
-        have = tuple(n for n, t in zip(STEP_IN, tangents) if t is not None)
-        if not have:
-            return (None,) * (len(NL_OUT) + 1)
-        # in jvp, ctx.saved_tensors is what save_for_forward kept: the 15 fields and qsat
-        with torch.no_grad():
-            out_i = _TLStep.apply(ctx.call._replace(have=have), *(f.detach() for f in ctx.saved_tensors),
-                                  *(t for t in tangents if t is not None))
-        return tuple(out_i) + (None,)
-
-    vmap = staticmethod(_refuse_batched_state)
 
 
 def cloudsc2_step(state: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
@@ -881,11 +819,5 @@ def cloudsc2_step(state: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: floa
     if "qsat" in state:
         raise ValueError("cloudsc2_step: `state` holds `qsat`, which the step forms itself from `ap` and `t`; for a qsat of "
                          "your own use `cloudsc2` (compose it with `saturation` for the total derivative)")
-    missing = [n for n in STEP_IN if n not in state]
-    if missing or len(state) != len(STEP_IN):
-        raise ValueError(f"cloudsc2_step: state must hold exactly the fields {STEP_IN}; missing {missing}")
-    for n in STEP_IN:
-        if isinstance(state[n], torch.Tensor) and not state[n].is_cuda:
-            raise ValueError(f"cloudsc2_step: {n} lives on {state[n].device}; fields must live on the GPU")
-    outs = _Cloudsc2Step.apply(eta, dt, externals, *(state[n] for n in STEP_IN))
+    outs = _Cloudsc2Step.apply(eta, dt, externals, *_state_fields("cloudsc2_step", state, STEP_IN))
     return dict(zip(NL_OUT + ("qsat",), outs))

@@ -1298,15 +1298,13 @@ ad_step_kernel(const ADMaskedArgs<T> A) {
     ad_masked_sweep<T, REG, FIX, true>(A);
 }
 
-// in_adj[f] == nullptr: forcing f is zero everywhere (read from `zero`); out_adj[f] == nullptr: adjoint f is not written.
-// The caller (cloudsc2_capi.hip) has refused the evaporation switches and fields of 4 GiB and more.  `step`: ad_step_kernel
-// (in[NL_IN_QSAT] is not read, out_adj[NL_IN_QSAT] is NULL).
+// The arguments of a masked adjoint call as the kernels take them (launch_ad_masked; launch_ad_dirs for direction 0):
+// in_adj[f] == nullptr: forcing f is zero everywhere (read from `zero`) and not in `have`; out_adj[f] == nullptr: adjoint f
+// is not in `want`, not written.
 template <typename T>
-int launch_ad_masked(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* const* in, const T* const* in_adj,
-                     const T* zero, const T* eta, const T* traj_l, const T* traj_n, T* const* out_adj, double dt,
-                     hipStream_t stream, bool step) {
-    if (p.LEVAPLS2 || p.LDRAIN1D || !fits_u32_offsets<T>(nz, ls)) return -2;
-    ADMaskedArgs<T> args;
+static void fill_ad_masked_args(ADMaskedArgs<T>& args, const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* const* in,
+                                const T* const* in_adj, const T* zero, const T* eta, const T* traj_l, const T* traj_n,
+                                T* const* out_adj, double dt) {
     args.e = make_ext<T>(p);
     args.kc = make_nlk<T>(p, dt, false);
     args.xk = make_expk<T>();
@@ -1325,6 +1323,17 @@ int launch_ad_masked(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const 
     args.dt = static_cast<T>(dt);
     args.traj_l = traj_l;
     args.traj_n = traj_n;
+}
+
+// The caller (cloudsc2_capi.hip) has refused the evaporation switches and fields of 4 GiB and more.  `step`: ad_step_kernel
+// (in[NL_IN_QSAT] is not read, out_adj[NL_IN_QSAT] is NULL).
+template <typename T>
+int launch_ad_masked(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* const* in, const T* const* in_adj,
+                     const T* zero, const T* eta, const T* traj_l, const T* traj_n, T* const* out_adj, double dt,
+                     hipStream_t stream, bool step) {
+    if (p.LEVAPLS2 || p.LDRAIN1D || !fits_u32_offsets<T>(nz, ls)) return -2;
+    ADMaskedArgs<T> args;
+    fill_ad_masked_args<T>(args, p, nx, nz, ls, in, in_adj, zero, eta, traj_l, traj_n, out_adj, dt);
     const dim3 grid((nx + kColBlock - 1) / kColBlock), block(kColBlock);
     const size_t smem = 2 * size_t(nz + 1) * sizeof(T) + (kADPark<T> ? size_t(CS2_AD_PARK_COUNT) * kColBlock * sizeof(T) : 0);
     if (smem > size_t(160) * 1024) return -2;
@@ -1533,24 +1542,7 @@ int launch_ad_dirs(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T*
     if (p.LEVAPLS2 || p.LDRAIN1D || !fits_u32_offsets<T>(nz, ls)) return -2;
     if (ndir < 1 || ndir > kADMaxDirs) return -1;
     ADDirsArgs<T> args;
-    args.m.e = make_ext<T>(p);
-    args.m.kc = make_nlk<T>(p, dt, false);
-    args.m.xk = make_expk<T>();
-    args.m.nx = nx; args.m.nz = nz; args.m.ls = ls;
-    args.m.have = args.m.want = 0;
-    for (int i = 0; i < NL_NUM_IN; ++i) {
-        args.m.in.p[i] = in[i];
-        args.m.oadj.p[i] = out_adj[i];
-        if (out_adj[i]) args.m.want |= 1u << i;
-    }
-    for (int i = 0; i < NL_NUM_OUT; ++i) {
-        args.m.adj.p[i] = in_adj[i] ? in_adj[i] : zero;
-        if (in_adj[i]) args.m.have |= 1u << i;
-    }
-    args.m.eta = eta;
-    args.m.dt = static_cast<T>(dt);
-    args.m.traj_l = traj_l;
-    args.m.traj_n = traj_n;
+    fill_ad_masked_args<T>(args.m, p, nx, nz, ls, in, in_adj, zero, eta, traj_l, traj_n, out_adj, dt);
     args.in_ds = in_ds; args.out_ds = out_ds; args.ndir = ndir;
     const dim3 grid((nx + kColBlock - 1) / kColBlock), block(kColBlock);
     const size_t smem = ad_dirs_lds_bytes<T>(nz, ndir);

@@ -1024,15 +1024,13 @@ tl_step_kernel(const TLMaskedArgs<T> A) {
     tl_masked_sweep<T, REG, EVAP, true>(A);
 }
 
-// in_i[f] == nullptr: perturbation f is zero everywhere (read from `zero`); out == nullptr: no NL outputs;
-// out_i[f] == nullptr: not written.  Always the register path; 32-bit offsets only.  `step`: tl_step_kernel (in[NL_IN_QSAT]
-// and in_i[NL_IN_QSAT] are not read).
+// The arguments of a masked tangent-linear call as the kernels take them (launch_tl_masked; launch_tl_dirs for direction 0):
+// in_i[f] == nullptr: perturbation f is zero everywhere (read from `zero`) and not in `have`; out == nullptr: no NL outputs;
+// out_i[f] == nullptr: not in `want`, not written.
 template <typename T>
-int launch_tl_masked(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* const* in, const T* const* in_i,
-                     const T* zero, const T* eta, T* const* out, T* const* out_i, double dt, hipStream_t stream, bool step) {
-    if (!fits_u32_offsets<T>(nz, ls)) return -2;
-    const bool evap = p.LEVAPLS2 || p.LDRAIN1D;
-    TLMaskedArgs<T> args;
+static void fill_tl_masked_args(TLMaskedArgs<T>& args, const Cloudsc2Params& p, bool evap, int nx, int nz, int64_t ls,
+                                const T* const* in, const T* const* in_i, const T* zero, const T* eta, T* const* out,
+                                T* const* out_i, double dt) {
     args.e = make_ext<T>(p);
     args.kc = make_nlk<T>(p, dt, evap);
     args.xk = make_expk<T>();
@@ -1051,6 +1049,16 @@ int launch_tl_masked(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const 
     }
     args.eta = eta;
     args.dt = static_cast<T>(dt);
+}
+
+// Always the register path; 32-bit offsets only.  `step`: tl_step_kernel (in[NL_IN_QSAT] and in_i[NL_IN_QSAT] are not read).
+template <typename T>
+int launch_tl_masked(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* const* in, const T* const* in_i,
+                     const T* zero, const T* eta, T* const* out, T* const* out_i, double dt, hipStream_t stream, bool step) {
+    if (!fits_u32_offsets<T>(nz, ls)) return -2;
+    const bool evap = p.LEVAPLS2 || p.LDRAIN1D;
+    TLMaskedArgs<T> args;
+    fill_tl_masked_args<T>(args, p, evap, nx, nz, ls, in, in_i, zero, eta, out, out_i, dt);
     const dim3 grid((nx + kColBlock - 1) / kColBlock), block(kColBlock);
     const size_t smem = 2 * size_t(nz + 1) * sizeof(T);
     with_flags(
@@ -1224,24 +1232,7 @@ int launch_tl_dirs(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T*
     if (!fits_u32_offsets<T>(nz, ls)) return -2;
     const bool evap = p.LEVAPLS2 || p.LDRAIN1D;
     TLDirsArgs<T> args;
-    args.m.e = make_ext<T>(p);
-    args.m.kc = make_nlk<T>(p, dt, evap);
-    args.m.xk = make_expk<T>();
-    args.m.nx = nx; args.m.nz = nz; args.m.ls = ls;
-    args.m.have = 0;
-    args.m.want = out ? kTLWantNL : 0u;
-    for (int i = 0; i < NL_NUM_IN; ++i) {
-        args.m.in.p[i] = in[i];
-        args.m.in_i.p[i] = in_i[i] ? in_i[i] : zero;
-        if (in_i[i]) args.m.have |= 1u << i;
-    }
-    for (int i = 0; i < NL_NUM_OUT; ++i) {
-        args.m.out.p[i] = out ? out[i] : nullptr;
-        args.m.out_i.p[i] = out_i[i];
-        if (out_i[i]) args.m.want |= 1u << i;
-    }
-    args.m.eta = eta;
-    args.m.dt = static_cast<T>(dt);
+    fill_tl_masked_args<T>(args.m, p, evap, nx, nz, ls, in, in_i, zero, eta, out, out_i, dt);
     args.in_ds = in_ds; args.out_ds = out_ds; args.ndir = ndir;
     const dim3 grid((nx + kColBlock - 1) / kColBlock), block(kColBlock);
     const size_t smem = tl_dirs_lds_bytes<T>(nz, ndir);
