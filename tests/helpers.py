@@ -147,6 +147,12 @@ def nlev_of(name: str, nz: int) -> int:
     return nz + 1 if half else nz
 
 
+def adjoint_nlev_of(name: str, nz: int) -> int:
+    """number of levels the adjoint stencil writes for an input's adjoint: the half-level fields `aph` and `lu` nz+1,
+    every other nz"""
+    return nz + 1 if name in ("aph", "lu") else nz
+
+
 def taylor_norms(nl0, nlp_of_f2, tl_i, f2s):
     """TaylorTest.get_norm (tangent_linear/validation.py:219-261) for each factor2."""
     import sys as _sys

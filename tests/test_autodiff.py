@@ -4,33 +4,21 @@ transposes of each other by the reference's symmetry rule."""
 import numpy as np
 import pytest
 
-from helpers import (NL_IN, NL_OUT, assert_close, externals, from_device, increments, nl_case, nlev_of, run_oracle_ad,
-                     run_oracle_nl, run_oracle_tl, to_device)
+from derivative_support import autodiff_case, device_state
+from helpers import (NL_IN, NL_OUT, assert_close, externals, from_device, increments, nlev_of, run_oracle_ad, run_oracle_tl,
+                     to_device)
 
 pytestmark = pytest.mark.gpu
-NX, NZ = 200, 137
-_host = {}
+NX, NZ = 200, 137          # `autodiff_case`'s own
 
 
 def _case(dtype):
-    key = np.dtype(dtype)
-    if key not in _host:
-        fields, eta, dt = nl_case(NX, NZ, dtype=dtype)
-        rng = np.random.default_rng(5)
-        w = rng.standard_normal(fields["in_t"].shape).astype(dtype)
-        _host[key] = (fields, eta, dt, w, run_oracle_nl(fields, eta, dt, externals()))
-    return _host[key]
+    c = autodiff_case(dtype)
+    return c["fields"], c["eta"], c["dt"], c["w"], c["nl0"]
 
 
 def _state(gpu, dtype, grad=()):
-    import torch
-
-    fields, eta, dt, w, nl0 = _case(dtype)
-    dev = to_device(fields, gpu)
-    state = {n: dev["in_" + n] for n in NL_IN}
-    for n in grad:
-        state[n].requires_grad_(True)
-    return state, torch.as_tensor(eta, device=gpu), dt, to_device({"w": w}, gpu)["w"]
+    return device_state(gpu, autodiff_case(dtype), NL_IN, grad)
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])

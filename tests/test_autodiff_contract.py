@@ -12,13 +12,11 @@ import re
 import numpy as np
 import pytest
 
-from helpers import NL_IN, NL_OUT, assert_close, externals, from_device, increments, nl_case
+from derivative_support import STATE4, STEP_IN, TND4, direction_case
+from helpers import NL_IN, NL_OUT, assert_close, externals, from_device
 
 pytestmark = pytest.mark.gpu
 
-STEP_IN = tuple(n for n in NL_IN if n != "qsat")
-STATE4 = ("t", "q", "ql", "qi")
-TND4 = ("tnd_t", "tnd_q", "tnd_ql", "tnd_qi")
 #: public name -> (kind, takes a batch of directions, the prefix of its messages, the names of its state)
 CALLS = {"tl_masked": ("tl", False, "tl_masked", NL_IN), "tl_step": ("tl", False, "tl_step", STEP_IN),
          "tl_multi": ("tl", True, "tl_multi", NL_IN), "tl_step_multi": ("tl", True, "tl_multi_step", STEP_IN),
@@ -115,7 +113,6 @@ def test_errors_are_raised_before_any_launch(gpu, no_launch, case, name):
 
 # ---- the chunk plan ---------------------------------------------------------------------------------------------------------
 NDIR = 11
-SEED = 20240807
 #: (ndir, width) -> the launches: the number of directions of each, 1 = the single-direction entry
 PLANS = {(11, 5): (5, 5, 1), (3, 1): (1, 1, 1), (8, 8): (8,)}
 
@@ -131,7 +128,7 @@ def cases():
 def _case(cases, gpu, kind, dtype):
     """63 columns x 137 levels (138 stored; one partial workgroup), 11 independent directions on the 4D-Var mask, and what
     the single call gives for each direction alone: computed once per kind and precision, never modified.
-    TL: the masked family, perturbations = `helpers.increments` of states drawn with other seeds (tests/test_hip_tl_multi.py);
+    TL: the masked family, perturbations = the directions of `derivative_support.direction_case`;
     AD: the step family, forcing = the perturbed outputs of `tl_step` on those (tests/test_hip_ad_multi.py)."""
     import torch
 
@@ -141,16 +138,15 @@ def _case(cases, gpu, kind, dtype):
     if key in cases:
         return cases[key]
     nx, nz = 63, 137
-    fields, eta, dt = nl_case(nx, nz, dtype=dtype, seed=SEED)
+    fields, eta, dt, others = direction_case(nx, nz, dtype, NDIR)
     names = NL_IN if kind == "tl" else STEP_IN
     state = {n: storage.from_klayout(fields["in_" + n], dtype, gpu) for n in names}
     eta = torch.as_tensor(eta, device=gpu)
     ext = externals(NLEV=nz)
     pert = {n: storage.zeros_batched(NDIR, nx, nz, dtype, gpu) for n in STATE4}
-    for d in range(NDIR):
-        other = increments(nl_case(nx, nz, dtype=dtype, seed=SEED + 1 + d)[0], 0.01 * (d + 1))
+    for d, other in enumerate(others):
         for n in STATE4:
-            storage.klayout(pert[n][d]).copy_(torch.as_tensor(other["in_" + n + "_i"]))
+            storage.klayout(pert[n][d]).copy_(torch.as_tensor(other[n]))
     single_tl = autodiff.tl_masked if kind == "tl" else autodiff.tl_step
     nl, rows = None, []
     for d in range(NDIR):

@@ -10,14 +10,13 @@ transpose of the JVP)."""
 import numpy as np
 import pytest
 
-from helpers import NL_IN, assert_close, externals, increments, nl_case, to_device
+from derivative_support import STEP_IN, host_case
+from helpers import NL_IN, assert_close, externals, increments, to_device
 
 pytestmark = pytest.mark.gpu
 NX, NZ = 2, 40
 NLEV = NZ + 1
-STEP_IN = tuple(n for n in NL_IN if n != "qsat")
 FUNCTIONS = ("cloudsc2_step", "cloudsc2", "saturation")
-_host = {}
 
 
 def _f(gpu, what, dtype):
@@ -26,10 +25,7 @@ def _f(gpu, what, dtype):
 
     import gt4py_dwarf_p_cloudsc2_tl_ad_amd as pkg
 
-    key = np.dtype(dtype)
-    if key not in _host:
-        _host[key] = nl_case(NX, NZ, dtype=dtype)
-    fields, eta, dt = _host[key]
+    fields, eta, dt = host_case(NX, NZ, dtype)
     dev = to_device(fields, gpu)
     eta = torch.as_tensor(eta, device=gpu)
     t = dev["in_t"]

@@ -8,15 +8,14 @@ Two columns of 40 levels, the case of tests/test_autodiff_func.py: 82 inputs, 82
 import numpy as np
 import pytest
 
-from helpers import NL_IN, assert_close, externals, nl_case, to_device
+from derivative_support import STEP_IN, host_case
+from helpers import NL_IN, assert_close, externals, to_device
 
 pytestmark = pytest.mark.gpu
 NX, NZ = 2, 40
 NLEV = NZ + 1
-STEP_IN = tuple(n for n in NL_IN if n != "qsat")
 KERNELS = {"cloudsc2_step": ("cs2::ad_dirs_step_kernel", "cs2::ad_step_kernel"),
            "cloudsc2": ("cs2::ad_dirs_kernel", "cs2::ad_masked_kernel")}
-_host = {}
 
 
 def _f(gpu, what, dtype):
@@ -25,10 +24,7 @@ def _f(gpu, what, dtype):
 
     import gt4py_dwarf_p_cloudsc2_tl_ad_amd as pkg
 
-    key = np.dtype(dtype)
-    if key not in _host:
-        _host[key] = nl_case(NX, NZ, dtype=dtype)
-    fields, eta, dt = _host[key]
+    fields, eta, dt = host_case(NX, NZ, dtype)
     dev = to_device(fields, gpu)
     eta = torch.as_tensor(eta, device=gpu)
     state = {n: dev["in_" + n] for n in (STEP_IN if what == "cloudsc2_step" else NL_IN)}

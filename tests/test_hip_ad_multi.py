@@ -11,90 +11,27 @@ fluxes are that launch's NL outputs.
 Bounds: |norm1 - norm2| / (eps |norm2|) < 1e4 per column and direction for the transpose identity against `tl_multi`
 (tests/test_step_grad.py); 100 x `assert_close` against the NumPy oracle, for the step family chained with the analytic
 derivative of `saturation` (tests/saturation_oracle.py) as tests/test_step_grad.py does."""
-import ctypes
-
 import numpy as np
 import pytest
 
-from helpers import (NL_IN, NL_OUT, assert_close, externals, from_device, increments, nl_case, run_oracle_ad, run_oracle_nl,
+from derivative_support import SHAPES, STATE4, STEP_IN, TND4, Box, compare_directions, direction_case, raw_ad, singles
+from helpers import (NL_IN, NL_OUT, adjoint_nlev_of, assert_close, externals, from_device, run_oracle_ad, run_oracle_nl,
                      run_oracle_tl)
 from saturation_oracle import saturation_derivative
 
 pytestmark = pytest.mark.gpu
 
-STATE4 = ("t", "q", "ql", "qi")
-TND4 = ("tnd_t", "tnd_q", "tnd_ql", "tnd_qi")
-STEP_IN = tuple(n for n in NL_IN if n != "qsat")
-SHAPES = [(1, 137, False), (63, 137, False), (200, 137, False), (333, 137, True), (130, 40, False)]
 #: family -> (C entry, single AD call, its kernel, multi kernel, input names, single TL call, multi TL call)
 FAMILIES = {"multi": ("cloudsc2_ad_multi", "ad_masked", "cs2::ad_masked_kernel", "cs2::ad_dirs_kernel", NL_IN, "tl_masked",
                       "tl_multi"),
             "step": ("cloudsc2_ad_multi_step", "ad_step", "cs2::ad_step_kernel", "cs2::ad_dirs_step_kernel", STEP_IN, "tl_step",
                      "tl_step_multi")}
-SEED = 20240807
-_cases = {}
 
 
 def _max_dirs():
     from gt4py_dwarf_p_cloudsc2_tl_ad_amd import _lib
 
     return _lib.AD_MAX_DIRS
-
-
-def _levels(name, nz):
-    """levels the adjoint stencil writes: the half-level fields `aph` and `lu` nz+1, every other nz"""
-    return nz + 1 if name in ("aph", "lu") else nz
-
-
-def _case(nx, nz, dtype, ndir):
-    """host state and `ndir` independent increments: computed once per shape, never modified; fewer directions are the
-    first ones of more"""
-    key = (nx, nz, np.dtype(dtype))
-    if key not in _cases:
-        _cases[key] = (nl_case(nx, nz, dtype=dtype, seed=SEED), [])
-    (fields, eta, dt), dirs = _cases[key]
-    while len(dirs) < ndir:
-        d = len(dirs)
-        other = nl_case(nx, nz, dtype=dtype, seed=SEED + 1 + d)[0]
-        dirs.append({k[3:-2]: v for k, v in increments(other, 0.01 * (d + 1)).items()})
-    return fields, eta, dt, dirs[:ndir]
-
-
-class Box:
-    """device fields of one geometry - dense storages, or column windows of wider allocations (lev_stride > nx) - and
-    batches of them: `slots` fields in one allocation, one behind the other"""
-
-    def __init__(self, nx, nz, dtype, device, window):
-        import torch
-
-        from gt4py_dwarf_p_cloudsc2_tl_ad_amd import storage
-
-        self.nx, self.nz, self.device, self.torch, self.storage = nx, nz, device, torch, storage
-        self.dt = storage.torch_dtype(dtype)
-        self.sfx = "f64" if self.dt == torch.float64 else "f32"
-        self.pitch = storage.level_pitch(nx, dtype) + (192 if window else 0)
-        self.col0 = 64 if window else 0
-
-    def nan(self, slots=None):
-        shape = (self.nz + 1, self.pitch) if slots is None else (slots, self.nz + 1, self.pitch)
-        buf = self.torch.full(shape, float("nan"), dtype=self.dt, device=self.device)[..., self.col0:self.col0 + self.nx]
-        return self.storage.logical_view(buf) if slots is None else buf.unsqueeze(2).permute(0, 3, 2, 1)
-
-    def put(self, arr):
-        f = self.nan()
-        self.storage.klayout(f).copy_(self.torch.as_tensor(arr))
-        return f
-
-    def batch(self, arrs, slots=None):
-        """(slots, nx, 1, nz+1) with direction d = arrs[d]; further slots stay NaN"""
-        f = self.nan(len(arrs) if slots is None else slots)
-        for d, a in enumerate(arrs):
-            self.storage.klayout(f[d]).copy_(self.torch.as_tensor(a))
-        return f
-
-    @property
-    def dir_stride(self):
-        return (self.nz + 1) * self.pitch
 
 
 def _setup(gpu, family, nx, nz, window, dtype, ndir, **flags):
@@ -104,10 +41,10 @@ def _setup(gpu, family, nx, nz, window, dtype, ndir, **flags):
 
     from gt4py_dwarf_p_cloudsc2_tl_ad_amd import autodiff
 
-    fields, eta, dt, dirs = _case(nx, nz, dtype, ndir)
+    fields, eta, dt, dirs = direction_case(nx, nz, dtype, ndir)
     box = Box(nx, nz, dtype, gpu, window)
     names = FAMILIES[family][4]
-    st = {n: box.put(fields["in_" + n]) for n in names}
+    st = box.state(fields, names)
     ext = externals(NLEV=nz, **flags)
     eta = torch.as_tensor(eta, device=gpu)
     tl = getattr(autodiff, FAMILIES[family][5])
@@ -120,49 +57,12 @@ def _setup(gpu, family, nx, nz, window, dtype, ndir, **flags):
     return box, ext, eta, dt, dirs, st, traj, forcing
 
 
-def _raw(entry, box, ext, state, forcing, eta, dt, traj, out_adj, ndir):
-    """the C entry itself on buffers the test supplies: `forcing` / `out_adj` map names to batches"""
-    import torch
-
-    from gt4py_dwarf_p_cloudsc2_tl_ad_amd import _lib, autodiff
-
-    p = autodiff._params(ext, box.nz)
-    rc = getattr(_lib.load(), f"{entry}_{box.sfx}")(
-        ctypes.byref(p), box.nx, box.nz, box.pitch, autodiff._ptrs(state, NL_IN),
-        autodiff._ptrs({n: f[0] for n, f in forcing.items()}, NL_OUT),
-        autodiff._zero_line(torch.device(box.device), box.dt).data_ptr(), eta.data_ptr(), traj["fplsl"].data_ptr(),
-        traj["fplsn"].data_ptr(), autodiff._ptrs({n: f[0] for n, f in out_adj.items()}, NL_IN), float(dt),
-        int(torch.cuda.current_stream().cuda_stream), ndir, box.dir_stride, box.dir_stride)
-    _lib.check(rc, entry)
-
-
 def _singles(family, state, forcing, eta, dt, ext, traj, want, ndir):
     """the single-direction launch for each cotangent alone -> per direction {name: host array}"""
-    from gt4py_dwarf_p_cloudsc2_tl_ad_amd import _lib, autodiff
+    from gt4py_dwarf_p_cloudsc2_tl_ad_amd import autodiff
 
-    single = getattr(autodiff, FAMILIES[family][1])
-    rows = []
-    for d in range(ndir):
-        adj = single(state, {n: f[d] for n, f in forcing.items()}, eta, dt, ext, traj=traj, want=want)
-        assert _lib.last_kernel() == FAMILIES[family][2]
-        rows.append({n: from_device(adj[n]) for n in want})
-    return rows
-
-
-def _compare(what, got_batch, rows, want, nz, dtype, ndir):
-    """direction by direction against the single launches; padding level and the slots behind `ndir` are untouched"""
-    equal = True
-    for n in want:
-        k = _levels(n, nz)
-        for d in range(ndir):
-            a, b = from_device(got_batch[n][d]), rows[d][n]
-            assert not np.isnan(a[:k]).any(), (what, n, d)
-            assert_close(f"{what} out_{n}_i[{d}]", a[:k], b[:k], dtype)
-            assert np.isnan(a[k:]).all(), f"{what} {n}[{d}]: padding level written"
-            equal = equal and np.array_equal(a[:k], b[:k])
-        for d in range(ndir, got_batch[n].shape[0]):
-            assert np.isnan(from_device(got_batch[n][d])).all(), f"{what} {n}: slot {d} >= ndir={ndir} written"
-    print(f"{what} ndir={ndir} {np.dtype(dtype).name}: bit-equal to the single launches: {equal}")
+    return singles(getattr(autodiff, FAMILIES[family][1]), FAMILIES[family][2], state, forcing, eta, dt, ext, want, ndir,
+                   traj=traj)
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
@@ -181,10 +81,10 @@ def test_full_mask_every_direction_equals_the_single_launch(gpu, nx, nz, window,
     assert all(r["t"][:nz].any() and r["aph"].any() for r in rows)
     for ndir in (1, 2, 3, top):
         out_adj = {n: box.nan(top + 1) for n in names}
-        _raw(entry, box, ext, st, forcing, eta, dt, traj, out_adj, ndir)
+        raw_ad(entry, box, ext, st, forcing, eta, dt, traj, out_adj, ndir)
         assert _lib.last_kernel() == kernel
         torch.cuda.synchronize()
-        _compare(f"{entry} {nx}x{nz}", out_adj, rows, names, nz, dtype, ndir)
+        compare_directions(f"{entry} {nx}x{nz}", out_adj, rows, names, nz, dtype, ndir, levels=adjoint_nlev_of)
 
 
 #: name -> (forcing present, adjoints wanted)
@@ -211,10 +111,10 @@ def test_masks(gpu, nx, nz, window, mask, family, dtype):
     forcing = {n: box.batch([w[d][n] for d in range(ndir)]) for n in have}
     rows = _singles(family, st, forcing, eta, dt, ext, traj, want, ndir)
     out_adj = {n: box.nan(ndir + 1) for n in want}
-    _raw(entry, box, ext, st, forcing, eta, dt, traj, out_adj, ndir)
+    raw_ad(entry, box, ext, st, forcing, eta, dt, traj, out_adj, ndir)
     assert _lib.last_kernel() == kernel
     torch.cuda.synchronize()
-    _compare(f"{entry} [{mask}]", out_adj, rows, want, nz, dtype, ndir)
+    compare_directions(f"{entry} [{mask}]", out_adj, rows, want, nz, dtype, ndir, levels=adjoint_nlev_of)
     for d in range(ndir):
         if "aph" in want:
             top = from_device(out_adj["aph"][d])[0]
@@ -239,10 +139,10 @@ def test_other_switches(gpu, flags, family, dtype):
     forcing = {n: box.batch([w[d][n] for d in range(ndir)]) for n in NL_OUT}
     rows = _singles(family, st, forcing, eta, dt, ext, traj, names, ndir)
     out_adj = {n: box.nan(ndir) for n in names}
-    _raw(entry, box, ext, st, forcing, eta, dt, traj, out_adj, ndir)
+    raw_ad(entry, box, ext, st, forcing, eta, dt, traj, out_adj, ndir)
     assert _lib.last_kernel() == kernel
     torch.cuda.synchronize()
-    _compare(f"{entry} {flags}", out_adj, rows, names, nz, dtype, ndir)
+    compare_directions(f"{entry} {flags}", out_adj, rows, names, nz, dtype, ndir, levels=adjoint_nlev_of)
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
@@ -288,7 +188,7 @@ def test_ad_multi_is_the_transpose_of_tl_multi(gpu, family, dtype):
 
     nx, nz, ndir = 63, 137, 3
     entry, _, _, kernel, names, _, tl_multi = FAMILIES[family]
-    fields, eta, dt, dirs = _case(nx, nz, dtype, ndir)
+    fields, eta, dt, dirs = direction_case(nx, nz, dtype, ndir)
     box = Box(nx, nz, dtype, gpu, False)
     st = {n: box.put(fields["in_" + n]) for n in names}
     ext = externals(NLEV=nz, AD_TRAJ_FIX=1)
@@ -318,7 +218,7 @@ def _oracle_case(dtype, ndir):
     key = np.dtype(dtype)
     if key not in _oracle:
         nx, nz = 63, 137
-        fields, eta, dt, dirs = _case(nx, nz, dtype, ndir)
+        fields, eta, dt, dirs = direction_case(nx, nz, dtype, ndir)
         ext = externals(NLEV=nz, AD_TRAJ_FIX=1)
         nl0 = run_oracle_nl(fields, eta, dt, ext)
         _, g_t, g_ap, _ = saturation_derivative(fields["in_ap"], fields["in_t"], ext)
@@ -345,7 +245,7 @@ def test_directions_equal_the_oracle(gpu, family, dtype):
     nx, nz, ndir = 63, 137, 2
     entry, _, _, kernel, names, tl_single, _ = FAMILIES[family]
     w, want = _oracle_case(dtype, ndir)
-    fields, eta, dt, dirs = _case(nx, nz, dtype, ndir)
+    fields, eta, dt, dirs = direction_case(nx, nz, dtype, ndir)
     box = Box(nx, nz, dtype, gpu, False)
     st = {n: box.put(fields["in_" + n]) for n in names}
     ext = externals(NLEV=nz, AD_TRAJ_FIX=1)
@@ -354,12 +254,12 @@ def test_directions_equal_the_oracle(gpu, family, dtype):
     nl, _ = getattr(autodiff, tl_single)(st, {"t": box.put(dirs[0]["t"])}, eta, dt, ext, want=("tnd_t",), write_nl=True)
     forcing = {n: box.batch([w[d][n] for d in range(ndir)]) for n in NL_OUT}
     out_adj = {n: box.nan(ndir) for n in names}
-    _raw(entry, box, ext, st, forcing, eta, dt, {"fplsl": nl["fplsl"], "fplsn": nl["fplsn"]}, out_adj, ndir)
+    raw_ad(entry, box, ext, st, forcing, eta, dt, {"fplsl": nl["fplsl"], "fplsn": nl["fplsn"]}, out_adj, ndir)
     torch.cuda.synchronize()
     failures = []
     for d in range(ndir):
         for n in names:
-            k = _levels(n, nz)
+            k = adjoint_nlev_of(n, nz)
             a, b = from_device(out_adj[n][d])[:k], want[d][family][n][:k]
             scale = float(np.abs(b).max())
             print(f"{entry} vs oracle {np.dtype(dtype).name} out_{n}_i[{d}]: max |err| / scale "

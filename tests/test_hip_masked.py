@@ -7,141 +7,21 @@ Comparisons with the NumPy oracle use `assert_close` with the factors the suite 
 import numpy as np
 import pytest
 
+from derivative_support import (SHAPES, STATE4, TND4, Box, host_case, host_increments, oracle_nl, oracle_tl_i, raw_ad,
+                                raw_tl)
 from helpers import (NL_IN, NL_OUT, assert_close, externals, from_device, increments, nl_case, nlev_of, run_oracle_ad,
-                     run_oracle_nl, run_oracle_tl)
+                     run_oracle_tl)
 
 pytestmark = pytest.mark.gpu
-
-STATE4 = ("t", "q", "ql", "qi")
-TND4 = ("tnd_t", "tnd_q", "tnd_ql", "tnd_qi")
-SHAPES = [(1, 137, False), (63, 137, False), (200, 137, False), (333, 137, True), (130, 40, False)]
-_cases = {}
-
-
-def _case(nx, nz, dtype, seed=20240807):
-    """host inputs, 1 % increments and the oracle's NL outputs - computed once per shape and never modified"""
-    key = (nx, nz, np.dtype(dtype), seed)
-    if key not in _cases:
-        fields, eta, dt = nl_case(nx, nz, dtype=dtype, seed=seed)
-        _cases[key] = (fields, eta, dt, increments(fields, 0.01), run_oracle_nl(fields, eta, dt, externals()))
-    return _cases[key]
-
-
-_tl = {}
-
-
-def _oracle_tl_i(nx, nz, dtype):
-    """the oracle's TL outputs for the 1 % increments (TL does not depend on AD_TRAJ_FIX): once per shape"""
-    key = (nx, nz, np.dtype(dtype))
-    if key not in _tl:
-        fields, eta, dt, fi, _ = _case(nx, nz, dtype)
-        _tl[key] = run_oracle_tl(fields, fi, eta, dt, externals(NLEV=nz))[1]
-    return _tl[key]
-
-
-class Box:
-    """device fields of one geometry: dense storages, or column windows of wider allocations (lev_stride > nx)"""
-
-    def __init__(self, nx, nz, dtype, device, window):
-        import torch
-
-        from gt4py_dwarf_p_cloudsc2_tl_ad_amd import storage
-
-        self.nx, self.nz, self.device, self.torch, self.storage = nx, nz, device, torch, storage
-        self.dt = storage.torch_dtype(dtype)
-        self.pitch = storage.level_pitch(nx, dtype) + (192 if window else 0)
-        self.col0 = 64 if window else 0
-
-    def nan(self):
-        buf = self.torch.full((self.nz + 1, self.pitch), float("nan"), dtype=self.dt, device=self.device)
-        return self.storage.logical_view(buf[:, self.col0:self.col0 + self.nx])
-
-    def put(self, arr):
-        f = self.nan()
-        self.storage.klayout(f).copy_(self.torch.as_tensor(arr))
-        return f
-
-    def zeros(self):
-        return self.put(np.zeros((self.nz + 1, self.nx)))
-
-    def state(self, fields):
-        return {n: self.put(fields["in_" + n]) for n in NL_IN}
-
-    def stencil(self, name, ext, eta, dt, **fields):
-        from gt4py_dwarf_p_cloudsc2_tl_ad_amd.stencils import compile_stencil
-
-        compile_stencil(name, ext)(**fields, in_eta=eta, dt=dt, origin=(0, 0, 0), domain=(self.nx, 1, self.nz + 1),
-                                   validate_args=True, exec_info=None)
-
-    def nl_fluxes(self, state, ext, eta, dt):
-        outs = {n: self.nan() for n in NL_OUT}
-        self.stencil("cloudsc2_nl", ext, eta, dt, **{"in_" + n: f for n, f in state.items()},
-                     **{"out_" + n: f for n, f in outs.items()})
-        return {"fplsl": outs["fplsl"], "fplsn": outs["fplsn"]}
-
-    def dense_ad_traj(self, state, forcing, traj, ext, eta, dt):
-        adj = {n: self.nan() for n in NL_IN}
-        self.stencil("cloudsc2_ad_from_trajectory", ext, eta, dt, **{"in_" + n: f for n, f in state.items()},
-                     **{"in_" + n + "_i": forcing[n] for n in NL_OUT}, traj_fplsl=traj["fplsl"], traj_fplsn=traj["fplsn"],
-                     **{"out_" + n + "_i": f for n, f in adj.items()})
-        return adj
-
-    def dense_tl(self, state, pert, ext, eta, dt):
-        out, out_i = {n: self.nan() for n in NL_OUT}, {n: self.nan() for n in NL_OUT}
-        self.stencil("cloudsc2_tl", ext, eta, dt, **{"in_" + n: f for n, f in state.items()},
-                     **{"in_" + n + "_i": pert[n] for n in NL_IN}, **{"out_" + n: f for n, f in out.items()},
-                     **{"out_" + n + "_i": f for n, f in out_i.items()})
-        return out, out_i
 
 
 def _setup(gpu, nx, nz, window, dtype, **flags):
     import torch
 
-    fields, eta, dt, fi, nl0 = _case(nx, nz, dtype)
+    fields, eta, dt = host_case(nx, nz, dtype)
     box = Box(nx, nz, dtype, gpu, window)
     ext = externals(NLEV=nz, **flags)
-    return box, ext, fields, torch.as_tensor(eta, device=gpu), dt, fi, box.state(fields)
-
-
-def _raw_masked_ad(box, ext, state, forcing, traj, eta, dt, out_adj):
-    """the C entry itself, with output buffers the test supplies (NaN-prefilled): `out_adj` maps wanted names to buffers"""
-    import ctypes
-
-    import torch
-
-    from gt4py_dwarf_p_cloudsc2_tl_ad_amd import _lib, autodiff
-
-    p = autodiff._params(ext, box.nz)
-    sfx = "f64" if box.dt == torch.float64 else "f32"
-    _, _, ls = box.storage.field_geometry(state["t"])
-    rc = getattr(_lib.load(), "cloudsc2_ad_masked_" + sfx)(
-        ctypes.byref(p), box.nx, box.nz, ls, autodiff._ptrs(state, NL_IN), autodiff._ptrs(forcing, NL_OUT),
-        autodiff._zero_line(gpu_device(box), box.dt).data_ptr(), eta.data_ptr(), traj["fplsl"].data_ptr(),
-        traj["fplsn"].data_ptr(), autodiff._ptrs(out_adj, NL_IN), float(dt), int(torch.cuda.current_stream().cuda_stream))
-    _lib.check(rc, "cloudsc2_ad_masked")
-
-
-def _raw_masked_tl(box, ext, state, pert, eta, dt, out, out_i):
-    """the TL entry itself on buffers the test supplies: `out` is None or all ten NL outputs, `out_i` the wanted ones"""
-    import ctypes
-
-    import torch
-
-    from gt4py_dwarf_p_cloudsc2_tl_ad_amd import _lib, autodiff
-
-    p = autodiff._params(ext, box.nz)
-    sfx = "f64" if box.dt == torch.float64 else "f32"
-    _, _, ls = box.storage.field_geometry(state["t"])
-    rc = getattr(_lib.load(), "cloudsc2_tl_masked_" + sfx)(
-        ctypes.byref(p), box.nx, box.nz, ls, autodiff._ptrs(state, NL_IN), autodiff._ptrs(pert, NL_IN),
-        autodiff._zero_line(gpu_device(box), box.dt).data_ptr(), eta.data_ptr(),
-        None if out is None else autodiff._ptrs(out, NL_OUT), autodiff._ptrs(out_i, NL_OUT), float(dt),
-        int(torch.cuda.current_stream().cuda_stream))
-    _lib.check(rc, "cloudsc2_tl_masked")
-
-
-def gpu_device(box):
-    return box.torch.device(box.device)
+    return box, ext, fields, torch.as_tensor(eta, device=gpu), dt, host_increments(nx, nz, dtype), box.state(fields)
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
@@ -154,7 +34,7 @@ def test_full_mask_ad_is_bit_equal_to_the_trajectory_kernel(gpu, nx, nz, window,
 
     box, ext, fields, eta, dt, fi, state = _setup(gpu, nx, nz, window, dtype, AD_TRAJ_FIX=fix)
     traj = box.nl_fluxes(state, ext, eta, dt)
-    tl_i = _oracle_tl_i(nx, nz, dtype)
+    tl_i = oracle_tl_i(nx, nz, dtype)
     forcing = {n: box.put(tl_i[n]) for n in NL_OUT}
     want = box.dense_ad_traj(state, forcing, traj, ext, eta, dt)
     assert _lib.last_kernel() == "cs2::ad_kernel<trajectory>"
@@ -196,11 +76,11 @@ def test_4dvar_mask_ad_is_bit_equal_to_dense_with_explicit_zeros(gpu, nx, nz, wi
 
     box, ext, fields, eta, dt, fi, state = _setup(gpu, nx, nz, window, dtype, AD_TRAJ_FIX=fix)
     traj = box.nl_fluxes(state, ext, eta, dt)
-    tl_i = _oracle_tl_i(nx, nz, dtype)
+    tl_i = oracle_tl_i(nx, nz, dtype)
     forcing = {n: box.put(tl_i[n]) for n in TND4}
     want = box.dense_ad_traj(state, {n: forcing.get(n) if n in forcing else box.zeros() for n in NL_OUT}, traj, ext, eta, dt)
     bufs = {n: box.nan() for n in NL_IN}                   # every buffer NaN-prefilled; only the wanted four are passed
-    _raw_masked_ad(box, ext, state, forcing, traj, eta, dt, {n: bufs[n] for n in STATE4})
+    raw_ad("cloudsc2_ad_masked", box, ext, state, forcing, eta, dt, traj, {n: bufs[n] for n in STATE4})
     torch.cuda.synchronize()
     for n in NL_IN:
         a = from_device(bufs[n])
@@ -220,12 +100,12 @@ def test_4dvar_mask_tl_matches_the_oracle_fed_explicit_zeros(gpu, nx, nz, window
 
     box, ext, fields, eta, dt, fi, state = _setup(gpu, nx, nz, window, dtype)
     zeros_i = {k: (v if k[3:-2] in STATE4 else np.zeros_like(v)) for k, v in fi.items()}
-    _, want_i = run_oracle_tl(fields, zeros_i, _case(nx, nz, dtype)[1], dt, ext)
+    _, want_i = run_oracle_tl(fields, zeros_i, host_case(nx, nz, dtype)[1], dt, ext)
     pert = {n: box.put(fi["in_" + n + "_i"]) for n in STATE4}
     out, got_i = autodiff.tl_masked(state, pert, eta, dt, ext, want=TND4)
     # and the entry itself on NaN-prefilled buffers: the six absent `out_i` and the ten absent `out` must stay untouched
     bufs, nl_bufs = {n: box.nan() for n in NL_OUT}, {n: box.nan() for n in NL_OUT}
-    _raw_masked_tl(box, ext, state, pert, eta, dt, None, {n: bufs[n] for n in TND4})
+    raw_tl("cloudsc2_tl_masked", box, ext, state, pert, eta, dt, None, {n: bufs[n] for n in TND4})
     torch.cuda.synchronize()
     assert out is None and sorted(got_i) == sorted(TND4)
     for n in TND4:
@@ -250,10 +130,10 @@ def test_each_forcing_alone_matches_the_oracle_adjoint(gpu, name, dtype):
 
     nx, nz = 200, 137
     box, ext, fields, eta, dt, fi, state = _setup(gpu, nx, nz, False, dtype, AD_TRAJ_FIX=1)
-    _, _, _, _, nl0 = _case(nx, nz, dtype)
-    tl_i = _oracle_tl_i(nx, nz, dtype)
+    nl0 = oracle_nl(nx, nz, dtype)
+    tl_i = oracle_tl_i(nx, nz, dtype)
     forcing = {n: (tl_i[n] if n == name else np.zeros_like(tl_i[n])) for n in NL_OUT}
-    _, want = run_oracle_ad(fields, forcing, _case(nx, nz, dtype)[1], dt, ext, traj=nl0)
+    _, want = run_oracle_ad(fields, forcing, host_case(nx, nz, dtype)[1], dt, ext, traj=nl0)
     traj = box.nl_fluxes(state, ext, eta, dt)
     got = autodiff.ad_masked(state, {name: box.put(tl_i[name])}, eta, dt, ext, traj=traj, want=NL_IN)
     torch.cuda.synchronize()
@@ -272,7 +152,7 @@ def test_each_perturbation_alone_matches_the_oracle_tl(gpu, name, dtype):
     nx, nz = 200, 137
     box, ext, fields, eta, dt, fi, state = _setup(gpu, nx, nz, False, dtype)
     one = {k: (v if k == "in_" + name + "_i" else np.zeros_like(v)) for k, v in fi.items()}
-    _, want_i = run_oracle_tl(fields, one, _case(nx, nz, dtype)[1], dt, ext)
+    _, want_i = run_oracle_tl(fields, one, host_case(nx, nz, dtype)[1], dt, ext)
     _, got_i = autodiff.tl_masked(state, {name: box.put(fi["in_" + name + "_i"])}, eta, dt, ext, want=NL_OUT)
     torch.cuda.synchronize()
     for n in NL_OUT:

@@ -7,24 +7,17 @@ Directions are independent: direction d is the `helpers.increments` of a state d
 0.01 (d + 1).  Against the NumPy oracle the perturbations are held to 100 x `assert_close`, as everywhere in the suite
 (tests/test_hip_tl_ad.py, tests/test_step_grad.py); for the step family the oracle's TL is chained with the analytic
 derivative of `saturation` (tests/saturation_oracle.py), as tests/test_step_grad.py does."""
-import ctypes
-
 import numpy as np
 import pytest
 
-from helpers import NL_IN, NL_OUT, assert_close, externals, from_device, increments, nl_case, nlev_of, run_oracle_tl
+from derivative_support import SHAPES, STATE4, STEP_IN, TND4, Box, compare_directions, direction_case, raw_tl, singles
+from helpers import NL_IN, NL_OUT, assert_close, externals, from_device, nlev_of, run_oracle_tl
 from saturation_oracle import saturation_derivative
 
 pytestmark = pytest.mark.gpu
 
-STATE4 = ("t", "q", "ql", "qi")
-TND4 = ("tnd_t", "tnd_q", "tnd_ql", "tnd_qi")
-STEP_IN = tuple(n for n in NL_IN if n != "qsat")
-SHAPES = [(1, 137, False), (63, 137, False), (200, 137, False), (333, 137, True), (130, 40, False)]
 FAMILIES = {"multi": ("cloudsc2_tl_multi", "tl_masked", "cs2::tl_dirs_kernel", NL_IN),
             "step": ("cloudsc2_tl_multi_step", "tl_step", "cs2::tl_dirs_step_kernel", STEP_IN)}
-SEED = 20240807
-_cases = {}
 
 
 def _max_dirs():
@@ -33,109 +26,21 @@ def _max_dirs():
     return _lib.TL_MAX_DIRS
 
 
-def _case(nx, nz, dtype, ndir):
-    """host state and `ndir` independent increments: computed once per shape, never modified; fewer directions are the
-    first ones of more"""
-    key = (nx, nz, np.dtype(dtype))
-    if key not in _cases:
-        _cases[key] = (nl_case(nx, nz, dtype=dtype, seed=SEED), [])
-    (fields, eta, dt), dirs = _cases[key]
-    while len(dirs) < ndir:
-        d = len(dirs)
-        other = nl_case(nx, nz, dtype=dtype, seed=SEED + 1 + d)[0]
-        dirs.append({k[3:-2]: v for k, v in increments(other, 0.01 * (d + 1)).items()})
-    return fields, eta, dt, dirs[:ndir]
-
-
-class Box:
-    """device fields of one geometry - dense storages, or column windows of wider allocations (lev_stride > nx) - and
-    batches of them: `slots` fields in one allocation, one behind the other"""
-
-    def __init__(self, nx, nz, dtype, device, window):
-        import torch
-
-        from gt4py_dwarf_p_cloudsc2_tl_ad_amd import storage
-
-        self.nx, self.nz, self.device, self.torch, self.storage = nx, nz, device, torch, storage
-        self.dt = storage.torch_dtype(dtype)
-        self.sfx = "f64" if self.dt == torch.float64 else "f32"
-        self.pitch = storage.level_pitch(nx, dtype) + (192 if window else 0)
-        self.col0 = 64 if window else 0
-
-    def nan(self, slots=None):
-        shape = (self.nz + 1, self.pitch) if slots is None else (slots, self.nz + 1, self.pitch)
-        buf = self.torch.full(shape, float("nan"), dtype=self.dt, device=self.device)[..., self.col0:self.col0 + self.nx]
-        return self.storage.logical_view(buf) if slots is None else buf.unsqueeze(2).permute(0, 3, 2, 1)
-
-    def put(self, arr):
-        f = self.nan()
-        self.storage.klayout(f).copy_(self.torch.as_tensor(arr))
-        return f
-
-    def batch(self, arrs, slots=None):
-        """(slots, nx, 1, nz+1) with direction d = arrs[d]; further slots stay NaN"""
-        f = self.nan(len(arrs) if slots is None else slots)
-        for d, a in enumerate(arrs):
-            self.storage.klayout(f[d]).copy_(self.torch.as_tensor(a))
-        return f
-
-    @property
-    def dir_stride(self):
-        return (self.nz + 1) * self.pitch
-
-
 def _setup(gpu, nx, nz, window, dtype, ndir, **flags):
     import torch
 
-    fields, eta, dt, dirs = _case(nx, nz, dtype, ndir)
+    fields, eta, dt, dirs = direction_case(nx, nz, dtype, ndir)
     box = Box(nx, nz, dtype, gpu, window)
-    state = {n: box.put(fields["in_" + n]) for n in NL_IN}
-    return box, externals(NLEV=nz, **flags), fields, torch.as_tensor(eta, device=gpu), dt, dirs, state
-
-
-def _raw(entry, box, ext, state, pert, eta, dt, out, out_i, ndir):
-    """the C entry itself on buffers the test supplies: `pert` / `out_i` map names to batches, `out` is None or ten fields"""
-    import torch
-
-    from gt4py_dwarf_p_cloudsc2_tl_ad_amd import _lib, autodiff
-
-    p = autodiff._params(ext, box.nz)
-    rc = getattr(_lib.load(), f"{entry}_{box.sfx}")(
-        ctypes.byref(p), box.nx, box.nz, box.pitch, autodiff._ptrs(state, NL_IN), autodiff._ptrs({n: f[0] for n, f in pert.items()}, NL_IN),
-        autodiff._zero_line(torch.device(box.device), box.dt).data_ptr(), eta.data_ptr(),
-        None if out is None else autodiff._ptrs(out, NL_OUT), autodiff._ptrs({n: f[0] for n, f in out_i.items()}, NL_OUT),
-        float(dt), int(torch.cuda.current_stream().cuda_stream), ndir, box.dir_stride, box.dir_stride)
-    _lib.check(rc, entry)
+    return box, externals(NLEV=nz, **flags), fields, torch.as_tensor(eta, device=gpu), dt, dirs, box.state(fields)
 
 
 def _singles(family, state, names, pert, eta, dt, ext, want, ndir):
     """the single-direction launch for each direction alone -> per direction {name: host array}"""
-    from gt4py_dwarf_p_cloudsc2_tl_ad_amd import _lib, autodiff
+    from gt4py_dwarf_p_cloudsc2_tl_ad_amd import autodiff
 
-    single = getattr(autodiff, FAMILIES[family][1])
-    st = {n: state[n] for n in names}
-    rows = []
-    for d in range(ndir):
-        _, out_i = single(st, {n: f[d] for n, f in pert.items()}, eta, dt, ext, want=want)
-        assert _lib.last_kernel() == "cs2::" + FAMILIES[family][1] + "_kernel"
-        rows.append({n: from_device(out_i[n]) for n in want})
-    return rows
-
-
-def _compare(what, got_batch, rows, want, nz, dtype, ndir):
-    """direction by direction against the single launches; the slots behind `ndir` are untouched"""
-    equal = True
-    for n in want:
-        k = nlev_of(n, nz)
-        for d in range(ndir):
-            a, b = from_device(got_batch[n][d]), rows[d][n]
-            assert not np.isnan(a[:k]).any(), (what, n, d)
-            assert_close(f"{what} out_{n}_i[{d}]", a[:k], b[:k], dtype)
-            assert np.isnan(a[k:]).all(), f"{what} {n}[{d}]: padding level written"
-            equal = equal and np.array_equal(a[:k], b[:k])
-        for d in range(ndir, got_batch[n].shape[0]):
-            assert np.isnan(from_device(got_batch[n][d])).all(), f"{what} {n}: slot {d} >= ndir={ndir} written"
-    print(f"{what} ndir={ndir} {np.dtype(dtype).name}: bit-equal to the single launches: {equal}")
+    single = FAMILIES[family][1]
+    return singles(getattr(autodiff, single), "cs2::" + single + "_kernel", {n: state[n] for n in names}, pert, eta, dt, ext,
+                   want, ndir)
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
@@ -155,10 +60,10 @@ def test_full_mask_every_direction_equals_the_single_launch(gpu, nx, nz, window,
     for ndir in (1, 2, 3, top):
         out_i = {n: box.nan(top + 1) for n in NL_OUT}
         out = {n: box.nan() for n in NL_OUT} if ndir == 3 else None
-        _raw(entry, box, ext, state, pert, eta, dt, out, out_i, ndir)
+        raw_tl(entry, box, ext, state, pert, eta, dt, out, out_i, ndir)
         assert _lib.last_kernel() == kernel
         torch.cuda.synchronize()
-        _compare(f"{entry} {nx}x{nz}", out_i, rows, NL_OUT, nz, dtype, ndir)
+        compare_directions(f"{entry} {nx}x{nz}", out_i, rows, NL_OUT, nz, dtype, ndir)
         if out is not None:                       # write_nl: the NL outputs are cloudsc2_nl's (on the step's own qsat)
             nl = {n: box.nan() for n in NL_OUT}
             ins = {"in_" + n: f for n, f in state.items()}
@@ -196,10 +101,10 @@ def test_masks(gpu, nx, nz, window, mask, family, dtype):
     pert = {n: box.batch([u[n] for u in dirs]) for n in have}
     rows = _singles(family, state, names, pert, eta, dt, ext, want, ndir)
     out_i = {n: box.nan(ndir + 1) for n in want}
-    _raw(entry, box, ext, state, pert, eta, dt, None, out_i, ndir)
+    raw_tl(entry, box, ext, state, pert, eta, dt, None, out_i, ndir)
     assert _lib.last_kernel() == kernel
     torch.cuda.synchronize()
-    _compare(f"{entry} [{mask}]", out_i, rows, want, nz, dtype, ndir)
+    compare_directions(f"{entry} [{mask}]", out_i, rows, want, nz, dtype, ndir)
     if "fplsl" in want:
         for d in range(ndir):
             assert not from_device(out_i["fplsl"][d])[0].any()
@@ -226,10 +131,10 @@ def test_other_switches(gpu, flags, family, dtype):
     if flags.get("LEVAPLS2"):                     # the block is exercised: the evaporation's cover perturbation is there
         assert all(np.isfinite(r[n]).all() for r in rows for n in NL_OUT) and all(r["covptot"].any() for r in rows)
     out_i = {n: box.nan(ndir) for n in NL_OUT}
-    _raw(entry, box, ext, state, pert, eta, dt, None, out_i, ndir)
+    raw_tl(entry, box, ext, state, pert, eta, dt, None, out_i, ndir)
     assert _lib.last_kernel() == kernel
     torch.cuda.synchronize()
-    _compare(f"{entry} {flags}", out_i, rows, NL_OUT, nz, dtype, ndir)
+    compare_directions(f"{entry} {flags}", out_i, rows, NL_OUT, nz, dtype, ndir)
 
 
 @pytest.mark.parametrize("dtype", [np.float64, np.float32])
@@ -274,7 +179,7 @@ def test_directions_equal_the_oracle(gpu, family, dtype):
     box, ext, fields, eta, dt, dirs, state = _setup(gpu, nx, nz, False, dtype, ndir)
     pert = {n: box.batch([u[n] for u in dirs]) for n in names}
     out_i = {n: box.nan(ndir) for n in NL_OUT}
-    _raw(entry, box, ext, state, pert, eta, dt, None, out_i, ndir)
+    raw_tl(entry, box, ext, state, pert, eta, dt, None, out_i, ndir)
     torch.cuda.synchronize()
     _, g_t, g_ap, _ = saturation_derivative(fields["in_ap"], fields["in_t"], ext)
     for d, u in enumerate(dirs):

@@ -4,35 +4,9 @@ import ctypes
 
 import pytest
 
+from abi_calls import call  # noqa: F401  (a fixture)
 
-@pytest.fixture()
-def call(hip_lib):
-    from gt4py_dwarf_p_cloudsc2_tl_ad_amd import _lib
-    from gt4py_dwarf_p_cloudsc2_tl_ad_amd.params import default_externals, make_params
-
-    class Call:
-        P = 4096                  # a non-NULL, 16-byte aligned dummy pointer: never dereferenced on these paths
-        arr = staticmethod(_lib.ptr_array)
-        err = staticmethod(_lib.last_error)
-
-        def params(self, **over):
-            return make_params(dict(default_externals(), NLEV=137, **over))
-
-        def tl(self, p, nx=64, ls=64, in_=None, in_i=None, zero=P, eta=P, out=None, out_i=None, sfx="f64"):
-            a = self.arr
-            return getattr(hip_lib, "cloudsc2_tl_masked_" + sfx)(
-                ctypes.byref(p), nx, 137, ls, a([self.P] * 16) if in_ is None else in_,
-                a([self.P] * 16) if in_i is None else in_i, zero, eta, out, a([self.P] * 10) if out_i is None else out_i,
-                3600.0, None)
-
-        def ad(self, p, nx=64, ls=64, in_=None, in_adj=None, zero=P, eta=P, tl=P, tn=P, out_adj=None, sfx="f64"):
-            a = self.arr
-            return getattr(hip_lib, "cloudsc2_ad_masked_" + sfx)(
-                ctypes.byref(p), nx, 137, ls, a([self.P] * 16) if in_ is None else in_,
-                a([self.P] * 10) if in_adj is None else in_adj, zero, eta, tl, tn,
-                a([self.P] * 16) if out_adj is None else out_adj, 3600.0, None)
-
-    return Call()
+FAMILY = "masked"
 
 
 def test_abi_version_is_4(hip_lib):

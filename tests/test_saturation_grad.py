@@ -14,6 +14,7 @@ import ctypes
 import numpy as np
 import pytest
 
+from derivative_support import Box
 from helpers import assert_close, externals, from_device, nl_case
 from saturation_oracle import ew_numpy, saturation_derivative
 
@@ -54,28 +55,11 @@ def _case(dtype, form):
     return _cases[key]
 
 
-class Dev:
-    """device fields of the case's geometry: dense storages, or column windows of wider allocations (lev_stride > nx)"""
+class Dev(Box):
+    """the `Box` of the case's geometry, and the pointwise C entries (field pointers, no pointer arrays) on its fields"""
 
     def __init__(self, gpu, dtype, window):
-        import torch
-
-        from gt4py_dwarf_p_cloudsc2_tl_ad_amd import storage
-
-        self.torch, self.storage, self.gpu, self.dtype = torch, storage, gpu, dtype
-        self.dt = storage.torch_dtype(dtype)
-        self.pitch = storage.level_pitch(NX, dtype) + (192 if window else 0)
-        self.col0 = 64 if window else 0
-        self.sfx = "f64" if np.dtype(dtype) == np.float64 else "f32"
-
-    def nan(self):
-        buf = self.torch.full((NZ + 1, self.pitch), float("nan"), dtype=self.dt, device=self.gpu)
-        return self.storage.logical_view(buf[:, self.col0:self.col0 + NX])
-
-    def put(self, arr):
-        f = self.nan()
-        self.storage.klayout(f).copy_(self.torch.as_tensor(arr))
-        return f
+        super().__init__(NX, NZ, dtype, gpu, window)
 
     def call(self, name, ext, *args):
         from gt4py_dwarf_p_cloudsc2_tl_ad_amd import _lib, autodiff

@@ -1,62 +1,19 @@
 """Host-side contract of the derivative entries of the whole step (`cloudsc2_saturation_tl_*` / `_ad_*`, `cloudsc2_tl_step_*`
 / `cloudsc2_ad_step_*`): every argument error is settled before anything is launched, so none of this needs a GPU."""
-import ctypes
-
 import pytest
 
-QSAT = 9     # NL_IN_QSAT
+from abi_calls import call  # noqa: F401  (a fixture)
+from abi_calls import header as _header
+
+FAMILY = "step"
 SYMBOLS = [f"cloudsc2_{n}_{s}" for n in ("saturation_tl", "saturation_ad", "tl_step", "ad_step") for s in ("f64", "f32")]
 
 
-@pytest.fixture()
-def call(hip_lib):
-    from gt4py_dwarf_p_cloudsc2_tl_ad_amd import _lib
-    from gt4py_dwarf_p_cloudsc2_tl_ad_amd.params import default_externals, make_params
-
-    class Call:
-        P = 4096                  # a non-NULL, 16-byte aligned dummy pointer: never dereferenced on these paths
-        arr = staticmethod(_lib.ptr_array)
-        err = staticmethod(_lib.last_error)
-
-        def params(self, **over):
-            return make_params(dict(default_externals(), NLEV=137, **over))
-
-        def no_qsat(self, n=16, fill=None):
-            fill = self.P if fill is None else fill
-            return self.arr([0 if i == QSAT else fill for i in range(n)])
-
-        def tl(self, p, nx=64, ls=64, in_=None, in_i=None, zero=P, eta=P, out=None, out_i=None, sfx="f64"):
-            a = self.arr
-            return getattr(hip_lib, "cloudsc2_tl_step_" + sfx)(
-                ctypes.byref(p), nx, 137, ls, self.no_qsat() if in_ is None else in_,
-                self.no_qsat() if in_i is None else in_i, zero, eta, out, a([self.P] * 10) if out_i is None else out_i,
-                3600.0, None)
-
-        def ad(self, p, nx=64, ls=64, in_=None, in_adj=None, zero=P, eta=P, tl=P, tn=P, out_adj=None, sfx="f64"):
-            a = self.arr
-            return getattr(hip_lib, "cloudsc2_ad_step_" + sfx)(
-                ctypes.byref(p), nx, 137, ls, self.no_qsat() if in_ is None else in_,
-                a([self.P] * 10) if in_adj is None else in_adj, zero, eta, tl, tn,
-                self.no_qsat() if out_adj is None else out_adj, 3600.0, None)
-
-        def sat_tl(self, p, nx=64, ap=P, t=P, ap_i=P, t_i=P, qsat=P, qsat_i=P, sfx="f64"):
-            return getattr(hip_lib, "cloudsc2_saturation_tl_" + sfx)(ctypes.byref(p), nx, 137, max(nx, 64), ap, t, ap_i, t_i,
-                                                                      qsat, qsat_i, None)
-
-        def sat_ad(self, p, nx=64, ap=P, t=P, q=P, ap_adj=P, t_adj=P, acc=0, sfx="f64"):
-            return getattr(hip_lib, "cloudsc2_saturation_ad_" + sfx)(ctypes.byref(p), nx, 137, max(nx, 64), ap, t, q, ap_adj,
-                                                                      t_adj, acc, None)
-
-    return Call()
-
-
 def test_the_eight_symbols_are_exported_and_declared(hip_lib):
-    import os
-
     from gt4py_dwarf_p_cloudsc2_tl_ad_amd import _lib
     from gt4py_dwarf_p_cloudsc2_tl_ad_amd.params import ABI_VERSION
 
-    header = open(os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "include", "cloudsc2_hip.h")).read()
+    header = _header()
     for s in SYMBOLS:
         assert s in _lib.EXPORTED_SYMBOLS and hasattr(hip_lib, s), s
         assert f"int32_t {s}(" in header, s

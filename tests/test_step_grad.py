@@ -9,37 +9,15 @@ differently (tests/test_hip_masked.py), |norm1 - norm2| / (eps norm2) < 1e4 per 
 import numpy as np
 import pytest
 
-from helpers import (NL_IN, NL_OUT, assert_close, externals, from_device, increments, nl_case, nlev_of, run_oracle_ad,
-                     run_oracle_nl, run_oracle_tl, to_device)
-from saturation_oracle import saturation_derivative
+from derivative_support import STEP_IN, autodiff_case as _case, device_state
+from helpers import NL_OUT, assert_close, externals, from_device, increments, nlev_of, run_oracle_ad, run_oracle_tl, to_device
 
 pytestmark = pytest.mark.gpu
-NX, NZ = 200, 137
-STEP_IN = tuple(n for n in NL_IN if n != "qsat")
-_host = {}
+NX, NZ = 200, 137          # `autodiff_case`'s own
 
 
-def _case(dtype, nx=NX, **flags):
-    """host inputs (in_qsat: the oracle's saturation), a weight field, the oracle's NL outputs and saturation's derivative"""
-    key = (np.dtype(dtype), nx, tuple(sorted(flags.items())))
-    if key not in _host:
-        ext = externals(**flags)
-        fields, eta, dt = nl_case(nx, NZ, dtype=dtype, ext=ext)
-        w = np.random.default_rng(5).standard_normal(fields["in_t"].shape).astype(dtype)
-        _, g_t, g_ap, _ = saturation_derivative(fields["in_ap"], fields["in_t"], ext)
-        _host[key] = dict(fields=fields, eta=eta, dt=dt, w=w, nl0=run_oracle_nl(fields, eta, dt, ext), g_t=g_t, g_ap=g_ap,
-                          ext=ext)
-    return _host[key]
-
-
-def _state(gpu, c, grad=(), with_qsat=False):
-    import torch
-
-    dev = to_device(c["fields"], gpu)
-    state = {n: dev["in_" + n] for n in (NL_IN if with_qsat else STEP_IN)}
-    for n in grad:
-        state[n].requires_grad_(True)
-    return state, torch.as_tensor(c["eta"], device=gpu), c["dt"], to_device({"w": c["w"]}, gpu)["w"]
+def _state(gpu, c, grad=()):
+    return device_state(gpu, c, STEP_IN, grad)
 
 
 def _forcing(c, **given):
