@@ -108,6 +108,10 @@ LAYOUTS: Dict[str, Layout] = {
 #: `in_dir_stride` and `out_dir_stride` (elements)
 MULTI_LAYOUTS: Dict[str, str] = {"tl_multi": "tl_masked", "tl_multi_step": "tl_step",
                                  "ad_multi": "ad_masked", "ad_multi_step": "ad_step"}
+#: the ensemble entries (autodiff calls them directly): name -> the single entry whose argument list they repeat, followed by
+#: `nmem` and `member_stride` (elements; one stride for every field of the call)
+ENS_LAYOUTS: Dict[str, str] = {"nl_ens": "nl", "nl_fused_ens": "nl_fused", "tl_ens": "tl_masked", "tl_step_ens": "tl_step",
+                               "ad_ens": "ad_masked", "ad_step_ens": "ad_step"}
 #: CLOUDSC2_TL_MAX_DIRS of include/cloudsc2_hip.h
 TL_MAX_DIRS = 8
 #: CLOUDSC2_AD_MAX_DIRS of include/cloudsc2_hip.h
@@ -148,6 +152,8 @@ def _signatures() -> Dict[str, Tuple[Any, Tuple[Any, ...]]]:
         for lay in LAYOUTS.values():
             sig[f"cloudsc2_{lay.entry}_{sfx}"] = (c_int32, (POINTER(Cloudsc2Params), c_int32, c_int32, c_int64)
                                                   + tuple(t for a in lay.args for t in _CTYPES[a.kind]))
+        for ens, single in ENS_LAYOUTS.items():
+            sig[f"cloudsc2_{ens}_{sfx}"] = (c_int32, sig[f"cloudsc2_{single}_{sfx}"][1] + (c_int32, c_int64))
     return sig
 
 

@@ -23,9 +23,21 @@ width per precision is `AD_MULTI_WIDTH`, set from the measurement of docs/TUNING
 over TANGENTS or COTANGENTS (`vmap` of `jvp`, which is what `jacfwd` is; `vmap` of a `vjp` function, which is what `jacrev`
 is).  Batched tangents run `tl_multi` / `tl_step_multi`; batched cotangents run `ad_multi` / `ad_step_multi` (the
 evaporation switches and the non-LPHYLIN step, which have no multi-direction kernel, loop over their single-cotangent
-fallbacks, and so does `saturation`, which is pointwise).  Not supported: `vmap` over the STATE (`NotImplementedError`),
-`torch.autograd.grad(..., is_grads_batched=True)` (the legacy vmap, which knows no `vmap` rule of a Function), second
-derivatives."""
+fallbacks, and so does `saturation`, which is pointwise).
+
+ENSEMBLES: many states, one launch.  `cloudsc2_ensemble` / `cloudsc2_step_ensemble` are the two Functions on member-major
+`(nmem, nx, 1, nz+1)` fields - the layout of `storage.zeros_batched`, of `torch.stack` and of every `*_multi` result; `eta`,
+`dt` and the externals are shared - and `tl_masked_ens` / `tl_step_ens` / `ad_masked_ens` / `ad_step_ens` the thin calls (C ABI
+`cloudsc2_{nl,nl_fused,tl,tl_step,ad,ad_step}_ens_*`: one workgroup serves one column block of one member; a tensor in
+another layout is copied once).  `vmap` over the STATE of `cloudsc2` / `cloudsc2_step` runs them - `vmap(f)`,
+`vmap(grad(cost))`, `grad` through `vmap`, `vmap` of `jvp` over states and tangents - for a WHOLE state: every field batched (a state batched in part is refused as
+before: `expand` the fields the members share), unbatched tangents / cotangents expanded.  What
+has no ensemble kernel loops over the members through the single paths: the evaporation switches in the adjoint, the
+non-LPHYLIN step, and `saturation` with its derivatives (pointwise).  docs/TUNING_LOG.md 3.20 has the measurement.
+
+Not supported: members TIMES directions in one call (nested `vmap`, e.g. `vmap(jacrev(f))`) and a batched `eta`
+(`NotImplementedError`), `torch.autograd.grad(..., is_grads_batched=True)` (the legacy vmap, which knows no `vmap` rule of a
+Function), second derivatives."""
 from __future__ import annotations
 
 import ctypes
@@ -36,7 +48,7 @@ import torch
 from . import _lib
 from ._lib import NL_IN, NL_OUT
 from .params import default_externals, make_params
-from .storage import direction_stride, field_geometry, zeros, zeros_batched
+from .storage import direction_stride, field_geometry, level_pitch, zeros, zeros_batched
 
 _SFX = {torch.float64: "f64", torch.float32: "f32"}
 #: the inputs of the step: those of `cloudsc2_nl` without `qsat`, which the step forms from `ap` and `t`
@@ -64,12 +76,13 @@ class _Family(NamedTuple):
     width: Dict[torch.dtype, int]    # directions per launch by default, per precision
     max_dirs: int                    # the most one launch takes
     adjoint: bool = False            # forcing (`NL_OUT` names) and `traj` in, adjoints of `names` out; else the tangent-linear
+    ens: str = ""                    # its ensemble form (`_lib.ENS_LAYOUTS`): the same arguments + (nmem, member_stride)
 
 
-_TL_MASKED = _Family("tl_masked", "tl_multi", NL_IN, MULTI_WIDTH, _lib.TL_MAX_DIRS)
-_TL_STEP = _Family("tl_step", "tl_multi_step", STEP_IN, MULTI_WIDTH, _lib.TL_MAX_DIRS)
-_AD_MASKED = _Family("ad_masked", "ad_multi", NL_IN, AD_MULTI_WIDTH, _lib.AD_MAX_DIRS, adjoint=True)
-_AD_STEP = _Family("ad_step", "ad_multi_step", STEP_IN, AD_MULTI_WIDTH, _lib.AD_MAX_DIRS, adjoint=True)
+_TL_MASKED = _Family("tl_masked", "tl_multi", NL_IN, MULTI_WIDTH, _lib.TL_MAX_DIRS, ens="tl_ens")
+_TL_STEP = _Family("tl_step", "tl_multi_step", STEP_IN, MULTI_WIDTH, _lib.TL_MAX_DIRS, ens="tl_step_ens")
+_AD_MASKED = _Family("ad_masked", "ad_multi", NL_IN, AD_MULTI_WIDTH, _lib.AD_MAX_DIRS, adjoint=True, ens="ad_ens")
+_AD_STEP = _Family("ad_step", "ad_multi_step", STEP_IN, AD_MULTI_WIDTH, _lib.AD_MAX_DIRS, adjoint=True, ens="ad_step_ens")
 _ZERO_LINE_BYTES = 512
 _zero_lines: Dict[Tuple[torch.device, torch.dtype], torch.Tensor] = {}
 
@@ -220,20 +233,77 @@ def ad_step_multi(state: Mapping[str, torch.Tensor], forcing: Mapping[str, torch
     return _call(_AD_STEP, True, state, forcing, eta, dt, externals, want, traj=traj, width=width)
 
 
-def _batched_layout(g: torch.Tensor, ref: torch.Tensor, geo) -> torch.Tensor:
-    """`g` as `ndir` fields of the call's geometry, one field behind the other: itself, or a copy into a `zeros_batched`
-    allocation (what `_in_layout` is for one direction)"""
+def tl_masked_ens(states: Mapping[str, torch.Tensor], perturbations: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+                  externals: Optional[Mapping[str, Any]] = None, *, want: Iterable[str], write_nl: bool = False):
+    """`tl_masked` for an ENSEMBLE of `nmem` states in ONE launch (`cloudsc2_tl_ens_*`): `states` and `perturbations` map
+    names to member-major `(nmem, nx, 1, nz+1)` tensors - the layout of `storage.zeros_batched`, of `torch.stack` and of
+    every `*_multi` result; `eta`, `dt` and the externals are shared.  Every member is an independent `tl_masked` call.
+    Returns `(nl_outputs or None, {name: (nmem, nx, 1, nz+1)})`, one `storage.zeros_batched` allocation per name.  A tensor
+    that is not laid out like the first state field (as `zeros_batched` gives) is copied into such a field first."""
+    return _call(_TL_MASKED, False, states, perturbations, eta, dt, externals, want, write_nl=write_nl, ens=True)
+
+
+def tl_step_ens(states: Mapping[str, torch.Tensor], perturbations: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+                externals: Optional[Mapping[str, Any]] = None, *, want: Iterable[str], write_nl: bool = False):
+    """`tl_step` for an ensemble of states in one launch (`cloudsc2_tl_step_ens_*`; `STEP_IN` names): see `tl_masked_ens`."""
+    return _call(_TL_STEP, False, states, perturbations, eta, dt, externals, want, write_nl=write_nl, ens=True)
+
+
+def ad_masked_ens(states: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+                  externals: Optional[Mapping[str, Any]] = None, *, traj: Mapping[str, torch.Tensor], want: Iterable[str]):
+    """`ad_masked` for an ensemble of `nmem` states in ONE launch (`cloudsc2_ad_ens_*`): `states`, `forcing` and `traj` map
+    names to member-major `(nmem, nx, 1, nz+1)` tensors (see `tl_masked_ens`); every member is an independent `ad_masked`
+    call.  Returns `{name: (nmem, nx, 1, nz+1)}`.  LEVAPLS2 / LDRAIN1D are refused (`ValueError`)."""
+    return _call(_AD_MASKED, False, states, forcing, eta, dt, externals, want, traj=traj, ens=True)
+
+
+def ad_step_ens(states: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+                externals: Optional[Mapping[str, Any]] = None, *, traj: Mapping[str, torch.Tensor], want: Iterable[str]):
+    """`ad_step` for an ensemble of states in one launch (`cloudsc2_ad_step_ens_*`; `STEP_IN` names): see `ad_masked_ens`."""
+    return _call(_AD_STEP, False, states, forcing, eta, dt, externals, want, traj=traj, ens=True)
+
+
+def _batched_layout(g: torch.Tensor, ref: torch.Tensor, geo, stride: Optional[int] = None) -> torch.Tensor:
+    """`g` as `ndir` fields of the call's geometry, one field behind the other (`stride` elements apart; by default packed,
+    as `zeros_batched` gives): itself, or a copy into such an allocation (what `_in_layout` is for one direction)"""
     g = _plain(g)
     nx, nlev, ls = geo
+    stride = nlev * ls if stride is None else stride
     if g.dtype == ref.dtype and g.device == ref.device and g.dim() == 4 and tuple(g.shape[1:]) == (nx, 1, nlev):
         try:
-            if field_geometry(g[0]) == geo and direction_stride(g) == nlev * ls:
+            if field_geometry(g[0]) == geo and direction_stride(g) == stride:
                 return g
         except ValueError:
             pass
-    f = zeros_batched(g.shape[0], nx, nlev - 1, ref.dtype, ref.device, ls)
+    f = _zeros_members(g.shape[0], geo, ref.dtype, ref.device, stride)
     f.copy_(g)
     return f
+
+
+def _zeros_members(n: int, geo, dtype, device, stride: int) -> torch.Tensor:
+    """`zeros_batched` with `stride` elements from one entry to the next (packed: one `zeros_batched` allocation)"""
+    nx, nlev, ls = geo
+    if stride == nlev * ls:
+        return zeros_batched(n, nx, nlev - 1, dtype, device, ls)
+    return torch.zeros((n, stride), dtype=dtype, device=device)[:, :nlev * ls].view(n, nlev, ls)[:, :, :nx] \
+        .unsqueeze(2).permute(0, 3, 2, 1)
+
+
+def _ens_geometry(what: str, first: torch.Tensor):
+    """(nmem, (nx, nlev, lev_stride), member stride) an ensemble call takes from its first state tensor: that tensor's own
+    if it is a batch of column-fastest fields, else the packed `zeros_batched` layout it will be copied into"""
+    if not isinstance(first, torch.Tensor) or first.dim() != 4 or first.shape[2] != 1 or first.shape[0] < 1:
+        raise ValueError(f"{what}: every field must be a member-major (nmem, nx, 1, nz+1) tensor, got "
+                         f"{tuple(getattr(first, 'shape', ()))}")
+    if not first.is_cuda:
+        raise ValueError(f"{what}: fields live on {first.device}; they must live on the GPU (there is no host path)")
+    try:
+        geo = field_geometry(first[0])
+        return first.shape[0], geo, direction_stride(first)
+    except ValueError:
+        nx, nlev = first.shape[1], first.shape[3]
+        geo = (nx, nlev, level_pitch(nx, first.dtype))
+        return first.shape[0], geo, geo[1] * geo[2]
 
 
 def _batch_size(what, noun, dirs, names, geo) -> int:
@@ -272,17 +342,34 @@ def _ad_args(p, geo, state, forcing, zero_line, eta, traj, out_adj, dt, stream, 
             stream) + tail
 
 
-def _call(fam: _Family, batched: bool, state, dirs, eta, dt, externals, want, *, traj=None, write_nl=False, width=None):
-    """The launch path of the eight thin calls.  Everything is checked ONCE, up front; then the directions are served in
+def _call(fam: _Family, batched: bool, state, dirs, eta, dt, externals, want, *, traj=None, write_nl=False, width=None,
+          ens=False):
+    """The launch path of the twelve thin calls.  Everything is checked ONCE, up front; then the directions are served in
     chunks of at most `width`: a chunk of one direction by the single-direction entry, a wider one by the multi-direction
     entry.  `batched`: `dirs` maps names to (ndir, nx, 1, nlev) batches and so do the results, which are one `zeros_batched`
     allocation per wanted name that every chunk writes through the views `f[d0]`; otherwise `dirs` and the results are
-    single fields and there is one launch.  The NL outputs of `write_nl` are new fields, written by the first launch."""
-    what = fam.multi if batched else fam.single
+    single fields and there is one launch.  The NL outputs of `write_nl` are new fields, written by the first launch.
+    `ens`: EVERY tensor of the call - state, `dirs`, `traj`, the results - is a member-major (nmem, nx, 1, nlev) batch of one
+    layout (that of the first state tensor, `_ens_geometry`); the checks run on member 0 and ONE launch of the family's
+    ensemble entry, given member 0's pointers and (nmem, member stride), serves all members."""
+    what = fam.ens if ens else fam.multi if batched else fam.single
     noun, dir_names, res_names = ("forcing", NL_OUT, fam.names) if fam.adjoint else ("perturbation", fam.names, NL_OUT)
     want = tuple(want)
     if not want or set(want) - set(res_names):
         raise ValueError(f"{what}: `want` must name at least one of {res_names}, got {want}")
+    nmem = mstride = 0
+    if ens:
+        first = state.get(fam.names[0])
+        nmem, egeo, mstride = _ens_geometry(what, first)
+
+        def members(fields):    # -> member 0 of every tensor, in the call's layout
+            for n, f in fields.items():
+                if not isinstance(f, torch.Tensor) or tuple(f.shape) != (nmem, egeo[0], 1, egeo[1]):
+                    raise ValueError(f"{what}: {n} must be a tensor of shape {(nmem, egeo[0], 1, egeo[1])} like the state's "
+                                     f"{fam.names[0]}, got {tuple(getattr(f, 'shape', ()))}")
+            return {n: _batched_layout(f, first, egeo, mstride)[0] for n, f in fields.items()}
+        state, dirs = members(state), members(dirs)
+        traj = members(traj) if fam.adjoint else None
     state = {n: _plain(f) for n, f in state.items()}
     groups = [(state, fam.names, True)]
     if not batched:
@@ -303,13 +390,24 @@ def _call(fam: _Family, batched: bool, state, dirs, eta, dt, externals, want, *,
             raise ValueError(f"{what}: width={width} outside [1, {fam.max_dirs}]")
         dirs = {n: _batched_layout(f, ref, geo) for n, f in dirs.items()}
         res = {n: zeros_batched(ndir, nx, nz, dtype, device, ls) for n in want}
-    else:
+    elif not ens:
         width = 1
         res = {n: _new_like(ref, nx, nz, ls) for n in want}
-    out = {n: _new_like(ref, nx, nz, ls) for n in NL_OUT} if write_nl else None
+    out = {n: _new_like(ref, nx, nz, ls) for n in NL_OUT} if write_nl and not ens else None
     p = _params(externals, nz)
     lib, zero, dstride = _lib.load(), _zero_line(device, dtype), nlev * ls
     stream = int(torch.cuda.current_stream(device).cuda_stream)
+    if ens:
+        new = lambda: _zeros_members(nmem, geo, dtype, device, mstride)  # noqa: E731
+        res, out = {n: new() for n in want}, ({n: new() for n in NL_OUT} if write_nl else None)
+        r0, o0 = {n: f[0] for n, f in res.items()}, (None if out is None else {n: f[0] for n, f in out.items()})
+        if fam.adjoint:
+            args = _ad_args(p, geo, state, dirs, zero, eta, traj, r0, dt, stream, (nmem, mstride))
+        else:
+            args = _tl_args(p, geo, state, dirs, zero, eta, o0, r0, dt, stream, (nmem, mstride))
+        with torch.cuda.device(device):
+            _lib.check(getattr(lib, f"cloudsc2_{fam.ens}_{_SFX[dtype]}")(*args), fam.ens)
+        return res if fam.adjoint else (out, res)
     with torch.cuda.device(device):
         for d0 in range(0, ndir, width):
             n = min(width, ndir - d0)
@@ -345,8 +443,43 @@ def _in_layout(g: torch.Tensor, ref: torch.Tensor, geo) -> torch.Tensor:
 # `backward` and `jvp` of the public Functions touch no storage: they hand what they were given to one of these, which holds
 # the layout normalisation and the launch - and a `vmap` rule, so that under `torch.func.vmap` (`jacfwd`, `jacrev`, `vmap` of
 # `jvp`) the rule sees all tangents / cotangents stacked, as ordinary tensors.  Outside `vmap` they are plain calls.
-_BATCHED_STATE = ("only tangents and cotangents may be batched: `vmap` over the state (a primal input of cloudsc2 / "
-                  "cloudsc2_step / saturation) is not supported - loop over the states, or put them side by side as columns")
+_BATCHED_STATE = ("`vmap` over the state (a primal input of cloudsc2 / cloudsc2_step / saturation) runs the ensemble "
+                  "launches, and `vmap` over tangents or cotangents the multi-direction ones, but not both at once: members "
+                  "times directions in one call (nested `vmap`, e.g. `vmap(jacrev(f))` or `vmap(vmap(f))`) is not supported "
+                  "- loop over the members, or over the directions")
+_BATCHED_ETA = ("`eta` is shared by all members of an ensemble: `vmap` over `eta` is not supported (in_dims must be None for "
+                "it) - loop over the level vectors")
+_PARTLY_BATCHED = ("beside a state of which SOME fields are batched and others are not, only tangents and cotangents may be "
+                   "batched: `vmap` over part of the state (of the primal inputs of cloudsc2 / cloudsc2_step / saturation) is "
+                   "not supported - an ensemble is a batch of WHOLE states: batch every field of the state (`torch.stack`, or "
+                   "`expand` the fields the members share), which runs the ensemble launch")
+
+
+def _whole_state(dims) -> bool:
+    """the `in_dims` of the state's tensors under `vmap`: all batched (an ensemble: True) or none (False); a state batched
+    in part is refused, as every batched state was before there were ensemble launches"""
+    batched = [d is not None for d in dims]
+    if any(batched) and not all(batched):
+        raise NotImplementedError(_PARTLY_BATCHED)
+    return any(batched)
+
+
+def _refuse_nested(tensors) -> None:
+    """a tensor still wrapped for an OUTER `vmap` inside a `vmap` rule: members times directions"""
+    if any(isinstance(t, torch.Tensor) and torch._C._functorch.is_batchedtensor(t) for t in tensors):
+        raise NotImplementedError(_BATCHED_STATE)
+
+
+def _as_field(t: torch.Tensor) -> torch.Tensor:
+    """a (nx, 1, nlev) tensor of any layout as a column-fastest field (differentiable; what the looping fallbacks hand a
+    member to the single paths as)"""
+    return t.permute(2, 1, 0).contiguous().permute(2, 1, 0)
+
+
+def _members(info, in_dims, tensors):
+    """every tensor of a `vmap` rule member-major, (batch, nx, 1, nlev): batched ones moved, unbatched ones expanded"""
+    return [t.unsqueeze(0).expand(info.batch_size, *t.shape) if d is None else t.movedim(d, 0)
+            for t, d in zip(tensors, in_dims)]
 
 
 class _Launch(NamedTuple):
@@ -360,10 +493,12 @@ class _Launch(NamedTuple):
     want: Tuple[str, ...] = ()
 
 
-def _unbatched_state(in_dims, nfixed):
-    """in_dims[0] belongs to the `_Launch` (a tuple like it: `eta` is its one tensor), the next `nfixed` to the state"""
-    if in_dims[0].eta is not None or any(d is not None for d in in_dims[1:1 + nfixed]):
-        raise NotImplementedError(_BATCHED_STATE)
+def _batched_state(in_dims, nfixed) -> bool:
+    """in_dims[0] belongs to the `_Launch` (a tuple like it: `eta` is its one tensor), the next `nfixed` to the state and
+    the trajectory: is any of those batched (an ensemble)?  A batched `eta` is refused."""
+    if in_dims[0].eta is not None:
+        raise NotImplementedError(_BATCHED_ETA)
+    return _whole_state(in_dims[1:1 + nfixed])
 
 
 def _stacked(info, in_dims, tensors, nfixed):
@@ -386,11 +521,12 @@ def _unpacked(names, step, adjoint, call, tensors, info=None, in_dims=None):
     they are stacked as (batch, nx, 1, nlev), and a batched state is refused."""
     nst = len(names)
     nfixed = nst + step + 2 * adjoint
-    if info is None:
+    if call.geo is None:      # an ensemble: `_call` brings every member-major tensor into one layout
+        rest = list(tensors[nfixed:])
+    elif info is None:
         ref = _plain(tensors[0])
         rest = [_in_layout(t, ref, call.geo) for t in tensors[nfixed:]]
     else:
-        _unbatched_state(in_dims, nfixed)
         rest = _stacked(info, in_dims, tensors, nfixed)
     qsat = tensors[nst] if step else None
     traj = {"fplsl": tensors[nfixed - 2], "fplsn": tensors[nfixed - 1]} if adjoint else None
@@ -409,11 +545,33 @@ def _saturation_tl_stacked(ap, t, pert, ext, geo):
     return qsat_i
 
 
+def _looped_members(one, call, tensors, nout):
+    """an ensemble where there is no ensemble kernel (the evaporation switches in the adjoint, the non-LPHYLIN step): the
+    single path `one(call, *fields)` member by member, results stacked member-major"""
+    rows = []
+    for m in range(tensors[0].shape[0]):
+        fields = [_as_field(_plain(t)[m]) for t in tensors]
+        rows.append(one(call._replace(geo=field_geometry(fields[0])), *fields))
+    return tuple(torch.stack([r[i] for r in rows]) for i in range(nout))
+
+
 def _tl_rule(fam, call, tensors, info=None, in_dims=None):
     """`forward` and, with `info` and `in_dims`, `vmap` of `_TLMasked` / `_TLStep`: batched tangents take the family's
     multi-direction launches.  The step without LPHYLIN has no kernel of its own: the qsat perturbation comes from
     `saturation_tl`, then the masked family runs on the step's `qsat`."""
     batched, step = info is not None, fam is _TL_STEP
+    nfixed = len(fam.names) + step
+    if batched:
+        _refuse_nested(tensors)
+        if _batched_state(in_dims, nfixed):     # an ensemble of states: every tensor member-major, one ensemble launch
+            outs = _tl_rule(fam, call._replace(geo=None), _members(info, in_dims[1:], tensors))
+            return outs, (0,) * len(outs)
+    if call.geo is None:
+        if step and not call.ext.get("LPHYLIN"):     # no ensemble kernel: the single path, member by member
+            return _looped_members(lambda c, *t: _tl_rule(fam, c, t), call, tensors, len(NL_OUT))
+        state, _, _, pert = _unpacked(fam.names, step, False, call, tensors)
+        out_i = _call(fam, False, state, pert, call.eta, call.dt, call.ext, NL_OUT, ens=True)[1]
+        return tuple(out_i[n] for n in NL_OUT)
     state, qsat, _, pert = _unpacked(fam.names, step, False, call, tensors, info, in_dims)
     if step and not call.ext.get("LPHYLIN"):
         if batched and ("ap" in pert or "t" in pert):
@@ -459,7 +617,10 @@ class _SaturationTL(_InnerFunction):
 
     @staticmethod
     def vmap(info, in_dims, call, ap, t, *tangents):
-        _unbatched_state(in_dims, 2)
+        _refuse_nested((ap, t) + tangents)
+        if _batched_state(in_dims, 2):      # an ensemble of states: pointwise, member by member
+            one = lambda c, *f: (_SaturationTL.forward(c, *f),)  # noqa: E731
+            return _looped_members(one, call, _members(info, in_dims[1:], (ap, t) + tangents), 1)[0], 0
         pert = dict(zip(call.have, _stacked(info, in_dims, (ap, t) + tangents, 2)))
         return _saturation_tl_stacked(ap, t, pert, call.ext, call.geo), 0
 
@@ -468,7 +629,9 @@ def _looped_adjoint(one, info, in_dims, call, tensors, nfixed, nout):
     """the `vmap` rule of the adjoint launches that have no multi-direction kernel (the evaporation switches, the
     non-LPHYLIN step, `saturation`): one single launch per cotangent, results stacked; `one(call, *tensors)` is the
     Function's own `forward`"""
-    _unbatched_state(in_dims, nfixed)
+    _refuse_nested(tensors)
+    if _batched_state(in_dims, nfixed):     # an ensemble of states: the single launch member by member
+        return _looped_members(one, call, _members(info, in_dims[1:], tensors), nout), (0,) * nout
     cot = _stacked(info, in_dims, tensors, nfixed)
     rows = [one(call, *tensors[:nfixed], *(g[b] for g in cot)) for b in range(info.batch_size)]
     return tuple(torch.stack([r[i] for r in rows]) for i in range(nout)), (0,) * nout
@@ -482,6 +645,18 @@ def _ad_rule(fam, call, tensors, info=None, in_dims=None):
     batched, step, want = info is not None, fam is _AD_STEP, call.want
     ext = dict(call.ext, AD_TRAJ_FIX=1)
     one_launch = not _evap(ext) and (not step or bool(ext.get("LPHYLIN")))
+    nfixed = len(fam.names) + step + 2
+    if batched:
+        _refuse_nested(tensors)
+        if one_launch and _batched_state(in_dims, nfixed):   # an ensemble of states: one ensemble launch
+            outs = _ad_rule(fam, call._replace(geo=None), _members(info, in_dims[1:], tensors))
+            return outs, (0,) * len(outs)
+    if call.geo is None:
+        if not one_launch:
+            return _looped_members(lambda c, *t: _ad_rule(fam, c, t), call, tensors, len(want))
+        state, _, traj, forcing = _unpacked(fam.names, step, True, call, tensors)
+        adj = _call(fam, False, state, forcing, call.eta, call.dt, ext, want, traj=traj, ens=True)
+        return tuple(adj[n] for n in want)
     if batched and not one_launch:
         return _looped_adjoint(lambda c, *t: _ad_rule(fam, c, t), info, in_dims, call, tensors, len(fam.names) + step + 2,
                                len(want))
@@ -544,6 +719,15 @@ def _refuse_batched_state(info, in_dims, *args):
     raise NotImplementedError(_BATCHED_STATE)
 
 
+def _geometry(field):
+    """`field_geometry`, or (-1, -1, -1) for a member of a state batched by `vmap` in some other layout: the derivative
+    rules then see a batched state and take the ensemble path, which settles the layout itself"""
+    try:
+        return field_geometry(field)
+    except ValueError:
+        return (-1, -1, -1)
+
+
 class _NLFunction(torch.autograd.Function):
     """What `_Cloudsc2` and `_Cloudsc2Step` share: everything but `forward`.  A subclass names its inputs behind (eta, dt,
     externals) in `names`, the inner Functions that launch its `jvp` / `backward` in `tl` / `ad`, and says `with_qsat` if its
@@ -552,13 +736,15 @@ class _NLFunction(torch.autograd.Function):
     names: Tuple[str, ...] = ()
     tl = ad = None
     with_qsat = False
+    ensemble = None      # the Function on member-major batches that `vmap` over the state runs; None: this is one
 
     @classmethod
     def setup_context(cls, ctx, inputs, outputs):
         eta, dt, externals, *fields = inputs
         qsat = outputs[len(NL_OUT):] if cls.with_qsat else ()
         ctx.set_materialize_grads(False)
-        ctx.call = _Launch(eta, float(dt), _ext_of(externals), field_geometry(fields[0]), ())
+        # an ensemble Function has no single geometry: `_Launch.geo` is None and `_call` settles the layout
+        ctx.call = _Launch(eta, float(dt), _ext_of(externals), None if cls.ensemble is None else _geometry(fields[0]), ())
         ctx.save_for_backward(*fields, *qsat, outputs[NL_OUT.index("fplsl")], outputs[NL_OUT.index("fplsn")])
         ctx.save_for_forward(*fields, *qsat)
         if qsat:
@@ -588,7 +774,18 @@ class _NLFunction(torch.autograd.Function):
                                  *(t for t in tangents if t is not None))
         return tuple(out_i) + (None,) * cls.with_qsat
 
-    vmap = staticmethod(_refuse_batched_state)
+    @classmethod
+    def vmap(cls, info, in_dims, eta, dt, externals, *fields):
+        """`vmap` over the WHOLE state (every field batched; a state batched in part is refused): the fields are moved to
+        dimension 0 and the ensemble Function runs on the member-major batch - one launch, and differentiable like this one"""
+        if in_dims[0] is not None:
+            raise NotImplementedError(_BATCHED_ETA)
+        if cls.ensemble is None:
+            raise NotImplementedError(_BATCHED_STATE)
+        _refuse_nested(fields)
+        _whole_state(in_dims[3:])
+        outs = cls.ensemble.apply(eta, dt, externals, *_members(info, in_dims[3:], fields))
+        return outs, (0,) * len(outs)
 
 
 def _state_fields(what, state, names):
@@ -734,7 +931,7 @@ class _Saturation(torch.autograd.Function):
     def setup_context(ctx, inputs, output):
         externals, ap, t = inputs
         ctx.set_materialize_grads(False)
-        ctx.call = _Launch(None, 0.0, _ext_of(externals), field_geometry(ap), ())
+        ctx.call = _Launch(None, 0.0, _ext_of(externals), _geometry(ap), ())
         ctx.save_for_backward(ap, t)
         ctx.save_for_forward(ap, t)
 
@@ -758,7 +955,14 @@ class _Saturation(torch.autograd.Function):
             return _SaturationTL.apply(ctx.call._replace(have=have), ap.detach(), t.detach(),
                                        *(g for g in (ap_i, t_i) if g is not None))
 
-    vmap = staticmethod(_refuse_batched_state)
+    @staticmethod
+    def vmap(info, in_dims, externals, ap, t):
+        """`vmap` over the state: `saturation` is pointwise - it loops over the members (differentiably) and stacks"""
+        _refuse_nested((ap, t))
+        _whole_state(in_dims[1:])
+        ap, t = _members(info, in_dims[1:], (ap, t))
+        return torch.stack([_Saturation.apply(externals, _as_field(ap[m]), _as_field(t[m]))
+                            for m in range(info.batch_size)]), 0
 
 
 def saturation(ap: torch.Tensor, t: torch.Tensor, externals: Optional[Mapping[str, Any]] = None) -> torch.Tensor:
@@ -820,4 +1024,117 @@ def cloudsc2_step(state: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: floa
         raise ValueError("cloudsc2_step: `state` holds `qsat`, which the step forms itself from `ap` and `t`; for a qsat of "
                          "your own use `cloudsc2` (compose it with `saturation` for the total derivative)")
     outs = _Cloudsc2Step.apply(eta, dt, externals, *_state_fields("cloudsc2_step", state, STEP_IN))
+    return dict(zip(NL_OUT + ("qsat",), outs))
+
+
+# ---- ensembles: member-major batches of states, one launch per call --------------------------------------------------------
+class _TLMaskedEns(_InnerFunction):
+    """(call, 16 member-major state fields, present tangents) -> the ten perturbed outputs, member-major"""
+    @staticmethod
+    def forward(call, *tensors):
+        return _tl_rule(_TL_MASKED, call._replace(geo=None), tensors)
+
+    vmap = staticmethod(_refuse_batched_state)
+
+
+class _TLStepEns(_InnerFunction):
+    @staticmethod
+    def forward(call, *tensors):
+        return _tl_rule(_TL_STEP, call._replace(geo=None), tensors)
+
+    vmap = staticmethod(_refuse_batched_state)
+
+
+class _ADMaskedEns(_InnerFunction):
+    """(call, 16 member-major state fields, traj fplsl, traj fplsn, present cotangents) -> the adjoints of `call.want`"""
+    @staticmethod
+    def forward(call, *tensors):
+        return _ad_rule(_AD_MASKED, call._replace(geo=None), tensors)
+
+    vmap = staticmethod(_refuse_batched_state)
+
+
+class _ADStepEns(_InnerFunction):
+    @staticmethod
+    def forward(call, *tensors):
+        return _ad_rule(_AD_STEP, call._replace(geo=None), tensors)
+
+    vmap = staticmethod(_refuse_batched_state)
+
+
+def _nl_ens(what, single, names, inputs, eta, dt, externals):
+    """forward of the ensemble Functions: ONE `cloudsc2_nl_ens_*` launch (`names` = NL_IN) or one `cloudsc2_nl_fused_ens_*`
+    launch (`names` = STEP_IN: `saturation` fused in, `qsat` returned behind the ten outputs).  The non-LPHYLIN step has no
+    fused kernel: it loops over the members through `single`, the forward of the single Function."""
+    ext, step = _ext_of(externals), names is STEP_IN
+    if step and not ext.get("LPHYLIN"):
+        rows = [single(eta, dt, externals, *(_as_field(_plain(f)[m]) for f in inputs)) for m in range(inputs[0].shape[0])]
+        return tuple(torch.stack([r[i] for r in rows]) for i in range(len(rows[0])))
+    first = _plain(inputs[0])
+    nmem, geo, ms = _ens_geometry(what, first)
+    nx, nlev, ls = geo
+    for n, f in zip(names, inputs):
+        if not isinstance(f, torch.Tensor) or tuple(f.shape) != (nmem, nx, 1, nlev):
+            raise ValueError(f"{what}: {n} must be a tensor of shape {(nmem, nx, 1, nlev)} like {names[0]}, got "
+                             f"{tuple(getattr(f, 'shape', ()))}")
+    fields = {n: _batched_layout(f, first, geo, ms) for n, f in zip(names, inputs)}
+    member0 = {n: f[0] for n, f in fields.items()}
+    _, dtype, device = _checked(what, ((member0, names, True),))
+    eta = _eta(what, eta, nlev - 1, dtype, device)
+    new = lambda: _zeros_members(nmem, geo, dtype, device, ms)  # noqa: E731
+    out = {n: new() for n in NL_OUT}
+    qsat = (new(),) if step else ()
+    p = _params(ext, nlev - 1)
+    head = (ctypes.byref(p), nx, nlev - 1, ls, _ptrs(member0, NL_IN))
+    tail = (eta.data_ptr(), _ptrs({n: f[0] for n, f in out.items()}, NL_OUT), float(dt),
+            int(torch.cuda.current_stream(device).cuda_stream), nmem, ms)
+    with torch.cuda.device(device):
+        if step:
+            rc = getattr(_lib.load(), "cloudsc2_nl_fused_ens_" + _SFX[dtype])(*head, None, 0.0, qsat[0][0].data_ptr(), *tail)
+        else:
+            rc = getattr(_lib.load(), "cloudsc2_nl_ens_" + _SFX[dtype])(*head, *tail)
+    _lib.check(rc, what)
+    return tuple(out[n] for n in NL_OUT) + qsat
+
+
+class _Cloudsc2Ens(_NLFunction):
+    names, tl, ad = NL_IN, _TLMaskedEns, _ADMaskedEns
+
+    @staticmethod
+    def forward(eta, dt, externals, *inputs):
+        return _nl_ens("cloudsc2_ensemble", _Cloudsc2.forward, NL_IN, inputs, eta, dt, externals)
+
+
+class _Cloudsc2StepEns(_NLFunction):
+    names, tl, ad, with_qsat = STEP_IN, _TLStepEns, _ADStepEns, True
+
+    @staticmethod
+    def forward(eta, dt, externals, *inputs):
+        return _nl_ens("cloudsc2_step_ensemble", _Cloudsc2Step.forward, STEP_IN, inputs, eta, dt, externals)
+
+
+_Cloudsc2.ensemble, _Cloudsc2Step.ensemble = _Cloudsc2Ens, _Cloudsc2StepEns
+
+
+def cloudsc2_ensemble(states: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+                      externals: Optional[Mapping[str, Any]] = None) -> Dict[str, torch.Tensor]:
+    """`cloudsc2` for an ENSEMBLE of `nmem` states: the 16 inputs as member-major `(nmem, nx, 1, nz+1)` tensors (the layout
+    of `storage.zeros_batched` and of `torch.stack`; anything else is copied into it) -> the 10 NL outputs, member-major;
+    `eta`, `dt` and the externals are shared.  Every member is an independent `cloudsc2` call with `cloudsc2`'s contract
+    (`AD_TRAJ_FIX=1` forced for the adjoint, `once_differentiable`).  Forward is ONE `cloudsc2_nl_ens` launch, `backward` one
+    `cloudsc2_ad_ens` launch, `jvp` one `cloudsc2_tl_ens` launch; with LEVAPLS2 / LDRAIN1D the backward loops over the
+    members through the dense `cloudsc2_ad`.  `torch.func.vmap` of `cloudsc2` over the state runs this Function."""
+    outs = _Cloudsc2Ens.apply(eta, dt, externals, *_state_fields("cloudsc2_ensemble", states, NL_IN))
+    return dict(zip(NL_OUT, outs))
+
+
+def cloudsc2_step_ensemble(states: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+                           externals: Optional[Mapping[str, Any]] = None) -> Dict[str, torch.Tensor]:
+    """`cloudsc2_step` for an ensemble of states (`STEP_IN` names, member-major; see `cloudsc2_ensemble`) -> the 10 NL
+    outputs plus `"qsat"`, which is not differentiable.  With LPHYLIN and without LEVAPLS2 / LDRAIN1D every call is one
+    launch: `cloudsc2_nl_fused_ens`, `cloudsc2_ad_step_ens`, `cloudsc2_tl_step_ens`.  Otherwise the part that has no
+    ensemble kernel loops over the members through the paths of `cloudsc2_step`."""
+    if "qsat" in states:
+        raise ValueError("cloudsc2_step_ensemble: `states` holds `qsat`, which the step forms itself from `ap` and `t`")
+    outs = _Cloudsc2StepEns.apply(eta, dt, externals, *_state_fields("cloudsc2_step_ensemble", states, STEP_IN))
     return dict(zip(NL_OUT + ("qsat",), outs))

@@ -1129,6 +1129,25 @@ struct ADMaskedFields : KernArgs<ADMaskedArgs<T>> {
     __device__ __forceinline__ const T* traj_l() const { return this->ka->traj_l; }
     __device__ __forceinline__ const T* traj_n() const { return this->ka->traj_n; }
 };
+// The same call for every MEMBER of an ensemble (ad_ens_kernel / ad_ens_step_kernel, C ABI cloudsc2_ad_ens_* /
+// cloudsc2_ad_step_ens_*): see ens_block.  ADEnsFields is ADMaskedFields moved to one member: the member's base `mb`
+// (elements; wave-uniform) is added to the field pointer as a 64-bit scalar, the way ad_dirs_sweep adds the direction base;
+// an absent forcing keeps the zero line's pointer (the line is 512 bytes long).  An unwanted adjoint's pointer is never used.
+template <typename T>
+struct ADEnsArgs {
+    ADMaskedArgs<T> m;           // at kernarg offset 0
+    EnsGeom g;
+};
+template <typename T>
+struct ADEnsFields : KernArgs<ADEnsArgs<T>> {
+    int64_t mb;
+    uint32_t have;
+    __device__ __forceinline__ const T* in(int i) const { return this->ka->m.in.p[i] + mb; }
+    __device__ __forceinline__ const T* adj(int i) const { return this->ka->m.adj.p[i] + ((have >> i & 1u) ? mb : int64_t(0)); }
+    __device__ __forceinline__ T* oadj(int i) const { return this->ka->m.oadj.p[i] + mb; }
+    __device__ __forceinline__ const T* traj_l() const { return this->ka->m.traj_l + mb; }
+    __device__ __forceinline__ const T* traj_n() const { return this->ka->m.traj_n + mb; }
+};
 
 // ad_load_force with a per-field offset: the field's own `o`, or `zo` into the zero line (raw words, as there)
 template <typename T, typename FP>
@@ -1181,8 +1200,9 @@ __device__ __forceinline__ void ad_store_masked(const FP& F, uint32_t want, uint
 // live range (the fp64 instantiation already parks trajectory words in LDS to stay within 256 VGPRs): the level's t and ap
 // (`pt`, `pap`: two words) are kept beside its adjoints and the derivative is formed where those are stored, one iteration
 // late and before the next level's arithmetic starts.
-template <typename T, bool REG, bool FIX, bool STEP>
-__device__ __forceinline__ void ad_masked_sweep(const ADMaskedArgs<T>& A) {
+// ENS: one member of an ensemble per workgroup (`g`: EnsGeom; the field pointers are ADEnsFields').
+template <typename T, bool REG, bool FIX, bool STEP, bool ENS = false>
+__device__ __forceinline__ void ad_masked_sweep(const ADMaskedArgs<T>& A, const EnsGeom g = EnsGeom{}) {
     Ext<T> e = A.e;
     NLK<T> kc = A.kc;
     ExpK<T> xk = A.xk;
@@ -1191,7 +1211,7 @@ __device__ __forceinline__ void ad_masked_sweep(const ADMaskedArgs<T>& A) {
     const T* __restrict__ eta = A.eta;
     T dt = A.dt;
     const uint32_t have = A.have, want = A.want;
-    ADMaskedFields<T> F;
+    typename std::conditional<ENS, ADEnsFields<T>, ADMaskedFields<T>>::type F;
     const auto F_in = [&](int i) { return F.in(i); };
     extern __shared__ __align__(16) unsigned char smem_raw[];
     T* s_eta = reinterpret_cast<T*>(smem_raw);
@@ -1204,7 +1224,15 @@ __device__ __forceinline__ void ad_masked_sweep(const ADMaskedArgs<T>& A) {
         pin_expk(xk);
     }
 
-    const int gcol = xcd_block() * kColBlock + threadIdx.x;
+    int gcol;
+    if constexpr (ENS) {
+        int member;
+        gcol = ens_block(g.bpm, member) * kColBlock + threadIdx.x;
+        F.mb = member * g.ms;
+        F.have = have;
+    } else {
+        gcol = xcd_block() * kColBlock + threadIdx.x;
+    }
     T* const park_lds = s_scalm + (nz + 1) + threadIdx.x;
     (void)park_lds;
     if (gcol >= nx) return;  // no later workgroup barrier: whole lanes may retire
@@ -1298,6 +1326,20 @@ ad_step_kernel(const ADMaskedArgs<T> A) {
     ad_masked_sweep<T, REG, FIX, true>(A);
 }
 
+// ad_masked_kernel / ad_step_kernel for the members of an ensemble, one launch (BUILD EXTENSION, C ABI cloudsc2_ad_ens_* /
+// cloudsc2_ad_step_ens_*): see ADEnsArgs
+template <typename T, bool REG, bool FIX>
+__global__ void __launch_bounds__(kColBlock, sizeof(T) == 4 ? 3 : 1)
+ad_ens_kernel(const ADEnsArgs<T> A) {
+    ad_masked_sweep<T, REG, FIX, false, true>(A.m, A.g);
+}
+
+template <typename T, bool REG, bool FIX>
+__global__ void __launch_bounds__(kColBlock, sizeof(T) == 4 ? 3 : 1)
+ad_ens_step_kernel(const ADEnsArgs<T> A) {
+    ad_masked_sweep<T, REG, FIX, true, true>(A.m, A.g);
+}
+
 // The arguments of a masked adjoint call as the kernels take them (launch_ad_masked; launch_ad_dirs for direction 0):
 // in_adj[f] == nullptr: forcing f is zero everywhere (read from `zero`) and not in `have`; out_adj[f] == nullptr: adjoint f
 // is not in `want`, not written.
@@ -1326,39 +1368,53 @@ static void fill_ad_masked_args(ADMaskedArgs<T>& args, const Cloudsc2Params& p, 
 }
 
 // The caller (cloudsc2_capi.hip) has refused the evaporation switches and fields of 4 GiB and more.  `step`: ad_step_kernel
-// (in[NL_IN_QSAT] is not read, out_adj[NL_IN_QSAT] is NULL).
+// (in[NL_IN_QSAT] is not read, out_adj[NL_IN_QSAT] is NULL).  nmem > 0: the ensemble form (ad_ens_kernel /
+// ad_ens_step_kernel) - every field pointer is member 0's, member m lies m * ms elements behind it; the caller has checked
+// nmem and ms.
 template <typename T>
 int launch_ad_masked(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* const* in, const T* const* in_adj,
                      const T* zero, const T* eta, const T* traj_l, const T* traj_n, T* const* out_adj, double dt,
-                     hipStream_t stream, bool step) {
+                     hipStream_t stream, bool step, int nmem, int64_t ms) {
     if (p.LEVAPLS2 || p.LDRAIN1D || !fits_u32_offsets<T>(nz, ls)) return -2;
-    ADMaskedArgs<T> args;
+    ADEnsArgs<T> ens;
+    ADMaskedArgs<T>& args = ens.m;
     fill_ad_masked_args<T>(args, p, nx, nz, ls, in, in_adj, zero, eta, traj_l, traj_n, out_adj, dt);
-    const dim3 grid((nx + kColBlock - 1) / kColBlock), block(kColBlock);
+    const int bpm = (nx + kColBlock - 1) / kColBlock;
+    const dim3 grid(bpm), block(kColBlock);
     const size_t smem = 2 * size_t(nz + 1) * sizeof(T) + (kADPark<T> ? size_t(CS2_AD_PARK_COUNT) * kColBlock * sizeof(T) : 0);
     if (smem > size_t(160) * 1024) return -2;
+    if (nmem > 0 && int64_t(nmem) * bpm > kMaxGrid) return -2;
+    ens.g.ms = ms; ens.g.bpm = bpm;
+    const dim3 egrid(unsigned(nmem > 0 ? nmem : 1) * unsigned(bpm));
     int dev = 0;
     if (smem > size_t(64) * 1024)
         if (const int rc = current_device(dev)) return rc;
     const int rc = with_flags(
-        [&](auto REG, auto FIX, auto STEP) {
-            constexpr auto kern = STEP ? ad_step_kernel<T, REG, FIX> : ad_masked_kernel<T, REG, FIX>;
-            if (smem > size_t(64) * 1024 && !lds_opt_in<kern>(dev, smem)) return -1;
-            hipLaunchKernelGGL(kern, grid, block, smem, stream, args);
+        [&](auto REG, auto FIX, auto STEP, auto ENS) {
+            if constexpr (ENS) {
+                constexpr auto kern = STEP ? ad_ens_step_kernel<T, REG, FIX> : ad_ens_kernel<T, REG, FIX>;
+                if (smem > size_t(64) * 1024 && !lds_opt_in<kern>(dev, smem)) return -1;
+                hipLaunchKernelGGL(kern, egrid, block, smem, stream, ens);
+            } else {
+                constexpr auto kern = STEP ? ad_step_kernel<T, REG, FIX> : ad_masked_kernel<T, REG, FIX>;
+                if (smem > size_t(64) * 1024 && !lds_opt_in<kern>(dev, smem)) return -1;
+                hipLaunchKernelGGL(kern, grid, block, smem, stream, args);
+            }
             return 0;
         },
-        p.LREGCL != 0, p.AD_TRAJ_FIX != 0, step);
+        p.LREGCL != 0, p.AD_TRAJ_FIX != 0, step, nmem > 0);
     if (rc) return rc;
-    note_kernel(step ? "cs2::ad_step_kernel" : "cs2::ad_masked_kernel");
+    if (nmem > 0) note_kernel(step ? "cs2::ad_ens_step_kernel" : "cs2::ad_ens_kernel");
+    else note_kernel(step ? "cs2::ad_step_kernel" : "cs2::ad_masked_kernel");
     return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 template int launch_ad_masked<double>(const Cloudsc2Params&, int, int, int64_t, const double* const*, const double* const*,
                                       const double*, const double*, const double*, const double*, double* const*, double,
-                                      hipStream_t, bool);
+                                      hipStream_t, bool, int, int64_t);
 template int launch_ad_masked<float>(const Cloudsc2Params&, int, int, int64_t, const float* const*, const float* const*,
                                      const float*, const float*, const float*, const float*, float* const*, double,
-                                     hipStream_t, bool);
+                                     hipStream_t, bool, int, int64_t);
 
 // ------------------------------------------------------------------------------------------------------------------
 // Masked adjoint over `ndir` DIRECTIONS on one trajectory (BUILD EXTENSION, C ABI cloudsc2_ad_multi_* /

@@ -27,16 +27,19 @@ int launch_ad(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T
               T* const*, double, hipStream_t, const T* traj_l = nullptr, const T* traj_n = nullptr);
 template <typename T>
 int launch_tl_masked(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T* const*, const T*, const T*,
-                     T* const*, T* const*, double, hipStream_t, bool step);
+                     T* const*, T* const*, double, hipStream_t, bool step, int nmem = 0, int64_t ms = 0);
 template <typename T>
 int launch_tl_dirs(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T* const*, const T*, const T*, T* const*,
                    T* const*, double, hipStream_t, bool step, int ndir, int64_t in_ds, int64_t out_ds);
 template <typename T>
 int launch_ad_masked(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T* const*, const T*, const T*,
-                     const T*, const T*, T* const*, double, hipStream_t, bool step);
+                     const T*, const T*, T* const*, double, hipStream_t, bool step, int nmem = 0, int64_t ms = 0);
 template <typename T>
 int launch_ad_dirs(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T* const*, const T*, const T*, const T*,
                    const T*, T* const*, double, hipStream_t, bool step, int ndir, int64_t in_ds, int64_t out_ds);
+template <typename T>
+int launch_nl_ens(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T*, T* const*, double, hipStream_t, T*,
+                  int nmem, int64_t ms);
 template <typename T>
 int launch_saturation(const Cloudsc2Params&, int, int, int64_t, const T*, const T*, T*, hipStream_t);
 template <typename T>
@@ -93,28 +96,59 @@ int launched(const char* fn, int rc) {
     return fail(CLOUDSC2_E_LAUNCH, "%s: HIP launch failed: %s", fn, hipGetErrorString(hipPeekAtLastError()));
 }
 
+// The member arguments of the cloudsc2_*_ens_* entries (include/cloudsc2_hip.h "ENSEMBLES"); `ens` false: not such an entry.
+// The bound of ONE member's extent (32-bit byte offsets) is check_masked_size's, the same as for a single masked call.
+template <typename T>
+int check_masked_size(const char* fn, int32_t nz, int64_t ls);
+template <typename T>
+int check_members(const char* fn, bool ens, int32_t nx, int32_t nz, int64_t ls, int32_t nmem, int64_t ms) {
+    if (!ens) return 0;
+    if (nmem < 1) return fail(CLOUDSC2_E_ARG, "%s: nmem=%d must be >= 1", fn, nmem);
+    const int64_t field = int64_t(nz + 1) * ls;
+    if (ms < field)
+        return fail(CLOUDSC2_E_ARG, "%s: member_stride=%lld < (nz+1) * lev_stride = %lld: the members of a field would "
+                    "overlap", fn, (long long)ms, (long long)field);
+    if (int rc = check_masked_size<T>(fn, nz, ls)) return rc;
+    const int64_t blocks = int64_t(nmem) * ((int64_t(nx) + cs2::kColBlock - 1) / cs2::kColBlock);
+    if (blocks > cs2::kMaxGrid)
+        return fail(CLOUDSC2_E_UNSUPPORTED, "%s: nmem * ceil(nx / %d) = %lld workgroups exceed the grid limit %lld: split "
+                    "the ensemble", fn, cs2::kColBlock, (long long)blocks, (long long)cs2::kMaxGrid);
+    return 0;
+}
+
+// `ens`: the cloudsc2_nl_ens_* entry (nl_ens_kernel)
 template <typename T>
 int nl_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,
-            const T* eta, T* const* out, double dt, void* stream) {
+            const T* eta, T* const* out, double dt, void* stream, bool ens = false, int32_t nmem = 0, int64_t ms = 0) {
     if (int rc = check_common(fn, p, nx, nz, ls)) return rc;
+    if (int rc = check_members<T>(fn, ens, nx, nz, ls, nmem, ms)) return rc;
     if (nx == 0) return CLOUDSC2_OK;   // empty call: nothing to check or launch (zero-size tensors carry NULL pointers)
     if (int rc = check_ptrs(fn, "in", in, NL_NUM_IN)) return rc;
     if (int rc = check_ptrs(fn, "out", const_cast<const T* const*>(out), NL_NUM_OUT)) return rc;
     if (!eta) return fail(CLOUDSC2_E_ARG, "%s: eta is NULL", fn);
     if (p->ICALL != 0) return fail(CLOUDSC2_E_UNSUPPORTED, "%s: ICALL=%d (the reference implements ICALL == 0 only)", fn, p->ICALL);
     if (!(dt > 0.0)) return fail(CLOUDSC2_E_ARG, "%s: dt=%g must be > 0", fn, dt);
+    if (ens)
+        return launched(fn, cs2::launch_nl_ens<T>(*p, nx, nz, ls, in, eta, out, dt, static_cast<hipStream_t>(stream), nullptr,
+                                                  nmem, ms));
     return launched(fn, cs2::launch_nl<T>(*p, nx, nz, ls, in, eta, out, dt, static_cast<hipStream_t>(stream), nullptr,
                                           0.0, nullptr, nullptr));
 }
 
-// Fused variants of cloudsc2_nl (build extensions): exactly one of `qsat_out` / `in_i` is non-NULL.
+// Fused variants of cloudsc2_nl (build extensions): exactly one of `qsat_out` / `in_i` is non-NULL.  `ens`: the
+// cloudsc2_nl_fused_ens_* entry (nl_ens_kernel), the saturation-fused form only.
 template <typename T>
 int nl_fused_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,
-                  const T* const* in_i, double pf, T* qsat_out, const T* eta, T* const* out, double dt, void* stream) {
+                  const T* const* in_i, double pf, T* qsat_out, const T* eta, T* const* out, double dt, void* stream,
+                  bool ens = false, int32_t nmem = 0, int64_t ms = 0) {
     if (int rc = check_common(fn, p, nx, nz, ls)) return rc;
+    if (int rc = check_members<T>(fn, ens, nx, nz, ls, nmem, ms)) return rc;
     if (nx == 0) return CLOUDSC2_OK;   // empty call: nothing to check or launch (zero-size tensors carry NULL pointers)
     if (int rc = check_ptrs(fn, "out", const_cast<const T* const*>(out), NL_NUM_OUT)) return rc;
     if (!in) return fail(CLOUDSC2_E_ARG, "%s: in is NULL", fn);
+    if (ens && (in_i || !qsat_out))
+        return fail(CLOUDSC2_E_ARG, "%s: the ensemble entry is the saturation-fused form: qsat_out is required and in_i must "
+                    "be NULL (the perturbed form has no ensemble kernel)", fn);
     if ((qsat_out != nullptr) == (in_i != nullptr))
         return fail(CLOUDSC2_E_ARG, "%s: exactly one of qsat_out (fused saturation) and in_i (fused perturbation) must be given", fn);
     for (int i = 0; i < NL_NUM_IN; ++i)
@@ -126,6 +160,9 @@ int nl_fused_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t n
     if (qsat_out && !p->LPHYLIN)
         return fail(CLOUDSC2_E_UNSUPPORTED, "%s: only the LPHYLIN form of saturation is available fused", fn);
     if (!(dt > 0.0)) return fail(CLOUDSC2_E_ARG, "%s: dt=%g must be > 0", fn, dt);
+    if (ens)
+        return launched(fn, cs2::launch_nl_ens<T>(*p, nx, nz, ls, in, eta, out, dt, static_cast<hipStream_t>(stream), qsat_out,
+                                                  nmem, ms));
     return launched(fn, cs2::launch_nl<T>(*p, nx, nz, ls, in, eta, out, dt, static_cast<hipStream_t>(stream), in_i, pf,
                                           qsat_out, nullptr));
 }
@@ -312,15 +349,17 @@ int check_dirs(const char* fn, int32_t nz, int64_t ls, int32_t ndir, int64_t in_
     return 0;
 }
 
-// `step`: the cloudsc2_tl_step_* entry (tl_step_kernel); `ndir` > 0: the cloudsc2_tl_multi_* entries (tl_dirs_kernel)
+// `step`: the cloudsc2_tl_step_* entry (tl_step_kernel); `ndir` > 0: the cloudsc2_tl_multi_* entries (tl_dirs_kernel);
+// `ens`: the cloudsc2_tl_ens_* / cloudsc2_tl_step_ens_* entries (tl_ens_kernel / tl_ens_step_kernel)
 template <typename T>
 int tl_masked_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,
                    const T* const* in_i, const T* zero_line, const T* eta, T* const* out, T* const* out_i, double dt,
                    void* stream, bool step = false, bool multi = false, int32_t ndir = 0, int64_t in_ds = 0,
-                   int64_t out_ds = 0) {
+                   int64_t out_ds = 0, bool ens = false, int32_t nmem = 0, int64_t ms = 0) {
     if (int rc = check_common(fn, p, nx, nz, ls)) return rc;
     if (multi)
         if (int rc = check_dirs(fn, nz, ls, ndir, in_ds, out_ds)) return rc;
+    if (int rc = check_members<T>(fn, ens, nx, nz, ls, nmem, ms)) return rc;
     if (nx == 0) return CLOUDSC2_OK;
     if (int rc = step ? check_step_trajectory(fn, in) : check_ptrs(fn, "in", in, NL_NUM_IN)) return rc;
     if (step && in_i && in_i[NL_IN_QSAT])
@@ -349,18 +388,20 @@ int tl_masked_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t 
         return launched(fn, cs2::launch_tl_dirs<T>(*p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt,
                                                    static_cast<hipStream_t>(stream), step, ndir, in_ds, out_ds));
     return launched(fn, cs2::launch_tl_masked<T>(*p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt,
-                                                 static_cast<hipStream_t>(stream), step));
+                                                 static_cast<hipStream_t>(stream), step, ens ? nmem : 0, ms));
 }
 
-// `step`: the cloudsc2_ad_step_* entry (ad_step_kernel); `multi`: the cloudsc2_ad_multi_* entries (ad_dirs_kernel)
+// `step`: the cloudsc2_ad_step_* entry (ad_step_kernel); `multi`: the cloudsc2_ad_multi_* entries (ad_dirs_kernel);
+// `ens`: the cloudsc2_ad_ens_* / cloudsc2_ad_step_ens_* entries (ad_ens_kernel / ad_ens_step_kernel)
 template <typename T>
 int ad_masked_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,
                    const T* const* in_adj, const T* zero_line, const T* eta, const T* traj_fplsl, const T* traj_fplsn,
                    T* const* out_adj, double dt, void* stream, bool step = false, bool multi = false, int32_t ndir = 0,
-                   int64_t in_ds = 0, int64_t out_ds = 0) {
+                   int64_t in_ds = 0, int64_t out_ds = 0, bool ens = false, int32_t nmem = 0, int64_t ms = 0) {
     if (int rc = check_common(fn, p, nx, nz, ls)) return rc;
     if (multi)
         if (int rc = check_dirs(fn, nz, ls, ndir, in_ds, out_ds, CLOUDSC2_AD_MAX_DIRS, "CLOUDSC2_AD_MAX_DIRS")) return rc;
+    if (int rc = check_members<T>(fn, ens, nx, nz, ls, nmem, ms)) return rc;
     if (nx == 0) return CLOUDSC2_OK;
     if (int rc = step ? check_step_trajectory(fn, in) : check_ptrs(fn, "in", in, NL_NUM_IN)) return rc;
     if (int rc = check_masked_inputs(fn, "in_adj", in_adj, NL_NUM_OUT, zero_line)) return rc;
@@ -383,7 +424,7 @@ int ad_masked_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t 
         return launched(fn, cs2::launch_ad_dirs<T>(*p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn, out_adj,
                                                    dt, static_cast<hipStream_t>(stream), step, ndir, in_ds, out_ds));
     return launched(fn, cs2::launch_ad_masked<T>(*p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn,
-                                                 out_adj, dt, static_cast<hipStream_t>(stream), step));
+                                                 out_adj, dt, static_cast<hipStream_t>(stream), step, ens ? nmem : 0, ms));
 }
 
 template <typename T>
@@ -703,5 +744,46 @@ int32_t cloudsc2_ad_multi_step_f32(const Cloudsc2Params* p, int32_t nx, int32_t 
     return ad_masked_impl<float>("cloudsc2_ad_multi_step_f32", p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn, out_adj, dt,
                            stream, true, true, ndir, in_ds, out_ds);
 }
+// ---- the ensemble entries: the single entry's arguments + (nmem, member_stride); one pair of definitions per precision
+#define CS2_ENS_ENTRIES(SFX, T)                                                                                                 \
+    int32_t cloudsc2_nl_ens_##SFX(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,             \
+                                  const T* eta, T* const* out, double dt, void* stream, int32_t nmem, int64_t ms) {            \
+        return nl_impl<T>("cloudsc2_nl_ens_" #SFX, p, nx, nz, ls, in, eta, out, dt, stream, true, nmem, ms);                   \
+    }                                                                                                                          \
+    int32_t cloudsc2_nl_fused_ens_##SFX(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,       \
+                                        const T* const* in_i, double pf, T* qsat_out, const T* eta, T* const* out, double dt,  \
+                                        void* stream, int32_t nmem, int64_t ms) {                                              \
+        return nl_fused_impl<T>("cloudsc2_nl_fused_ens_" #SFX, p, nx, nz, ls, in, in_i, pf, qsat_out, eta, out, dt, stream,    \
+                                true, nmem, ms);                                                                               \
+    }                                                                                                                          \
+    int32_t cloudsc2_tl_ens_##SFX(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,             \
+                                  const T* const* in_i, const T* zero_line, const T* eta, T* const* out, T* const* out_i,      \
+                                  double dt, void* stream, int32_t nmem, int64_t ms) {                                         \
+        return tl_masked_impl<T>("cloudsc2_tl_ens_" #SFX, p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt, stream,     \
+                                 false, false, 0, 0, 0, true, nmem, ms);                                                       \
+    }                                                                                                                          \
+    int32_t cloudsc2_tl_step_ens_##SFX(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,        \
+                                       const T* const* in_i, const T* zero_line, const T* eta, T* const* out,                  \
+                                       T* const* out_i, double dt, void* stream, int32_t nmem, int64_t ms) {                   \
+        return tl_masked_impl<T>("cloudsc2_tl_step_ens_" #SFX, p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt,        \
+                                 stream, true, false, 0, 0, 0, true, nmem, ms);                                                \
+    }                                                                                                                          \
+    int32_t cloudsc2_ad_ens_##SFX(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,             \
+                                  const T* const* in_adj, const T* zero_line, const T* eta, const T* traj_fplsl,               \
+                                  const T* traj_fplsn, T* const* out_adj, double dt, void* stream, int32_t nmem,               \
+                                  int64_t ms) {                                                                                \
+        return ad_masked_impl<T>("cloudsc2_ad_ens_" #SFX, p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn,   \
+                                 out_adj, dt, stream, false, false, 0, 0, 0, true, nmem, ms);                                  \
+    }                                                                                                                          \
+    int32_t cloudsc2_ad_step_ens_##SFX(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,        \
+                                       const T* const* in_adj, const T* zero_line, const T* eta, const T* traj_fplsl,          \
+                                       const T* traj_fplsn, T* const* out_adj, double dt, void* stream, int32_t nmem,          \
+                                       int64_t ms) {                                                                           \
+        return ad_masked_impl<T>("cloudsc2_ad_step_ens_" #SFX, p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl,          \
+                                 traj_fplsn, out_adj, dt, stream, true, false, 0, 0, 0, true, nmem, ms);                       \
+    }
+CS2_ENS_ENTRIES(f64, double)
+CS2_ENS_ENTRIES(f32, float)
+#undef CS2_ENS_ENTRIES
 
 }  // extern "C"

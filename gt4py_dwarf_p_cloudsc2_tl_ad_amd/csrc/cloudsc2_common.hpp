@@ -39,6 +39,25 @@ __device__ __forceinline__ int xcd_block() {
     return b;
 }
 
+// Ensemble launches (the *_ens_kernel families; C ABI cloudsc2_*_ens_*): a one-dimensional grid of nmem * bpm workgroups,
+// bpm = ceil(nx / kColBlock) column blocks per member.  The remapped block index of xcd_block() - a permutation of
+// [0, gridDim.x) for every grid size - is split as member * bpm + column block, so every (member, column block) pair is
+// served by exactly one workgroup, and with the remap active the workgroups of one XCD own one contiguous eighth of that
+// order: whole members, or one contiguous run of a member's columns.  Both values are workgroup-uniform and are held in
+// SGPRs (readfirstlane states it).  Returns the column block.
+__device__ __forceinline__ int ens_block(int bpm, int& member) {
+    const uint32_t v = uint32_t(xcd_block()), m = v / uint32_t(bpm);
+    member = __builtin_amdgcn_readfirstlane(int(m));
+    return __builtin_amdgcn_readfirstlane(int(v - m * uint32_t(bpm)));
+}
+// What an ensemble kernel takes beside the arguments of its single form: the member stride in elements (one per call, for
+// every field) and the column blocks per member.  The launchers check nmem * bpm against the grid limit.
+struct EnsGeom {
+    int64_t ms;
+    int bpm;
+};
+constexpr int64_t kMaxGrid = 0x7FFFFFFF;   // workgroups of a one-dimensional grid
+
 // ---- math in the working precision --------------------------------------------------------
 template <typename T> __device__ __forceinline__ T rexp(T x);
 template <> __device__ __forceinline__ double rexp<double>(double x) { return exp(x); }

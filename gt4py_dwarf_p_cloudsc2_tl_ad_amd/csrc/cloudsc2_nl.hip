@@ -466,6 +466,72 @@ nl_kernel(Ext<T> e, NLK<T> kc, ExpK<T> xk, int nx, int nz, int64_t ls, CPtrs<T, 
     }
 }
 
+// nl_kernel for the members of an ensemble, one launch (BUILD EXTENSION, C ABI cloudsc2_nl_ens_* / cloudsc2_nl_fused_ens_*;
+// FUSE 0 and 1 of nl_kernel): one member per workgroup (ens_block).  `in`, `out` and `qsat_out` point at member 0; the
+// member's base (elements; workgroup-uniform) is added to them as a 64-bit scalar and the lanes' byte offsets stay 32-bit.
+// A body of its own over the shared nl_level / load_level / nl_store / nl_saturation - the sweep of nl_kernel without the
+// perturbed variants: hoisting nl_kernel's body into a function both call changed the register allocation of existing
+// nl_kernel instantiations (measured on the ISA), so that kernel is left exactly as it was.
+template <typename T, bool EVAP, bool LIN, bool PINK, int FUSE>
+__global__ void __launch_bounds__(kColBlock, (sizeof(T) == 4 ? kF32Waves : 1))
+nl_ens_kernel(Ext<T> e, NLK<T> kc, ExpK<T> xk, int nx, int nz, int64_t ls, CPtrs<T, NL_NUM_IN> in, const T* __restrict__ eta,
+              MPtrs<T, NL_NUM_OUT> out, T dt, T* __restrict__ qsat_out, int keepq, EnsGeom g) {
+    static_assert(FUSE == 0 || FUSE == 1, "the perturbed variants have no ensemble form");
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    T* s_eta = reinterpret_cast<T*>(smem_raw);
+    T* s_scalm = s_eta + (nz + 1);
+    int klo, khi;
+    build_level_table<T>(eta, nz, e, s_eta, s_scalm, klo, khi);
+    if constexpr (PINK) pin_nl_constants(e, kc, xk, dt);
+
+    int member;
+    const int gcol = ens_block(g.bpm, member) * kColBlock + threadIdx.x;
+    if (gcol >= nx) return;   // see nl_kernel
+    const int64_t mb = member * g.ms;
+#pragma unroll
+    for (int i = 0; i < NL_NUM_IN; ++i) in.p[i] += mb;   // FUSE 1: in_qsat is NULL and is not read
+#pragma unroll
+    for (int i = 0; i < NL_NUM_OUT; ++i) out.p[i] += mb;
+    if constexpr (FUSE == 1) qsat_out += mb;
+    using O = uint32_t;
+    const O lsb = O(ls) * O(sizeof(T));
+    const O colb = O(gcol) * O(sizeof(T));
+    const T trpaus = trpaus_prescan<T, false, O>(in.p[NL_IN_T], in.p[NL_IN_TND_CML_T], lsb, colb, dt, s_eta, klo, khi);
+    const CrhCol<T> crh = crh_setup<T>(trpaus);
+
+    // :93-100
+    NLCarry<T> c;
+    c.rfl = T(0.0);
+    c.sfl = T(0.0);
+    c.covptot = T(0.0);
+    c.aph_k = ldg(in.p[NL_IN_APH], colb);
+    T aph_s = EVAP ? ldg(in.p[NL_IN_APH], O(nz) * lsb + colb) : T(1.0);
+    stg(out.p[NL_OUT_FPLSL], colb, T(0.0));   // top half level: see nl_kernel
+    stg(out.p[NL_OUT_FPLSN], colb, T(0.0));
+    stg(out.p[NL_OUT_FHPSL], colb, T(0.0));
+    stg(out.p[NL_OUT_FHPSN], colb, T(0.0));
+
+    // the level sweep of nl_kernel: one level of software prefetch, handed over by register copies
+    LevelIn<T> xa = load_level<T, O>(in, lsb, colb, FUSE == 1, keepq != 0);
+    landed(c.aph_k);   // first read inside the loop: see landed()
+    if constexpr (EVAP) landed(aph_s);
+    O o = colb;
+    for (int k = 0; k < nz; ++k) {
+        LevelIn<T> xn = xa;
+        if (k + 1 < nz) xn = load_level<T, O>(in, lsb, o + lsb, FUSE == 1, keepq != 0);
+        LevelIn<T> x = xa;
+        if constexpr (FUSE == 1) {
+            x.qsat = nl_saturation<T>(e, xk, x.ap, x.t);
+            stg(qsat_out, o, x.qsat);
+        }
+        const NLOut<T> r = nl_level<T, EVAP, LIN>(e, kc, xk, x, s_eta[k], s_scalm[k], crh, dt, aph_s, c);
+        nl_store<T, O>(out, e, lsb, o, r);
+        drain_vmem();   // see drain_vmem
+        xa = xn;
+        o += lsb;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // LDS-ring variant of the sweep (plain cloudsc2_nl, FUSE = 0).  Same prologue, same nl_level / nl_store; only the
 // way the 16 input words of a level reach the lane differs:
@@ -764,6 +830,47 @@ template int launch_nl<double>(const Cloudsc2Params&, int, int, int64_t, const d
                                double* const*, double, hipStream_t, const double* const*, double, double*, double*);
 template int launch_nl<float>(const Cloudsc2Params&, int, int, int64_t, const float* const*, const float*,
                               float* const*, double, hipStream_t, const float* const*, double, float*, double*);
+
+// cloudsc2_nl (qsat_out == nullptr) or `saturation` + cloudsc2_nl (qsat_out given) for `nmem` members in one launch: always
+// the register path (nl_ens_kernel), 32-bit offsets within a member.  Every field pointer is member 0's, member m lies
+// m * ms elements behind it; the caller has checked nmem and ms.
+template <typename T>
+int launch_nl_ens(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* const* in, const T* eta, T* const* out,
+                  double dt, hipStream_t stream, T* qsat_out, int nmem, int64_t ms) {
+    if (!fits_u32_offsets<T>(nz, ls)) return -2;
+    if (qsat_out && !p.LPHYLIN) return -2;    // only the LPHYLIN form of `saturation` is fused
+    const int bpm = (nx + kColBlock - 1) / kColBlock;
+    if (int64_t(nmem) * bpm > kMaxGrid) return -2;
+    const Ext<T> e = make_ext<T>(p);
+    CPtrs<T, NL_NUM_IN> ci;
+    MPtrs<T, NL_NUM_OUT> co;
+    for (int i = 0; i < NL_NUM_IN; ++i) ci.p[i] = in[i];
+    for (int i = 0; i < NL_NUM_OUT; ++i) co.p[i] = out[i];
+    const dim3 grid(unsigned(nmem) * unsigned(bpm)), block(kColBlock);
+    const size_t smem = 2 * size_t(nz + 1) * sizeof(T);
+    const bool evap = p.LEVAPLS2 || p.LDRAIN1D;
+    const bool lin = p.LPHYLIN || p.LDRAIN1D;
+    const T tdt = static_cast<T>(dt);
+    const NLK<T> kc = make_nlk<T>(p, dt, evap);
+    const ExpK<T> xk = make_expk<T>();
+    // in_qsat: default cache policy only when the qsat of ALL members fits (see qsat_fits_cache)
+    const int keepq = static_cast<uint64_t>(nmem) * static_cast<uint64_t>(ms) * sizeof(T) <= (uint64_t(128) << 20) ? 1 : 0;
+    const EnsGeom g{ms, bpm};
+    with_flags(
+        [&](auto EV, auto LN, auto SF) {
+            hipLaunchKernelGGL((nl_ens_kernel<T, EV, LN, sizeof(T) == 8, (SF ? 1 : 0)>), grid, block, smem, stream, e, kc, xk, nx,
+                               nz, ls, ci, eta, co, tdt, qsat_out, keepq, g);
+            return 0;
+        },
+        evap, lin, qsat_out != nullptr);
+    note_kernel(qsat_out ? "cs2::nl_ens_kernel<saturation>" : "cs2::nl_ens_kernel");
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+template int launch_nl_ens<double>(const Cloudsc2Params&, int, int, int64_t, const double* const*, const double*,
+                                   double* const*, double, hipStream_t, double*, int, int64_t);
+template int launch_nl_ens<float>(const Cloudsc2Params&, int, int, int64_t, const float* const*, const float*,
+                                  float* const*, double, hipStream_t, float*, int, int64_t);
 
 // ------------------------------------------------------------------------------------------------
 // The Taylor test's perturbed runs for NF step sizes in ONE launch (build extension, C ABI cloudsc2_nl_taylor_multi_*;

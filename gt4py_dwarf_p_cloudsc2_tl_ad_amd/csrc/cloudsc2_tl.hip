@@ -876,6 +876,24 @@ struct TLMaskedFields : KernArgs<TLMaskedArgs<T>> {
     __device__ __forceinline__ T* out(int i) const { return this->ka->out.p[i]; }
     __device__ __forceinline__ T* out_i(int i) const { return this->ka->out_i.p[i]; }
 };
+// The same call for every MEMBER of an ensemble (tl_ens_kernel / tl_ens_step_kernel, C ABI cloudsc2_tl_ens_* /
+// cloudsc2_tl_step_ens_*): see ens_block.  TLEnsFields is TLMaskedFields moved to one member: the member's base `mb`
+// (elements; wave-uniform) is added to the field pointer as a 64-bit scalar, the way tl_dirs_sweep adds the direction base;
+// an absent perturbation keeps the zero line's pointer (the line is 512 bytes long).  An unwanted output's pointer is never used.
+template <typename T>
+struct TLEnsArgs {
+    TLMaskedArgs<T> m;            // at kernarg offset 0
+    EnsGeom g;
+};
+template <typename T>
+struct TLEnsFields : KernArgs<TLEnsArgs<T>> {
+    int64_t mb;
+    uint32_t have;
+    __device__ __forceinline__ const T* in(int i) const { return this->ka->m.in.p[i] + mb; }
+    __device__ __forceinline__ const T* in_i(int i) const { return this->ka->m.in_i.p[i] + ((have >> i & 1u) ? mb : int64_t(0)); }
+    __device__ __forceinline__ T* out(int i) const { return this->ka->m.out.p[i] + mb; }
+    __device__ __forceinline__ T* out_i(int i) const { return this->ka->m.out_i.p[i] + mb; }
+};
 
 // load_level with a per-field offset: the field's own, or `zo` into the zero line.  SKIPQ: the qsat word is not read (the
 // step kernels form it from the level's t and ap words)
@@ -937,8 +955,9 @@ __device__ __forceinline__ void tl_store_masked(const FP& F, uint32_t want, cons
 // (C ABI cloudsc2_tl_step_*): in_qsat and its perturbation are not read; the level's qsat is saturation_point_d's value of
 // the level's t and ap words (LPHYLIN form, what cloudsc2_nl_fused_* computes) and the perturbation the level function
 // sees is g_t * t_i + g_ap * ap_i - formed at the head of the level's arithmetic, behind the prefetch of the next level.
-template <typename T, bool REG, bool EVAP, bool STEP>
-__device__ __forceinline__ void tl_masked_sweep(const TLMaskedArgs<T>& A) {
+// ENS: one member of an ensemble per workgroup (`g`: EnsGeom; the field pointers are TLEnsFields').
+template <typename T, bool REG, bool EVAP, bool STEP, bool ENS = false>
+__device__ __forceinline__ void tl_masked_sweep(const TLMaskedArgs<T>& A, const EnsGeom g = EnsGeom{}) {
     Ext<T> e = A.e;
     NLK<T> kc = A.kc;
     ExpK<T> xk = A.xk;
@@ -947,7 +966,7 @@ __device__ __forceinline__ void tl_masked_sweep(const TLMaskedArgs<T>& A) {
     const T* __restrict__ eta = A.eta;
     T dt = A.dt;
     const uint32_t have = A.have, want = A.want;
-    TLMaskedFields<T> F;
+    typename std::conditional<ENS, TLEnsFields<T>, TLMaskedFields<T>>::type F;
     const auto F_in = [&](int i) { return F.in(i); };
     const auto F_in_i = [&](int i) { return F.in_i(i); };
     extern __shared__ __align__(16) unsigned char smem_raw[];
@@ -957,7 +976,15 @@ __device__ __forceinline__ void tl_masked_sweep(const TLMaskedArgs<T>& A) {
     build_level_table<T>(eta, nz, e, s_eta, s_scalm, klo, khi);
     if constexpr (sizeof(T) == 8) pin_tl_constants(e, kc, xk, dt);
 
-    const int gcol = xcd_block() * kColBlock + threadIdx.x;
+    int gcol;
+    if constexpr (ENS) {
+        int member;
+        gcol = ens_block(g.bpm, member) * kColBlock + threadIdx.x;
+        F.mb = member * g.ms;
+        F.have = have;
+    } else {
+        gcol = xcd_block() * kColBlock + threadIdx.x;
+    }
     if (gcol >= nx) return;   // see tl_kernel
     using O = uint32_t;
     const O lsb = O(ls) * O(sizeof(T));
@@ -1024,6 +1051,20 @@ tl_step_kernel(const TLMaskedArgs<T> A) {
     tl_masked_sweep<T, REG, EVAP, true>(A);
 }
 
+// tl_masked_kernel / tl_step_kernel for the members of an ensemble, one launch (BUILD EXTENSION, C ABI cloudsc2_tl_ens_* /
+// cloudsc2_tl_step_ens_*): see TLEnsArgs
+template <typename T, bool REG, bool EVAP>
+__global__ void __launch_bounds__(kColBlock)
+tl_ens_kernel(const TLEnsArgs<T> A) {
+    tl_masked_sweep<T, REG, EVAP, false, true>(A.m, A.g);
+}
+
+template <typename T, bool REG, bool EVAP>
+__global__ void __launch_bounds__(kColBlock)
+tl_ens_step_kernel(const TLEnsArgs<T> A) {
+    tl_masked_sweep<T, REG, EVAP, true, true>(A.m, A.g);
+}
+
 // The arguments of a masked tangent-linear call as the kernels take them (launch_tl_masked; launch_tl_dirs for direction 0):
 // in_i[f] == nullptr: perturbation f is zero everywhere (read from `zero`) and not in `have`; out == nullptr: no NL outputs;
 // out_i[f] == nullptr: not in `want`, not written.
@@ -1052,15 +1093,34 @@ static void fill_tl_masked_args(TLMaskedArgs<T>& args, const Cloudsc2Params& p, 
 }
 
 // Always the register path; 32-bit offsets only.  `step`: tl_step_kernel (in[NL_IN_QSAT] and in_i[NL_IN_QSAT] are not read).
+// nmem > 0: the ensemble form (tl_ens_kernel / tl_ens_step_kernel) - every field pointer is member 0's, member m lies
+// m * ms elements behind it; the caller has checked nmem and ms.
 template <typename T>
 int launch_tl_masked(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* const* in, const T* const* in_i,
-                     const T* zero, const T* eta, T* const* out, T* const* out_i, double dt, hipStream_t stream, bool step) {
+                     const T* zero, const T* eta, T* const* out, T* const* out_i, double dt, hipStream_t stream, bool step,
+                     int nmem, int64_t ms) {
     if (!fits_u32_offsets<T>(nz, ls)) return -2;
     const bool evap = p.LEVAPLS2 || p.LDRAIN1D;
-    TLMaskedArgs<T> args;
+    TLEnsArgs<T> ens;
+    TLMaskedArgs<T>& args = ens.m;
     fill_tl_masked_args<T>(args, p, evap, nx, nz, ls, in, in_i, zero, eta, out, out_i, dt);
-    const dim3 grid((nx + kColBlock - 1) / kColBlock), block(kColBlock);
+    const int bpm = (nx + kColBlock - 1) / kColBlock;
+    const dim3 grid(bpm), block(kColBlock);
     const size_t smem = 2 * size_t(nz + 1) * sizeof(T);
+    if (nmem > 0) {
+        if (int64_t(nmem) * bpm > kMaxGrid) return -2;
+        ens.g.ms = ms; ens.g.bpm = bpm;
+        const dim3 egrid(unsigned(nmem) * unsigned(bpm));
+        with_flags(
+            [&](auto REG, auto EVAP, auto STEP) {
+                if constexpr (STEP) hipLaunchKernelGGL((tl_ens_step_kernel<T, REG, EVAP>), egrid, block, smem, stream, ens);
+                else hipLaunchKernelGGL((tl_ens_kernel<T, REG, EVAP>), egrid, block, smem, stream, ens);
+                return 0;
+            },
+            p.LREGCL != 0, evap, step);
+        note_kernel(step ? "cs2::tl_ens_step_kernel" : "cs2::tl_ens_kernel");
+        return hipGetLastError() == hipSuccess ? 0 : -1;
+    }
     with_flags(
         [&](auto REG, auto EVAP, auto STEP) {
             if constexpr (STEP) hipLaunchKernelGGL((tl_step_kernel<T, REG, EVAP>), grid, block, smem, stream, args);
@@ -1073,9 +1133,11 @@ int launch_tl_masked(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const 
 }
 
 template int launch_tl_masked<double>(const Cloudsc2Params&, int, int, int64_t, const double* const*, const double* const*,
-                                      const double*, const double*, double* const*, double* const*, double, hipStream_t, bool);
+                                      const double*, const double*, double* const*, double* const*, double, hipStream_t, bool,
+                                      int, int64_t);
 template int launch_tl_masked<float>(const Cloudsc2Params&, int, int, int64_t, const float* const*, const float* const*,
-                                     const float*, const float*, float* const*, float* const*, double, hipStream_t, bool);
+                                     const float*, const float*, float* const*, float* const*, double, hipStream_t, bool, int,
+                                     int64_t);
 
 // ------------------------------------------------------------------------------------------------------------------
 // Masked tangent-linear over `ndir` DIRECTIONS on one trajectory (BUILD EXTENSION, C ABI cloudsc2_tl_multi_* /

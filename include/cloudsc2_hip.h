@@ -439,6 +439,79 @@ int32_t cloudsc2_ad_multi_step_f32(const Cloudsc2Params* p, int32_t nx, int32_t 
                                    float* const* out_adj, double dt, void* stream,
                                    int32_t ndir, int64_t in_dir_stride, int64_t out_dir_stride);
 
+/* ---- ENSEMBLES: the NL step, the masked TL / AD and the step TL / AD for `nmem` MEMBERS in one launch (BUILD EXTENSIONS):
+ * an ensemble of model states, per-member gradients, an ML batch.  Unlike the multi-direction entries above EVERYTHING a
+ * call has is batched - state, perturbations or forcing, trajectory fluxes, every output, qsat_out - and every member is a
+ * complete, independent call.  Arguments are those of the single entry named in the table, followed by:
+ *   nmem            number of members, >= 1 (CLOUDSC2_E_ARG otherwise);
+ *   member_stride   in ELEMENTS, ONE value for every field of the call: each non-NULL field pointer points at member 0
+ *                   and member m of it starts m * member_stride elements later.  At least (nz+1) * lev_stride
+ *                   (CLOUDSC2_E_ARG): the members of a field do not overlap.
+ *       ensemble entry              single entry                 kernel reported by cloudsc2_last_kernel
+ *       cloudsc2_nl_ens_*           cloudsc2_nl_*                cs2::nl_ens_kernel
+ *       cloudsc2_nl_fused_ens_*     cloudsc2_nl_fused_*          cs2::nl_ens_kernel<saturation>
+ *       cloudsc2_tl_ens_*           cloudsc2_tl_masked_*         cs2::tl_ens_kernel
+ *       cloudsc2_tl_step_ens_*      cloudsc2_tl_step_*           cs2::tl_ens_step_kernel
+ *       cloudsc2_ad_ens_*           cloudsc2_ad_masked_*         cs2::ad_ens_kernel
+ *       cloudsc2_ad_step_ens_*      cloudsc2_ad_step_*           cs2::ad_ens_step_kernel
+ * The rules of the single entry hold, all settled on the host before any launch (ICALL, dt > 0, NLEV, NULL entries and the
+ * zero line, LEVAPLS2 / LDRAIN1D refused by the adjoints, LPHYLIN for the step and the fused entries; nx == 0 is a
+ * successful no-op).  `eta`, `dt`, the switches and the zero line are shared by all members; a field is present or absent
+ * for all members alike, and an absent input is read from the zero line by every member.  cloudsc2_nl_fused_ens_* is the
+ * saturation-fused form only: qsat_out is required, in_i must be NULL and pf is ignored.
+ * Sizes: ONE MEMBER of a field stays below 4 GiB, (nz+1) * lev_stride * sizeof(element) < 2^32 (CLOUDSC2_E_UNSUPPORTED
+ * otherwise; the lanes' byte offsets are 32-bit); the ensemble as a whole may be larger - the member's base is added to the
+ * field pointers as a 64-bit scalar.  nmem * ceil(nx / 256) workgroups must fit a one-dimensional grid, 2^31 - 1
+ * (CLOUDSC2_E_UNSUPPORTED).  Always the register-path kernels (no LDS ring).
+ * Every member of every written field equals what the single entry writes for that member alone (the same level functions
+ * on the same words).  Elements between the members (member_stride beyond a member's extent) are not touched. */
+int32_t cloudsc2_nl_ens_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                            const double* const* in, const double* eta, double* const* out, double dt, void* stream,
+                            int32_t nmem, int64_t member_stride);
+int32_t cloudsc2_nl_ens_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                            const float* const* in, const float* eta, float* const* out, double dt, void* stream,
+                            int32_t nmem, int64_t member_stride);
+int32_t cloudsc2_nl_fused_ens_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                  const double* const* in, const double* const* in_i, double pf, double* qsat_out,
+                                  const double* eta, double* const* out, double dt, void* stream,
+                                  int32_t nmem, int64_t member_stride);
+int32_t cloudsc2_nl_fused_ens_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                  const float* const* in, const float* const* in_i, double pf, float* qsat_out,
+                                  const float* eta, float* const* out, double dt, void* stream,
+                                  int32_t nmem, int64_t member_stride);
+int32_t cloudsc2_tl_ens_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                            const double* const* in, const double* const* in_i, const double* zero_line,
+                            const double* eta, double* const* out, double* const* out_i, double dt, void* stream,
+                            int32_t nmem, int64_t member_stride);
+int32_t cloudsc2_tl_ens_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                            const float* const* in, const float* const* in_i, const float* zero_line,
+                            const float* eta, float* const* out, float* const* out_i, double dt, void* stream,
+                            int32_t nmem, int64_t member_stride);
+int32_t cloudsc2_tl_step_ens_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                 const double* const* in, const double* const* in_i, const double* zero_line,
+                                 const double* eta, double* const* out, double* const* out_i, double dt, void* stream,
+                                 int32_t nmem, int64_t member_stride);
+int32_t cloudsc2_tl_step_ens_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                 const float* const* in, const float* const* in_i, const float* zero_line,
+                                 const float* eta, float* const* out, float* const* out_i, double dt, void* stream,
+                                 int32_t nmem, int64_t member_stride);
+int32_t cloudsc2_ad_ens_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                            const double* const* in, const double* const* in_adj, const double* zero_line,
+                            const double* eta, const double* traj_fplsl, const double* traj_fplsn,
+                            double* const* out_adj, double dt, void* stream, int32_t nmem, int64_t member_stride);
+int32_t cloudsc2_ad_ens_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                            const float* const* in, const float* const* in_adj, const float* zero_line,
+                            const float* eta, const float* traj_fplsl, const float* traj_fplsn,
+                            float* const* out_adj, double dt, void* stream, int32_t nmem, int64_t member_stride);
+int32_t cloudsc2_ad_step_ens_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                 const double* const* in, const double* const* in_adj, const double* zero_line,
+                                 const double* eta, const double* traj_fplsl, const double* traj_fplsn,
+                                 double* const* out_adj, double dt, void* stream, int32_t nmem, int64_t member_stride);
+int32_t cloudsc2_ad_step_ens_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                 const float* const* in, const float* const* in_adj, const float* zero_line,
+                                 const float* eta, const float* traj_fplsl, const float* traj_fplsn,
+                                 float* const* out_adj, double dt, void* stream, int32_t nmem, int64_t member_stride);
+
 #ifdef __cplusplus
 }
 #endif
