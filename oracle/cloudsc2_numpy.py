@@ -161,12 +161,13 @@ def f_cuadjtqs_nl(ap, t, q, e):
 # --------------------------------------------------------------------------------------
 # shared pieces of the three sweeps
 # --------------------------------------------------------------------------------------
-def _trpaus(eta, t, nz, dtype):
+def _trpaus(eta, t, nz, dtype, bc=None):
     """cloudsc2.py:107-111 - eta of the LAST level k in [0, nz-2] with 0.1<eta<0.4 and t[k]>t[k+1]."""
     nx = t.shape[1]
     trpaus = np.full(nx, 0.1, dtype=dtype)
     for k in range(nz - 1):
         if eta[k] > 0.1 and eta[k] < 0.4:
+            _count(bc, "trpaus_equal_temperatures", t[k] == t[k + 1])
             trpaus = _where(t[k] > t[k + 1], eta[k], trpaus)
     return trpaus
 
@@ -219,6 +220,22 @@ def _count(bc, name, mask) -> None:
         bc[name] = bc.get(name, 0) + int(np.count_nonzero(mask))
 
 
+#: the counters of `branch_counts` that count TIES: grid points where the two sides of a comparison of the scheme are
+#: equal.  Where equal operands alone would not make the comparison matter, the counter also asks for what it multiplies:
+#: condensate for the phase split, new precipitation for the freezing test, an active evaporation block for min(q, qsat)
+#: (counted with LEVAPLS2 / LDRAIN1D only).  `covptot_equals_clc_nonzero` is the exception: max(covptot, clc) at 1 == 1
+#: has equal values and zero derivatives on both sides, so no result can depend on it.
+TIE_COUNTERS = ("trpaus_equal_temperatures",                 # :110 t[k] > t[k+1]
+                "t_equals_RTT", "t_equals_RTICE",            # :141 t < RTT with condensate to split, :189 t < RTICE
+                "q_equals_qsat",                             # :163 min(q, qsat), read by the evaporation block (:288)
+                "qt_equals_qcrit", "qt_equals_qsat",         # :196 qt < qcrit, :201 qt >= qsat
+                "lu_equals_ZEPS2",                           # :212 lu[k+1] >= ZEPS2 (with lude >= RLMIN)
+                "mass_fluxes_cancel",                        # :224 mfu + mfd == 0 with fluxes present
+                "covptot_equals_clc_nonzero",                # :234 max(covptot, clc)
+                "t_equals_meltp2_with_snow",                 # :239 max(t - (RTT + 2), 0) where snow enters
+                "t_equals_RTT_at_freezing")                  # :277 t < RTT after melting, with new precipitation
+
+
 def cloudsc2_nl(fields: Dict[str, np.ndarray], in_eta: np.ndarray, dt, externals, branch_counts=None) -> None:
     """nonlinear/_stencils/cloudsc2.py:93-399.  `fields` holds the 16 `in_*` and 10 `out_*`
     arrays (nz+1, nx); outputs are written in place.  `out_fplsl[0]`/`out_fplsn[0]` are NOT
@@ -249,7 +266,7 @@ def cloudsc2_nl(fields: Dict[str, np.ndarray], in_eta: np.ndarray, dt, externals
         # :102-104
         t3d = F["in_t"][:nz] + dt * F["in_tnd_cml_t"][:nz]
         # :107-111
-        tmp_trpaus = _trpaus(eta, t3d, nz, dtype)
+        tmp_trpaus = _trpaus(eta, t3d, nz, dtype, bc)
 
         fplsl = np.zeros((nz, nx), dtype)
         fplsn = np.zeros((nz, nx), dtype)
@@ -312,6 +329,9 @@ def cloudsc2_nl(fields: Dict[str, np.ndarray], in_eta: np.ndarray, dt, externals
             _count(bc, "partial", ~clear & ~overcast)
             _count(bc, "cold_fwat", t < RTT)
             _count(bc, "ice_supersaturation", t < e["RTICE"])
+            _count(bc, "t_equals_RTICE", t == e["RTICE"])
+            _count(bc, "qt_equals_qcrit", qt == qcrit)
+            _count(bc, "qt_equals_qsat", qt == qsat)
             if e["LPHYLIN"] or e["LDRAIN1D"]:
                 _count(bc, "esdp_clipped", foeew / ap > e["ZQMAX"])
             clc = _where(clear, 0.0, _where(overcast, 1.0, clc_p))
@@ -324,6 +344,7 @@ def cloudsc2_nl(fields: Dict[str, np.ndarray], in_eta: np.ndarray, dt, externals
             lo1 = (lude >= e["RLMIN"]) & (in_lu[k + 1] >= ZEPS2)
             _count(bc, "detrainment", lo1)
             _count(bc, "detrainment_without_updraught_condensate", (lude >= e["RLMIN"]) & ~lo1)
+            _count(bc, "lu_equals_ZEPS2", (lude >= e["RLMIN"]) & (in_lu[k + 1] == ZEPS2))
             clc = _where(lo1, clc + (1.0 - clc) * (1.0 - np.exp(-lude / in_lu[k + 1])), clc)
             qc = _where(lo1, qc + lude, qc)
             # :218-224
@@ -335,13 +356,16 @@ def cloudsc2_nl(fields: Dict[str, np.ndarray], in_eta: np.ndarray, dt, externals
             dqc = np.minimum(dt * dqsdz * (in_mfu[k] + in_mfd[k]) / rho, qc)
             _count(bc, "subsidence_evaporates_all_condensate", (dqc >= qc) & (qc > 0.0))
             _count(bc, "subsidence_evaporates_part", (dqc < qc) & (dqc > 0.0))
+            _count(bc, "mass_fluxes_cancel", (in_mfu[k] + in_mfd[k] == 0.0) & (in_mfu[k] != 0.0))
             qc = qc - dqc
             # :227-230
+            _count(bc, "t_equals_RTT", (t == RTT) & (qc > 0.0))
             qlwc = qc * fwat
             qiwc = qc * (1.0 - fwat)
             condl = (qlwc - ql) / dt
             condi = (qiwc - qi) / dt
             # :234-235
+            _count(bc, "covptot_equals_clc_nonzero", (tmp_covptot == clc) & (clc != 0.0))
             tmp_covptot = np.maximum(tmp_covptot, clc)
             covpclr = np.maximum(tmp_covptot - clc, 0.0)
             # :238-246
@@ -349,6 +373,7 @@ def cloudsc2_nl(fields: Dict[str, np.ndarray], in_eta: np.ndarray, dt, externals
             cons = cons2 * dp / lfdcp
             snmlt = np.minimum(tmp_sfl, cons * np.maximum(t - meltp2, 0.0))
             _count(bc, "snow_enters_level", melt)
+            _count(bc, "t_equals_meltp2_with_snow", melt & (t == meltp2))
             _count(bc, "melting", melt & (snmlt > 0.0))
             _count(bc, "melting_all_snow", melt & (snmlt > 0.0) & (snmlt >= tmp_sfl))
             _count(bc, "melting_part_of_snow", melt & (snmlt > 0.0) & (snmlt < tmp_sfl))
@@ -371,6 +396,7 @@ def cloudsc2_nl(fields: Dict[str, np.ndarray], in_eta: np.ndarray, dt, externals
             dr = cons2 * dp * (prr + prs)
             frz = t < RTT
             _count(bc, "autoconversion", cloudy)
+            _count(bc, "t_equals_RTT_at_freezing", (t == RTT) & (dr > 0.0))
             _count(bc, "new_precip_as_snow", frz & (dr > 0.0))
             _count(bc, "new_precip_as_rain", ~frz & (dr > 0.0))
             _count(bc, "rain_refreezes", frz & (prr > 0.0))
@@ -391,6 +417,7 @@ def cloudsc2_nl(fields: Dict[str, np.ndarray], in_eta: np.ndarray, dt, externals
                 dpr = np.minimum(covpclr * b / dtgdp, preclr)
                 preclr = preclr - dpr
                 _count(bc, "evaporation", ev)
+                _count(bc, "q_equals_qsat", ev & (q == qs_in))
                 _count(bc, "evaporation_of_all_precip", ev & (preclr <= 0.0))
                 tmp_covptot = _where(ev & (preclr <= 0.0), clc, tmp_covptot)
                 out_covptot_k = _where(ev, tmp_covptot, 0.0)

@@ -64,13 +64,17 @@ def test_nl_case_reaches_every_nl_branch(nx, evap):
 
 
 def test_counting_does_not_change_results():
-    fields, eta, dt = nl_case(64)
-    outs = []
-    for bc in (None, {}):
-        F = dict(fields)
+    """with the branch counters and the tie counters (`oracle.TIE_COUNTERS`), on random data and on planted ties"""
+    from grid_support import tie_case
+
+    for fields, eta, dt in (nl_case(64), tie_case(40, np.float64)[:3]):
+        outs, bc = [], {}
+        for counts in (None, bc):
+            F = dict(fields)
+            for n in NL_OUT:
+                F["out_" + n] = np.zeros_like(fields["in_ap"])
+            oracle.cloudsc2_nl(F, eta, dt, externals(), branch_counts=counts)
+            outs.append({n: F["out_" + n] for n in NL_OUT})
+        assert set(oracle.TIE_COUNTERS) - {"q_equals_qsat"} <= set(bc)      # that one is counted in the evaporation block
         for n in NL_OUT:
-            F["out_" + n] = np.zeros_like(fields["in_ap"])
-        oracle.cloudsc2_nl(F, eta, dt, externals(), branch_counts=bc)
-        outs.append({n: F["out_" + n] for n in NL_OUT})
-    for n in NL_OUT:
-        assert np.array_equal(outs[0][n], outs[1][n]), n
+            assert np.array_equal(outs[0][n], outs[1][n]), n

@@ -12,12 +12,10 @@ Bounds: `assert_close` at its default against the single launches; |norm1 - norm
 member for the transpose identity (tests/test_hip_ad_multi.py); against the NumPy oracle `assert_close` at its default for
 the NL outputs and 100 x for the TL outputs and the adjoints (tests/test_hip_masked.py, tests/test_hip_ad_multi.py), for the
 step chained with the analytic derivative of `saturation` (tests/saturation_oracle.py)."""
-import ctypes
-
 import numpy as np
 import pytest
 
-from derivative_support import SEED, STATE4, STEP_IN, TND4, Box
+from derivative_support import SEED, STATE4, STEP_IN, TND4, Box, Ens, ens_ad, ens_nl, ens_tl
 from helpers import (NL_IN, NL_OUT, adjoint_nlev_of, assert_close, externals, from_device, increments, nl_case, nlev_of,
                      run_oracle_ad, run_oracle_nl, run_oracle_tl)
 from saturation_oracle import saturation_derivative
@@ -38,70 +36,6 @@ def _members(nmem, nx, nz, dtype):
     if key not in _cases:
         _cases[key] = [nl_case(nx, nz, dtype=dtype, seed=SEED + 100 + m) for m in range(nmem)]
     return _cases[key]
-
-
-class Ens:
-    """NaN-prefilled member-major batches of one geometry: member m of a field starts m * ms elements behind member 0"""
-
-    def __init__(self, box, nmem, gap):
-        self.box, self.nmem, self.ms, self.bufs = box, nmem, box.dir_stride + gap, []
-
-    def nan(self):
-        b = self.box
-        buf = b.torch.full((self.nmem, self.ms), float("nan"), dtype=b.dt, device=b.device)
-        self.bufs.append(buf)
-        return buf[:, :b.dir_stride].view(self.nmem, b.nz + 1, b.pitch)[:, :, b.col0:b.col0 + b.nx].unsqueeze(2).permute(0, 3, 2, 1)
-
-    def put(self, arrs):
-        f = self.nan()
-        for m, a in enumerate(arrs):
-            self.box.storage.klayout(f[m]).copy_(self.box.torch.as_tensor(a))
-        return f
-
-    def gaps_untouched(self):
-        return all(bool(buf[:, self.box.dir_stride:].isnan().all()) for buf in self.bufs)
-
-
-def _launch(entry, ens, ext, args_of):
-    """one ensemble entry; `args_of(p, geo, zero, stream)` -> the single entry's arguments"""
-    import torch
-
-    from gt4py_dwarf_p_cloudsc2_tl_ad_amd import _lib, autodiff
-
-    box = ens.box
-    p = autodiff._params(ext, box.nz)
-    zero = autodiff._zero_line(torch.device(box.device), box.dt)
-    args = args_of(p, (box.nx, box.nz + 1, box.pitch), zero, int(torch.cuda.current_stream().cuda_stream))
-    _lib.check(getattr(_lib.load(), f"cloudsc2_{entry}_{box.sfx}")(*args, ens.nmem, ens.ms), entry)
-    torch.cuda.synchronize()
-
-
-def _m0(fields):
-    return {n: f[0] for n, f in fields.items()}
-
-
-def ens_tl(entry, ens, ext, state, pert, eta, dt, out, out_i):
-    from gt4py_dwarf_p_cloudsc2_tl_ad_amd import autodiff
-
-    _launch(entry, ens, ext, lambda p, geo, zero, stream: autodiff._tl_args(
-        p, geo, _m0(state), _m0(pert), zero, eta, None if out is None else _m0(out), _m0(out_i), dt, stream))
-
-
-def ens_ad(entry, ens, ext, state, forcing, eta, dt, traj, out_adj):
-    from gt4py_dwarf_p_cloudsc2_tl_ad_amd import autodiff
-
-    _launch(entry, ens, ext, lambda p, geo, zero, stream: autodiff._ad_args(
-        p, geo, _m0(state), _m0(forcing), zero, eta, _m0(traj), _m0(out_adj), dt, stream))
-
-
-def ens_nl(ens, ext, state, eta, dt, out, qsat=None):
-    from gt4py_dwarf_p_cloudsc2_tl_ad_amd import autodiff
-
-    def args(p, geo, zero, stream):
-        head = (ctypes.byref(p), geo[0], geo[1] - 1, geo[2], autodiff._ptrs(_m0(state), NL_IN))
-        tail = (eta.data_ptr(), autodiff._ptrs(_m0(out), NL_OUT), float(dt), stream)
-        return head + tail if qsat is None else head + (None, 0.0, qsat[0].data_ptr()) + tail
-    _launch("nl_ens" if qsat is None else "nl_fused_ens", ens, ext, args)
 
 
 def compare_members(what, got, rows, names, nz, dtype, levels, ens):
