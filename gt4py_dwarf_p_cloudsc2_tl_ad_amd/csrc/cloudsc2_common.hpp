@@ -289,7 +289,8 @@ __device__ __forceinline__ T saturation_point(const Ext<T>& e, const ExpK<T>& xk
 // qsat, g_t = d qsat / d t and g_ap = d qsat / d ap of one point.  The value is saturation_point's own sequence (same
 // primitives, same comparisons, each exponential evaluated once), so the two agree bit for bit and the derivative is taken
 // on the branch the value took; a clamped branch has derivative 0:
-//     alfa' = 2 (t - TI) RI^2  for TI < t < RTWAT, else 0   (at t == RTWAT the inner and the outer clamp of alfa meet: 0)
+//     alfa' = 2 (t - TI) RI^2  for TI < t < RTWAT and alfa < 1, else 0   (RI is handed in, not formed from
+//             RTWAT - TI: only where RI == 1 / (RTWAT - TI) do the inner and the outer clamp of alfa meet at t == RTWAT)
 //     ew_t  = alfa' (el - ei) + alfa el R3LES (RTT - R4LES) / (t - R4LES)^2 + (1 - alfa) ei R3IES (RTT - R4IES) / (t - R4IES)^2
 //     clipped at QMAX (the value's own `ew / ap < QMAX` is false): qs_t = qs_ap = 0;  else qs_t = ew_t / ap, qs_ap = -ew / ap^2
 //     g_t = qs_t / (1 - RETV qs)^2,  g_ap = qs_ap / (1 - RETV qs)^2
@@ -319,7 +320,12 @@ __device__ __forceinline__ SatD<T> saturation_point_d(const Ext<T>& e, const Exp
     const bool open = q0 < e.QMAX;            // rmin's own comparison
     const T qs = open ? q0 : e.QMAX;
     const T rden = frcp<T>(T(1.0) - e.RETV * qs);
-    const T dalfa = (ti < tt && tt < e.RTWAT) ? T(2.0) * (tt - ti) * ri * ri : T(0.0);
+    // the outer clamp min(1, .) of alfa binds below RTWAT whenever RI (RTWAT - TI) > 1 (RI is a parameter of its own):
+    // alfa < 1 is that clamp's own comparison on the value already formed.  At the tie alfa == 1 with t < RTWAT the
+    // derivative is taken as 0, like at the other clamps here (a subgradient; tests/saturation_oracle.py's torch.clamp
+    // passes the gradient at x == max, so the two differ on that one point).  Written as a factor, which keeps
+    // tl_ens_step_kernel<double> free of scratch (held by tests/test_ensemble_isa.py).
+    const T dalfa = (ti < tt && tt < e.RTWAT) ? T(2.0) * (tt - ti) * ri * ri * (alfa < T(1.0) ? T(1.0) : T(0.0)) : T(0.0);
     const T ew_t = dalfa * (el - ei) + alfa * el * (e.R3LES * (e.RTT - e.R4LES)) * (rdl * rdl) +
                    (T(1.0) - alfa) * ei * (e.R3IES * (e.RTT - e.R4IES)) * (rdi * rdi);
     const T cor2 = rden * rden;

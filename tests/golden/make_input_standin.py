@@ -34,7 +34,15 @@ PREFIX = {"YrecldpParams": "YRECLDP_", "YrephliParams": "YREPHLI_"}
 
 
 def model_fields():
-    """[(dataset name, 'float' | 'int' | 'bool')] for every field of the reference's parameter models."""
+    """[(dataset name, 'float' | 'int' | 'bool')] for every field of the reference's parameter models; where the reference
+    checkout is absent, the names and kinds the committed stand-in file was written with (a logical is an 'int' there)."""
+    if not os.path.exists(REF_IOX):
+        sys.path.insert(0, ROOT)
+        from gt4py_dwarf_p_cloudsc2_tl_ad_amd.framework import h5lite
+
+        with h5lite.File(OUT) as f:
+            return [(k, "float" if f[k].dtype == np.float64 else "int") for k in sorted(f.keys())
+                    if f[k].shape == (1,) and k not in ("KLEV", "KLON", "PTSPHY")]
     out, cls = [], None
     for line in open(REF_IOX):
         m = re.match(r"class (\w+Params)\(BaseModel\):", line)
@@ -49,11 +57,21 @@ def model_fields():
     return out
 
 
-def stage1():
+def have_writer():
+    """the HDF5 library is reachable: stage 2 can run"""
+    return os.path.exists(H5PY_PYTHON)
+
+
+def stage1(out=OUT, values=None):
+    """`values`: parameter name -> value written instead of the stand-in's own, under the bare name and under its
+    YRECLDP_ / YREPHLI_ spellings (a test of the reader path writes a file off the provisional parameters with it)"""
     sys.path.insert(0, ROOT)
     from gt4py_dwarf_p_cloudsc2_tl_ad_amd.framework.iox import synthetic_dataset
 
     d = synthetic_dataset()
+    for k, v in (values or {}).items():
+        for name in (k, "YRECLDP_" + k, "YREPHLI_" + k):
+            d[name] = np.array([v])
     data = {}
     for k in ("KLEV", "KLON"):
         data[k] = np.asarray(d[k], dtype=np.int32).reshape(1)
@@ -71,8 +89,8 @@ def stage1():
     with tempfile.TemporaryDirectory() as tmp:
         npz = os.path.join(tmp, "standin.npz")
         np.savez(npz, **data)
-        subprocess.run([H5PY_PYTHON, os.path.abspath(__file__), "--write", npz, OUT], check=True)
-    print(OUT, os.path.getsize(OUT), "bytes,", len(data), "datasets")
+        subprocess.run([H5PY_PYTHON, os.path.abspath(__file__), "--write", npz, out], check=True)
+    print(out, os.path.getsize(out), "bytes,", len(data), "datasets")
 
 
 def stage2(npz, out):

@@ -2,8 +2,9 @@
 /root/reference, never copied) through tests/golden/gtscript_exec.py on seeded synthetic columns.
 
 Run in the build container only:  python tests/golden/make_reference_exec.py
-Writes tests/golden/reference_exec.npz, reference_exec_evap.npz (fp64) and reference_exec_f32.npz (float32 fields:
-the drivers' cases + LEVAPLS2; see main() for the fp32 semantics) - inputs + outputs, data only.  The GPU box has no
+Writes tests/golden/reference_exec.npz, reference_exec_evap.npz (fp64), reference_exec_f32.npz (float32 fields:
+the drivers' cases + LEVAPLS2; see main() for the fp32 semantics) and reference_exec_params.npz (fp64, the joint
+parameter set of tests/param_support.py; see main_params()) - inputs + outputs, data only.  The GPU box has no
 /root/reference, so the tests read the .npz.
 
 What the vectors pin: saturation, cloudsc2_nl (driver flags, and LEVAPLS2=True), cloudsc2_tl
@@ -233,6 +234,92 @@ def main(dtype=np.float64):
     print(path, len(ev), "arrays", os.path.getsize(path) // 1024, "KiB")
 
 
+def main_params(nx=16):
+    """`reference_exec_params.npz`: the reference's stencils under the joint parameter set of tests/param_support.py (every
+    real of the externals moved by its own factor, RVTMP2 = 0.6 x its factor - no identity of the provisional set holds),
+    fp64, 16 columns: saturation in its three forms, cloudsc2_nl, cloudsc2_tl with general increments and cloudsc2_ad with
+    general forcing.  Inputs, parameter values and outputs - data only."""
+    global DTYPE
+    DTYPE = np.float64
+    sys.path.insert(0, os.path.dirname(HERE))
+    from param_support import SATURATION_MODES, joint_set
+
+    defs = load_definitions(reference_stencil_files(REFERENCE))
+    params = joint_set(1)
+    ext = {**default_externals(), **params, "NLEV": NZ}
+    dt = DEFAULT_TIMESTEP_S
+    s = make_state(nx, NZ, seed=SEED + 2, dtype=DTYPE)
+    eta = eta_levels(NZ, seed=SEED + 2, dtype=DTYPE)
+    out = {"eta": eta, "dt": np.float64(dt), "nz": np.int64(NZ)}
+    for n, v in params.items():
+        out["param_" + n] = np.float64(v)
+    ins = {"in_" + k[2:]: v.copy() for k, v in s.items()}
+    for mode, sw in SATURATION_MODES.items():
+        qsat = zeros(nx)
+        _Exec(defs, {**ext, "KFLAG": 1, **sw}).run(
+            "saturation", {"in_ap": ins["in_ap"], "in_t": ins["in_t"], "out_qsat": qsat}, {}, NZ, domain_levels=NZ)
+        out["qsat_" + mode] = qsat
+    ins["in_qsat"] = out["qsat_lphylin"]
+    for n in NL_IN:
+        out["in_" + n] = ins["in_" + n]
+    klevel = np.arange(0, NZ + 1)
+    ij = lambda: np.zeros(nx, DTYPE)  # noqa: E731
+
+    f = {k: v.copy() for k, v in ins.items()}
+    f["in_eta"] = eta
+    for n in NL_OUT:
+        f["out_" + n] = zeros(nx)
+    for n in ("tmp_aph_s", "tmp_covptot", "tmp_rfl", "tmp_sfl", "tmp_trpaus"):
+        f[n] = ij()
+    _Exec(defs, ext).run("cloudsc2_nl", f, {"dt": dt}, NZ)
+    for n in NL_OUT:
+        out["nl_out_" + n] = f["out_" + n]
+
+    rng = np.random.default_rng(SEED + 3)
+    for n in NL_IN:
+        out[f"gen_{n}_i"] = ins["in_" + n] * rng.uniform(-0.02, 0.02, size=ins["in_" + n].shape)
+    out["gen_t_i"] = rng.normal(0.0, 0.3, size=ins["in_t"].shape) * (ins["in_t"] != 0)
+    f = {k: v.copy() for k, v in ins.items()}
+    f.update({"in_" + n + "_i": out[f"gen_{n}_i"].copy() for n in NL_IN})
+    f["in_eta"] = eta
+    f["tmp_klevel"] = klevel
+    for n in NL_OUT:
+        f["out_" + n] = zeros(nx)
+        f["out_" + n + "_i"] = zeros(nx)
+    for n in ("tmp_aph_s", "tmp_aph_s_i", "tmp_covptot", "tmp_covptot_i", "tmp_rfl", "tmp_rfl_i", "tmp_sfl", "tmp_sfl_i",
+              "tmp_trpaus"):
+        f[n] = ij()
+    _Exec(defs, ext).run("cloudsc2_tl", f, {"dt": dt}, NZ)
+    for n in NL_OUT:
+        out[f"tl_out_{n}"] = f["out_" + n]
+        out[f"tl_out_{n}_i"] = f["out_" + n + "_i"]
+
+    for n in NL_OUT:
+        scale = max(float(np.abs(out[f"nl_out_{n}"]).max()), 1e-30) if n != "covptot" else 1.0
+        out[f"genf_{n}"] = rng.normal(0.0, 1.0, size=(NZ + 1, nx)) * scale
+        out[f"genf_{n}"][NZ if n in ("clc", "covptot", "tnd_q", "tnd_qi", "tnd_ql", "tnd_t") else NZ + 1:] = 0.0
+    f = {k: v.copy() for k, v in ins.items()}
+    f["in_eta"] = eta
+    f["tmp_klevel"] = klevel
+    for n in NL_OUT:
+        f["in_" + n + "_i"] = out[f"genf_{n}"].copy()
+        f["out_" + n] = zeros(nx)
+    for n in NL_IN:
+        f["out_" + n + "_i"] = zeros(nx)
+    for n in ("tmp_aph_s", "tmp_aph_s_i", "tmp_covptotp", "tmp_rfln", "tmp_rfln_i", "tmp_sfln", "tmp_sfln_i", "tmp_trpaus"):
+        f[n] = ij()
+    _Exec(defs, ext).run("cloudsc2_ad", f, {"dt": dt}, NZ)
+    for n in NL_OUT:
+        out[f"ad_out_{n}"] = f["out_" + n]
+    for n in NL_IN:
+        out[f"ad_out_{n}_i"] = f["out_" + n + "_i"]
+    path = os.path.join(HERE, "reference_exec_params.npz")
+    np.savez_compressed(path, **out)
+    print(path, len(out), "arrays", os.path.getsize(path) // 1024, "KiB")
+
+
 if __name__ == "__main__":
-    main(np.float64)
-    main(np.float32)
+    if sys.argv[1:] != ["params"]:         # `params`: the parameter-set file alone
+        main(np.float64)
+        main(np.float32)
+    main_params()

@@ -11,7 +11,7 @@ import numpy as np
 
 from derivative_support import STEP_IN, Box, Ens, _once, ens_ad, ens_nl, ens_tl, host_case, host_directions
 from helpers import (NL_IN, NL_OUT, TOL, adjoint_nlev_of, assert_close, eta_levels, externals, from_device, nl_case, nlev_of,
-                     oracle, run_oracle_ad, run_oracle_nl, run_oracle_tl, symmetry_norm3)
+                     oracle, run_oracle_ad, run_oracle_nl, run_oracle_tl, symmetry_norm3, to_device)
 from saturation_oracle import saturation_derivative
 
 
@@ -339,6 +339,48 @@ def hold_nl(held, gpu, case, nx, path):
     if fused:
         held.field(f"nl[{path}, nx={nx}] qsat", from_device(extra["out_qsat"])[:nz], cut(case.fields["in_qsat"], nx)[:nz])
     return outs
+
+
+def hold_perturbed(held, gpu, case, inc, f2s):
+    """`cloudsc2_nl_perturbed` at f2s[0] point by point; the all-step-sizes `cloudsc2_nl_taylor_multi` and, one launch per
+    step size, `cloudsc2_nl_taylor` by their sums against the oracle's separate perturbed_state + cloudsc2_nl calls,
+    bounded as tests/test_hip_fused_oracle.py bounds them.  `inc`: in_*_i increments of the case's fields"""
+    import torch
+
+    from gt4py_dwarf_p_cloudsc2_tl_ad_amd import _lib
+    from gt4py_dwarf_p_cloudsc2_tl_ad_amd.stencils import compile_stencil, taylor_blocks
+    from test_hip_fused_oracle import _oracle_perturbed, _oracle_taylor_sums
+
+    nx, nz, dtype, ext = case.nx, case.nz, case.dtype, case.ext()
+    want = _oracle_perturbed(case.fields, inc, f2s[0], case.eta, case.dt, ext)
+    box = Box(nx, nz, dtype, gpu, False)
+    dev, dev_i = to_device(case.fields, gpu), to_device(inc, gpu)
+    com = dict(in_eta=device_eta(gpu, case.eta), dt=case.dt, origin=(0, 0, 0), domain=(nx, 1, nz + 1), validate_args=True,
+               exec_info=None)
+    outs = {n: box.nan() for n in NL_OUT}
+    compile_stencil("cloudsc2_nl_perturbed", ext)(**dev, **dev_i, **{"out_" + n: f for n, f in outs.items()}, f=f2s[0], **com)
+    assert _lib.last_kernel() == "cs2::nl_kernel"
+    held.fields("nl_perturbed", outs, want, NL_OUT, nlev_of, nz, nx)
+    ref = {n: box.nan() for n in NL_OUT}
+    compile_stencil("cloudsc2_nl", ext)(**dev, **{"out_" + n: f for n, f in ref.items()}, **com)
+    for f in ref.values():
+        f.nan_to_num_(nan=0.0)                     # the padding level of the reference outputs is read, and is zero
+    refs = {"ref_" + n: f for n, f in ref.items()}
+    part = torch.full((taylor_blocks(nx), len(f2s), len(NL_OUT)), float("nan"), dtype=torch.float64, device=gpu)
+    compile_stencil("cloudsc2_nl_taylor_multi", ext)(**dev, **dev_i, **refs, out_partials=part, fs=f2s, **com)
+    assert _lib.last_kernel() == "cs2::nl_taylor_multi_kernel"
+    single = torch.full((len(f2s), taylor_blocks(nx), len(NL_OUT)), float("nan"), dtype=torch.float64, device=gpu)
+    one = compile_stencil("cloudsc2_nl_taylor", ext)
+    for j, f2 in enumerate(f2s):
+        one(**dev, **dev_i, **refs, out_partials=single[j], f=f2, **com)
+    torch.cuda.synchronize()
+    got, got1 = part.sum(dim=0).cpu().numpy(), single.sum(dim=1).cpu().numpy()
+    base, sums, _ = _oracle_taylor_sums(case.fields, inc, f2s, case.eta, case.dt, ext)
+    tol = TOL[np.dtype(dtype)]
+    for fi, n in enumerate(NL_OUT):
+        bound = 2.0 * (tol["rtol"] + tol["atol_rel"]) * float(np.abs(base[n]).sum(dtype=np.float64)) + 1e-300
+        assert np.all(np.abs(got[:, fi] - sums[:, fi]) <= bound), (n, got[:, fi], sums[:, fi], bound)
+        assert np.all(np.abs(got1[:, fi] - sums[:, fi]) <= bound), (n, got1[:, fi], sums[:, fi], bound)
 
 
 def _put_dir(box, u, names, nx):

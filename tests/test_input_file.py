@@ -146,3 +146,113 @@ def test_oracle_reproduces_the_golden_file_from_the_real_input(oracle_numpy_back
 @pytest.mark.parametrize("cols", [100, 65536])
 def test_hip_reproduces_the_golden_file_from_the_real_input(gpu, precision, cols):
     _assert_golden(_run("hip", cols, REAL, precision, ("--enable-validation",)), precision)
+
+
+# ------------------------------------------------------------------------- parameters off the provisional point
+#: the reals a component sets itself (physics.py: `_microphysics_externals`, `Saturation`), whatever the file holds
+COMPONENT_LITERALS = {"ZEPS1": 1e-12, "ZEPS2": 1e-10, "ZQMAX": 0.5, "ZSCAL": 0.9, "QMAX": 0.5}
+_PARAM_RUNS = [(driver, flags + ["--precision", precision])
+               for precision in ("double", "single")
+               for driver, flags in (("run_nonlinear", []), ("run_nonlinear", ["--fused"]), ("run_taylor_test", []),
+                                     ("run_taylor_test", ["--fused-all"]), ("run_symmetry_test", []),
+                                     ("run_symmetry_test", ["--fused", "--ad-traj-fix"]))]
+
+
+def _record_params(record, h5file):
+    """runs in a process of its own, under the recording fake of the C ABI (tests/run_reference_on_recording_hip.py): the
+    three drivers on `h5file` -> [[run, entry point, the reals of the `Cloudsc2Params` it was called with], ...]"""
+    import contextlib
+    import io
+    import json
+    import sys
+
+    sys.path.insert(0, os.path.dirname(HERE))
+    sys.path.insert(0, HERE)
+    import run_reference_on_recording_hip as fake
+
+    fake.install_fakes()
+    from gt4py_dwarf_p_cloudsc2_tl_ad_amd.params import _REAL_FIELDS
+
+    calls = []
+    for driver, flags in _PARAM_RUNS:
+        module = __import__("gt4py_dwarf_p_cloudsc2_tl_ad_amd.drivers." + driver, fromlist=["main"])
+        with contextlib.redirect_stdout(io.StringIO()):
+            module.main(["--num-cols", "8", "--num-runs", "1", "--input", h5file] + flags)
+        for c in fake.ABI_CALLS:
+            for a in c["args"]:
+                if isinstance(a, dict) and "params" in a:
+                    calls.append([" ".join([driver] + flags), c["entry"], {n: a["params"][n] for n in _REAL_FIELDS}])
+        del fake.ABI_CALLS[:], fake.STENCIL_CALLS[:]
+    with open(record, "w") as fh:
+        json.dump(calls, fh)
+
+
+def test_parameters_of_an_input_file_reach_the_launched_struct(tmp_path):
+    """A stand-in HDF5 file that carries the joint parameter set of tests/param_support.py (every real moved by its own
+    factor, RVTMP2 non-zero, no two equal), written by the stand-in's own writer, read through framework/iox.py, handed
+    through the drivers' parameter groups and physics.py to the stencil objects: every real a stencil family reads is,
+    in the `Cloudsc2Params` its C entry is called with, the file's value bit for bit - or, for the five reals the
+    components set themselves, the component's literal - in double and in single precision (the struct holds doubles in
+    both).  A dropped, swapped or defaulted parameter on that path would show here.  What a family reads:
+    `param_support.READS`, asserted against the oracle's lookups in tests/test_parameter_sets.py."""
+    import json
+    import subprocess
+    import sys
+
+    sys.path.insert(0, os.path.join(HERE, "golden"))
+    import make_input_standin
+
+    from gt4py_dwarf_p_cloudsc2_tl_ad_amd.drivers._common import _PARAM_GROUPS
+    from gt4py_dwarf_p_cloudsc2_tl_ad_amd.framework import h5lite
+    from gt4py_dwarf_p_cloudsc2_tl_ad_amd.params import _REAL_FIELDS, default_externals
+    from param_support import READS, joint_set
+
+    if not make_input_standin.have_writer():
+        pytest.skip("no interpreter with the HDF5 library here: the stand-in file cannot be written")
+    joint = joint_set(1)
+    in_file = {n for n in _REAL_FIELDS if any(n in keys for keys in _PARAM_GROUPS.values())}
+    assert in_file | set(COMPONENT_LITERALS) == set(_REAL_FIELDS) and not in_file & set(COMPONENT_LITERALS)
+    h5file = str(tmp_path / "input_joint.h5")
+    make_input_standin.stage1(h5file, values=joint)
+    with h5lite.File(h5file) as f:                                   # the file holds the set, under every spelling
+        for n in in_file:
+            for key in (n, "YRECLDP_" + n, "YREPHLI_" + n):
+                assert key not in f or float(f[key][0]) == joint[n], key
+        assert float(f["RVTMP2"][0]) == joint["RVTMP2"] != 0.0 and float(f["YRECLDP_RCLCRIT"][0]) == joint["RCLCRIT"]
+    record = tmp_path / "params.json"
+    p = subprocess.run([sys.executable, os.path.abspath(__file__), "--record-params", str(record), h5file],
+                       capture_output=True, text=True, timeout=600, cwd=os.path.dirname(HERE),
+                       env=dict(os.environ, PYTHONDONTWRITEBYTECODE="1"))
+    assert p.returncode == 0, p.stdout[-2000:] + p.stderr[-6000:]
+    calls = json.loads(record.read_text())
+    want = {n: (joint[n] if n in in_file else COMPONENT_LITERALS[n]) for n in _REAL_FIELDS}
+    base = default_externals()
+    assert all(want[n] != base[n] for n in in_file)
+    saturation = READS["saturation[lphylin]"] | READS["saturation[kflag1]"] | READS["saturation[kflag0]"]
+    column = READS["nl[evap]"] | READS["nl[nolin]"]
+    seen = {}                                                        # (family, precision) -> the reals held to `want`
+    for run, entry, params in calls:
+        reads = set()
+        if "saturation" in entry or "nl_fused" in entry:            # `cloudsc2_nl_fused`: saturation inside cloudsc2_nl
+            reads |= saturation
+        if any(x in entry for x in ("_nl", "_tl", "_ad")):
+            reads |= column
+        if not reads:
+            continue                                                 # state_increment, perturbed_state: no parameter read
+        for n in reads:
+            assert params[n] == want[n], f"{run}: {entry} is called with {n} = {params[n]!r}, the file gives {want[n]!r}"
+        family = "saturation" if reads == saturation else "column" if reads == column else "fused"
+        seen.setdefault((family, entry[-3:]), set()).update(reads)
+    assert set(seen) == {(fam, sfx) for fam in ("saturation", "column", "fused") for sfx in ("f64", "f32")}, sorted(seen)
+    for sfx in ("f64", "f32"):
+        assert seen[("saturation", sfx)] | seen[("column", sfx)] == set(_REAL_FIELDS) == seen[("fused", sfx)]
+    entries = {entry for _, entry, _ in calls}
+    for name in ("cloudsc2_saturation", "cloudsc2_nl", "cloudsc2_tl", "cloudsc2_ad"):
+        assert name + "_f64" in entries and name + "_f32" in entries, sorted(entries)
+
+
+if __name__ == "__main__":
+    import sys
+
+    if len(sys.argv) == 4 and sys.argv[1] == "--record-params":
+        _record_params(sys.argv[2], sys.argv[3])

@@ -20,7 +20,10 @@ def _close(name, got, want):
 @pytest.mark.parametrize("nx", [37, 512])
 def test_c_nl_matches_numpy_oracle(sw, nx):
     ext = externals(**sw)
-    fields, eta, dt = nl_case(nx, 137, np.float64, ext=ext)
+    _hold_nl(ext, *nl_case(nx, 137, np.float64, ext=ext))
+
+
+def _hold_nl(ext, fields, eta, dt):
     want = run_oracle_nl(fields, eta, dt, ext)
     F = dict(fields)
     for n in NL_OUT:
@@ -41,13 +44,36 @@ def test_c_nl_matches_numpy_oracle(sw, nx):
 
 @pytest.mark.parametrize("sw", [dict(), dict(LPHYLIN=False, KFLAG=1), dict(LPHYLIN=False, KFLAG=0)])
 def test_c_saturation_matches_numpy_oracle(sw):
-    ext = externals(**sw)
-    fields, _, _ = nl_case(300, 137, np.float64)
+    _hold_saturation(externals(**sw), nl_case(300, 137, np.float64)[0])
+
+
+def _hold_saturation(ext, fields):
     want = np.zeros_like(fields["in_t"])
     cloudsc2_numpy.saturation(fields["in_ap"], fields["in_t"], want, ext)
     got = np.zeros_like(want)
     cloudsc2_c.saturation(fields["in_ap"], fields["in_t"], got, ext, nthreads=2)
     _close("qsat", got, want)
+
+
+@pytest.mark.parametrize("name", ["joint", "joint_opposite"])
+@pytest.mark.parametrize("sw", ["default", "evap", "nolin"])
+def test_c_nl_follows_the_joint_parameter_sets(sw, name):
+    """every real of `Cloudsc2Params` moved by its own factor, RVTMP2 non-zero (tests/param_support.py): the C restatement
+    reads the struct it is handed, as the NumPy oracle reads its externals; tests/test_parameter_sets.py shows that the
+    sets change the oracle's outputs by far more than 1e-12"""
+    from param_support import param_case
+
+    case = param_case(name, np.float64, sw, own_qsat=True)
+    _hold_nl(case.ext(), case.fields, case.eta, case.dt)
+
+
+@pytest.mark.parametrize("name", ["joint", "joint_opposite"])
+@pytest.mark.parametrize("mode", ["lphylin", "kflag1", "kflag0"])
+def test_c_saturation_follows_the_joint_parameter_sets(mode, name):
+    from param_support import SATURATION_MODES, param_case
+
+    case = param_case(name, np.float64)
+    _hold_saturation(case.ext(**SATURATION_MODES[mode]), case.fields)
 
 
 def test_thread_count_does_not_change_results():

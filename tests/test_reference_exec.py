@@ -157,6 +157,50 @@ def test_oracle_increment_and_perturbation_bit_exact(gold):
         assert np.array_equal(out[n], g[f"pert_{n}"]), n
 
 
+# ------------------------------------------------------------- off the provisional parameter point
+@pytest.fixture(scope="module")
+def gold_params():
+    """The reference's stencils executed under the joint parameter set of tests/param_support.py (RVTMP2 non-zero, no
+    identity of the provisional set left; tests/golden/make_reference_exec.py, `main_params`): 16 columns, fp64.
+    -> the file, the externals it was made with, the NL inputs"""
+    from param_support import joint_set
+
+    g = np.load(os.path.join(HERE, "golden", "reference_exec_params.npz"))
+    params = {k[len("param_"):]: float(g[k]) for k in g.files if k.startswith("param_")}
+    assert params == joint_set(1)                      # the file was made with the set the other tests use
+    return g, externals(NLEV=NZ, **params), {"in_" + n: g["in_" + n] for n in NL_IN}
+
+
+def test_oracle_under_the_joint_parameter_set_bit_exact(gold_params):
+    """saturation in its three forms, cloudsc2_nl, cloudsc2_tl with general increments and cloudsc2_ad with general forcing:
+    the oracle's RVTMP2 terms and its reading of the unequal pairs are the reference source's, as the vectors at the
+    provisional point are reproduced (the adjoints within 1e-12 of each column's scale: a few sums are grouped differently)"""
+    from param_support import SATURATION_MODES
+
+    g, ext, fields = gold_params
+    eta, dt = g["eta"], float(g["dt"])
+    for mode, sw in SATURATION_MODES.items():
+        q = np.zeros_like(fields["in_t"])
+        oracle.saturation(fields["in_ap"], fields["in_t"], q, {**ext, "KFLAG": 1, **sw})
+        assert np.array_equal(q, g["qsat_" + mode]), mode
+    assert not np.array_equal(g["qsat_kflag1"], g["qsat_kflag0"])          # RTICECU != RTICE is seen
+    o = run_oracle_nl(fields, eta, dt, ext)
+    for n in NL_OUT:
+        assert np.array_equal(o[n], g[f"nl_out_{n}"]), n
+    o, oi = run_oracle_tl(fields, {"in_" + n + "_i": g[f"gen_{n}_i"] for n in NL_IN}, eta, dt, ext)
+    for n in NL_OUT:
+        assert np.array_equal(o[n], g[f"tl_out_{n}"]), n
+        assert np.array_equal(oi[n], g[f"tl_out_{n}_i"]), n + "_i"
+    assert np.abs(g["tl_out_clc_i"]).max() > 1e-3
+    o, oi = run_oracle_ad(fields, {n: g[f"genf_{n}"] for n in NL_OUT}, eta, dt, ext)
+    for n in NL_OUT:
+        assert np.array_equal(o[n], g[f"ad_out_{n}"]), n
+    for n in NL_IN:
+        want = g[f"ad_out_{n}_i"]
+        scale = np.abs(want).max(axis=0, keepdims=True)
+        assert (np.abs(oi[n] - want) <= 1e-12 * scale).all(), (n, np.abs(oi[n] - want).max())
+
+
 # ------------------------------------------------------------------------------------------ GPU
 @pytest.mark.gpu
 @pytest.mark.parametrize("tag,flags", [("nl", {}), ("nl_evap", dict(LEVAPLS2=True)), ("nl_nolin", dict(LPHYLIN=False))])
@@ -291,3 +335,43 @@ def test_hip_saturation_matches_reference_source(gpu, gold):
                                                 validate_args=True, exec_info=None)
     torch.cuda.synchronize()
     assert_close("qsat", from_device(out)[:NZ], g["in_qsat"][:NZ])
+
+
+@pytest.mark.gpu
+def test_hip_under_the_joint_parameter_set_matches_reference_source(gpu, gold_params):
+    """the kernels against the executed reference source off the provisional parameter point, at the tolerances of the
+    general-increment vectors above: 1e-9 of a column's scale for values, 1e-8 for TL outputs, 1e-7 for adjoints"""
+    from derivative_support import Box
+    from gt4py_dwarf_p_cloudsc2_tl_ad_amd.stencils import compile_stencil
+    from helpers import from_device
+    from param_support import SATURATION_MODES
+    from test_hip_tl_ad import run_hip_ad, run_hip_tl
+
+    g, ext, fields = gold_params
+    eta, dt, nx = g["eta"], float(g["dt"]), fields["in_ap"].shape[1]
+    box = Box(nx, NZ, np.float64, gpu, False)
+    for mode, sw in SATURATION_MODES.items():
+        out = box.nan()
+        compile_stencil("saturation", {**ext, "KFLAG": 1, **sw})(
+            in_ap=box.put(fields["in_ap"]), in_t=box.put(fields["in_t"]), out_qsat=out, origin=(0, 0, 0), domain=(nx, 1, NZ),
+            validate_args=True, exec_info=None)
+        assert_close("qsat " + mode, from_device(out)[:NZ], g["qsat_" + mode][:NZ])
+    got, got_i = run_hip_tl(fields, {"in_" + n + "_i": g[f"gen_{n}_i"] for n in NL_IN}, eta, dt, ext, gpu, nx, NZ)
+    for n in NL_OUT:
+        k = nlev_of(n, NZ)
+        _close_by_column(f"params nl out_{n}", got[n][:k], g[f"nl_out_{n}"][:k], 1e-9)
+        _close_by_column(f"params tl out_{n}", got[n][:k], g[f"tl_out_{n}"][:k], 1e-9)
+        _close_by_column(f"params tl out_{n}_i", got_i[n][:k], g[f"tl_out_{n}_i"][:k], 1e-8)
+    outs = {n: box.nan() for n in NL_OUT}
+    box.stencil("cloudsc2_nl", ext, box.torch.as_tensor(eta, device=gpu), dt, **{k: box.put(v) for k, v in fields.items()},
+                **{"out_" + n: f for n, f in outs.items()})
+    for n in NL_OUT:
+        k = nlev_of(n, NZ)
+        _close_by_column(f"params cloudsc2_nl out_{n}", from_device(outs[n])[:k], g[f"nl_out_{n}"][:k], 1e-9)
+    got, got_i = run_hip_ad(fields, {n: g[f"genf_{n}"] for n in NL_OUT}, eta, dt, ext, gpu, nx, NZ)
+    for n in NL_OUT:
+        k = nlev_of(n, NZ)
+        _close_by_column(f"params ad out_{n}", got[n][:k], g[f"ad_out_{n}"][:k], 1e-9)
+    for n in NL_IN:
+        k = 138 if n in ("aph", "lu") else 137
+        _close_by_column(f"params ad out_{n}_i", got_i[n][:k], g[f"ad_out_{n}_i"][:k], 1e-7)

@@ -18,8 +18,8 @@ import numpy as np
 import pytest
 
 from grid_support import (CORE_GRIDS, Held, eta_family, grid_case, hold_dense, hold_ensemble, hold_masked, hold_multi, hold_nl,
-                          tropopause_window)
-from helpers import NL_OUT, eta_levels, nlev_of, to_device
+                          hold_perturbed, tropopause_window)
+from helpers import eta_levels
 
 ALL_GRIDS = ("synthetic", "uniform", "no_window_above", "no_window_below", "all_inside", "bottom_up", "nps_eq_klo",
              "nps_eq_klo_plus_1", "edge_values", "chunk_tail", "hole", "hole_overlapped")
@@ -118,45 +118,13 @@ def _general_increments(case):
 def test_perturbed_kernels_on_the_grid(gpu, nz, grid, dtype):
     """`cloudsc2_nl_perturbed` (`trpaus_prescan` on the perturbed t, chunks of 8) point by point, and the all-step-sizes
     `cloudsc2_nl_taylor_multi` (`trpaus_prescan_multi`) by its sums, bounded as tests/test_hip_fused_oracle.py bounds them"""
-    import torch
-
-    from gt4py_dwarf_p_cloudsc2_tl_ad_amd import _lib
-    from gt4py_dwarf_p_cloudsc2_tl_ad_amd.stencils import compile_stencil, taylor_blocks
-    from grid_support import Box, device_eta
-    from helpers import TOL
-    from test_hip_fused_oracle import _oracle_perturbed, _oracle_taylor_sums
-
     case = grid_case(grid, nz, dtype)
-    nx, ext, f2s = case.nx, case.ext(), (1.0, 0.5, 1e-2)
     inc = _general_increments(case)
-    want = _oracle_perturbed(case.fields, inc, f2s[0], case.eta, case.dt, ext)
     if tropopause_window(case.eta, nz)[2] > 0:      # the perturbation must move the tropopause, or the pre-scan's
         moved = {k: (v + inc[k + "_i"]).astype(case.dtype) for k, v in case.fields.items()}      # perturbed reads prove nothing
         assert (case.trpaus(moved) != case.trpaus()).any()
-    box = Box(nx, nz, dtype, gpu, False)
-    dev, dev_i = to_device(case.fields, gpu), to_device(inc, gpu)
-    com = dict(in_eta=device_eta(gpu, case.eta), dt=case.dt, origin=(0, 0, 0), domain=(nx, 1, nz + 1), validate_args=True,
-               exec_info=None)
-    outs = {n: box.nan() for n in NL_OUT}
-    compile_stencil("cloudsc2_nl_perturbed", ext)(**dev, **dev_i, **{"out_" + n: f for n, f in outs.items()}, f=f2s[0], **com)
-    assert _lib.last_kernel() == "cs2::nl_kernel"
     held = Held(f"perturbed {grid} nz={nz}", dtype)
-    held.fields("nl_perturbed", outs, want, NL_OUT, nlev_of, nz, nx)
-    ref = {n: box.nan() for n in NL_OUT}
-    compile_stencil("cloudsc2_nl", ext)(**dev, **{"out_" + n: f for n, f in ref.items()}, **com)
-    for f in ref.values():
-        f.nan_to_num_(nan=0.0)                     # the padding level of the reference outputs is read, and is zero
-    part = torch.full((taylor_blocks(nx), len(f2s), len(NL_OUT)), float("nan"), dtype=torch.float64, device=gpu)
-    compile_stencil("cloudsc2_nl_taylor_multi", ext)(**dev, **dev_i, **{"ref_" + n: f for n, f in ref.items()},
-                                                      out_partials=part, fs=f2s, **com)
-    assert _lib.last_kernel() == "cs2::nl_taylor_multi_kernel"
-    torch.cuda.synchronize()
-    got = part.sum(dim=0).cpu().numpy()
-    base, sums, _ = _oracle_taylor_sums(case.fields, inc, f2s, case.eta, case.dt, ext)
-    tol = TOL[np.dtype(dtype)]
-    for fi, n in enumerate(NL_OUT):
-        bound = 2.0 * (tol["rtol"] + tol["atol_rel"]) * float(np.abs(base[n]).sum(dtype=np.float64)) + 1e-300
-        assert np.all(np.abs(got[:, fi] - sums[:, fi]) <= bound), (n, got[:, fi], sums[:, fi], bound)
+    hold_perturbed(held, gpu, case, inc, (1.0, 0.5, 1e-2))
     held.done()
 
 
