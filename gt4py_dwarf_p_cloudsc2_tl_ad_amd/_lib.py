@@ -108,6 +108,12 @@ LAYOUTS: Dict[str, Layout] = {
 #: `in_dir_stride` and `out_dir_stride` (elements)
 MULTI_LAYOUTS: Dict[str, str] = {"tl_multi": "tl_masked", "tl_multi_step": "tl_step",
                                  "ad_multi": "ad_masked", "ad_multi_step": "ad_step"}
+#: the trajectory adjoints WITH the evaporation block (LEVAPLS2 / LDRAIN1D; autodiff.ad_masked_evap / ad_step_evap /
+#: ad_multi_evap / ad_step_multi_evap call them directly), one entry per stencil: name -> the entry whose argument list they
+#: repeat, followed by `cover` (a caller-owned device field) and `cover_ready` - in front of `stream` for the single entries,
+#: behind the direction arguments for the multi entries
+EVAP_LAYOUTS: Dict[str, str] = {"ad_evap": "ad_masked", "ad_evap_step": "ad_step",
+                                "ad_evap_multi": "ad_multi", "ad_evap_multi_step": "ad_multi_step"}
 #: the ensemble entries (autodiff calls them directly): name -> the single entry whose argument list they repeat, followed by
 #: `nmem` and `member_stride` (elements; one stride for every field of the call)
 ENS_LAYOUTS: Dict[str, str] = {"nl_ens": "nl", "nl_fused_ens": "nl_fused", "tl_ens": "tl_masked", "tl_step_ens": "tl_step",
@@ -145,6 +151,10 @@ def _signatures() -> Dict[str, Tuple[Any, Tuple[Any, ...]]]:
         sig[f"cloudsc2_ad_step_{sfx}"] = (c_int32, ad_masked)
         for multi, single in MULTI_LAYOUTS.items():
             sig[f"cloudsc2_{multi}_{sfx}"] = (c_int32, sig[f"cloudsc2_{single}_{sfx}"][1] + (c_int32, c_int64, c_int64))
+        for evap, base in EVAP_LAYOUTS.items():
+            args = sig[f"cloudsc2_{base}_{sfx}"][1]
+            extra = (c_void_p, c_int32)
+            sig[f"cloudsc2_{evap}_{sfx}"] = (c_int32, args + extra if base in MULTI_LAYOUTS else args[:-1] + extra + args[-1:])
         sig[f"cloudsc2_saturation_tl_{sfx}"] = (c_int32, sat_tl)
         sig[f"cloudsc2_saturation_ad_{sfx}"] = (c_int32, sat_ad)
         sig[f"cloudsc2_field_sums_{sfx}"] = (c_int32, reduction + (c_void_p,))

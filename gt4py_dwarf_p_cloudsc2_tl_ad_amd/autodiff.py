@@ -22,8 +22,15 @@ width per precision is `AD_MULTI_WIDTH`, set from the measurement of docs/TUNING
 `cloudsc2`, `cloudsc2_step` and `saturation` work under `torch.func`: `jvp`, `vjp`, `grad`, `jacfwd`, `jacrev`, and `vmap`
 over TANGENTS or COTANGENTS (`vmap` of `jvp`, which is what `jacfwd` is; `vmap` of a `vjp` function, which is what `jacrev`
 is).  Batched tangents run `tl_multi` / `tl_step_multi`; batched cotangents run `ad_multi` / `ad_step_multi` (the
-evaporation switches and the non-LPHYLIN step, which have no multi-direction kernel, loop over their single-cotangent
-fallbacks, and so does `saturation`, which is pointwise).
+non-LPHYLIN step, which has no multi-direction kernel, loops over its single-cotangent fallback, and so does `saturation`,
+which is pointwise).
+
+THE EVAPORATION SWITCHES (LEVAPLS2 / LDRAIN1D) in the adjoint.  `ad_masked_evap` / `ad_step_evap` / `ad_multi_evap` /
+`ad_step_multi_evap` are `ad_masked` / `ad_step` / `ad_multi` / `ad_step_multi` for them (C ABI `cloudsc2_ad_evap_*`): one launch
+that first parks the precipitation cover entering each level in a `cover` field and then runs the masked sweep with the
+evaporation block; `cover_ready=True` reuses a filled field.  The derivative rules use them only when the module-level
+`EVAP_ADJOINT` is `"trajectory"`; with its default `"dense"` a backward with the switches is the dense `cloudsc2_ad`, and
+batched cotangents loop over it, as before (docs/TUNING_LOG.md 3.22).
 
 ENSEMBLES: many states, one launch.  `cloudsc2_ensemble` / `cloudsc2_step_ensemble` are the two Functions on member-major
 `(nmem, nx, 1, nz+1)` fields - the layout of `storage.zeros_batched`, of `torch.stack` and of every `*_multi` result; `eta`,
@@ -32,8 +39,9 @@ ENSEMBLES: many states, one launch.  `cloudsc2_ensemble` / `cloudsc2_step_ensemb
 another layout is copied once).  `vmap` over the STATE of `cloudsc2` / `cloudsc2_step` runs them - `vmap(f)`,
 `vmap(grad(cost))`, `grad` through `vmap`, `vmap` of `jvp` over states and tangents - for a WHOLE state: every field batched (a state batched in part is refused as
 before: `expand` the fields the members share), unbatched tangents / cotangents expanded.  What
-has no ensemble kernel loops over the members through the single paths: the evaporation switches in the adjoint, the
-non-LPHYLIN step, and `saturation` with its derivatives (pointwise).  docs/TUNING_LOG.md 3.20 has the measurement.
+has no ensemble kernel loops over the members through the single paths: the evaporation switches in the adjoint (in either
+`EVAP_ADJOINT` mode: the cover kernels have no ensemble form), the non-LPHYLIN step, and `saturation` with its derivatives
+(pointwise).  docs/TUNING_LOG.md 3.20 has the measurement.
 
 Not supported: members TIMES directions in one call (nested `vmap`, e.g. `vmap(jacrev(f))`) and a batched `eta`
 (`NotImplementedError`), `torch.autograd.grad(..., is_grads_batched=True)` (the legacy vmap, which knows no `vmap` rule of a
@@ -66,6 +74,12 @@ MULTI_WIDTH: Dict[torch.dtype, int] = {torch.float64: 1, torch.float32: 1}
 #:   fp32 524 288 columns   D=2 1 896 -> 1 889   D=4 1 865 -> 1 441   D=8 1 823 -> 2 086   (4 launches 7 458 us +- 273, one 5 765 us)
 #: fp32 loses at 8: its 83 KB of LDS leave one workgroup per CU where 4 directions (59 KB) leave two.
 AD_MULTI_WIDTH: Dict[torch.dtype, int] = {torch.float64: 8, torch.float32: 4}
+#: how `backward` of `cloudsc2` / `cloudsc2_step` (and `jacrev` over them) runs with LEVAPLS2 / LDRAIN1D; read at backward time.
+#:   "dense"       the dense `cloudsc2_ad` (plus `saturation_ad` for the step), one launch per cotangent: what shipped before
+#:                 the trajectory kernels of the evaporation block existed, and still the default
+#:   "trajectory"  `ad_masked_evap` / `ad_step_evap`, batched cotangents `ad_multi_evap` / `ad_step_multi_evap`
+#: docs/TUNING_LOG.md 3.22 says when to set it.  Ensembles loop over their members either way.
+EVAP_ADJOINT = "dense"
 
 
 class _Family(NamedTuple):
@@ -83,6 +97,8 @@ _TL_MASKED = _Family("tl_masked", "tl_multi", NL_IN, MULTI_WIDTH, _lib.TL_MAX_DI
 _TL_STEP = _Family("tl_step", "tl_multi_step", STEP_IN, MULTI_WIDTH, _lib.TL_MAX_DIRS, ens="tl_step_ens")
 _AD_MASKED = _Family("ad_masked", "ad_multi", NL_IN, AD_MULTI_WIDTH, _lib.AD_MAX_DIRS, adjoint=True, ens="ad_ens")
 _AD_STEP = _Family("ad_step", "ad_multi_step", STEP_IN, AD_MULTI_WIDTH, _lib.AD_MAX_DIRS, adjoint=True, ens="ad_step_ens")
+_AD_MASKED_EVAP = _Family("ad_evap", "ad_evap_multi", NL_IN, AD_MULTI_WIDTH, _lib.AD_MAX_DIRS, adjoint=True)
+_AD_STEP_EVAP = _Family("ad_evap_step", "ad_evap_multi_step", STEP_IN, AD_MULTI_WIDTH, _lib.AD_MAX_DIRS, adjoint=True)
 _ZERO_LINE_BYTES = 512
 _zero_lines: Dict[Tuple[torch.device, torch.dtype], torch.Tensor] = {}
 
@@ -233,6 +249,47 @@ def ad_step_multi(state: Mapping[str, torch.Tensor], forcing: Mapping[str, torch
     return _call(_AD_STEP, True, state, forcing, eta, dt, externals, want, traj=traj, width=width)
 
 
+def ad_masked_evap(state: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+                   externals: Optional[Mapping[str, Any]] = None, *, traj: Mapping[str, torch.Tensor], want: Iterable[str],
+                   cover: Optional[torch.Tensor] = None, cover_ready: bool = False):
+    """`ad_masked` WITH the evaporation block (`cloudsc2_ad_evap_*`; LEVAPLS2 or LDRAIN1D must be set, `ValueError`
+    otherwise): the same arguments and result.  `cover` is the field the launch parks the precipitation cover entering each
+    level in (`storage` layout of the state; a new one when None).  `cover_ready=True`: `cover` already holds what an
+    earlier such call left for the same state, `traj`, `eta`, `dt` and externals - it is only read, and the forward cover
+    sweep is skipped.  Ensembles have no such kernel: loop over the members."""
+    return _call(_AD_MASKED_EVAP, False, state, forcing, eta, dt, externals, want, traj=traj, cover=cover,
+                 cover_ready=cover_ready)
+
+
+def ad_step_evap(state: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+                 externals: Optional[Mapping[str, Any]] = None, *, traj: Mapping[str, torch.Tensor], want: Iterable[str],
+                 cover: Optional[torch.Tensor] = None, cover_ready: bool = False):
+    """`ad_step` with the evaporation block in ONE launch (`cloudsc2_ad_evap_step_*`; `STEP_IN` names): see `ad_masked_evap`.
+    LPHYLIN only."""
+    return _call(_AD_STEP_EVAP, False, state, forcing, eta, dt, externals, want, traj=traj, cover=cover,
+                 cover_ready=cover_ready)
+
+
+def ad_multi_evap(state: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+                  externals: Optional[Mapping[str, Any]] = None, *, traj: Mapping[str, torch.Tensor], want: Iterable[str],
+                  width: Optional[int] = None, cover: Optional[torch.Tensor] = None, cover_ready: bool = False):
+    """`ad_multi` with the evaporation block (`cloudsc2_ad_evap_multi_*`): see `ad_multi` and `ad_masked_evap`.  The cover
+    field is not batched; the first chunk of `width` cotangents fills it (unless `cover_ready`), every later chunk reads it
+    (`cover_ready = 1`)."""
+    return _call(_AD_MASKED_EVAP, True, state, forcing, eta, dt, externals, want, traj=traj, width=width, cover=cover,
+                 cover_ready=cover_ready)
+
+
+def ad_step_multi_evap(state: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+                       externals: Optional[Mapping[str, Any]] = None, *, traj: Mapping[str, torch.Tensor],
+                       want: Iterable[str], width: Optional[int] = None, cover: Optional[torch.Tensor] = None,
+                       cover_ready: bool = False):
+    """`ad_step_multi` with the evaporation block (`cloudsc2_ad_evap_multi_step_*`; `STEP_IN` names): see `ad_multi_evap`.
+    LPHYLIN only."""
+    return _call(_AD_STEP_EVAP, True, state, forcing, eta, dt, externals, want, traj=traj, width=width, cover=cover,
+                 cover_ready=cover_ready)
+
+
 def tl_masked_ens(states: Mapping[str, torch.Tensor], perturbations: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
                   externals: Optional[Mapping[str, Any]] = None, *, want: Iterable[str], write_nl: bool = False):
     """`tl_masked` for an ENSEMBLE of `nmem` states in ONE launch (`cloudsc2_tl_ens_*`): `states` and `perturbations` map
@@ -334,16 +391,17 @@ def _tl_args(p, geo, state, pert, zero_line, eta, out, out_i, dt, stream, tail=(
             None if out is None else _ptrs(out, NL_OUT), _ptrs(out_i, NL_OUT), float(dt), stream) + tail
 
 
-def _ad_args(p, geo, state, forcing, zero_line, eta, traj, out_adj, dt, stream, tail=()):
-    """the arguments of `cloudsc2_ad_masked_*` / `_ad_step_*`; `tail` as for `_tl_args`"""
+def _ad_args(p, geo, state, forcing, zero_line, eta, traj, out_adj, dt, stream, tail=(), cover=()):
+    """the arguments of `cloudsc2_ad_masked_*` / `_ad_step_*`; `tail` as for `_tl_args`; `cover` = (pointer, cover_ready):
+    those of the `cloudsc2_ad_evap_*` entries (`_lib.EVAP_LAYOUTS`) - in front of `stream`, or behind a multi entry's `tail`"""
     nx, nlev, ls = geo
-    return (ctypes.byref(p), nx, nlev - 1, ls, _ptrs(state, NL_IN), _ptrs(forcing, NL_OUT), zero_line.data_ptr(),
-            eta.data_ptr(), traj["fplsl"].data_ptr(), traj["fplsn"].data_ptr(), _ptrs(out_adj, NL_IN), float(dt),
-            stream) + tail
+    head = (ctypes.byref(p), nx, nlev - 1, ls, _ptrs(state, NL_IN), _ptrs(forcing, NL_OUT), zero_line.data_ptr(),
+            eta.data_ptr(), traj["fplsl"].data_ptr(), traj["fplsn"].data_ptr(), _ptrs(out_adj, NL_IN), float(dt))
+    return head + (stream,) + tail + cover if tail else head + cover + (stream,)
 
 
 def _call(fam: _Family, batched: bool, state, dirs, eta, dt, externals, want, *, traj=None, write_nl=False, width=None,
-          ens=False):
+          ens=False, cover=None, cover_ready=False):
     """The launch path of the twelve thin calls.  Everything is checked ONCE, up front; then the directions are served in
     chunks of at most `width`: a chunk of one direction by the single-direction entry, a wider one by the multi-direction
     entry.  `batched`: `dirs` maps names to (ndir, nx, 1, nlev) batches and so do the results, which are one `zeros_batched`
@@ -351,7 +409,9 @@ def _call(fam: _Family, batched: bool, state, dirs, eta, dt, externals, want, *,
     single fields and there is one launch.  The NL outputs of `write_nl` are new fields, written by the first launch.
     `ens`: EVERY tensor of the call - state, `dirs`, `traj`, the results - is a member-major (nmem, nx, 1, nlev) batch of one
     layout (that of the first state tensor, `_ens_geometry`); the checks run on member 0 and ONE launch of the family's
-    ensemble entry, given member 0's pointers and (nmem, member stride), serves all members."""
+    ensemble entry, given member 0's pointers and (nmem, member stride), serves all members.
+    `cover`, `cover_ready`: the evaporation families' cover field (a new one when None); every chunk behind the first reads
+    what the first left in it."""
     what = fam.ens if ens else fam.multi if batched else fam.single
     noun, dir_names, res_names = ("forcing", NL_OUT, fam.names) if fam.adjoint else ("perturbation", fam.names, NL_OUT)
     want = tuple(want)
@@ -378,6 +438,11 @@ def _call(fam: _Family, batched: bool, state, dirs, eta, dt, externals, want, *,
     if fam.adjoint:
         traj = {n: _plain(f) for n, f in traj.items()}
         groups.append((traj, ("fplsl", "fplsn"), True))
+    evap = fam.single in _lib.EVAP_LAYOUTS
+    if evap and cover is not None:
+        groups.append(({"cover": _plain(cover)}, ("cover",), True))
+    elif cover_ready:
+        raise ValueError(f"{what}: cover_ready without a `cover` field that an earlier call filled")
     geo, dtype, device = _checked(what, groups)
     nx, nlev, ls = geo
     nz = nlev - 1
@@ -397,6 +462,8 @@ def _call(fam: _Family, batched: bool, state, dirs, eta, dt, externals, want, *,
     p = _params(externals, nz)
     lib, zero, dstride = _lib.load(), _zero_line(device, dtype), nlev * ls
     stream = int(torch.cuda.current_stream(device).cuda_stream)
+    if evap:
+        cover = _new_like(ref, nx, nz, ls) if cover is None else _plain(cover)
     if ens:
         new = lambda: _zeros_members(nmem, geo, dtype, device, mstride)  # noqa: E731
         res, out = {n: new() for n in want}, ({n: new() for n in NL_OUT} if write_nl else None)
@@ -416,7 +483,8 @@ def _call(fam: _Family, batched: bool, state, dirs, eta, dt, externals, want, *,
             d = {k: f[d0] for k, f in dirs.items()} if batched else dirs
             r = {k: f[d0] for k, f in res.items()} if batched else res
             if fam.adjoint:
-                args = _ad_args(p, geo, state, d, zero, eta, traj, r, dt, stream, tail)
+                park = (cover.data_ptr(), int(bool(cover_ready) or d0 > 0)) if evap else ()
+                args = _ad_args(p, geo, state, d, zero, eta, traj, r, dt, stream, tail, park)
             else:
                 args = _tl_args(p, geo, state, d, zero, eta, out if d0 == 0 else None, r, dt, stream, tail)
             _lib.check(getattr(lib, f"cloudsc2_{entry}_{_SFX[dtype]}")(*args), entry)
@@ -639,15 +707,24 @@ def _looped_adjoint(one, info, in_dims, call, tensors, nfixed, nout):
 
 def _ad_rule(fam, call, tensors, info=None, in_dims=None):
     """`forward` and, with `info` and `in_dims`, `vmap` of `_ADMasked` / `_ADStep`.  Where the adjoint is ONE launch of the
-    family - not with the evaporation switches, and the step with LPHYLIN only - batched cotangents take its multi-direction
-    launches.  Elsewhere they loop over this rule for one cotangent: the dense `cloudsc2_ad` (evaporation) or `ad_masked`,
-    for the step producing the adjoint of its `qsat`, which `saturation_ad` adds into those of `ap` and `t`."""
+    family - the step with LPHYLIN only; with the evaporation switches only under `EVAP_ADJOINT = "trajectory"`, which
+    swaps in the evaporation families (`ad_masked_evap` ...), and then for a single state only - batched cotangents take
+    its multi-direction launches.  Elsewhere they loop over this rule for one cotangent: the dense `cloudsc2_ad`
+    (evaporation, `EVAP_ADJOINT = "dense"`), `ad_masked_evap` or `ad_masked`, for the step producing the adjoint of its
+    `qsat`, which `saturation_ad` adds into those of `ap` and `t`.  Ensembles with the evaporation switches loop over their
+    members in either mode."""
     batched, step, want = info is not None, fam is _AD_STEP, call.want
     ext = dict(call.ext, AD_TRAJ_FIX=1)
-    one_launch = not _evap(ext) and (not step or bool(ext.get("LPHYLIN")))
+    if EVAP_ADJOINT not in ("dense", "trajectory"):
+        raise ValueError(f"autodiff.EVAP_ADJOINT must be 'dense' or 'trajectory', got {EVAP_ADJOINT!r}")
+    evap_traj = _evap(ext) and EVAP_ADJOINT == "trajectory"     # the cover kernels: single states only, no ensemble form
+    one_launch = (not _evap(ext) or (evap_traj and call.geo is not None)) and (not step or bool(ext.get("LPHYLIN")))
+    launch = (_AD_STEP_EVAP if step else _AD_MASKED_EVAP) if evap_traj else fam     # the family `_call` runs
     nfixed = len(fam.names) + step + 2
     if batched:
         _refuse_nested(tensors)
+        if one_launch and evap_traj and _batched_state(in_dims, nfixed):   # an ensemble of states: member by member
+            return _looped_adjoint(lambda c, *t: _ad_rule(fam, c, t), info, in_dims, call, tensors, nfixed, len(want))
         if one_launch and _batched_state(in_dims, nfixed):   # an ensemble of states: one ensemble launch
             outs = _ad_rule(fam, call._replace(geo=None), _members(info, in_dims[1:], tensors))
             return outs, (0,) * len(outs)
@@ -662,12 +739,14 @@ def _ad_rule(fam, call, tensors, info=None, in_dims=None):
                                len(want))
     state, qsat, traj, forcing = _unpacked(fam.names, step, True, call, tensors, info, in_dims)
     if one_launch:
-        adj = _call(fam, batched, state, forcing, call.eta, call.dt, ext, want, traj=traj)
+        adj = _call(launch, batched, state, forcing, call.eta, call.dt, ext, want, traj=traj)
     else:
         through = tuple(n for n in ("ap", "t") if step and n in want)    # the adjoints the path through qsat arrives in
         if step:
             state, want = dict(state, qsat=qsat), want + (("qsat",) if through else ())
-        if _evap(ext):
+        if evap_traj:
+            adj = ad_masked_evap(state, forcing, call.eta, call.dt, ext, traj=traj, want=want)
+        elif _evap(ext):
             adj = _dense_ad(state, forcing, call.eta, call.dt, ext, call.geo, want)
         else:
             adj = ad_masked(state, forcing, call.eta, call.dt, ext, traj=traj, want=want)
@@ -848,7 +927,8 @@ def cloudsc2(state: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
     `backward` is ONE masked adjoint launch: forcing = the gradients that arrived, results = the inputs that require one;
     `jvp` is one masked tangent-linear launch.  With LEVAPLS2 / LDRAIN1D the backward falls back to the dense
     `cloudsc2_ad` (which recomputes the trajectory: 70 words per level and column plus ten zero-filled forcing fields and
-    26 scratch results) - same gradients, at that cost.  Second derivatives are not available (`once_differentiable`)."""
+    26 scratch results) - same gradients, at that cost - unless `autodiff.EVAP_ADJOINT = "trajectory"`, which makes it one
+    `ad_masked_evap` launch (one cover field allocated per backward).  Second derivatives are not available (`once_differentiable`)."""
     outs = _Cloudsc2.apply(eta, dt, externals, *_state_fields("cloudsc2", state, NL_IN))
     return dict(zip(NL_OUT, outs))
 
@@ -1017,8 +1097,9 @@ def cloudsc2_step(state: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: floa
 
     `"qsat"` is returned for inspection and is not differentiable; who needs gradients through it composes `saturation`
     with `cloudsc2`.  Forward, LPHYLIN: one launch (`cloudsc2_nl_saturation`), otherwise `saturation` then `cloudsc2_nl`.
-    `backward` with LPHYLIN and without LEVAPLS2 / LDRAIN1D is ONE `cloudsc2_ad_step` launch; otherwise `ad_masked` (or the
-    dense `cloudsc2_ad` for the evaporation switches) producing the `qsat` adjoint, then `saturation_ad` adding into the
+    `backward` with LPHYLIN and without LEVAPLS2 / LDRAIN1D is ONE `cloudsc2_ad_step` launch (with the switches and
+    `EVAP_ADJOINT = "trajectory"`: one `cloudsc2_ad_evap_step` launch); otherwise `ad_masked` (or the dense `cloudsc2_ad`
+    for the evaporation switches, or `ad_masked_evap` under `"trajectory"`) producing the `qsat` adjoint, then `saturation_ad` adding into the
     `t` / `ap` adjoints.  `jvp` is one `cloudsc2_tl_step` launch, or `saturation_tl` then `tl_masked`."""
     if "qsat" in state:
         raise ValueError("cloudsc2_step: `state` holds `qsat`, which the step forms itself from `ap` and `t`; for a qsat of "

@@ -439,6 +439,80 @@ int32_t cloudsc2_ad_multi_step_f32(const Cloudsc2Params* p, int32_t nx, int32_t 
                                    float* const* out_adj, double dt, void* stream,
                                    int32_t ndir, int64_t in_dir_stride, int64_t out_dir_stride);
 
+/* ---- TRAJECTORY ADJOINTS WITH THE EVAPORATION BLOCK (BUILD EXTENSIONS): cloudsc2_ad_masked_*, cloudsc2_ad_step_*,
+ * cloudsc2_ad_multi_* and cloudsc2_ad_multi_step_* for LEVAPLS2 / LDRAIN1D, which those entries refuse.
+ *       entry                          arguments of                   kernel
+ *       cloudsc2_ad_evap_*             cloudsc2_ad_masked_*           cs2::ad_cover_kernel
+ *       cloudsc2_ad_evap_step_*        cloudsc2_ad_step_*             cs2::ad_cover_step_kernel
+ *       cloudsc2_ad_evap_multi_*       cloudsc2_ad_multi_*            cs2::ad_cover_dirs_kernel
+ *       cloudsc2_ad_evap_multi_step_*  cloudsc2_ad_multi_step_*       cs2::ad_cover_dirs_step_kernel
+ * plus two arguments - before `stream` in the single entries, behind the direction arguments in the multi entries:
+ *   cover        caller-owned DEVICE field of nz+1 levels at the call's lev_stride (the library still never allocates), not
+ *                batched over directions.  It must not overlap any other field of the call.  Level nz is never touched.
+ *                NULL is CLOUDSC2_E_ARG.
+ *   cover_ready  0: the launch fills `cover`, then reads it.  Non-zero: `cover` already holds what such a launch left for the
+ *                same state, trajectory fluxes, eta, dt and parameters; it is then read-only.  (The second and later chunks
+ *                of more than CLOUDSC2_AD_MAX_DIRS cotangents; repeated backward passes on one forward.)
+ * Why: with the evaporation block the precipitation cover ENTERING a level is loop-carried trajectory besides the two
+ * fluxes, and no NL output holds it (out_covptot is 0 both where the block did not run and where everything evaporated).
+ * Each launch therefore runs two sweeps, one lane per column: sweep 1 (levels 0 .. nz-1; skipped with cover_ready) takes the
+ * fluxes entering each level from traj_fplsl / traj_fplsn, recomputes the level and stores the cover entering it to
+ * cover[level]; sweep 2 is the masked / step / multi-direction adjoint sweep with the evaporation block, reading cover[level]
+ * with the level's words.  in_adj[NL_OUT_COVPTOT] is a forcing like the others; out_adj[NL_IN_APH] at level nz also
+ * receives the accumulated adjoint of the surface pressure.  The adjoints equal those of cloudsc2_ad given the same
+ * forcing, AD_TRAJ_FIX and a trajectory from cloudsc2_nl, to rounding (each kernel contracts the level functions itself).
+ * Everything the masked, step and multi entries check is checked here in the same way; a call with NEITHER LEVAPLS2 nor
+ * LDRAIN1D is CLOUDSC2_E_UNSUPPORTED (the message names the entry to use instead); nx == 0 is a successful no-op.
+ * LDS of the multi entries: the level table; six carry words per direction (6 * ndir * 256 elements: two pairs of the
+ * backward carry are kept as their sums, which is exact); parked trajectory words, 34 * 256 elements in fp32 and 30 * 256
+ * in fp64 (there the level's trajectory would not fit the registers across the direction loop).  ndir = 8, nz = 137: about
+ * 158 KB in fp64, 83 KB in fp32; beyond 160 KB the call is refused (fp64: ndir = 8 beyond nz = 255).  Ensembles have no
+ * such entry.
+ * Words moved per level and column: sweep 1 reads 16 (step: 15) + 2 and writes 1; sweep 2 moves 16 (15) + 2 + 1 + ndir *
+ * ((present in_adj) + (wanted out_adj)).  Forcing on the four tendencies, adjoints of t, q, ql, qi, one direction:
+ * 19 + 19 + 8 = 46 against 70 of cloudsc2_ad; eight directions: 38 + 64 = 102 against 560.  With cover_ready sweep 1's 19
+ * drop out. */
+int32_t cloudsc2_ad_evap_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                             const double* const* in, const double* const* in_adj, const double* zero_line,
+                             const double* eta, const double* traj_fplsl, const double* traj_fplsn,
+                             double* const* out_adj, double dt, double* cover, int32_t cover_ready, void* stream);
+int32_t cloudsc2_ad_evap_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                             const float* const* in, const float* const* in_adj, const float* zero_line,
+                             const float* eta, const float* traj_fplsl, const float* traj_fplsn,
+                             float* const* out_adj, double dt, float* cover, int32_t cover_ready, void* stream);
+int32_t cloudsc2_ad_evap_step_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                  const double* const* in, const double* const* in_adj, const double* zero_line,
+                                  const double* eta, const double* traj_fplsl, const double* traj_fplsn,
+                                  double* const* out_adj, double dt, double* cover, int32_t cover_ready, void* stream);
+int32_t cloudsc2_ad_evap_step_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                  const float* const* in, const float* const* in_adj, const float* zero_line,
+                                  const float* eta, const float* traj_fplsl, const float* traj_fplsn,
+                                  float* const* out_adj, double dt, float* cover, int32_t cover_ready, void* stream);
+int32_t cloudsc2_ad_evap_multi_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                   const double* const* in, const double* const* in_adj, const double* zero_line,
+                                   const double* eta, const double* traj_fplsl, const double* traj_fplsn,
+                                   double* const* out_adj, double dt, void* stream,
+                                   int32_t ndir, int64_t in_dir_stride, int64_t out_dir_stride,
+                                   double* cover, int32_t cover_ready);
+int32_t cloudsc2_ad_evap_multi_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                   const float* const* in, const float* const* in_adj, const float* zero_line,
+                                   const float* eta, const float* traj_fplsl, const float* traj_fplsn,
+                                   float* const* out_adj, double dt, void* stream,
+                                   int32_t ndir, int64_t in_dir_stride, int64_t out_dir_stride,
+                                   float* cover, int32_t cover_ready);
+int32_t cloudsc2_ad_evap_multi_step_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                        const double* const* in, const double* const* in_adj, const double* zero_line,
+                                        const double* eta, const double* traj_fplsl, const double* traj_fplsn,
+                                        double* const* out_adj, double dt, void* stream,
+                                        int32_t ndir, int64_t in_dir_stride, int64_t out_dir_stride,
+                                        double* cover, int32_t cover_ready);
+int32_t cloudsc2_ad_evap_multi_step_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                        const float* const* in, const float* const* in_adj, const float* zero_line,
+                                        const float* eta, const float* traj_fplsl, const float* traj_fplsn,
+                                        float* const* out_adj, double dt, void* stream,
+                                        int32_t ndir, int64_t in_dir_stride, int64_t out_dir_stride,
+                                        float* cover, int32_t cover_ready);
+
 /* ---- ENSEMBLES: the NL step, the masked TL / AD and the step TL / AD for `nmem` MEMBERS in one launch (BUILD EXTENSIONS):
  * an ensemble of model states, per-member gradients, an ML batch.  Unlike the multi-direction entries above EVERYTHING a
  * call has is batched - state, perturbations or forcing, trajectory fluxes, every output, qsat_out - and every member is a
