@@ -150,10 +150,7 @@ ad_kernel(const ADArgs<T> A) {
     }   // !TRAJ
 
     // ---------------- sweep 2: adjoint (:479-996), k = nz-1 .. 0
-    ADBack<T> b;
-    b.tmp_rfln_i = b.tmp_sfln_i = b.rfl_i = b.sfl_i = b.daph_i = b.dp_i = T(0.0);
-    b.covptot_i = b.aph_s_i = T(0.0);
-    b.aph_s = aph_s;
+    ADBack<T> b = zero_back<T>(aph_s);
     {
         int k = nz - 1;
         O o = O(k) * lsb + colb;
@@ -231,33 +228,23 @@ int launch_ad(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* cons
     MPtrs<T, NL_NUM_IN> coa;
     for (int i = 0; i < NL_NUM_IN; ++i) { ci.p[i] = in[i]; coa.p[i] = out_adj[i]; }
     for (int i = 0; i < NL_NUM_OUT; ++i) { ca.p[i] = in_adj[i]; co.p[i] = out ? out[i] : nullptr; }
-    const dim3 grid((nx + kColBlock - 1) / kColBlock), block(kColBlock);
+    const dim3 grid((nx + kColBlock - 1) / kColBlock);
     const size_t smem = 2 * size_t(nz + 1) * sizeof(T) + (kADPark<T> ? size_t(CS2_AD_PARK_COUNT) * kColBlock * sizeof(T) : 0);
     const T tdt = static_cast<T>(dt);
     const NLK<T> kc = make_nlk<T>(p, dt, evap);
     const ExpK<T> xk = make_expk<T>();
     const bool big = !fits_u32_offsets<T>(nz, ls);
-    if (smem > size_t(160) * 1024) return -2;
-    int dev = 0;
-    if (smem > size_t(64) * 1024)
-        if (const int rc = current_device(dev)) return rc;
-    if (traj && (evap || big)) return -2;   // the trajectory variant: driver switches, 32-bit offsets
+    // the trajectory variant: driver switches, 32-bit offsets.  (Refused in front of the launch tail's device look-up, which
+    // it used to follow: both refuse without a side effect, and the entry that leads here checks the same before it calls.)
+    if (traj && (evap || big)) return -2;
     const ADArgs<T> args = {e, kc, xk, nx, nz, ls, ci, ca, eta, co, coa, tdt, traj_l, traj_n};
-    const int rc = with_flags(
+    const char* const name = traj ? "cs2::ad_kernel<trajectory>" : big ? "cs2::ad_kernel<big>" : "cs2::ad_kernel";
+    return with_flags(
         [&](auto REG, auto FIX, auto TRAJ, auto EVAP, auto BIG) {
-            if constexpr (TRAJ && (EVAP || BIG)) {
-                return 0;   // refused above: no such instantiation
-            } else {
-                constexpr auto kern = ad_kernel<T, REG, FIX, EVAP, BIG, TRAJ>;
-                if (smem > size_t(64) * 1024 && !lds_opt_in<kern>(dev, smem)) return -1;
-                hipLaunchKernelGGL(kern, grid, block, smem, stream, args);
-                return 0;
-            }
+            if constexpr (TRAJ && (EVAP || BIG)) return -2;   // refused above: no such instantiation
+            else return launch_ad_tail<ad_kernel<T, REG, FIX, EVAP, BIG, TRAJ>>(grid, smem, stream, args, name);
         },
         p.LREGCL != 0, p.AD_TRAJ_FIX != 0, traj, evap, big);
-    if (rc) return rc;
-    note_kernel(traj ? "cs2::ad_kernel<trajectory>" : big ? "cs2::ad_kernel<big>" : "cs2::ad_kernel");
-    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 template int launch_ad<double>(const Cloudsc2Params&, int, int, int64_t, const double* const*, const double* const*,
@@ -354,10 +341,7 @@ __device__ __forceinline__ void ad_masked_sweep(const ADMaskedArgs<T>& A, const 
     const T trpaus = trpaus_prescan<T, false, O>(F.in(NL_IN_T), F.in(NL_IN_TND_CML_T), lsb, colb, dt, s_eta, klo, khi);
     const CrhCol<T> crh = crh_setup<T>(trpaus);
 
-    ADBack<T> b;
-    b.tmp_rfln_i = b.tmp_sfln_i = b.rfl_i = b.sfl_i = b.daph_i = b.dp_i = T(0.0);
-    b.covptot_i = b.aph_s_i = T(0.0);
-    b.aph_s = T(1.0);
+    ADBack<T> b = zero_back<T>(T(1.0));
     // ONE loop, k = nz .. -1, and nothing of a level outside it: iteration k requests level k-1's words, stores level k+1's
     // adjoints and computes level k (the first iteration only requests, the last only stores).
     //   * A level's adjoints are stored ONE ITERATION LATE, right behind the next prefetch: with the store count unknown,
@@ -367,13 +351,9 @@ __device__ __forceinline__ void ad_masked_sweep(const ADMaskedArgs<T>& A, const 
     //   * No prologue batch and no epilogue stores: hipcc lays such blocks out around the loop as it pleases, and
     //     check_ring_isa.check_prefetch_distance reads every backward branch as a loop.
     O o = O(nz) * lsb + colb, po = o;
-    ADOut<T> pa;
-    pa.ap = pa.t = pa.q = pa.ql = pa.qi = pa.qsat = pa.lude = pa.mfd = pa.mfu = pa.aph1 = pa.lu1 = T(0.0);
-    LevelIn<T> xa;
-    xa.ap = xa.aph1 = xa.lu1 = xa.lude = xa.mfd = xa.mfu = xa.q = xa.qi = xa.ql = xa.qsat = xa.supsat = xa.t = xa.tq = xa.tqi =
-        xa.tql = xa.tt = T(0.0);
-    ADForce<T> fa;
-    fa.clc = fa.tnd_q = fa.tnd_qi = fa.tnd_ql = fa.tnd_t = fa.fplsl1 = fa.fplsn1 = fa.fhpsl1 = fa.fhpsn1 = fa.covptot = T(0.0);
+    ADOut<T> pa = zero_out<T>();
+    LevelIn<T> xa = zero_level<T>();
+    ADForce<T> fa = zero_force<T>();
     T aph_k = ldg(F.in(NL_IN_APH), o), sfl = T(0.0), rfl = T(0.0);   // aph[nz]: level nz-1's lower half level
     T pt = T(273.0), pap = T(1.0e5);   // STEP: t and ap of the level whose adjoints `pa` holds
     for (int k = nz; k >= -1; --k) {
@@ -464,33 +444,22 @@ int launch_ad_masked(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const 
     ADMaskedArgs<T>& args = ens.m;
     fill_ad_masked_args<T>(args, p, nx, nz, ls, in, in_adj, zero, eta, traj_l, traj_n, out_adj, dt);
     const int bpm = (nx + kColBlock - 1) / kColBlock;
-    const dim3 grid(bpm), block(kColBlock);
+    const dim3 grid(bpm);
     const size_t smem = 2 * size_t(nz + 1) * sizeof(T) + (kADPark<T> ? size_t(CS2_AD_PARK_COUNT) * kColBlock * sizeof(T) : 0);
-    if (smem > size_t(160) * 1024) return -2;
     if (nmem > 0 && int64_t(nmem) * bpm > kMaxGrid) return -2;
     ens.g.ms = ms; ens.g.bpm = bpm;
     const dim3 egrid(unsigned(nmem > 0 ? nmem : 1) * unsigned(bpm));
-    int dev = 0;
-    if (smem > size_t(64) * 1024)
-        if (const int rc = current_device(dev)) return rc;
-    const int rc = with_flags(
+    return with_flags(
         [&](auto REG, auto FIX, auto STEP, auto ENS) {
             if constexpr (ENS) {
                 constexpr auto kern = STEP ? ad_ens_step_kernel<T, REG, FIX> : ad_ens_kernel<T, REG, FIX>;
-                if (smem > size_t(64) * 1024 && !lds_opt_in<kern>(dev, smem)) return -1;
-                hipLaunchKernelGGL(kern, egrid, block, smem, stream, ens);
+                return launch_ad_tail<kern>(egrid, smem, stream, ens, step ? "cs2::ad_ens_step_kernel" : "cs2::ad_ens_kernel");
             } else {
                 constexpr auto kern = STEP ? ad_step_kernel<T, REG, FIX> : ad_masked_kernel<T, REG, FIX>;
-                if (smem > size_t(64) * 1024 && !lds_opt_in<kern>(dev, smem)) return -1;
-                hipLaunchKernelGGL(kern, grid, block, smem, stream, args);
+                return launch_ad_tail<kern>(grid, smem, stream, args, step ? "cs2::ad_step_kernel" : "cs2::ad_masked_kernel");
             }
-            return 0;
         },
         p.LREGCL != 0, p.AD_TRAJ_FIX != 0, step, nmem > 0);
-    if (rc) return rc;
-    if (nmem > 0) note_kernel(step ? "cs2::ad_ens_step_kernel" : "cs2::ad_ens_kernel");
-    else note_kernel(step ? "cs2::ad_step_kernel" : "cs2::ad_masked_kernel");
-    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 template int launch_ad_masked<double>(const Cloudsc2Params&, int, int, int64_t, const double* const*, const double* const*,
@@ -582,11 +551,8 @@ __device__ __forceinline__ void ad_dirs_sweep(const ADDirsArgs<T>& A) {
     // level k-1's state words and computes level k; the first iteration only requests - its direction loop runs the last
     // direction's look-ahead alone, which is direction 0 of level nz-1.
     O o = O(nz) * lsb + colb;
-    LevelIn<T> xa;
-    xa.ap = xa.aph1 = xa.lu1 = xa.lude = xa.mfd = xa.mfu = xa.q = xa.qi = xa.ql = xa.qsat = xa.supsat = xa.t = xa.tq = xa.tqi =
-        xa.tql = xa.tt = T(0.0);
-    ADForce<T> fa;
-    fa.clc = fa.tnd_q = fa.tnd_qi = fa.tnd_ql = fa.tnd_t = fa.fplsl1 = fa.fplsn1 = fa.fhpsl1 = fa.fhpsn1 = fa.covptot = T(0.0);
+    LevelIn<T> xa = zero_level<T>();
+    ADForce<T> fa = zero_force<T>();
     T aph_k = ldg(F.in(NL_IN_APH), o), sfl = T(0.0), rfl = T(0.0);   // aph[nz]: level nz-1's lower half level
     for (int k = nz; k >= 0; --k) {
         const bool more = k > 0, live = k < nz;
@@ -668,22 +634,18 @@ int launch_ad_dirs(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T*
     ADDirsArgs<T> args;
     fill_ad_masked_args<T>(args.m, p, nx, nz, ls, in, in_adj, zero, eta, traj_l, traj_n, out_adj, dt);
     args.in_ds = in_ds; args.out_ds = out_ds; args.ndir = ndir;
-    const dim3 grid((nx + kColBlock - 1) / kColBlock), block(kColBlock);
+    const dim3 grid((nx + kColBlock - 1) / kColBlock);
     const size_t smem = ad_dirs_lds_bytes<T>(nz, ndir);
-    if (smem > size_t(160) * 1024) return -2;
-    int dev = 0;
-    if (const int rc = current_device(dev)) return rc;
-    const int rc = with_flags(
+    // device_always: this launcher has looked the device up below 64 KiB of LDS as well since it was written (as
+    // launch_tl_dirs does), so a device ordinal beyond kMaxDevices is refused here (-2) where the single-direction
+    // launchers still run.  Nothing in the launch needs it; kept so that no call changes its outcome.
+    return with_flags(
         [&](auto REG, auto FIX, auto STEP) {
             constexpr auto kern = STEP ? ad_dirs_step_kernel<T, REG, FIX> : ad_dirs_kernel<T, REG, FIX>;
-            if (smem > size_t(64) * 1024 && !lds_opt_in<kern>(dev, smem)) return -1;
-            hipLaunchKernelGGL(kern, grid, block, smem, stream, args);
-            return 0;
+            return launch_ad_tail<kern>(grid, smem, stream, args, step ? "cs2::ad_dirs_step_kernel" : "cs2::ad_dirs_kernel",
+                                        true);
         },
         p.LREGCL != 0, p.AD_TRAJ_FIX != 0, step);
-    if (rc) return rc;
-    note_kernel(step ? "cs2::ad_dirs_step_kernel" : "cs2::ad_dirs_kernel");
-    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 template int launch_ad_dirs<double>(const Cloudsc2Params&, int, int, int64_t, const double* const*, const double* const*,

@@ -10,8 +10,8 @@
 //           trajectory fields, not carried: the level's ad_forward is then the very computation sweep 2 repeats),
 //           ad_forward<T, FIX, true>, and ONE store - the cover entering level k to `cover[k]`, a caller-owned field; the
 //           level's resulting cover is carried.  hipcc drops what of ad_forward the cover does not depend on;
-//   sweep 2 (k = nz-1 .. 0): the loop of ad_masked_sweep (one level of prefetch, absent forcings from the zero line, stores
-//           one iteration late under `want`, fp32 parking) with EVAP = true: `cover[k]` joins the level batch, the forcing
+//   sweep 2 (k = nz-1 .. 0): a copy of the loop of ad_masked_sweep (kept apart from it: docs/TUNING_LOG.md 3.23; one level
+//           of prefetch, absent forcings from the zero line, stores one iteration late under `want`, fp32 parking) with EVAP = true: `cover[k]` joins the level batch, the forcing
 //           on covptot is read, aph[nz] is the surface pressure, and the accumulated adjoint of the surface pressure is
 //           added into out_adj[NL_IN_APH] at level nz behind the loop (ad_kernel's :970-971).
 // A lane's cover words are written and later read by that lane only: no cross-lane dependency, no barrier (as with the
@@ -131,20 +131,6 @@ __device__ __forceinline__ bool ad_cover_setup(const ADMaskedArgs<T>& A, const A
     return true;
 }
 
-template <typename T>
-__device__ __forceinline__ LevelIn<T> zero_level() {
-    LevelIn<T> x;
-    x.ap = x.aph1 = x.lu1 = x.lude = x.mfd = x.mfu = x.q = x.qi = x.ql = x.qsat = x.supsat = x.t = x.tq = x.tqi = x.tql = x.tt =
-        T(0.0);
-    return x;
-}
-template <typename T>
-__device__ __forceinline__ ADForce<T> zero_force() {
-    ADForce<T> f;
-    f.clc = f.tnd_q = f.tnd_qi = f.tnd_ql = f.tnd_t = f.fplsl1 = f.fplsn1 = f.fhpsl1 = f.fhpsn1 = f.covptot = T(0.0);
-    return f;
-}
-
 // Sweep 1: cover[k] = the precipitation cover entering level k, k = 0 .. nz-1.
 template <typename T, bool FIX, bool STEP>
 __device__ __forceinline__ void ad_cover_fill(ADMaskedFields<T>& F, const ADCoverCol<T>& c, T* __restrict__ cover) {
@@ -209,14 +195,10 @@ __device__ __forceinline__ void ad_cover_sweep(const ADCoverArgs<T>& A) {
     const int nz = c.nz;
     const O lsb = c.lsb, colb = c.colb, zo = c.zo;
     const T dt = c.dt;
-    ADBack<T> b;
-    b.tmp_rfln_i = b.tmp_sfln_i = b.rfl_i = b.sfl_i = b.daph_i = b.dp_i = T(0.0);
-    b.covptot_i = b.aph_s_i = T(0.0);
-    b.aph_s = c.aph_s;
+    ADBack<T> b = zero_back<T>(c.aph_s);
     // ONE loop, k = nz .. -1: iteration k requests level k-1's words, stores level k+1's adjoints and computes level k
     O o = O(nz) * lsb + colb, po = o;
-    ADOut<T> pa;
-    pa.ap = pa.t = pa.q = pa.ql = pa.qi = pa.qsat = pa.lude = pa.mfd = pa.mfu = pa.aph1 = pa.lu1 = T(0.0);
+    ADOut<T> pa = zero_out<T>();
     LevelIn<T> xa = zero_level<T>();
     ADForce<T> fa = zero_force<T>();
     T aph_k = c.aph_s, sfl = T(0.0), rfl = T(0.0), cov = T(0.0);   // aph[nz]: level nz-1's lower half level
@@ -419,31 +401,21 @@ int launch_ad_cover(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T
     dargs.d.in_ds = in_ds; dargs.d.out_ds = out_ds; dargs.d.ndir = ndir;
     dargs.cover = sargs.cover = cover;
     dargs.cover_ready = sargs.cover_ready = cover_ready;
-    const dim3 grid((nx + kColBlock - 1) / kColBlock), block(kColBlock);
+    const dim3 grid((nx + kColBlock - 1) / kColBlock);
     const size_t smem = ndir > 0 ? ad_cover_dirs_lds_bytes<T>(nz, ndir)
                                  : 2 * size_t(nz + 1) * sizeof(T) + (kADPark<T> ? size_t(CS2_AD_PARK_COUNT) * kColBlock * sizeof(T) : 0);
-    if (smem > size_t(160) * 1024) return -2;
-    int dev = 0;
-    if (smem > size_t(64) * 1024)
-        if (const int rc = current_device(dev)) return rc;
-    const int rc = with_flags(
+    return with_flags(
         [&](auto REG, auto FIX, auto STEP, auto DIRS) {
             if constexpr (DIRS) {
                 constexpr auto kern = STEP ? ad_cover_dirs_step_kernel<T, REG, FIX> : ad_cover_dirs_kernel<T, REG, FIX>;
-                if (smem > size_t(64) * 1024 && !lds_opt_in<kern>(dev, smem)) return -1;
-                hipLaunchKernelGGL(kern, grid, block, smem, stream, dargs);
+                return launch_ad_tail<kern>(grid, smem, stream, dargs,
+                                            step ? "cs2::ad_cover_dirs_step_kernel" : "cs2::ad_cover_dirs_kernel");
             } else {
                 constexpr auto kern = STEP ? ad_cover_step_kernel<T, REG, FIX> : ad_cover_kernel<T, REG, FIX>;
-                if (smem > size_t(64) * 1024 && !lds_opt_in<kern>(dev, smem)) return -1;
-                hipLaunchKernelGGL(kern, grid, block, smem, stream, sargs);
+                return launch_ad_tail<kern>(grid, smem, stream, sargs, step ? "cs2::ad_cover_step_kernel" : "cs2::ad_cover_kernel");
             }
-            return 0;
         },
         p.LREGCL != 0, p.AD_TRAJ_FIX != 0, step, ndir > 0);
-    if (rc) return rc;
-    if (ndir > 0) note_kernel(step ? "cs2::ad_cover_dirs_step_kernel" : "cs2::ad_cover_dirs_kernel");
-    else note_kernel(step ? "cs2::ad_cover_step_kernel" : "cs2::ad_cover_kernel");
-    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 template int launch_ad_cover<double>(const Cloudsc2Params&, int, int, int64_t, const double* const*, const double* const*,

@@ -1,6 +1,7 @@
 // The level functions and argument bundles of the adjoint kernels: what cloudsc2_ad.hip (dense, trajectory, masked, step,
 // multi-direction and ensemble adjoints) and cloudsc2_ad_evap.hip (the trajectory adjoints WITH the evaporation block)
-// share.  Line numbers refer to the reference files named at the top of cloudsc2_ad.hip.
+// share: the level functions, the zero values of the bundles the sweeps carry, the masked load / store helpers and the
+// launchers' common tail (launch_ad_tail).  Line numbers refer to the reference files named at the top of cloudsc2_ad.hip.
 #pragma once
 #include "cloudsc2_common.hpp"
 
@@ -440,6 +441,36 @@ template <typename T>
 struct ADOut {
     T ap, t, q, ql, qi, qsat, lude, mfd, mfu, aph1, lu1;
 };
+
+// ---- zero values of the bundles the sweeps carry from level to level
+template <typename T>
+__device__ __forceinline__ LevelIn<T> zero_level() {
+    LevelIn<T> x;
+    x.ap = x.aph1 = x.lu1 = x.lude = x.mfd = x.mfu = x.q = x.qi = x.ql = x.qsat = x.supsat = x.t = x.tq = x.tqi = x.tql = x.tt =
+        T(0.0);
+    return x;
+}
+template <typename T>
+__device__ __forceinline__ ADForce<T> zero_force() {
+    ADForce<T> f;
+    f.clc = f.tnd_q = f.tnd_qi = f.tnd_ql = f.tnd_t = f.fplsl1 = f.fplsn1 = f.fhpsl1 = f.fhpsn1 = f.covptot = T(0.0);
+    return f;
+}
+template <typename T>
+__device__ __forceinline__ ADOut<T> zero_out() {
+    ADOut<T> a;
+    a.ap = a.t = a.q = a.ql = a.qi = a.qsat = a.lude = a.mfd = a.mfu = a.aph1 = a.lu1 = T(0.0);
+    return a;
+}
+// the backward carry below the lowest level; aph_s: the surface pressure (read by the evaporation block only, 1 without it)
+template <typename T>
+__device__ __forceinline__ ADBack<T> zero_back(T aph_s) {
+    ADBack<T> b;
+    b.tmp_rfln_i = b.tmp_sfln_i = b.rfl_i = b.sfl_i = b.daph_i = b.dp_i = T(0.0);
+    b.covptot_i = b.aph_s_i = T(0.0);
+    b.aph_s = aph_s;
+    return b;
+}
 
 // LDS parking of trajectory values across the first half of ad_backward (kADPark): one 8-byte (4-byte) slot per
 // value and lane, [value][lane] - consecutive lanes hit consecutive banks.  The empty asm statements with a memory
@@ -945,5 +976,23 @@ struct ADDirFields {
     __device__ __forceinline__ const T* adj(int i) const { return F.adj(i) + ((have >> i & 1u) ? ib : int64_t(0)); }
     __device__ __forceinline__ T* oadj(int i) const { return F.oadj(i) + ob; }
 };
+
+// ---- the tail of every adjoint launcher (launch_ad, launch_ad_masked, launch_ad_dirs, launch_ad_cover): refuse more than
+// 160 KiB of LDS (-2); above 64 KiB look the device up (current_device: -1 / -2) and opt this kernel in (-1 when that
+// fails); launch; record the kernel's name; 0, or -1 when the launch was refused.  device_always: look the device up below
+// 64 KiB as well (see launch_ad_dirs).
+template <auto K, typename ARGS>
+inline int launch_ad_tail(dim3 grid, size_t smem, hipStream_t stream, const ARGS& args, const char* name,
+                          bool device_always = false) {
+    if (smem > size_t(160) * 1024) return -2;
+    if (device_always || smem > size_t(64) * 1024) {
+        int dev = 0;
+        if (const int rc = current_device(dev)) return rc;
+        if (smem > size_t(64) * 1024 && !lds_opt_in<K>(dev, smem)) return -1;
+    }
+    hipLaunchKernelGGL(K, grid, dim3(kColBlock), smem, stream, args);
+    note_kernel(name);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
 
 }  // namespace cs2

@@ -396,12 +396,15 @@ int tl_masked_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t 
 }
 
 // `step`: the cloudsc2_ad_step_* entry (ad_step_kernel); `multi`: the cloudsc2_ad_multi_* entries (ad_dirs_kernel);
-// `ens`: the cloudsc2_ad_ens_* / cloudsc2_ad_step_ens_* entries (ad_ens_kernel / ad_ens_step_kernel)
+// `ens`: the cloudsc2_ad_ens_* / cloudsc2_ad_step_ens_* entries (ad_ens_kernel / ad_ens_step_kernel);
+// `evap`: the trajectory adjoints WITH the evaporation block (cloudsc2_ad_evap_* / _step_* / _multi_* / _multi_step_*:
+// ad_cover_kernel and its siblings) - the same checks, the switches required instead of refused, and the caller's cover field.
 template <typename T>
 int ad_masked_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,
                    const T* const* in_adj, const T* zero_line, const T* eta, const T* traj_fplsl, const T* traj_fplsn,
                    T* const* out_adj, double dt, void* stream, bool step = false, bool multi = false, int32_t ndir = 0,
-                   int64_t in_ds = 0, int64_t out_ds = 0, bool ens = false, int32_t nmem = 0, int64_t ms = 0) {
+                   int64_t in_ds = 0, int64_t out_ds = 0, bool ens = false, int32_t nmem = 0, int64_t ms = 0,
+                   bool evap = false, T* cover = nullptr, int32_t cover_ready = 0) {
     if (int rc = check_common(fn, p, nx, nz, ls)) return rc;
     if (multi)
         if (int rc = check_dirs(fn, nz, ls, ndir, in_ds, out_ds, CLOUDSC2_AD_MAX_DIRS, "CLOUDSC2_AD_MAX_DIRS")) return rc;
@@ -411,47 +414,18 @@ int ad_masked_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t 
     if (int rc = check_masked_inputs(fn, "in_adj", in_adj, NL_NUM_OUT, zero_line)) return rc;
     if (step && out_adj && out_adj[NL_IN_QSAT])
         return fail(CLOUDSC2_E_ARG, "%s: out_adj[NL_IN_QSAT] (out_adj[%d]) must be NULL: the qsat adjoint is folded into "
-                    "out_adj[NL_IN_T] and out_adj[NL_IN_AP] (use cloudsc2_ad_masked to have it stored)", fn, NL_IN_QSAT);
+                    "out_adj[NL_IN_T] and out_adj[NL_IN_AP] (use cloudsc2_ad_%s to have it stored)", fn, NL_IN_QSAT,
+                    evap ? "evap" : "masked");
     if (int rc = check_masked_outputs(fn, "out_adj", out_adj, NL_NUM_IN)) return rc;
     if (!eta || !traj_fplsl || !traj_fplsn) return fail(CLOUDSC2_E_ARG, "%s: eta / traj_fplsl / traj_fplsn is NULL", fn);
+    if (evap && !cover)
+        return fail(CLOUDSC2_E_ARG, "%s: cover is NULL (a caller-owned field of nz+1 levels at lev_stride)", fn);
     if (p->ICALL != 0) return fail(CLOUDSC2_E_UNSUPPORTED, "%s: ICALL=%d unsupported", fn, p->ICALL);
-    if (p->LEVAPLS2 || p->LDRAIN1D)
+    if (!evap && (p->LEVAPLS2 || p->LDRAIN1D))
         return fail(CLOUDSC2_E_UNSUPPORTED, "%s: LEVAPLS2 / LDRAIN1D: the masked adjoint reads its trajectory like "
                     "cloudsc2_ad_from_trajectory and covers the driver switches only (the evaporation block's parked "
                     "precipitation cover has no counterpart among the NL outputs) - use cloudsc2_ad", fn);
-    if (!(dt > 0.0)) return fail(CLOUDSC2_E_ARG, "%s: dt=%g must be > 0", fn, dt);
-    if (p->NLEV != nz) return fail(CLOUDSC2_E_ARG, "%s: NLEV=%d != nz=%d", fn, p->NLEV, nz);
-    if (step)
-        if (int rc = check_step_saturation(fn, p)) return rc;
-    if (int rc = check_masked_size<T>(fn, nz, ls)) return rc;
-    if (multi)
-        return launched(fn, cs2::launch_ad_dirs<T>(*p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn, out_adj,
-                                                   dt, static_cast<hipStream_t>(stream), step, ndir, in_ds, out_ds));
-    return launched(fn, cs2::launch_ad_masked<T>(*p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn,
-                                                 out_adj, dt, static_cast<hipStream_t>(stream), step, ens ? nmem : 0, ms));
-}
-
-// The trajectory adjoints WITH the evaporation block (cloudsc2_ad_evap_* / _step_* / _multi_* / _multi_step_*: ad_cover_kernel
-// and its siblings): the checks of ad_masked_impl, the switches required instead of refused, and the caller's cover field.
-template <typename T>
-int ad_evap_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,
-                 const T* const* in_adj, const T* zero_line, const T* eta, const T* traj_fplsl, const T* traj_fplsn,
-                 T* const* out_adj, double dt, T* cover, int32_t cover_ready, void* stream, bool step, bool multi = false,
-                 int32_t ndir = 0, int64_t in_ds = 0, int64_t out_ds = 0) {
-    if (int rc = check_common(fn, p, nx, nz, ls)) return rc;
-    if (multi)
-        if (int rc = check_dirs(fn, nz, ls, ndir, in_ds, out_ds, CLOUDSC2_AD_MAX_DIRS, "CLOUDSC2_AD_MAX_DIRS")) return rc;
-    if (nx == 0) return CLOUDSC2_OK;
-    if (int rc = step ? check_step_trajectory(fn, in) : check_ptrs(fn, "in", in, NL_NUM_IN)) return rc;
-    if (int rc = check_masked_inputs(fn, "in_adj", in_adj, NL_NUM_OUT, zero_line)) return rc;
-    if (step && out_adj && out_adj[NL_IN_QSAT])
-        return fail(CLOUDSC2_E_ARG, "%s: out_adj[NL_IN_QSAT] (out_adj[%d]) must be NULL: the qsat adjoint is folded into "
-                    "out_adj[NL_IN_T] and out_adj[NL_IN_AP] (use cloudsc2_ad_evap to have it stored)", fn, NL_IN_QSAT);
-    if (int rc = check_masked_outputs(fn, "out_adj", out_adj, NL_NUM_IN)) return rc;
-    if (!eta || !traj_fplsl || !traj_fplsn) return fail(CLOUDSC2_E_ARG, "%s: eta / traj_fplsl / traj_fplsn is NULL", fn);
-    if (!cover) return fail(CLOUDSC2_E_ARG, "%s: cover is NULL (a caller-owned field of nz+1 levels at lev_stride)", fn);
-    if (p->ICALL != 0) return fail(CLOUDSC2_E_UNSUPPORTED, "%s: ICALL=%d unsupported", fn, p->ICALL);
-    if (!(p->LEVAPLS2 || p->LDRAIN1D))
+    if (evap && !(p->LEVAPLS2 || p->LDRAIN1D))
         return fail(CLOUDSC2_E_UNSUPPORTED, "%s: neither LEVAPLS2 nor LDRAIN1D is set: without the evaporation block there is "
                     "no precipitation cover to carry - use cloudsc2_ad_%s", fn,
                     multi ? (step ? "multi_step" : "multi") : (step ? "step" : "masked"));
@@ -460,9 +434,15 @@ int ad_evap_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t nz
     if (step)
         if (int rc = check_step_saturation(fn, p)) return rc;
     if (int rc = check_masked_size<T>(fn, nz, ls)) return rc;
-    return launched(fn, cs2::launch_ad_cover<T>(*p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn, out_adj, dt,
-                                                static_cast<hipStream_t>(stream), step, multi ? ndir : 0, in_ds, out_ds, cover,
-                                                cover_ready != 0));
+    if (evap)
+        return launched(fn, cs2::launch_ad_cover<T>(*p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn, out_adj, dt,
+                                                    static_cast<hipStream_t>(stream), step, multi ? ndir : 0, in_ds, out_ds, cover,
+                                                    cover_ready != 0));
+    if (multi)
+        return launched(fn, cs2::launch_ad_dirs<T>(*p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn, out_adj,
+                                                   dt, static_cast<hipStream_t>(stream), step, ndir, in_ds, out_ds));
+    return launched(fn, cs2::launch_ad_masked<T>(*p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn,
+                                                 out_adj, dt, static_cast<hipStream_t>(stream), step, ens ? nmem : 0, ms));
 }
 
 template <typename T>
@@ -826,29 +806,31 @@ int32_t cloudsc2_ad_multi_step_f32(const Cloudsc2Params* p, int32_t nx, int32_t 
                                    const T* const* in_adj, const T* zero_line, const T* eta, const T* traj_fplsl,              \
                                    const T* traj_fplsn, T* const* out_adj, double dt, T* cover, int32_t cover_ready,           \
                                    void* stream) {                                                                             \
-        return ad_evap_impl<T>("cloudsc2_ad_evap_" #SFX, p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn,    \
-                               out_adj, dt, cover, cover_ready, stream, false);                                                \
+        return ad_masked_impl<T>("cloudsc2_ad_evap_" #SFX, p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn,  \
+                                 out_adj, dt, stream, false, false, 0, 0, 0, false, 0, 0, true, cover, cover_ready);           \
     }                                                                                                                          \
     int32_t cloudsc2_ad_evap_step_##SFX(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,       \
                                         const T* const* in_adj, const T* zero_line, const T* eta, const T* traj_fplsl,         \
                                         const T* traj_fplsn, T* const* out_adj, double dt, T* cover, int32_t cover_ready,      \
                                         void* stream) {                                                                        \
-        return ad_evap_impl<T>("cloudsc2_ad_evap_step_" #SFX, p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl,           \
-                               traj_fplsn, out_adj, dt, cover, cover_ready, stream, true);                                     \
+        return ad_masked_impl<T>("cloudsc2_ad_evap_step_" #SFX, p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl,         \
+                                 traj_fplsn, out_adj, dt, stream, true, false, 0, 0, 0, false, 0, 0, true, cover, cover_ready); \
     }                                                                                                                          \
     int32_t cloudsc2_ad_evap_multi_##SFX(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,      \
                                          const T* const* in_adj, const T* zero_line, const T* eta, const T* traj_fplsl,        \
                                          const T* traj_fplsn, T* const* out_adj, double dt, void* stream, int32_t ndir,        \
                                          int64_t in_ds, int64_t out_ds, T* cover, int32_t cover_ready) {                       \
-        return ad_evap_impl<T>("cloudsc2_ad_evap_multi_" #SFX, p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl,          \
-                               traj_fplsn, out_adj, dt, cover, cover_ready, stream, false, true, ndir, in_ds, out_ds);         \
+        return ad_masked_impl<T>("cloudsc2_ad_evap_multi_" #SFX, p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl,        \
+                                 traj_fplsn, out_adj, dt, stream, false, true, ndir, in_ds, out_ds, false, 0, 0, true, cover,  \
+                                 cover_ready);                                                                                 \
     }                                                                                                                          \
     int32_t cloudsc2_ad_evap_multi_step_##SFX(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in, \
                                               const T* const* in_adj, const T* zero_line, const T* eta, const T* traj_fplsl,   \
                                               const T* traj_fplsn, T* const* out_adj, double dt, void* stream, int32_t ndir,   \
                                               int64_t in_ds, int64_t out_ds, T* cover, int32_t cover_ready) {                  \
-        return ad_evap_impl<T>("cloudsc2_ad_evap_multi_step_" #SFX, p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl,     \
-                               traj_fplsn, out_adj, dt, cover, cover_ready, stream, true, true, ndir, in_ds, out_ds);          \
+        return ad_masked_impl<T>("cloudsc2_ad_evap_multi_step_" #SFX, p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl,   \
+                                 traj_fplsn, out_adj, dt, stream, true, true, ndir, in_ds, out_ds, false, 0, 0, true, cover,   \
+                                 cover_ready);                                                                                 \
     }
 CS2_EVAP_ENTRIES(f64, double)
 CS2_EVAP_ENTRIES(f32, float)
