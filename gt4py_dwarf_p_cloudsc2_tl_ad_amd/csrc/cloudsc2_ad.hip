@@ -220,14 +220,12 @@ int launch_ad(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* cons
               const T* eta, T* const* out, T* const* out_adj, double dt, hipStream_t stream, const T* traj_l,
               const T* traj_n) {
     const bool traj = traj_l != nullptr && traj_n != nullptr;
-    const bool evap = p.LEVAPLS2 || p.LDRAIN1D;
+    const bool evap = evap_on(p);
     const Ext<T> e = make_ext<T>(p);
-    CPtrs<T, NL_NUM_IN> ci;
-    CPtrs<T, NL_NUM_OUT> ca;
-    MPtrs<T, NL_NUM_OUT> co;
-    MPtrs<T, NL_NUM_IN> coa;
-    for (int i = 0; i < NL_NUM_IN; ++i) { ci.p[i] = in[i]; coa.p[i] = out_adj[i]; }
-    for (int i = 0; i < NL_NUM_OUT; ++i) { ca.p[i] = in_adj[i]; co.p[i] = out ? out[i] : nullptr; }
+    const auto ci = pack_ptrs<CPtrs<T, NL_NUM_IN>>(in);
+    const auto ca = pack_ptrs<CPtrs<T, NL_NUM_OUT>>(in_adj);
+    const auto co = pack_ptrs<MPtrs<T, NL_NUM_OUT>>(out);
+    const auto coa = pack_ptrs<MPtrs<T, NL_NUM_IN>>(out_adj);
     const dim3 grid((nx + kColBlock - 1) / kColBlock);
     const size_t smem = 2 * size_t(nz + 1) * sizeof(T) + (kADPark<T> ? size_t(CS2_AD_PARK_COUNT) * kColBlock * sizeof(T) : 0);
     const T tdt = static_cast<T>(dt);
@@ -238,11 +236,11 @@ int launch_ad(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* cons
     // it used to follow: both refuse without a side effect, and the entry that leads here checks the same before it calls.)
     if (traj && (evap || big)) return -2;
     const ADArgs<T> args = {e, kc, xk, nx, nz, ls, ci, ca, eta, co, coa, tdt, traj_l, traj_n};
-    const char* const name = traj ? "cs2::ad_kernel<trajectory>" : big ? "cs2::ad_kernel<big>" : "cs2::ad_kernel";
+    const Launch l{grid, smem, stream, traj ? "cs2::ad_kernel<trajectory>" : big ? "cs2::ad_kernel<big>" : "cs2::ad_kernel"};
     return with_flags(
         [&](auto REG, auto FIX, auto TRAJ, auto EVAP, auto BIG) {
             if constexpr (TRAJ && (EVAP || BIG)) return -2;   // refused above: no such instantiation
-            else return launch_ad_tail<ad_kernel<T, REG, FIX, EVAP, BIG, TRAJ>>(grid, smem, stream, args, name);
+            else return launch_tail<ad_kernel<T, REG, FIX, EVAP, BIG, TRAJ>>(l, args);
         },
         p.LREGCL != 0, p.AD_TRAJ_FIX != 0, traj, evap, big);
 }
@@ -439,7 +437,7 @@ template <typename T>
 int launch_ad_masked(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* const* in, const T* const* in_adj,
                      const T* zero, const T* eta, const T* traj_l, const T* traj_n, T* const* out_adj, double dt,
                      hipStream_t stream, bool step, int nmem, int64_t ms) {
-    if (p.LEVAPLS2 || p.LDRAIN1D || !fits_u32_offsets<T>(nz, ls)) return -2;
+    if (evap_on(p) || !fits_u32_offsets<T>(nz, ls)) return -2;
     ADEnsArgs<T> ens;
     ADMaskedArgs<T>& args = ens.m;
     fill_ad_masked_args<T>(args, p, nx, nz, ls, in, in_adj, zero, eta, traj_l, traj_n, out_adj, dt);
@@ -453,10 +451,10 @@ int launch_ad_masked(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const 
         [&](auto REG, auto FIX, auto STEP, auto ENS) {
             if constexpr (ENS) {
                 constexpr auto kern = STEP ? ad_ens_step_kernel<T, REG, FIX> : ad_ens_kernel<T, REG, FIX>;
-                return launch_ad_tail<kern>(egrid, smem, stream, ens, step ? "cs2::ad_ens_step_kernel" : "cs2::ad_ens_kernel");
+                return launch_tail<kern>({egrid, smem, stream, step ? "cs2::ad_ens_step_kernel" : "cs2::ad_ens_kernel"}, ens);
             } else {
                 constexpr auto kern = STEP ? ad_step_kernel<T, REG, FIX> : ad_masked_kernel<T, REG, FIX>;
-                return launch_ad_tail<kern>(grid, smem, stream, args, step ? "cs2::ad_step_kernel" : "cs2::ad_masked_kernel");
+                return launch_tail<kern>({grid, smem, stream, step ? "cs2::ad_step_kernel" : "cs2::ad_masked_kernel"}, args);
             }
         },
         p.LREGCL != 0, p.AD_TRAJ_FIX != 0, step, nmem > 0);
@@ -629,7 +627,7 @@ template <typename T>
 int launch_ad_dirs(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* const* in, const T* const* in_adj,
                    const T* zero, const T* eta, const T* traj_l, const T* traj_n, T* const* out_adj, double dt,
                    hipStream_t stream, bool step, int ndir, int64_t in_ds, int64_t out_ds) {
-    if (p.LEVAPLS2 || p.LDRAIN1D || !fits_u32_offsets<T>(nz, ls)) return -2;
+    if (evap_on(p) || !fits_u32_offsets<T>(nz, ls)) return -2;
     if (ndir < 1 || ndir > kADMaxDirs) return -1;
     ADDirsArgs<T> args;
     fill_ad_masked_args<T>(args.m, p, nx, nz, ls, in, in_adj, zero, eta, traj_l, traj_n, out_adj, dt);
@@ -642,8 +640,7 @@ int launch_ad_dirs(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T*
     return with_flags(
         [&](auto REG, auto FIX, auto STEP) {
             constexpr auto kern = STEP ? ad_dirs_step_kernel<T, REG, FIX> : ad_dirs_kernel<T, REG, FIX>;
-            return launch_ad_tail<kern>(grid, smem, stream, args, step ? "cs2::ad_dirs_step_kernel" : "cs2::ad_dirs_kernel",
-                                        true);
+            return launch_tail<kern>({grid, smem, stream, step ? "cs2::ad_dirs_step_kernel" : "cs2::ad_dirs_kernel", true}, args);
         },
         p.LREGCL != 0, p.AD_TRAJ_FIX != 0, step);
 }

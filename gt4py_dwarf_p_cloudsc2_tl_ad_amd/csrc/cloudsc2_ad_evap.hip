@@ -391,7 +391,7 @@ template <typename T>
 int launch_ad_cover(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* const* in, const T* const* in_adj,
                     const T* zero, const T* eta, const T* traj_l, const T* traj_n, T* const* out_adj, double dt,
                     hipStream_t stream, bool step, int ndir, int64_t in_ds, int64_t out_ds, T* cover, int cover_ready) {
-    if (!(p.LEVAPLS2 || p.LDRAIN1D) || !fits_u32_offsets<T>(nz, ls) || !cover) return -2;
+    if (!evap_on(p) || !fits_u32_offsets<T>(nz, ls) || !cover) return -2;
     if (ndir < 0 || ndir > kADMaxDirs) return -1;
     ADCoverDirsArgs<T> dargs;
     ADCoverArgs<T> sargs;
@@ -408,11 +408,11 @@ int launch_ad_cover(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T
         [&](auto REG, auto FIX, auto STEP, auto DIRS) {
             if constexpr (DIRS) {
                 constexpr auto kern = STEP ? ad_cover_dirs_step_kernel<T, REG, FIX> : ad_cover_dirs_kernel<T, REG, FIX>;
-                return launch_ad_tail<kern>(grid, smem, stream, dargs,
-                                            step ? "cs2::ad_cover_dirs_step_kernel" : "cs2::ad_cover_dirs_kernel");
+                return launch_tail<kern>({grid, smem, stream, step ? "cs2::ad_cover_dirs_step_kernel" : "cs2::ad_cover_dirs_kernel"},
+                                         dargs);
             } else {
                 constexpr auto kern = STEP ? ad_cover_step_kernel<T, REG, FIX> : ad_cover_kernel<T, REG, FIX>;
-                return launch_ad_tail<kern>(grid, smem, stream, sargs, step ? "cs2::ad_cover_step_kernel" : "cs2::ad_cover_kernel");
+                return launch_tail<kern>({grid, smem, stream, step ? "cs2::ad_cover_step_kernel" : "cs2::ad_cover_kernel"}, sargs);
             }
         },
         p.LREGCL != 0, p.AD_TRAJ_FIX != 0, step, ndir > 0);

@@ -1,7 +1,8 @@
 // The level functions and argument bundles of the adjoint kernels: what cloudsc2_ad.hip (dense, trajectory, masked, step,
 // multi-direction and ensemble adjoints) and cloudsc2_ad_evap.hip (the trajectory adjoints WITH the evaporation block)
-// share: the level functions, the zero values of the bundles the sweeps carry, the masked load / store helpers and the
-// launchers' common tail (launch_ad_tail).  Line numbers refer to the reference files named at the top of cloudsc2_ad.hip.
+// share: the level functions, the zero values of the bundles the sweeps carry and the masked load / store helpers (the
+// launchers end in cloudsc2_common.hpp's launch_tail).  Line numbers refer to the reference files named at the top of
+// cloudsc2_ad.hip.
 #pragma once
 #include "cloudsc2_common.hpp"
 
@@ -944,11 +945,10 @@ static void fill_ad_masked_args(ADMaskedArgs<T>& args, const Cloudsc2Params& p, 
     args.xk = make_expk<T>();
     args.nx = nx; args.nz = nz; args.ls = ls;
     args.have = args.want = 0;
-    for (int i = 0; i < NL_NUM_IN; ++i) {
-        args.in.p[i] = in[i];
-        args.oadj.p[i] = out_adj[i];
+    args.in = pack_ptrs<CPtrs<T, NL_NUM_IN>>(in);
+    args.oadj = pack_ptrs<MPtrs<T, NL_NUM_IN>>(out_adj);
+    for (int i = 0; i < NL_NUM_IN; ++i)
         if (out_adj[i]) args.want |= 1u << i;
-    }
     for (int i = 0; i < NL_NUM_OUT; ++i) {
         args.adj.p[i] = in_adj[i] ? in_adj[i] : zero;
         if (in_adj[i]) args.have |= 1u << i;
@@ -976,23 +976,5 @@ struct ADDirFields {
     __device__ __forceinline__ const T* adj(int i) const { return F.adj(i) + ((have >> i & 1u) ? ib : int64_t(0)); }
     __device__ __forceinline__ T* oadj(int i) const { return F.oadj(i) + ob; }
 };
-
-// ---- the tail of every adjoint launcher (launch_ad, launch_ad_masked, launch_ad_dirs, launch_ad_cover): refuse more than
-// 160 KiB of LDS (-2); above 64 KiB look the device up (current_device: -1 / -2) and opt this kernel in (-1 when that
-// fails); launch; record the kernel's name; 0, or -1 when the launch was refused.  device_always: look the device up below
-// 64 KiB as well (see launch_ad_dirs).
-template <auto K, typename ARGS>
-inline int launch_ad_tail(dim3 grid, size_t smem, hipStream_t stream, const ARGS& args, const char* name,
-                          bool device_always = false) {
-    if (smem > size_t(160) * 1024) return -2;
-    if (device_always || smem > size_t(64) * 1024) {
-        int dev = 0;
-        if (const int rc = current_device(dev)) return rc;
-        if (smem > size_t(64) * 1024 && !lds_opt_in<K>(dev, smem)) return -1;
-    }
-    hipLaunchKernelGGL(K, grid, dim3(kColBlock), smem, stream, args);
-    note_kernel(name);
-    return hipGetLastError() == hipSuccess ? 0 : -1;
-}
 
 }  // namespace cs2

@@ -617,6 +617,43 @@ inline int with_int(int v, F&& f) {
     return rc;
 }
 
+// ---- the tail of every launcher: LDS bound, opt-in, launch, recorded name, outcome ---------------------------------
+constexpr size_t kLdsPerCU = size_t(160) * 1024;   // LDS of a CU: what one workgroup can ask for at most
+constexpr size_t kLdsOptIn = size_t(64) * 1024;    // dynamic LDS beyond this needs lds_opt_in
+// What a launch needs beside the kernel and its arguments.  device_always: look the device up below kLdsOptIn as well
+// (see launch_ad_dirs).  dev >= 0: the ordinal current_device() gave the caller, who needed device_cus() to choose the
+// kernel (the ring paths) - it is not looked up again.
+struct Launch {
+    dim3 grid;
+    size_t smem;
+    hipStream_t stream;
+    const char* name;             // what cloudsc2_last_kernel() reports
+    bool device_always = false;
+    int dev = -1;
+};
+// Refuse more than kLdsPerCU of LDS (-2); above kLdsOptIn look the device up (current_device: -1 / -2) and opt kernel K in
+// (-1 when that fails: no launch, no name recorded); launch kColBlock threads per workgroup; record the name; 0, or -1 when
+// the launch was refused.
+template <auto K, typename... A>
+inline int launch_tail(const Launch& l, const A&... args) {
+    if (l.smem > kLdsPerCU) return -2;
+    int dev = l.dev;
+    if (dev < 0 && (l.device_always || l.smem > kLdsOptIn))
+        if (const int rc = current_device(dev)) return rc;
+    if (l.smem > kLdsOptIn && !lds_opt_in<K>(dev, l.smem)) return -1;
+    hipLaunchKernelGGL(K, l.grid, dim3(kColBlock), l.smem, l.stream, args...);
+    note_kernel(l.name);
+    return hipGetLastError() == hipSuccess ? 0 : -1;
+}
+
+// A pointer bundle B (CPtrs / MPtrs) from the caller's pointer array; a null array gives null entries.
+template <typename B, typename P>
+inline B pack_ptrs(const P* a) {
+    B b;
+    for (size_t i = 0; i < sizeof(b.p) / sizeof(b.p[0]); ++i) b.p[i] = a ? a[i] : nullptr;
+    return b;
+}
+
 // Per-level LDS table: eta[k] and scalm[k] = ZSCAL * max(eta[k]-0.2, ZEPS1)^0.2
 // (nonlinear/_stencils/cloudsc2.py:127).  `pow` is evaluated once per level per workgroup instead
 // of once per level per column.  Also returns the tropopause search window [klo, khi]: the levels
@@ -647,6 +684,11 @@ template <typename T>
 struct NLK {
     T rdt, ckcodtl, ckcodti, cons2, rgdt, cons3, meltp2, rlcrit, ricrit, rRD, rRCPD, rRLMLT, cormax, fw2;
 };
+
+// The two switch combinations the kernels are instantiated for: the precipitation-evaporation block (and make_nlk's
+// thresholds), and the linearised-physics forms.
+inline bool evap_on(const Cloudsc2Params& p) { return p.LEVAPLS2 || p.LDRAIN1D; }
+inline bool lin_on(const Cloudsc2Params& p) { return p.LPHYLIN || p.LDRAIN1D; }
 
 template <typename T>
 inline NLK<T> make_nlk(const Cloudsc2Params& p, double dt, bool evap) {

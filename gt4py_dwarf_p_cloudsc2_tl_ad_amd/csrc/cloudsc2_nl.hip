@@ -755,17 +755,11 @@ int launch_nl(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* cons
               double dt, hipStream_t stream, const T* const* in_i = nullptr, double pf = 0.0, T* qsat_out = nullptr,
               double* partials = nullptr) {
     const Ext<T> e = make_ext<T>(p);
-    CPtrs<T, NL_NUM_IN> ci, cii;
-    MPtrs<T, NL_NUM_OUT> co;
-    for (int i = 0; i < NL_NUM_IN; ++i) {
-        ci.p[i] = in[i];
-        cii.p[i] = in_i ? in_i[i] : nullptr;
-    }
-    for (int i = 0; i < NL_NUM_OUT; ++i) co.p[i] = out[i];
-    const dim3 grid((nx + kColBlock - 1) / kColBlock), block(kColBlock);
+    const auto ci = pack_ptrs<CPtrs<T, NL_NUM_IN>>(in), cii = pack_ptrs<CPtrs<T, NL_NUM_IN>>(in_i);
+    const auto co = pack_ptrs<MPtrs<T, NL_NUM_OUT>>(out);
+    const dim3 grid((nx + kColBlock - 1) / kColBlock);
     const size_t smem = 2 * size_t(nz + 1) * sizeof(T);
-    const bool evap = p.LEVAPLS2 || p.LDRAIN1D;
-    const bool lin = p.LPHYLIN || p.LDRAIN1D;
+    const bool evap = evap_on(p), lin = lin_on(p);
     const T tdt = static_cast<T>(dt);
     const T tpf = static_cast<T>(pf);
     const NLK<T> kc = make_nlk<T>(p, dt, evap);
@@ -793,37 +787,34 @@ int launch_nl(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* cons
         if (const int rc = current_device(dev)) return rc;
         const bool deep = int64_t(grid.x) * 2 <= int64_t(device_cus(dev)) * 3;
         const size_t rsmem = ring_lds_bytes<NLRingGeom<T>, T>(nz, deep ? kNLRing : 2);
-        if (rsmem <= size_t(160) * 1024) {   // LDS of a CU; very tall columns (table > 46 KB) take the register path
+        if (rsmem <= kLdsPerCU) {   // very tall columns (table > 46 KB) take the register path
             const bool ragged = nx % 64 != 0;
-            const int rc = with_flags(
+            return with_flags(
                 [&](auto EV, auto LN, auto DEEP, auto SF, auto RG) {
                     constexpr auto kern = nl_ring_kernel<T, EV, LN, sizeof(T) == 8, (DEEP ? kNLRing : 2), SF, RG>;
+                    // Opted in whatever the size, as ever, which launch_tail would not do: this ring's demand can stay below
+                    // kLdsOptIn.  ring_lds_bytes<NLRingGeom<T>, T>(nz = kNLRing, 2) = 1 KiB of table + 4 waves x 2 slots x
+                    // (16 fields x 64 columns + 1 KiB) = 41 984 B in fp32 (74 752 B in fp64); the deep fp32 ring of 137
+                    // levels is 63 488 B.  launch_tail's own opt-in then finds the size on record.
                     if (!lds_opt_in<kern>(dev, rsmem)) return -1;
-                    hipLaunchKernelGGL(kern, grid, block, rsmem, stream, e, kc, xk, nx, nz, ls, ci, eta, co, tdt, qsat_out,
-                                       keepq);
-                    return 0;
+                    return launch_tail<kern>(
+                        {grid, rsmem, stream, ragged ? "cs2::nl_ring_kernel<ragged>" : "cs2::nl_ring_kernel", false, dev}, e, kc, xk,
+                        nx, nz, ls, ci, eta, co, tdt, qsat_out, keepq);
                 },
                 evap, lin, deep, fuse == 1, ragged);
-            if (rc) return rc;
-            note_kernel(ragged ? "cs2::nl_ring_kernel<ragged>" : "cs2::nl_ring_kernel");
-            return hipGetLastError() == hipSuccess ? 0 : -1;
         }
     }
-    const auto launch = [&](auto kern) {
-        hipLaunchKernelGGL(kern, grid, block, smem, stream, e, kc, xk, nx, nz, ls, ci, eta, co, tdt, cii, tpf, qsat_out,
-                           partials, keepq);
-        return 0;
-    };
-    if (big) {       // fields of 4 GiB and more: the register-path kernel with 64-bit offsets (FUSE = 0 only)
-        with_flags([&](auto EV, auto LN) { return launch(nl_kernel<T, EV, LN, sizeof(T) == 8, 0, true>); }, evap, lin);
-        note_kernel("cs2::nl_kernel<big>");
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-    }
-    with_int<0, 1, 2, 3>(fuse, [&](auto FU) {
-        return with_flags([&](auto EV, auto LN) { return launch(nl_kernel<T, EV, LN, sizeof(T) == 8, FU>); }, evap, lin);
+    // fields of 4 GiB and more: the register-path kernel with 64-bit offsets (FUSE = 0 only)
+    const Launch l{grid, smem, stream, big ? "cs2::nl_kernel<big>" : "cs2::nl_kernel"};
+    return with_int<0, 1, 2, 3>(fuse, [&](auto FU) {
+        return with_flags(
+            [&](auto EV, auto LN, auto BIG) {
+                if constexpr (BIG && FU != 0) return -2;   // refused above: no such instantiation
+                else return launch_tail<nl_kernel<T, EV, LN, sizeof(T) == 8, FU, BIG>>(l, e, kc, xk, nx, nz, ls, ci, eta, co, tdt, cii,
+                                                                                       tpf, qsat_out, partials, keepq);
+            },
+            evap, lin, big);
     });
-    note_kernel("cs2::nl_kernel");
-    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 template int launch_nl<double>(const Cloudsc2Params&, int, int, int64_t, const double* const*, const double*,
@@ -842,29 +833,24 @@ int launch_nl_ens(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* 
     const int bpm = (nx + kColBlock - 1) / kColBlock;
     if (int64_t(nmem) * bpm > kMaxGrid) return -2;
     const Ext<T> e = make_ext<T>(p);
-    CPtrs<T, NL_NUM_IN> ci;
-    MPtrs<T, NL_NUM_OUT> co;
-    for (int i = 0; i < NL_NUM_IN; ++i) ci.p[i] = in[i];
-    for (int i = 0; i < NL_NUM_OUT; ++i) co.p[i] = out[i];
-    const dim3 grid(unsigned(nmem) * unsigned(bpm)), block(kColBlock);
+    const auto ci = pack_ptrs<CPtrs<T, NL_NUM_IN>>(in);
+    const auto co = pack_ptrs<MPtrs<T, NL_NUM_OUT>>(out);
+    const dim3 grid(unsigned(nmem) * unsigned(bpm));
     const size_t smem = 2 * size_t(nz + 1) * sizeof(T);
-    const bool evap = p.LEVAPLS2 || p.LDRAIN1D;
-    const bool lin = p.LPHYLIN || p.LDRAIN1D;
+    const bool evap = evap_on(p), lin = lin_on(p);
     const T tdt = static_cast<T>(dt);
     const NLK<T> kc = make_nlk<T>(p, dt, evap);
     const ExpK<T> xk = make_expk<T>();
     // in_qsat: default cache policy only when the qsat of ALL members fits (see qsat_fits_cache)
     const int keepq = static_cast<uint64_t>(nmem) * static_cast<uint64_t>(ms) * sizeof(T) <= (uint64_t(128) << 20) ? 1 : 0;
     const EnsGeom g{ms, bpm};
-    with_flags(
+    const Launch l{grid, smem, stream, qsat_out ? "cs2::nl_ens_kernel<saturation>" : "cs2::nl_ens_kernel"};
+    return with_flags(
         [&](auto EV, auto LN, auto SF) {
-            hipLaunchKernelGGL((nl_ens_kernel<T, EV, LN, sizeof(T) == 8, (SF ? 1 : 0)>), grid, block, smem, stream, e, kc, xk, nx,
-                               nz, ls, ci, eta, co, tdt, qsat_out, keepq, g);
-            return 0;
+            return launch_tail<nl_ens_kernel<T, EV, LN, sizeof(T) == 8, (SF ? 1 : 0)>>(l, e, kc, xk, nx, nz, ls, ci, eta, co, tdt,
+                                                                                       qsat_out, keepq, g);
         },
         evap, lin, qsat_out != nullptr);
-    note_kernel(qsat_out ? "cs2::nl_ens_kernel<saturation>" : "cs2::nl_ens_kernel");
-    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 template int launch_nl_ens<double>(const Cloudsc2Params&, int, int, int64_t, const double* const*, const double*,
@@ -1122,13 +1108,10 @@ int launch_nl_taylor_multi(const Cloudsc2Params& p, int nx, int nz, int64_t ls, 
     const T tinc = static_cast<T>(inc_f);
     const int zsi = p.IGNORE_SUPSAT ? 1 : 0;
     const Ext<T> e = make_ext<T>(p);
-    CPtrs<T, NL_NUM_IN> ci, cii;
-    CPtrs<T, NL_NUM_OUT> cr;
-    for (int i = 0; i < NL_NUM_IN; ++i) { ci.p[i] = in[i]; cii.p[i] = inc ? nullptr : in_i[i]; }
-    for (int i = 0; i < NL_NUM_OUT; ++i) cr.p[i] = ref_out[i];
-    const dim3 grid((nx + kColBlock - 1) / kColBlock), block(kColBlock);
-    const bool evap = p.LEVAPLS2 || p.LDRAIN1D;
-    const bool lin = p.LPHYLIN || p.LDRAIN1D;
+    const auto ci = pack_ptrs<CPtrs<T, NL_NUM_IN>>(in), cii = pack_ptrs<CPtrs<T, NL_NUM_IN>>(in_i);
+    const auto cr = pack_ptrs<CPtrs<T, NL_NUM_OUT>>(ref_out);
+    const dim3 grid((nx + kColBlock - 1) / kColBlock);
+    const bool evap = evap_on(p), lin = lin_on(p);
     const T tdt = static_cast<T>(dt);
     const NLK<T> kc = make_nlk<T>(p, dt, evap);
     const ExpK<T> xk = make_expk<T>();
@@ -1144,21 +1127,19 @@ int launch_nl_taylor_multi(const Cloudsc2Params& p, int nx, int nz, int64_t ls, 
                 [&](auto EV, auto LN, auto INC) {
                     constexpr auto kern = nl_taylor_multi_kernel<T, EV, LN, sizeof(T) == 8, NFV, INC>;
                     const size_t smem = tab + size_t(NFV) * NL_NUM_OUT * kColBlock * sizeof(double);
-                    if (smem + sizeof(double) * (kColBlock / 64) * NFV * NL_NUM_OUT > size_t(160) * 1024) return -2;
-                    if (smem > size_t(64) * 1024 && !lds_opt_in<kern>(dev, smem)) return -1;
+                    // the kernel's static s_red shares the CU's LDS with the dynamic part: bounded here, in front of the tail
+                    if (smem + sizeof(double) * (kColBlock / 64) * NFV * NL_NUM_OUT > kLdsPerCU) return -2;
                     PFs<T, NFV> pf;
                     for (int j = 0; j < NFV; ++j) pf.f[j] = static_cast<T>(pfs[f0 + j]);
                     const NLMArgs<T, NFV> margs = {e, kc, xk, nx, nz, ls, ci, cii, cr, eta, tdt, pf, partials, nf, f0, tinc, zsi};
-                    hipLaunchKernelGGL(kern, grid, block, smem, stream, margs);
-                    return 0;
+                    return launch_tail<kern>({grid, smem, stream, "cs2::nl_taylor_multi_kernel", false, dev}, margs);
                 },
                 evap, lin, inc);
         });
-        if (rc) return rc;
+        if (rc) return rc;   // a chunk that was refused or failed to launch ends the call: no later chunk is launched
         f0 += nfv;
     }
-    note_kernel("cs2::nl_taylor_multi_kernel");
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    return 0;
 }
 
 template int launch_nl_taylor_multi<double>(const Cloudsc2Params&, int, int, int64_t, const double* const*,

@@ -523,6 +523,28 @@ __device__ __forceinline__ void pin_tl_constants(Ext<T>& e, NLK<T>& kc, ExpK<T>&
     pin_expk(xk);
 }
 
+// :124-135, the carry at the top of a column.  Trajectory half: zero fluxes, aph[0] at byte offset `colb` and, for the
+// evaporation block, the surface pressure aph[nz] at `surfb`.  Perturbation half: loaded at the column's own offsets (or at
+// the zero line's, tl_masked_sweep), or formed as finc * trajectory (INC, see increment).
+template <typename T, bool EVAP, typename O>
+__device__ __forceinline__ TLCarry<T> tl_carry_top(const T* aph, O colb, O surfb) {
+    TLCarry<T> c;
+    c.rfl = c.rfl_i = c.sfl = c.sfl_i = c.covptot = c.covptot_i = T(0.0);
+    c.aph_k = ldg(aph, colb);
+    c.aph_s = EVAP ? ldg(aph, surfb) : T(1.0);
+    return c;
+}
+template <typename T, bool EVAP, typename O>
+__device__ __forceinline__ void tl_carry_top_i(TLCarry<T>& c, const T* aph_i, O colb, O surfb) {
+    c.aph_k_i = ldg(aph_i, colb);
+    c.aph_s_i = EVAP ? ldg(aph_i, surfb) : T(0.0);
+}
+template <typename T, bool EVAP>
+__device__ __forceinline__ void tl_carry_top_inc(TLCarry<T>& c, T finc) {
+    c.aph_k_i = rounded_product<T>(finc, c.aph_k);
+    c.aph_s_i = EVAP ? rounded_product<T>(finc, c.aph_s) : T(0.0);
+}
+
 // INC: the perturbation fields are not read but formed as finc * in (state_increment fused in, see increment):
 // 16 input streams instead of 32, no landing buffer for the second 16.
 // BIG: 64-bit byte offsets (fields of 4 GiB and more, see offset_t in cloudsc2_common.hpp); instantiated without INC only.
@@ -556,17 +578,9 @@ tl_kernel(Ext<T> e, NLK<T> kc, ExpK<T> xk, int nx, int nz, int64_t ls, CPtrs<T, 
     const CrhCol<T> crh = crh_setup<T>(trpaus);
 
     // :124-135
-    TLCarry<T> c;
-    c.rfl = c.rfl_i = c.sfl = c.sfl_i = c.covptot = c.covptot_i = T(0.0);
-    c.aph_k = ldg(in.p[NL_IN_APH], colb);
-    c.aph_s = EVAP ? ldg(in.p[NL_IN_APH], O(nz) * lsb + colb) : T(1.0);
-    if constexpr (INC) {
-        c.aph_k_i = rounded_product<T>(finc, c.aph_k);
-        c.aph_s_i = EVAP ? rounded_product<T>(finc, c.aph_s) : T(0.0);
-    } else {
-        c.aph_k_i = ldg(in_i.p[NL_IN_APH], colb);
-        c.aph_s_i = EVAP ? ldg(in_i.p[NL_IN_APH], O(nz) * lsb + colb) : T(0.0);
-    }
+    TLCarry<T> c = tl_carry_top<T, EVAP, O>(in.p[NL_IN_APH], colb, O(nz) * lsb + colb);
+    if constexpr (INC) tl_carry_top_inc<T, EVAP>(c, finc);
+    else tl_carry_top_i<T, EVAP, O>(c, in_i.p[NL_IN_APH], colb, O(nz) * lsb + colb);
 
     // :757-765
     stg(out.p[NL_OUT_FPLSL], colb, T(0.0));
@@ -686,12 +700,8 @@ tl_ring_kernel(Ext<T> e, NLK<T> kc, ExpK<T> xk, int nx, int nz, int64_t ls, CPtr
     const CrhCol<T> crh = crh_setup<T>(trpaus);
 
     // :124-135
-    TLCarry<T> c;
-    c.rfl = c.rfl_i = c.sfl = c.sfl_i = c.covptot = c.covptot_i = T(0.0);
-    c.aph_k = ldg(in.p[NL_IN_APH], colb);
-    c.aph_k_i = ldg(in_i.p[NL_IN_APH], colb);
-    c.aph_s = EVAP ? ldg(in.p[NL_IN_APH], uint32_t(nz) * lsb + colb) : T(1.0);
-    c.aph_s_i = EVAP ? ldg(in_i.p[NL_IN_APH], uint32_t(nz) * lsb + colb) : T(0.0);
+    TLCarry<T> c = tl_carry_top<T, EVAP, uint32_t>(in.p[NL_IN_APH], colb, uint32_t(nz) * lsb + colb);
+    tl_carry_top_i<T, EVAP, uint32_t>(c, in_i.p[NL_IN_APH], colb, uint32_t(nz) * lsb + colb);
     // :757-765
     stg(out.p[NL_OUT_FPLSL], colb, T(0.0));
     stg(out_i.p[NL_OUT_FPLSL], colb, T(0.0));
@@ -779,34 +789,24 @@ int launch_tl(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* cons
     const bool inc = in_i == nullptr;
     const T tinc = static_cast<T>(inc_f);
     const int zsi = p.IGNORE_SUPSAT ? 1 : 0;
-    const bool evap = p.LEVAPLS2 || p.LDRAIN1D;
+    const bool evap = evap_on(p);
     const Ext<T> e = make_ext<T>(p);
-    CPtrs<T, NL_NUM_IN> ci, cii;
-    MPtrs<T, NL_NUM_OUT> co, coi;
-    for (int i = 0; i < NL_NUM_IN; ++i) { ci.p[i] = in[i]; cii.p[i] = inc ? nullptr : in_i[i]; }
-    for (int i = 0; i < NL_NUM_OUT; ++i) { co.p[i] = out[i]; coi.p[i] = out_i[i]; }
-    const dim3 grid((nx + kColBlock - 1) / kColBlock), block(kColBlock);
+    const auto ci = pack_ptrs<CPtrs<T, NL_NUM_IN>>(in), cii = pack_ptrs<CPtrs<T, NL_NUM_IN>>(in_i);
+    const auto co = pack_ptrs<MPtrs<T, NL_NUM_OUT>>(out), coi = pack_ptrs<MPtrs<T, NL_NUM_OUT>>(out_i);
+    const dim3 grid((nx + kColBlock - 1) / kColBlock);
     const size_t smem = 2 * size_t(nz + 1) * sizeof(T);
     const T tdt = static_cast<T>(dt);
     const NLK<T> kc = make_nlk<T>(p, dt, evap);
     const ExpK<T> xk = make_expk<T>();
+    // fields of 4 GiB and more: the register-path kernel with 64-bit offsets (not the fused-increment variant)
     const bool big = !fits_u32_offsets<T>(nz, ls);
-    const auto launch = [&](auto kern) {
-        hipLaunchKernelGGL(kern, grid, block, smem, stream, e, kc, xk, nx, nz, ls, ci, cii, eta, co, coi, tdt, tinc, zsi);
-        return 0;
-    };
-    if (big) {       // fields of 4 GiB and more: the register-path kernel with 64-bit offsets (not the fused-increment variant)
-        if (inc) return -2;
-        with_flags([&](auto REG, auto EVAP) { return launch(tl_kernel<T, REG, EVAP, false, true>); }, p.LREGCL != 0, evap);
-        note_kernel("cs2::tl_kernel<big>");
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-    }
+    if (big && inc) return -2;
     // LDS-ring variant: whole waves, 16-byte aligned rows of every input field (the DMA moves 16 B per lane)
-    bool ring = !inc && nx % 64 == 0 && nz >= kTLRing && (ls * int64_t(sizeof(T))) % 16 == 0;
+    bool ring = !big && !inc && nx % 64 == 0 && nz >= kTLRing && (ls * int64_t(sizeof(T))) % 16 == 0;
     for (int i = 0; i < NL_NUM_IN && ring; ++i)
         ring = reinterpret_cast<uintptr_t>(in[i]) % 16 == 0 && reinterpret_cast<uintptr_t>(in_i[i]) % 16 == 0;
     const size_t rsmem = ring_lds_bytes<TLRingGeom<T>, T>(nz, kTLRing);
-    ring = ring && rsmem <= size_t(160) * 1024;   // LDS of a CU; very tall columns take the register path
+    ring = ring && rsmem <= kLdsPerCU;   // very tall columns take the register path
     int dev = 0;
     if (ring)
         if (const int rc = current_device(dev)) return rc;
@@ -821,22 +821,23 @@ int launch_tl(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* cons
         const int64_t full = gx / c, rounds = (gx + c - 1) / c;
         ring = 4 * full < 3 * rounds;
     }
-    if (ring) {
-        const int rc = with_flags(
+    // The ring always needs the opt-in, which launch_tail makes above kLdsOptIn: its kColBlock / 64 = 4 waves x kTLRing = 2
+    // slots of 32 fields x 64 columns are 4 x 2 x 8 KiB = 64 KiB in fp32 and 4 x 2 x 16 KiB = 128 KiB in fp64, and the
+    // level table in front of them is at least 1 KiB (ring_lds_bytes rounds it up).
+    if (ring)
+        return with_flags(
             [&](auto REG, auto EVAP) {
-                constexpr auto kern = tl_ring_kernel<T, REG, EVAP, kTLRing>;
-                if (!lds_opt_in<kern>(dev, rsmem)) return -1;
-                hipLaunchKernelGGL(kern, grid, block, rsmem, stream, e, kc, xk, nx, nz, ls, ci, cii, eta, co, coi, tdt);
-                return 0;
+                return launch_tail<tl_ring_kernel<T, REG, EVAP, kTLRing>>({grid, rsmem, stream, "cs2::tl_ring_kernel", false, dev}, e,
+                                                                          kc, xk, nx, nz, ls, ci, cii, eta, co, coi, tdt);
             },
             p.LREGCL != 0, evap);
-        if (rc) return rc;
-        note_kernel("cs2::tl_ring_kernel");
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-    }
-    with_flags([&](auto REG, auto EVAP, auto INC) { return launch(tl_kernel<T, REG, EVAP, INC>); }, p.LREGCL != 0, evap, inc);
-    note_kernel(inc ? "cs2::tl_kernel<inc>" : "cs2::tl_kernel");
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+    const Launch l{grid, smem, stream, big ? "cs2::tl_kernel<big>" : inc ? "cs2::tl_kernel<inc>" : "cs2::tl_kernel"};
+    return with_flags(
+        [&](auto REG, auto EVAP, auto INC, auto BIG) {
+            if constexpr (INC && BIG) return -2;   // refused above: no such instantiation
+            else return launch_tail<tl_kernel<T, REG, EVAP, INC, BIG>>(l, e, kc, xk, nx, nz, ls, ci, cii, eta, co, coi, tdt, tinc, zsi);
+        },
+        p.LREGCL != 0, evap, inc, big);
 }
 
 template int launch_tl<double>(const Cloudsc2Params&, int, int, int64_t, const double* const*, const double* const*,
@@ -950,6 +951,20 @@ __device__ __forceinline__ void tl_store_masked(const FP& F, uint32_t want, cons
     if (CS2_WANT(NL_OUT_FHPSN)) stg(F.out_i(NL_OUT_FHPSN), i + lsb, -o.sfln_i * e.RLSTT);
 #undef CS2_WANT
 }
+// :757-765: zeros on the top flux half-level, under the same bits
+template <typename T, typename FP, typename O>
+__device__ __forceinline__ void tl_zero_top_flux(const FP& F, uint32_t want, O colb) {
+    if (want & kTLWantNL) {
+        stg(F.out(NL_OUT_FPLSL), colb, T(0.0));
+        stg(F.out(NL_OUT_FPLSN), colb, T(0.0));
+        stg(F.out(NL_OUT_FHPSL), colb, T(0.0));
+        stg(F.out(NL_OUT_FHPSN), colb, T(0.0));
+    }
+    if (want >> NL_OUT_FPLSL & 1u) stg(F.out_i(NL_OUT_FPLSL), colb, T(0.0));
+    if (want >> NL_OUT_FPLSN & 1u) stg(F.out_i(NL_OUT_FPLSN), colb, T(0.0));
+    if (want >> NL_OUT_FHPSL & 1u) stg(F.out_i(NL_OUT_FHPSL), colb, T(0.0));
+    if (want >> NL_OUT_FHPSN & 1u) stg(F.out_i(NL_OUT_FHPSN), colb, T(0.0));
+}
 
 // The sweep of tl_masked_kernel and of tl_step_kernel (one copy).  STEP: `saturation` and its tangent-linear are fused in
 // (C ABI cloudsc2_tl_step_*): in_qsat and its perturbation are not read; the level's qsat is saturation_point_d's value of
@@ -996,24 +1011,9 @@ __device__ __forceinline__ void tl_masked_sweep(const TLMaskedArgs<T>& A, const 
     const CrhCol<T> crh = crh_setup<T>(trpaus);
 
     // :124-135
-    TLCarry<T> c;
-    c.rfl = c.rfl_i = c.sfl = c.sfl_i = c.covptot = c.covptot_i = T(0.0);
-    c.aph_k = ldg(F.in(NL_IN_APH), colb);
-    c.aph_s = EVAP ? ldg(F.in(NL_IN_APH), O(nz) * lsb + colb) : T(1.0);
-    c.aph_k_i = ldg(F.in_i(NL_IN_APH), at_aph(colb));
-    c.aph_s_i = EVAP ? ldg(F.in_i(NL_IN_APH), at_aph(O(nz) * lsb + colb)) : T(0.0);
-
-    // :757-765
-    if (want & kTLWantNL) {
-        stg(F.out(NL_OUT_FPLSL), colb, T(0.0));
-        stg(F.out(NL_OUT_FPLSN), colb, T(0.0));
-        stg(F.out(NL_OUT_FHPSL), colb, T(0.0));
-        stg(F.out(NL_OUT_FHPSN), colb, T(0.0));
-    }
-    if (want >> NL_OUT_FPLSL & 1u) stg(F.out_i(NL_OUT_FPLSL), colb, T(0.0));
-    if (want >> NL_OUT_FPLSN & 1u) stg(F.out_i(NL_OUT_FPLSN), colb, T(0.0));
-    if (want >> NL_OUT_FHPSL & 1u) stg(F.out_i(NL_OUT_FHPSL), colb, T(0.0));
-    if (want >> NL_OUT_FHPSN & 1u) stg(F.out_i(NL_OUT_FHPSN), colb, T(0.0));
+    TLCarry<T> c = tl_carry_top<T, EVAP, O>(F.in(NL_IN_APH), colb, O(nz) * lsb + colb);
+    tl_carry_top_i<T, EVAP, O>(c, F.in_i(NL_IN_APH), at_aph(colb), at_aph(O(nz) * lsb + colb));
+    tl_zero_top_flux<T>(F, want, colb);   // :757-765
 
     O o = colb;
     LevelIn<T> xa = load_level<T, O>(F_in, lsb, o, STEP), ya = load_level_masked<T, STEP>(F_in_i, have, lsb, o, zo);
@@ -1078,16 +1078,15 @@ static void fill_tl_masked_args(TLMaskedArgs<T>& args, const Cloudsc2Params& p, 
     args.nx = nx; args.nz = nz; args.ls = ls;
     args.have = 0;
     args.want = out ? kTLWantNL : 0u;
+    args.in = pack_ptrs<CPtrs<T, NL_NUM_IN>>(in);
+    args.out = pack_ptrs<MPtrs<T, NL_NUM_OUT>>(out);
+    args.out_i = pack_ptrs<MPtrs<T, NL_NUM_OUT>>(out_i);
     for (int i = 0; i < NL_NUM_IN; ++i) {
-        args.in.p[i] = in[i];
         args.in_i.p[i] = in_i[i] ? in_i[i] : zero;
         if (in_i[i]) args.have |= 1u << i;
     }
-    for (int i = 0; i < NL_NUM_OUT; ++i) {
-        args.out.p[i] = out ? out[i] : nullptr;
-        args.out_i.p[i] = out_i[i];
+    for (int i = 0; i < NL_NUM_OUT; ++i)
         if (out_i[i]) args.want |= 1u << i;
-    }
     args.eta = eta;
     args.dt = static_cast<T>(dt);
 }
@@ -1100,36 +1099,27 @@ int launch_tl_masked(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const 
                      const T* zero, const T* eta, T* const* out, T* const* out_i, double dt, hipStream_t stream, bool step,
                      int nmem, int64_t ms) {
     if (!fits_u32_offsets<T>(nz, ls)) return -2;
-    const bool evap = p.LEVAPLS2 || p.LDRAIN1D;
+    const bool evap = evap_on(p);
     TLEnsArgs<T> ens;
     TLMaskedArgs<T>& args = ens.m;
     fill_tl_masked_args<T>(args, p, evap, nx, nz, ls, in, in_i, zero, eta, out, out_i, dt);
     const int bpm = (nx + kColBlock - 1) / kColBlock;
-    const dim3 grid(bpm), block(kColBlock);
+    const dim3 grid(bpm);
     const size_t smem = 2 * size_t(nz + 1) * sizeof(T);
-    if (nmem > 0) {
-        if (int64_t(nmem) * bpm > kMaxGrid) return -2;
-        ens.g.ms = ms; ens.g.bpm = bpm;
-        const dim3 egrid(unsigned(nmem) * unsigned(bpm));
-        with_flags(
-            [&](auto REG, auto EVAP, auto STEP) {
-                if constexpr (STEP) hipLaunchKernelGGL((tl_ens_step_kernel<T, REG, EVAP>), egrid, block, smem, stream, ens);
-                else hipLaunchKernelGGL((tl_ens_kernel<T, REG, EVAP>), egrid, block, smem, stream, ens);
-                return 0;
-            },
-            p.LREGCL != 0, evap, step);
-        note_kernel(step ? "cs2::tl_ens_step_kernel" : "cs2::tl_ens_kernel");
-        return hipGetLastError() == hipSuccess ? 0 : -1;
-    }
-    with_flags(
-        [&](auto REG, auto EVAP, auto STEP) {
-            if constexpr (STEP) hipLaunchKernelGGL((tl_step_kernel<T, REG, EVAP>), grid, block, smem, stream, args);
-            else hipLaunchKernelGGL((tl_masked_kernel<T, REG, EVAP>), grid, block, smem, stream, args);
-            return 0;
+    if (nmem > 0 && int64_t(nmem) * bpm > kMaxGrid) return -2;
+    ens.g.ms = ms; ens.g.bpm = bpm;
+    const dim3 egrid(unsigned(nmem > 0 ? nmem : 1) * unsigned(bpm));
+    return with_flags(
+        [&](auto REG, auto EVAP, auto STEP, auto ENS) {
+            if constexpr (ENS) {
+                constexpr auto kern = STEP ? tl_ens_step_kernel<T, REG, EVAP> : tl_ens_kernel<T, REG, EVAP>;
+                return launch_tail<kern>({egrid, smem, stream, step ? "cs2::tl_ens_step_kernel" : "cs2::tl_ens_kernel"}, ens);
+            } else {
+                constexpr auto kern = STEP ? tl_step_kernel<T, REG, EVAP> : tl_masked_kernel<T, REG, EVAP>;
+                return launch_tail<kern>({grid, smem, stream, step ? "cs2::tl_step_kernel" : "cs2::tl_masked_kernel"}, args);
+            }
         },
-        p.LREGCL != 0, evap, step);
-    note_kernel(step ? "cs2::tl_step_kernel" : "cs2::tl_masked_kernel");
-    return hipGetLastError() == hipSuccess ? 0 : -1;
+        p.LREGCL != 0, evap, step, nmem > 0);
 }
 
 template int launch_tl_masked<double>(const Cloudsc2Params&, int, int, int64_t, const double* const*, const double* const*,
@@ -1210,16 +1200,8 @@ __device__ __forceinline__ void tl_dirs_sweep(const TLDirsArgs<T>& A) {
     const CrhCol<T> crh = crh_setup<T>(trpaus);
 
     // :124-135, :757-765
-    TLCarry<T> c;
-    c.rfl = c.sfl = c.covptot = T(0.0);
-    c.aph_k = ldg(F.in(NL_IN_APH), colb);
-    c.aph_s = EVAP ? ldg(F.in(NL_IN_APH), O(nz) * lsb + colb) : T(1.0);
-    if (want & kTLWantNL) {
-        stg(F.out(NL_OUT_FPLSL), colb, T(0.0));
-        stg(F.out(NL_OUT_FPLSN), colb, T(0.0));
-        stg(F.out(NL_OUT_FHPSL), colb, T(0.0));
-        stg(F.out(NL_OUT_FHPSN), colb, T(0.0));
-    }
+    TLCarry<T> c = tl_carry_top<T, EVAP, O>(F.in(NL_IN_APH), colb, O(nz) * lsb + colb);
+    tl_zero_top_flux<T>(F, want & kTLWantNL, colb);
     for (int d = 0; d < ndir; ++d) {
         const T* aph_i = F.in_i(NL_IN_APH) + ((have >> NL_IN_APH & 1u) ? d * in_ds : int64_t(0));
         slot(0, d) = T(0.0);
@@ -1227,11 +1209,7 @@ __device__ __forceinline__ void tl_dirs_sweep(const TLDirsArgs<T>& A) {
         slot(2, d) = T(0.0);
         slot(3, d) = ldg(aph_i, at_aph(colb));
         slot(4, d) = EVAP ? ldg(aph_i, at_aph(O(nz) * lsb + colb)) : T(0.0);
-        const int64_t ob = d * out_ds;
-        if (want >> NL_OUT_FPLSL & 1u) stg(F.out_i(NL_OUT_FPLSL) + ob, colb, T(0.0));
-        if (want >> NL_OUT_FPLSN & 1u) stg(F.out_i(NL_OUT_FPLSN) + ob, colb, T(0.0));
-        if (want >> NL_OUT_FHPSL & 1u) stg(F.out_i(NL_OUT_FHPSL) + ob, colb, T(0.0));
-        if (want >> NL_OUT_FHPSN & 1u) stg(F.out_i(NL_OUT_FHPSN) + ob, colb, T(0.0));
+        tl_zero_top_flux<T>(TLDirFields<T>{F, d * out_ds}, want & ~kTLWantNL, colb);
     }
 
     // perturbation words of direction d at byte offset o
@@ -1292,26 +1270,19 @@ int launch_tl_dirs(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T*
                    const T* zero, const T* eta, T* const* out, T* const* out_i, double dt, hipStream_t stream, bool step,
                    int ndir, int64_t in_ds, int64_t out_ds) {
     if (!fits_u32_offsets<T>(nz, ls)) return -2;
-    const bool evap = p.LEVAPLS2 || p.LDRAIN1D;
+    const bool evap = evap_on(p);
     TLDirsArgs<T> args;
     fill_tl_masked_args<T>(args.m, p, evap, nx, nz, ls, in, in_i, zero, eta, out, out_i, dt);
     args.in_ds = in_ds; args.out_ds = out_ds; args.ndir = ndir;
-    const dim3 grid((nx + kColBlock - 1) / kColBlock), block(kColBlock);
+    const dim3 grid((nx + kColBlock - 1) / kColBlock);
     const size_t smem = tl_dirs_lds_bytes<T>(nz, ndir);
-    if (smem > size_t(160) * 1024) return -2;
-    int dev = 0;
-    if (const int rc = current_device(dev)) return rc;
-    const int rc = with_flags(
+    // device_always: the device is looked up whatever the LDS demand (an ordinal beyond kMaxDevices is refused, -2)
+    return with_flags(
         [&](auto REG, auto EVAP, auto STEP) {
             constexpr auto kern = STEP ? tl_dirs_step_kernel<T, REG, EVAP> : tl_dirs_kernel<T, REG, EVAP>;
-            if (smem > size_t(64) * 1024 && !lds_opt_in<kern>(dev, smem)) return -1;
-            hipLaunchKernelGGL(kern, grid, block, smem, stream, args);
-            return 0;
+            return launch_tail<kern>({grid, smem, stream, step ? "cs2::tl_dirs_step_kernel" : "cs2::tl_dirs_kernel", true}, args);
         },
         p.LREGCL != 0, evap, step);
-    if (rc) return rc;
-    note_kernel(step ? "cs2::tl_dirs_step_kernel" : "cs2::tl_dirs_kernel");
-    return hipGetLastError() == hipSuccess ? 0 : -1;
 }
 
 template int launch_tl_dirs<double>(const Cloudsc2Params&, int, int, int64_t, const double* const*, const double* const*,
