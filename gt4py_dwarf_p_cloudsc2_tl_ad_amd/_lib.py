@@ -118,6 +118,10 @@ EVAP_LAYOUTS: Dict[str, str] = {"ad_evap": "ad_masked", "ad_evap_step": "ad_step
 #: `nmem` and `member_stride` (elements; one stride for every field of the call)
 ENS_LAYOUTS: Dict[str, str] = {"nl_ens": "nl", "nl_fused_ens": "nl_fused", "tl_ens": "tl_masked", "tl_step_ens": "tl_step",
                                "ad_ens": "ad_masked", "ad_step_ens": "ad_step"}
+#: the ensemble forms of the two single evaporation entries (autodiff.ad_masked_evap_ens / ad_step_evap_ens call them
+#: directly): name -> the `EVAP_LAYOUTS` entry whose argument list they repeat, followed by `nmem` and `member_stride`;
+#: `cover` is batched over the members like every other field of the call
+EVAP_ENS_LAYOUTS: Dict[str, str] = {"ad_evap_ens": "ad_evap", "ad_evap_step_ens": "ad_evap_step"}
 #: CLOUDSC2_TL_MAX_DIRS of include/cloudsc2_hip.h
 TL_MAX_DIRS = 8
 #: CLOUDSC2_AD_MAX_DIRS of include/cloudsc2_hip.h
@@ -162,7 +166,7 @@ def _signatures() -> Dict[str, Tuple[Any, Tuple[Any, ...]]]:
         for lay in LAYOUTS.values():
             sig[f"cloudsc2_{lay.entry}_{sfx}"] = (c_int32, (POINTER(Cloudsc2Params), c_int32, c_int32, c_int64)
                                                   + tuple(t for a in lay.args for t in _CTYPES[a.kind]))
-        for ens, single in ENS_LAYOUTS.items():
+        for ens, single in {**ENS_LAYOUTS, **EVAP_ENS_LAYOUTS}.items():
             sig[f"cloudsc2_{ens}_{sfx}"] = (c_int32, sig[f"cloudsc2_{single}_{sfx}"][1] + (c_int32, c_int64))
     return sig
 

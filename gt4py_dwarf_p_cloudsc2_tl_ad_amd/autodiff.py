@@ -39,9 +39,16 @@ ENSEMBLES: many states, one launch.  `cloudsc2_ensemble` / `cloudsc2_step_ensemb
 another layout is copied once).  `vmap` over the STATE of `cloudsc2` / `cloudsc2_step` runs them - `vmap(f)`,
 `vmap(grad(cost))`, `grad` through `vmap`, `vmap` of `jvp` over states and tangents - for a WHOLE state: every field batched (a state batched in part is refused as
 before: `expand` the fields the members share), unbatched tangents / cotangents expanded.  What
-has no ensemble kernel loops over the members through the single paths: the evaporation switches in the adjoint (in either
-`EVAP_ADJOINT` mode: the cover kernels have no ensemble form), the non-LPHYLIN step, and `saturation` with its derivatives
-(pointwise).  docs/TUNING_LOG.md 3.20 has the measurement.
+has no ensemble kernel loops over the members through the single paths: the non-LPHYLIN step, `saturation` with its
+derivatives (pointwise), and BY DEFAULT the evaporation switches in the adjoint, in either `EVAP_ADJOINT` mode.
+docs/TUNING_LOG.md 3.21 has the measurement.
+
+ENSEMBLES WITH THE EVAPORATION SWITCHES.  `ad_masked_evap_ens` / `ad_step_evap_ens` are `ad_masked_evap` / `ad_step_evap` for all
+members in one launch (C ABI `cloudsc2_ad_evap_ens_*` / `cloudsc2_ad_evap_step_ens_*`; `cover` is member-major like every other
+tensor).  The derivative rules - `backward` of `cloudsc2_ensemble` / `cloudsc2_step_ensemble`, `vmap(grad(cost))` and `grad`
+through `vmap` over the state - use them only when the module-level `EVAP_ENSEMBLE` is true AND `EVAP_ADJOINT` is
+`"trajectory"`.  `EVAP_ENSEMBLE` is False by default: the looped launches are what shipped, and tests pin their kernel
+names under the existing settings; docs/TUNING_LOG.md 3.25 has the measurement of the one launch against the loop.
 
 Not supported: members TIMES directions in one call (nested `vmap`, e.g. `vmap(jacrev(f))`) and a batched `eta`
 (`NotImplementedError`), `torch.autograd.grad(..., is_grads_batched=True)` (the legacy vmap, which knows no `vmap` rule of a
@@ -78,8 +85,13 @@ AD_MULTI_WIDTH: Dict[torch.dtype, int] = {torch.float64: 8, torch.float32: 4}
 #:   "dense"       the dense `cloudsc2_ad` (plus `saturation_ad` for the step), one launch per cotangent: what shipped before
 #:                 the trajectory kernels of the evaporation block existed, and still the default
 #:   "trajectory"  `ad_masked_evap` / `ad_step_evap`, batched cotangents `ad_multi_evap` / `ad_step_multi_evap`
-#: docs/TUNING_LOG.md 3.22 says when to set it.  Ensembles loop over their members either way.
+#: docs/TUNING_LOG.md 3.22 says when to set it.  Ensembles loop over their members either way, unless `EVAP_ENSEMBLE` is set.
 EVAP_ADJOINT = "dense"
+#: whether an ENSEMBLE's backward with LEVAPLS2 / LDRAIN1D is ONE launch for all members (`ad_masked_evap_ens` /
+#: `ad_step_evap_ens`); read at backward time, and only under `EVAP_ADJOINT = "trajectory"` (the kernels are the trajectory
+#: kernels' ensemble forms).  False, the default: the members are looped, one `ad_masked_evap` launch each, as before these
+#: kernels existed.  docs/TUNING_LOG.md 3.25 has the measurement.
+EVAP_ENSEMBLE = False
 
 
 class _Family(NamedTuple):
@@ -90,15 +102,16 @@ class _Family(NamedTuple):
     width: Dict[torch.dtype, int]    # directions per launch by default, per precision
     max_dirs: int                    # the most one launch takes
     adjoint: bool = False            # forcing (`NL_OUT` names) and `traj` in, adjoints of `names` out; else the tangent-linear
-    ens: str = ""                    # its ensemble form (`_lib.ENS_LAYOUTS`): the same arguments + (nmem, member_stride)
+    ens: str = ""                    # its ensemble form (`_lib.ENS_LAYOUTS`, `_lib.EVAP_ENS_LAYOUTS`): + (nmem, member_stride)
 
 
 _TL_MASKED = _Family("tl_masked", "tl_multi", NL_IN, MULTI_WIDTH, _lib.TL_MAX_DIRS, ens="tl_ens")
 _TL_STEP = _Family("tl_step", "tl_multi_step", STEP_IN, MULTI_WIDTH, _lib.TL_MAX_DIRS, ens="tl_step_ens")
 _AD_MASKED = _Family("ad_masked", "ad_multi", NL_IN, AD_MULTI_WIDTH, _lib.AD_MAX_DIRS, adjoint=True, ens="ad_ens")
 _AD_STEP = _Family("ad_step", "ad_multi_step", STEP_IN, AD_MULTI_WIDTH, _lib.AD_MAX_DIRS, adjoint=True, ens="ad_step_ens")
-_AD_MASKED_EVAP = _Family("ad_evap", "ad_evap_multi", NL_IN, AD_MULTI_WIDTH, _lib.AD_MAX_DIRS, adjoint=True)
-_AD_STEP_EVAP = _Family("ad_evap_step", "ad_evap_multi_step", STEP_IN, AD_MULTI_WIDTH, _lib.AD_MAX_DIRS, adjoint=True)
+_AD_MASKED_EVAP = _Family("ad_evap", "ad_evap_multi", NL_IN, AD_MULTI_WIDTH, _lib.AD_MAX_DIRS, adjoint=True, ens="ad_evap_ens")
+_AD_STEP_EVAP = _Family("ad_evap_step", "ad_evap_multi_step", STEP_IN, AD_MULTI_WIDTH, _lib.AD_MAX_DIRS, adjoint=True,
+                        ens="ad_evap_step_ens")
 _ZERO_LINE_BYTES = 512
 _zero_lines: Dict[Tuple[torch.device, torch.dtype], torch.Tensor] = {}
 
@@ -256,7 +269,7 @@ def ad_masked_evap(state: Mapping[str, torch.Tensor], forcing: Mapping[str, torc
     otherwise): the same arguments and result.  `cover` is the field the launch parks the precipitation cover entering each
     level in (`storage` layout of the state; a new one when None).  `cover_ready=True`: `cover` already holds what an
     earlier such call left for the same state, `traj`, `eta`, `dt` and externals - it is only read, and the forward cover
-    sweep is skipped.  Ensembles have no such kernel: loop over the members."""
+    sweep is skipped.  `ad_masked_evap_ens` is the same call for the members of an ensemble."""
     return _call(_AD_MASKED_EVAP, False, state, forcing, eta, dt, externals, want, traj=traj, cover=cover,
                  cover_ready=cover_ready)
 
@@ -318,6 +331,28 @@ def ad_step_ens(states: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.
                 externals: Optional[Mapping[str, Any]] = None, *, traj: Mapping[str, torch.Tensor], want: Iterable[str]):
     """`ad_step` for an ensemble of states in one launch (`cloudsc2_ad_step_ens_*`; `STEP_IN` names): see `ad_masked_ens`."""
     return _call(_AD_STEP, False, states, forcing, eta, dt, externals, want, traj=traj, ens=True)
+
+
+def ad_masked_evap_ens(states: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+                       externals: Optional[Mapping[str, Any]] = None, *, traj: Mapping[str, torch.Tensor], want: Iterable[str],
+                       cover: Optional[torch.Tensor] = None, cover_ready: bool = False):
+    """`ad_masked_evap` for an ensemble of `nmem` states in ONE launch (`cloudsc2_ad_evap_ens_*`; LEVAPLS2 or LDRAIN1D must be
+    set): the arguments and the result of `ad_masked_ens`, one cotangent per member.  `cover` is member-major like every
+    other tensor of the call, `(nmem, nx, 1, nz+1)` as `storage.zeros_batched` gives (a new one when None); the launch
+    parks every member's precipitation cover in it.  `cover_ready=True`: `cover` holds what an earlier such call left for
+    the same states, `traj`, `eta`, `dt` and externals, and is only read.  A `cover` in another layout is copied into the
+    call's like any other tensor, and what the launch parked is copied back into it."""
+    return _call(_AD_MASKED_EVAP, False, states, forcing, eta, dt, externals, want, traj=traj, ens=True, cover=cover,
+                 cover_ready=cover_ready)
+
+
+def ad_step_evap_ens(states: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+                     externals: Optional[Mapping[str, Any]] = None, *, traj: Mapping[str, torch.Tensor], want: Iterable[str],
+                     cover: Optional[torch.Tensor] = None, cover_ready: bool = False):
+    """`ad_step_evap` for an ensemble of states in one launch (`cloudsc2_ad_evap_step_ens_*`; `STEP_IN` names): see
+    `ad_masked_evap_ens`.  LPHYLIN only."""
+    return _call(_AD_STEP_EVAP, False, states, forcing, eta, dt, externals, want, traj=traj, ens=True, cover=cover,
+                 cover_ready=cover_ready)
 
 
 def _batched_layout(g: torch.Tensor, ref: torch.Tensor, geo, stride: Optional[int] = None) -> torch.Tensor:
@@ -391,18 +426,19 @@ def _tl_args(p, geo, state, pert, zero_line, eta, out, out_i, dt, stream, tail=(
             None if out is None else _ptrs(out, NL_OUT), _ptrs(out_i, NL_OUT), float(dt), stream) + tail
 
 
-def _ad_args(p, geo, state, forcing, zero_line, eta, traj, out_adj, dt, stream, tail=(), cover=()):
+def _ad_args(p, geo, state, forcing, zero_line, eta, traj, out_adj, dt, stream, tail=(), cover=(), members=()):
     """the arguments of `cloudsc2_ad_masked_*` / `_ad_step_*`; `tail` as for `_tl_args`; `cover` = (pointer, cover_ready):
-    those of the `cloudsc2_ad_evap_*` entries (`_lib.EVAP_LAYOUTS`) - in front of `stream`, or behind a multi entry's `tail`"""
+    those of the `cloudsc2_ad_evap_*` entries (`_lib.EVAP_LAYOUTS`) - in front of `stream`, or behind a multi entry's `tail`;
+    `members` = (nmem, member_stride): those of the ensemble form of either (`_lib.ENS_LAYOUTS`, `_lib.EVAP_ENS_LAYOUTS`)"""
     nx, nlev, ls = geo
     head = (ctypes.byref(p), nx, nlev - 1, ls, _ptrs(state, NL_IN), _ptrs(forcing, NL_OUT), zero_line.data_ptr(),
             eta.data_ptr(), traj["fplsl"].data_ptr(), traj["fplsn"].data_ptr(), _ptrs(out_adj, NL_IN), float(dt))
-    return head + (stream,) + tail + cover if tail else head + cover + (stream,)
+    return (head + (stream,) + tail + cover if tail else head + cover + (stream,)) + members
 
 
 def _call(fam: _Family, batched: bool, state, dirs, eta, dt, externals, want, *, traj=None, write_nl=False, width=None,
           ens=False, cover=None, cover_ready=False):
-    """The launch path of the twelve thin calls.  Everything is checked ONCE, up front; then the directions are served in
+    """The launch path of the eighteen thin calls.  Everything is checked ONCE, up front; then the directions are served in
     chunks of at most `width`: a chunk of one direction by the single-direction entry, a wider one by the multi-direction
     entry.  `batched`: `dirs` maps names to (ndir, nx, 1, nlev) batches and so do the results, which are one `zeros_batched`
     allocation per wanted name that every chunk writes through the views `f[d0]`; otherwise `dirs` and the results are
@@ -411,25 +447,32 @@ def _call(fam: _Family, batched: bool, state, dirs, eta, dt, externals, want, *,
     layout (that of the first state tensor, `_ens_geometry`); the checks run on member 0 and ONE launch of the family's
     ensemble entry, given member 0's pointers and (nmem, member stride), serves all members.
     `cover`, `cover_ready`: the evaporation families' cover field (a new one when None); every chunk behind the first reads
-    what the first left in it."""
+    what the first left in it.  With `ens` it is a member-major batch like every other tensor of the call."""
     what = fam.ens if ens else fam.multi if batched else fam.single
     noun, dir_names, res_names = ("forcing", NL_OUT, fam.names) if fam.adjoint else ("perturbation", fam.names, NL_OUT)
     want = tuple(want)
     if not want or set(want) - set(res_names):
         raise ValueError(f"{what}: `want` must name at least one of {res_names}, got {want}")
     nmem = mstride = 0
+    cover_given = cover_all = None
     if ens:
         first = state.get(fam.names[0])
         nmem, egeo, mstride = _ens_geometry(what, first)
 
-        def members(fields):    # -> member 0 of every tensor, in the call's layout
+        def laid_out(fields):    # -> every tensor in the call's layout
             for n, f in fields.items():
                 if not isinstance(f, torch.Tensor) or tuple(f.shape) != (nmem, egeo[0], 1, egeo[1]):
                     raise ValueError(f"{what}: {n} must be a tensor of shape {(nmem, egeo[0], 1, egeo[1])} like the state's "
                                      f"{fam.names[0]}, got {tuple(getattr(f, 'shape', ()))}")
-            return {n: _batched_layout(f, first, egeo, mstride)[0] for n, f in fields.items()}
+            return {n: _batched_layout(f, first, egeo, mstride) for n, f in fields.items()}
+
+        def members(fields):    # -> member 0 of every tensor, in the call's layout
+            return {n: f[0] for n, f in laid_out(fields).items()}
         state, dirs = members(state), members(dirs)
         traj = members(traj) if fam.adjoint else None
+        if cover is not None:   # the checks below see member 0, the launch gets the batch
+            cover_given, cover_all = cover, laid_out({"cover": cover})["cover"]
+            cover = cover_all[0]
     state = {n: _plain(f) for n, f in state.items()}
     groups = [(state, fam.names, True)]
     if not batched:
@@ -462,18 +505,24 @@ def _call(fam: _Family, batched: bool, state, dirs, eta, dt, externals, want, *,
     p = _params(externals, nz)
     lib, zero, dstride = _lib.load(), _zero_line(device, dtype), nlev * ls
     stream = int(torch.cuda.current_stream(device).cuda_stream)
-    if evap:
+    if evap and not ens:
         cover = _new_like(ref, nx, nz, ls) if cover is None else _plain(cover)
     if ens:
         new = lambda: _zeros_members(nmem, geo, dtype, device, mstride)  # noqa: E731
         res, out = {n: new() for n in want}, ({n: new() for n in NL_OUT} if write_nl else None)
         r0, o0 = {n: f[0] for n, f in res.items()}, (None if out is None else {n: f[0] for n, f in out.items()})
         if fam.adjoint:
-            args = _ad_args(p, geo, state, dirs, zero, eta, traj, r0, dt, stream, (nmem, mstride))
+            park = ()
+            if evap:
+                cover_all = new() if cover_all is None else cover_all
+                park = (cover_all[0].data_ptr(), int(bool(cover_ready)))
+            args = _ad_args(p, geo, state, dirs, zero, eta, traj, r0, dt, stream, cover=park, members=(nmem, mstride))
         else:
             args = _tl_args(p, geo, state, dirs, zero, eta, o0, r0, dt, stream, (nmem, mstride))
         with torch.cuda.device(device):
             _lib.check(getattr(lib, f"cloudsc2_{fam.ens}_{_SFX[dtype]}")(*args), fam.ens)
+        if cover_given is not None and not cover_ready and cover_all.data_ptr() != cover_given.data_ptr():
+            _plain(cover_given).copy_(cover_all)     # the caller's field was in another layout: hand back what was parked
         return res if fam.adjoint else (out, res)
     with torch.cuda.device(device):
         for d0 in range(0, ndir, width):
@@ -712,18 +761,21 @@ def _ad_rule(fam, call, tensors, info=None, in_dims=None):
     its multi-direction launches.  Elsewhere they loop over this rule for one cotangent: the dense `cloudsc2_ad`
     (evaporation, `EVAP_ADJOINT = "dense"`), `ad_masked_evap` or `ad_masked`, for the step producing the adjoint of its
     `qsat`, which `saturation_ad` adds into those of `ap` and `t`.  Ensembles with the evaporation switches loop over their
-    members in either mode."""
+    members in either mode, unless `EVAP_ENSEMBLE` is set: then, under `"trajectory"`, they are one launch of the evaporation
+    family's ensemble entry (`ad_masked_evap_ens` / `ad_step_evap_ens`; the non-LPHYLIN step still loops)."""
     batched, step, want = info is not None, fam is _AD_STEP, call.want
     ext = dict(call.ext, AD_TRAJ_FIX=1)
     if EVAP_ADJOINT not in ("dense", "trajectory"):
         raise ValueError(f"autodiff.EVAP_ADJOINT must be 'dense' or 'trajectory', got {EVAP_ADJOINT!r}")
-    evap_traj = _evap(ext) and EVAP_ADJOINT == "trajectory"     # the cover kernels: single states only, no ensemble form
-    one_launch = (not _evap(ext) or (evap_traj and call.geo is not None)) and (not step or bool(ext.get("LPHYLIN")))
+    evap_traj = _evap(ext) and EVAP_ADJOINT == "trajectory"     # the cover kernels; their ensemble form only on request
+    evap_ens = evap_traj and bool(EVAP_ENSEMBLE)
+    one_launch = (not _evap(ext) or (evap_traj and (call.geo is not None or evap_ens))) and \
+        (not step or bool(ext.get("LPHYLIN")))
     launch = (_AD_STEP_EVAP if step else _AD_MASKED_EVAP) if evap_traj else fam     # the family `_call` runs
     nfixed = len(fam.names) + step + 2
     if batched:
         _refuse_nested(tensors)
-        if one_launch and evap_traj and _batched_state(in_dims, nfixed):   # an ensemble of states: member by member
+        if one_launch and evap_traj and not evap_ens and _batched_state(in_dims, nfixed):   # an ensemble: member by member
             return _looped_adjoint(lambda c, *t: _ad_rule(fam, c, t), info, in_dims, call, tensors, nfixed, len(want))
         if one_launch and _batched_state(in_dims, nfixed):   # an ensemble of states: one ensemble launch
             outs = _ad_rule(fam, call._replace(geo=None), _members(info, in_dims[1:], tensors))
@@ -732,7 +784,7 @@ def _ad_rule(fam, call, tensors, info=None, in_dims=None):
         if not one_launch:
             return _looped_members(lambda c, *t: _ad_rule(fam, c, t), call, tensors, len(want))
         state, _, traj, forcing = _unpacked(fam.names, step, True, call, tensors)
-        adj = _call(fam, False, state, forcing, call.eta, call.dt, ext, want, traj=traj, ens=True)
+        adj = _call(launch, False, state, forcing, call.eta, call.dt, ext, want, traj=traj, ens=True)
         return tuple(adj[n] for n in want)
     if batched and not one_launch:
         return _looped_adjoint(lambda c, *t: _ad_rule(fam, c, t), info, in_dims, call, tensors, len(fam.names) + step + 2,

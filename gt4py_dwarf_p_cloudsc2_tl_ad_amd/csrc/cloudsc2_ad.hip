@@ -271,22 +271,7 @@ template int launch_ad<float>(const Cloudsc2Params&, int, int, int64_t, const fl
 // cloudsc2_ad_step_ens_*): see ens_block.  ADEnsFields is ADMaskedFields moved to one member: the member's base `mb`
 // (elements; wave-uniform) is added to the field pointer as a 64-bit scalar, the way ad_dirs_sweep adds the direction base;
 // an absent forcing keeps the zero line's pointer (the line is 512 bytes long).  An unwanted adjoint's pointer is never used.
-template <typename T>
-struct ADEnsArgs {
-    ADMaskedArgs<T> m;           // at kernarg offset 0
-    EnsGeom g;
-};
-template <typename T>
-struct ADEnsFields : KernArgs<ADEnsArgs<T>> {
-    int64_t mb;
-    uint32_t have;
-    __device__ __forceinline__ const T* in(int i) const { return this->ka->m.in.p[i] + mb; }
-    __device__ __forceinline__ const T* adj(int i) const { return this->ka->m.adj.p[i] + ((have >> i & 1u) ? mb : int64_t(0)); }
-    __device__ __forceinline__ T* oadj(int i) const { return this->ka->m.oadj.p[i] + mb; }
-    __device__ __forceinline__ const T* traj_l() const { return this->ka->m.traj_l + mb; }
-    __device__ __forceinline__ const T* traj_n() const { return this->ka->m.traj_n + mb; }
-};
-
+// (ADEnsArgs / ADEnsFields: cloudsc2_ad_level.hpp - the cover kernels' ensemble forms in cloudsc2_ad_evap.hip use them too.)
 
 // The sweep of ad_masked_kernel and of ad_step_kernel (one copy).  STEP: the adjoint of `saturation` is fused in (C ABI
 // cloudsc2_ad_step_*).  in_qsat is not read: the level's qsat is saturation_point's value of the level's t and ap words

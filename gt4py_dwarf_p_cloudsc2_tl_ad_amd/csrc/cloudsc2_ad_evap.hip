@@ -1,5 +1,6 @@
 // Trajectory adjoints WITH the evaporation block (LEVAPLS2 / LDRAIN1D; BUILD EXTENSION, C ABI cloudsc2_ad_evap_*,
-// cloudsc2_ad_evap_step_*, cloudsc2_ad_evap_multi_*, cloudsc2_ad_evap_multi_step_*).
+// cloudsc2_ad_evap_step_*, cloudsc2_ad_evap_multi_*, cloudsc2_ad_evap_multi_step_*, and for the members of an ensemble
+// cloudsc2_ad_evap_ens_*, cloudsc2_ad_evap_step_ens_*).
 //
 // The masked, step and multi-direction adjoints of cloudsc2_ad.hip read their trajectory - the two precipitation fluxes
 // entering each level - from a cloudsc2_nl / cloudsc2_tl call on the same state and have no forward sweep.  With the
@@ -27,6 +28,14 @@ struct ADCoverArgs {
     ADMaskedArgs<T> m;             // at kernarg offset 0: ADMaskedFields reads the pointers from there
     T* cover;                      // [nz+1 levels][lev_stride]: level k = the cover entering level k; level nz is not touched
     int cover_ready;               // != 0: `cover` is already filled for this state and trajectory; sweep 1 is skipped
+};
+// The single kernels for every MEMBER of an ensemble (ad_cover_ens_kernel / ad_cover_ens_step_kernel, C ABI
+// cloudsc2_ad_evap_ens_* / cloudsc2_ad_evap_step_ens_*): ad_ens_kernel's member decode (ens_block) and base add (ADEnsFields),
+// and `cover` is batched like every other field - the member's base is added to it as well.
+template <typename T>
+struct ADCoverEnsArgs {
+    ADCoverArgs<T> c;              // at kernarg offset 0 (its ADMaskedArgs first: ADEnsFields reads the pointers from there)
+    EnsGeom g;
 };
 template <typename T>
 struct ADCoverDirsArgs {
@@ -96,9 +105,10 @@ struct ADCoverCol {
     T aph_s, aph_top;              // aph[nz] (:146 the surface pressure), aph[0]
 };
 
-// -> false: this lane has no column (it retires; there is no later workgroup barrier)
-template <typename T>
-__device__ __forceinline__ bool ad_cover_setup(const ADMaskedArgs<T>& A, const ADMaskedFields<T>& F, ADCoverCol<T>& c) {
+// -> false: this lane has no column (it retires; there is no later workgroup barrier).  ENS: one member of an ensemble per
+// workgroup (`g`: EnsGeom; `F`: ADEnsFields, whose member base is set here)
+template <typename T, bool ENS = false, typename FP>
+__device__ __forceinline__ bool ad_cover_setup(const ADMaskedArgs<T>& A, FP& F, ADCoverCol<T>& c, const EnsGeom g = EnsGeom{}) {
     c.e = A.e;
     c.kc = A.kc;
     c.xk = A.xk;
@@ -115,7 +125,15 @@ __device__ __forceinline__ bool ad_cover_setup(const ADMaskedArgs<T>& A, const A
     // No pin_vgprs / pin_expk here (ad_masked_sweep pins 20 fp64 constants and the exponential's coefficients in VGPRs): with
     // the evaporation block's trajectory words live as well, the pinned fp64 instantiations spill (12 - 28 bytes of scratch
     // in the single kernels, ~420 in the multi-direction ones); unpinned, the single kernels need 256 + ~190 registers.
-    const int gcol = xcd_block() * kColBlock + threadIdx.x;
+    int gcol;
+    if constexpr (ENS) {
+        int member;
+        gcol = ens_block(g.bpm, member) * kColBlock + threadIdx.x;
+        F.mb = member * g.ms;
+        F.have = A.have;
+    } else {
+        gcol = xcd_block() * kColBlock + threadIdx.x;
+    }
     c.park_lds = c.s_scalm + (nz + 1) + threadIdx.x;
     if (gcol >= nx) return false;
     c.lsb = uint32_t(ls) * uint32_t(sizeof(T));
@@ -132,8 +150,8 @@ __device__ __forceinline__ bool ad_cover_setup(const ADMaskedArgs<T>& A, const A
 }
 
 // Sweep 1: cover[k] = the precipitation cover entering level k, k = 0 .. nz-1.
-template <typename T, bool FIX, bool STEP>
-__device__ __forceinline__ void ad_cover_fill(ADMaskedFields<T>& F, const ADCoverCol<T>& c, T* __restrict__ cover) {
+template <typename T, bool FIX, bool STEP, typename FP>
+__device__ __forceinline__ void ad_cover_fill(FP& F, const ADCoverCol<T>& c, T* __restrict__ cover) {
     using O = uint32_t;
     const auto F_in = [&](int i) { return F.in(i); };
     const int nz = c.nz;
@@ -181,14 +199,23 @@ __device__ __forceinline__ ADForce<T> ad_cover_load_force(const FP& F, uint32_t 
 }
 
 // Single direction: ad_masked_sweep's loop with the evaporation block (see the head of this file and ad_masked_sweep).
-template <typename T, bool REG, bool FIX, bool STEP>
-__device__ __forceinline__ void ad_cover_sweep(const ADCoverArgs<T>& A) {
-    ADMaskedFields<T> F;
+// ENS: one member of an ensemble per workgroup; the member's base is added to `cover` as to every field pointer.  Every
+// pointer then costs a second SGPR pair (the sum), and with the pointers of a whole level batch fetched at once
+// ad_cover_ens_kernel<double, true, true> computed wrong adjoints on an MI355X in the columns where the evaporation block
+// runs (fp32 and the step form of the same text gave the single kernel's bits).  NOT explained: docs/TUNING_LOG.md 3.25 lists
+// what was ruled out.  With `fresh()` between the batches of a level - state, forcing, the rest, the stores - the kernarg
+// loads stay beside their uses and all sixteen instantiations give the single kernels' results.  That is held by tests
+// alone (tests/test_hip_evap_ensemble.py: every instantiation, and the fp64 kernels on a full chip against the looped
+// launches): rerun them after any change to this sweep, to ADEnsFields or to the compiler.
+template <typename T, bool REG, bool FIX, bool STEP, bool ENS = false>
+__device__ __forceinline__ void ad_cover_sweep(const ADCoverArgs<T>& A, const EnsGeom g = EnsGeom{}) {
+    typename std::conditional<ENS, ADEnsFields<T>, ADMaskedFields<T>>::type F;
     ADCoverCol<T> c;
-    if (!ad_cover_setup<T>(A.m, F, c)) return;
+    if (!ad_cover_setup<T, ENS>(A.m, F, c, g)) return;
     const auto F_in = [&](int i) { return F.in(i); };
     const uint32_t have = A.m.have, want = A.m.want;
     T* __restrict__ cover = A.cover;
+    if constexpr (ENS) cover += F.mb;
     if (A.cover_ready == 0) ad_cover_fill<T, FIX, STEP>(F, c, cover);
 
     using O = uint32_t;
@@ -212,12 +239,15 @@ __device__ __forceinline__ void ad_cover_sweep(const ADCoverArgs<T>& A) {
             const O om = o - lsb;
             xn = load_level<T>(F_in, lsb, om, STEP);
             xn.aph1 = aph_k;   // aph[k]: already here as this level's upper half level
+            if constexpr (ENS) F.fresh();   // see the head of this function
             fn = ad_cover_load_force<T>(F, have, lsb, om, zo);
+            if constexpr (ENS) F.fresh();
             aph_n = ldg(F.in(NL_IN_APH), om);
             sfl_n = ldg(F.traj_n(), om);
             rfl_n = ldg(F.traj_l(), om);
             cov_n = ldg(static_cast<const T*>(cover), om);
         }
+        if constexpr (ENS) F.fresh();
         if (k < nz - 1) {
             if constexpr (STEP) {
                 const SatD<T> s = saturation_point_d<T, 0>(c.e, c.xk, pt, pap);
@@ -267,6 +297,19 @@ template <typename T, bool REG, bool FIX>
 __global__ void __launch_bounds__(kColBlock, sizeof(T) == 4 ? 2 : 1)
 ad_cover_step_kernel(const ADCoverArgs<T> A) {
     ad_cover_sweep<T, REG, FIX, true>(A);
+}
+
+// ad_cover_kernel / ad_cover_step_kernel for the members of an ensemble, one launch: see ADCoverEnsArgs
+template <typename T, bool REG, bool FIX>
+__global__ void __launch_bounds__(kColBlock, sizeof(T) == 4 ? 2 : 1)
+ad_cover_ens_kernel(const ADCoverEnsArgs<T> A) {
+    ad_cover_sweep<T, REG, FIX, false, true>(A.c, A.g);
+}
+
+template <typename T, bool REG, bool FIX>
+__global__ void __launch_bounds__(kColBlock, sizeof(T) == 4 ? 2 : 1)
+ad_cover_ens_step_kernel(const ADCoverEnsArgs<T> A) {
+    ad_cover_sweep<T, REG, FIX, true, true>(A.c, A.g);
 }
 
 // `ndir` directions on one trajectory: ad_dirs_sweep with the evaporation block.  Sweep 1 runs once; per level ad_forward
@@ -386,27 +429,40 @@ ad_cover_dirs_step_kernel(const ADCoverDirsArgs<T> A) {
 
 // The caller (cloudsc2_capi.hip) has checked every argument: one of the evaporation switches is on, fields below 4 GiB,
 // `cover` not NULL, and with ndir > 0 the direction arguments (the multi-direction kernels; ndir == 0: the single ones).
-// `step`: in[NL_IN_QSAT] is not read, out_adj[NL_IN_QSAT] is NULL.
+// `step`: in[NL_IN_QSAT] is not read, out_adj[NL_IN_QSAT] is NULL.  nmem > 0 (with ndir == 0 only): the ensemble form of the
+// single kernels - every field pointer, `cover` included, is member 0's, member m lies m * ms elements behind it; the caller
+// has checked nmem and ms.
 template <typename T>
 int launch_ad_cover(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* const* in, const T* const* in_adj,
                     const T* zero, const T* eta, const T* traj_l, const T* traj_n, T* const* out_adj, double dt,
-                    hipStream_t stream, bool step, int ndir, int64_t in_ds, int64_t out_ds, T* cover, int cover_ready) {
+                    hipStream_t stream, bool step, int ndir, int64_t in_ds, int64_t out_ds, T* cover, int cover_ready,
+                    int nmem, int64_t ms) {
     if (!evap_on(p) || !fits_u32_offsets<T>(nz, ls) || !cover) return -2;
-    if (ndir < 0 || ndir > kADMaxDirs) return -1;
+    if (ndir < 0 || ndir > kADMaxDirs || (ndir > 0 && nmem > 0)) return -1;
     ADCoverDirsArgs<T> dargs;
-    ADCoverArgs<T> sargs;
+    ADCoverEnsArgs<T> eargs;
+    ADCoverArgs<T>& sargs = eargs.c;
     ADMaskedArgs<T>& m = ndir > 0 ? dargs.d.m : sargs.m;
     fill_ad_masked_args<T>(m, p, nx, nz, ls, in, in_adj, zero, eta, traj_l, traj_n, out_adj, dt);
     m.kc = make_nlk<T>(p, dt, true);
     dargs.d.in_ds = in_ds; dargs.d.out_ds = out_ds; dargs.d.ndir = ndir;
     dargs.cover = sargs.cover = cover;
     dargs.cover_ready = sargs.cover_ready = cover_ready;
-    const dim3 grid((nx + kColBlock - 1) / kColBlock);
+    const int bpm = (nx + kColBlock - 1) / kColBlock;
+    if (nmem > 0 && int64_t(nmem) * bpm > kMaxGrid) return -2;
+    eargs.g.ms = ms; eargs.g.bpm = bpm;
+    const dim3 grid(unsigned(nmem > 0 ? nmem : 1) * unsigned(bpm));
     const size_t smem = ndir > 0 ? ad_cover_dirs_lds_bytes<T>(nz, ndir)
                                  : 2 * size_t(nz + 1) * sizeof(T) + (kADPark<T> ? size_t(CS2_AD_PARK_COUNT) * kColBlock * sizeof(T) : 0);
     return with_flags(
-        [&](auto REG, auto FIX, auto STEP, auto DIRS) {
-            if constexpr (DIRS) {
+        [&](auto REG, auto FIX, auto STEP, auto DIRS, auto ENS) {
+            if constexpr (DIRS && ENS) {
+                return -1;   // refused above: no such instantiation
+            } else if constexpr (ENS) {
+                constexpr auto kern = STEP ? ad_cover_ens_step_kernel<T, REG, FIX> : ad_cover_ens_kernel<T, REG, FIX>;
+                return launch_tail<kern>({grid, smem, stream, step ? "cs2::ad_cover_ens_step_kernel" : "cs2::ad_cover_ens_kernel"},
+                                         eargs);
+            } else if constexpr (DIRS) {
                 constexpr auto kern = STEP ? ad_cover_dirs_step_kernel<T, REG, FIX> : ad_cover_dirs_kernel<T, REG, FIX>;
                 return launch_tail<kern>({grid, smem, stream, step ? "cs2::ad_cover_dirs_step_kernel" : "cs2::ad_cover_dirs_kernel"},
                                          dargs);
@@ -415,14 +471,14 @@ int launch_ad_cover(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T
                 return launch_tail<kern>({grid, smem, stream, step ? "cs2::ad_cover_step_kernel" : "cs2::ad_cover_kernel"}, sargs);
             }
         },
-        p.LREGCL != 0, p.AD_TRAJ_FIX != 0, step, ndir > 0);
+        p.LREGCL != 0, p.AD_TRAJ_FIX != 0, step, ndir > 0, nmem > 0);
 }
 
 template int launch_ad_cover<double>(const Cloudsc2Params&, int, int, int64_t, const double* const*, const double* const*,
                                      const double*, const double*, const double*, const double*, double* const*, double,
-                                     hipStream_t, bool, int, int64_t, int64_t, double*, int);
+                                     hipStream_t, bool, int, int64_t, int64_t, double*, int, int, int64_t);
 template int launch_ad_cover<float>(const Cloudsc2Params&, int, int, int64_t, const float* const*, const float* const*,
                                     const float*, const float*, const float*, const float*, float* const*, double,
-                                    hipStream_t, bool, int, int64_t, int64_t, float*, int);
+                                    hipStream_t, bool, int, int64_t, int64_t, float*, int, int, int64_t);
 
 }  // namespace cs2

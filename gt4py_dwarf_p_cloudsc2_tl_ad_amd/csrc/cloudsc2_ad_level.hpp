@@ -888,6 +888,24 @@ struct ADMaskedFields : KernArgs<ADMaskedArgs<T>> {
     __device__ __forceinline__ const T* traj_l() const { return this->ka->traj_l; }
     __device__ __forceinline__ const T* traj_n() const { return this->ka->traj_n; }
 };
+// The ensemble forms (ad_ens_kernel / ad_ens_step_kernel in cloudsc2_ad.hip, ad_cover_ens_kernel / ad_cover_ens_step_kernel in
+// cloudsc2_ad_evap.hip): ADMaskedFields moved to one member, see ad_masked_sweep.  Any argument struct whose ADMaskedArgs
+// stands at kernarg offset 0 is read through this view.
+template <typename T>
+struct ADEnsArgs {
+    ADMaskedArgs<T> m;           // at kernarg offset 0
+    EnsGeom g;
+};
+template <typename T>
+struct ADEnsFields : KernArgs<ADEnsArgs<T>> {
+    int64_t mb;
+    uint32_t have;
+    __device__ __forceinline__ const T* in(int i) const { return this->ka->m.in.p[i] + mb; }
+    __device__ __forceinline__ const T* adj(int i) const { return this->ka->m.adj.p[i] + ((have >> i & 1u) ? mb : int64_t(0)); }
+    __device__ __forceinline__ T* oadj(int i) const { return this->ka->m.oadj.p[i] + mb; }
+    __device__ __forceinline__ const T* traj_l() const { return this->ka->m.traj_l + mb; }
+    __device__ __forceinline__ const T* traj_n() const { return this->ka->m.traj_n + mb; }
+};
 
 // ad_load_force with a per-field offset: the field's own `o`, or `zo` into the zero line (raw words, as there)
 template <typename T, typename FP>

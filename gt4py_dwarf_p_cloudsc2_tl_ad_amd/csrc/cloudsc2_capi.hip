@@ -40,7 +40,7 @@ int launch_ad_dirs(const Cloudsc2Params&, int, int, int64_t, const T* const*, co
 template <typename T>
 int launch_ad_cover(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T* const*, const T*, const T*, const T*,
                     const T*, T* const*, double, hipStream_t, bool step, int ndir, int64_t in_ds, int64_t out_ds, T* cover,
-                    int cover_ready);
+                    int cover_ready, int nmem = 0, int64_t ms = 0);
 template <typename T>
 int launch_nl_ens(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T*, T* const*, double, hipStream_t, T*,
                   int nmem, int64_t ms);
@@ -395,10 +395,47 @@ int tl_masked_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t 
                                                  static_cast<hipStream_t>(stream), step, ens ? nmem : 0, ms));
 }
 
+// The evaporation ensemble entries: sweep 1 WRITES `cover` while every other field of the call is read (or written by sweep
+// 2), so a `cover` that shares storage with one of them is refused.  Judged on bounding ranges: one member of a field spans
+// `ea` / `eb` bytes, member m starts m * `sb` bytes behind member 0; `a` has `na` members, `b` has `nb` (1: the zero line, eta).
+// Member i of `a` meets member j of `b` iff -ea < (a - b) + (i - j) * sb < eb.
+bool member_ranges_overlap(const void* a, int64_t ea, int64_t na, const void* b, int64_t eb, int64_t nb, int64_t sb) {
+    const int64_t delta = int64_t(reinterpret_cast<intptr_t>(a) - reinterpret_cast<intptr_t>(b));
+    const auto floor_div = [](int64_t x, int64_t y) { return x / y - ((x % y != 0 && x < 0) ? 1 : 0); };   // y > 0
+    const int64_t dmin = floor_div(-ea - delta, sb) + 1;       // the d = i - j with -ea < delta + d * sb ...
+    const int64_t dmax = -floor_div(delta - eb, sb) - 1;       // ... and delta + d * sb < eb
+    return std::max(dmin, -(nb - 1)) <= std::min(dmax, na - 1);
+}
+
+template <typename T>
+int check_cover_disjoint(const char* fn, int32_t nx, int32_t nz, int64_t ls, const T* const* in, const T* const* in_adj,
+                         const T* zero_line, const T* eta, const T* traj_fplsl, const T* traj_fplsn, T* const* out_adj,
+                         const T* cover, int32_t nmem, int64_t ms) {
+    const int64_t ext = (int64_t(nz) * ls + nx) * int64_t(sizeof(T)), sb = ms * int64_t(sizeof(T));
+    const auto hits = [&](const T* f, int64_t ef, int64_t nf) {
+        return f && member_ranges_overlap(cover, ext, nmem, f, ef, nf, sb);
+    };
+    const auto refuse = [&](const char* what, int i) {
+        return fail(CLOUDSC2_E_ARG, "%s: cover overlaps %s[%d] in some member: cover must not share storage with any other "
+                    "field of the call", fn, what, i);
+    };
+    for (int i = 0; i < NL_NUM_IN; ++i) {
+        if (hits(in[i], ext, nmem)) return refuse("in", i);
+        if (hits(out_adj[i], ext, nmem)) return refuse("out_adj", i);
+    }
+    for (int i = 0; i < NL_NUM_OUT; ++i)
+        if (hits(in_adj[i], ext, nmem)) return refuse("in_adj", i);
+    if (hits(traj_fplsl, ext, nmem) || hits(traj_fplsn, ext, nmem)) return refuse("traj_fplsl / traj_fplsn", 0);
+    if (hits(zero_line, 512, 1)) return refuse("zero_line", 0);
+    if (hits(eta, int64_t(nz + 1) * int64_t(sizeof(T)), 1)) return refuse("eta", 0);
+    return 0;
+}
+
 // `step`: the cloudsc2_ad_step_* entry (ad_step_kernel); `multi`: the cloudsc2_ad_multi_* entries (ad_dirs_kernel);
 // `ens`: the cloudsc2_ad_ens_* / cloudsc2_ad_step_ens_* entries (ad_ens_kernel / ad_ens_step_kernel);
 // `evap`: the trajectory adjoints WITH the evaporation block (cloudsc2_ad_evap_* / _step_* / _multi_* / _multi_step_*:
-// ad_cover_kernel and its siblings) - the same checks, the switches required instead of refused, and the caller's cover field.
+// ad_cover_kernel and its siblings) - the same checks, the switches required instead of refused, and the caller's cover field;
+// `evap` and `ens`: cloudsc2_ad_evap_ens_* / _step_ens_* (ad_cover_ens_kernel / ad_cover_ens_step_kernel), `cover` batched too.
 template <typename T>
 int ad_masked_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,
                    const T* const* in_adj, const T* zero_line, const T* eta, const T* traj_fplsl, const T* traj_fplsn,
@@ -428,16 +465,20 @@ int ad_masked_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t 
     if (evap && !(p->LEVAPLS2 || p->LDRAIN1D))
         return fail(CLOUDSC2_E_UNSUPPORTED, "%s: neither LEVAPLS2 nor LDRAIN1D is set: without the evaporation block there is "
                     "no precipitation cover to carry - use cloudsc2_ad_%s", fn,
-                    multi ? (step ? "multi_step" : "multi") : (step ? "step" : "masked"));
+                    ens ? (step ? "step_ens" : "ens") : multi ? (step ? "multi_step" : "multi") : (step ? "step" : "masked"));
     if (!(dt > 0.0)) return fail(CLOUDSC2_E_ARG, "%s: dt=%g must be > 0", fn, dt);
     if (p->NLEV != nz) return fail(CLOUDSC2_E_ARG, "%s: NLEV=%d != nz=%d", fn, p->NLEV, nz);
     if (step)
         if (int rc = check_step_saturation(fn, p)) return rc;
     if (int rc = check_masked_size<T>(fn, nz, ls)) return rc;
+    if (evap && ens)
+        if (int rc = check_cover_disjoint<T>(fn, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn, out_adj, cover,
+                                             nmem, ms))
+            return rc;
     if (evap)
         return launched(fn, cs2::launch_ad_cover<T>(*p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn, out_adj, dt,
                                                     static_cast<hipStream_t>(stream), step, multi ? ndir : 0, in_ds, out_ds, cover,
-                                                    cover_ready != 0));
+                                                    cover_ready != 0, ens ? nmem : 0, ms));
     if (multi)
         return launched(fn, cs2::launch_ad_dirs<T>(*p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn, out_adj,
                                                    dt, static_cast<hipStream_t>(stream), step, ndir, in_ds, out_ds));
@@ -832,6 +873,27 @@ int32_t cloudsc2_ad_multi_step_f32(const Cloudsc2Params* p, int32_t nx, int32_t 
                                  traj_fplsn, out_adj, dt, stream, true, true, ndir, in_ds, out_ds, false, 0, 0, true, cover,   \
                                  cover_ready);                                                                                 \
     }
+// ---- their ensemble forms: the single evaporation entry's arguments + (nmem, member_stride)
+#define CS2_EVAP_ENS_ENTRIES(SFX, T)                                                                                            \
+    int32_t cloudsc2_ad_evap_ens_##SFX(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,        \
+                                       const T* const* in_adj, const T* zero_line, const T* eta, const T* traj_fplsl,          \
+                                       const T* traj_fplsn, T* const* out_adj, double dt, T* cover, int32_t cover_ready,       \
+                                       void* stream, int32_t nmem, int64_t ms) {                                               \
+        return ad_masked_impl<T>("cloudsc2_ad_evap_ens_" #SFX, p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl,          \
+                                 traj_fplsn, out_adj, dt, stream, false, false, 0, 0, 0, true, nmem, ms, true, cover,          \
+                                 cover_ready);                                                                                 \
+    }                                                                                                                          \
+    int32_t cloudsc2_ad_evap_step_ens_##SFX(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,   \
+                                            const T* const* in_adj, const T* zero_line, const T* eta, const T* traj_fplsl,     \
+                                            const T* traj_fplsn, T* const* out_adj, double dt, T* cover, int32_t cover_ready,  \
+                                            void* stream, int32_t nmem, int64_t ms) {                                          \
+        return ad_masked_impl<T>("cloudsc2_ad_evap_step_ens_" #SFX, p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl,     \
+                                 traj_fplsn, out_adj, dt, stream, true, false, 0, 0, 0, true, nmem, ms, true, cover,           \
+                                 cover_ready);                                                                                 \
+    }
+CS2_EVAP_ENS_ENTRIES(f64, double)
+CS2_EVAP_ENS_ENTRIES(f32, float)
+#undef CS2_EVAP_ENS_ENTRIES
 CS2_EVAP_ENTRIES(f64, double)
 CS2_EVAP_ENTRIES(f32, float)
 #undef CS2_EVAP_ENTRIES

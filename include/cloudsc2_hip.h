@@ -466,8 +466,8 @@ int32_t cloudsc2_ad_multi_step_f32(const Cloudsc2Params* p, int32_t nx, int32_t 
  * LDS of the multi entries: the level table; six carry words per direction (6 * ndir * 256 elements: two pairs of the
  * backward carry are kept as their sums, which is exact); parked trajectory words, 34 * 256 elements in fp32 and 30 * 256
  * in fp64 (there the level's trajectory would not fit the registers across the direction loop).  ndir = 8, nz = 137: about
- * 158 KB in fp64, 83 KB in fp32; beyond 160 KB the call is refused (fp64: ndir = 8 beyond nz = 255).  Ensembles have no
- * such entry.
+ * 158 KB in fp64, 83 KB in fp32; beyond 160 KB the call is refused (fp64: ndir = 8 beyond nz = 255).  The
+ * ensemble forms of the two single entries are declared at the end of this file ("ENSEMBLES WITH THE EVAPORATION BLOCK").
  * Words moved per level and column: sweep 1 reads 16 (step: 15) + 2 and writes 1; sweep 2 moves 16 (15) + 2 + 1 + ndir *
  * ((present in_adj) + (wanted out_adj)).  Forcing on the four tendencies, adjoints of t, q, ql, qi, one direction:
  * 19 + 19 + 8 = 46 against 70 of cloudsc2_ad; eight directions: 38 + 64 = 102 against 560.  With cover_ready sweep 1's 19
@@ -585,6 +585,50 @@ int32_t cloudsc2_ad_step_ens_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz
                                  const float* const* in, const float* const* in_adj, const float* zero_line,
                                  const float* eta, const float* traj_fplsl, const float* traj_fplsn,
                                  float* const* out_adj, double dt, void* stream, int32_t nmem, int64_t member_stride);
+
+/* ---- ENSEMBLES WITH THE EVAPORATION BLOCK (BUILD EXTENSIONS): cloudsc2_ad_evap_* and cloudsc2_ad_evap_step_* for `nmem`
+ * members in one launch, one cotangent per member.  Arguments are those of the single entry, `cover` and `cover_ready` in
+ * front of `stream` included, followed by `nmem` and `member_stride` as in every ensemble entry above:
+ *       ensemble entry               single entry               kernel reported by cloudsc2_last_kernel
+ *       cloudsc2_ad_evap_ens_*       cloudsc2_ad_evap_*         cs2::ad_cover_ens_kernel
+ *       cloudsc2_ad_evap_step_ens_*  cloudsc2_ad_evap_step_*    cs2::ad_cover_ens_step_kernel
+ * Everything is batched, `cover` too: it is member-major with the call's lev_stride and the call's ONE member_stride, member
+ * m's level k = the cover entering level k of member m; level nz of no member is touched.  `eta`, `dt`, the switches and the
+ * zero line are shared; an absent forcing is read from the zero line by every member.  cover_ready holds for all members.
+ * One workgroup serves one column block of one member and runs both sweeps for its columns: the grid is nmem * ceil(nx / 256)
+ * workgroups, none depends on another.  The member's base is added to the field pointers as a 64-bit scalar, the lanes' byte
+ * offsets stay 32-bit; elements between the members are not touched.
+ * Refused on the host, before any launch - what the single evaporation entries and what the ensemble adjoints refuse:
+ * cover == NULL, nmem < 1, member_stride < (nz+1) * lev_stride (CLOUDSC2_E_ARG); a `cover` of which any member overlaps any
+ * member of another field of the call, the zero line or `eta` (CLOUDSC2_E_ARG: sweep 1 writes it while the other is read);
+ * NEITHER LEVAPLS2 nor LDRAIN1D (CLOUDSC2_E_UNSUPPORTED; the message names cloudsc2_ad_ens_* / cloudsc2_ad_step_ens_*);
+ * the step entry without LPHYLIN (CLOUDSC2_E_UNSUPPORTED) or with out_adj[NL_IN_QSAT] (CLOUDSC2_E_ARG); no adjoint wanted
+ * (CLOUDSC2_E_ARG); one member of a field at 4 GiB or more, or more than 2^31 - 1 workgroups (CLOUDSC2_E_UNSUPPORTED).
+ * nx == 0 is a successful no-op.
+ * Words moved per level and column: the single entry's, per member - sweep 1 reads 16 (step: 15) + 2 and writes 1; sweep 2
+ * moves 16 (15) + 2 + 1 + (present in_adj) + (wanted out_adj).  With cover_ready sweep 1's 19 (18) drop out.
+ * Every member of every written adjoint and of `cover` equals what the single entry writes for that member alone, to
+ * rounding (each kernel contracts the level functions itself).  Members times directions in one call: no such entry. */
+int32_t cloudsc2_ad_evap_ens_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                 const double* const* in, const double* const* in_adj, const double* zero_line,
+                                 const double* eta, const double* traj_fplsl, const double* traj_fplsn,
+                                 double* const* out_adj, double dt, double* cover, int32_t cover_ready, void* stream,
+                                 int32_t nmem, int64_t member_stride);
+int32_t cloudsc2_ad_evap_ens_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                 const float* const* in, const float* const* in_adj, const float* zero_line,
+                                 const float* eta, const float* traj_fplsl, const float* traj_fplsn,
+                                 float* const* out_adj, double dt, float* cover, int32_t cover_ready, void* stream,
+                                 int32_t nmem, int64_t member_stride);
+int32_t cloudsc2_ad_evap_step_ens_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                      const double* const* in, const double* const* in_adj, const double* zero_line,
+                                      const double* eta, const double* traj_fplsl, const double* traj_fplsn,
+                                      double* const* out_adj, double dt, double* cover, int32_t cover_ready, void* stream,
+                                      int32_t nmem, int64_t member_stride);
+int32_t cloudsc2_ad_evap_step_ens_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                      const float* const* in, const float* const* in_adj, const float* zero_line,
+                                      const float* eta, const float* traj_fplsl, const float* traj_fplsn,
+                                      float* const* out_adj, double dt, float* cover, int32_t cover_ready, void* stream,
+                                      int32_t nmem, int64_t member_stride);
 
 #ifdef __cplusplus
 }
