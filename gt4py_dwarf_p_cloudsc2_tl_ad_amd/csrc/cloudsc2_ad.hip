@@ -414,43 +414,38 @@ ad_ens_step_kernel(const ADEnsArgs<T> A) {
 }
 
 
-// The caller (cloudsc2_capi.hip) has refused the evaporation switches and fields of 4 GiB and more.  `step`: ad_step_kernel
-// (in[NL_IN_QSAT] is not read, out_adj[NL_IN_QSAT] is NULL).  nmem > 0: the ensemble form (ad_ens_kernel /
+// The caller (cloudsc2_capi.hip) has refused the evaporation switches and fields of 4 GiB and more.  kStep: ad_step_kernel
+// (in[NL_IN_QSAT] is not read, out_adj[NL_IN_QSAT] is NULL).  kEns: the ensemble form (ad_ens_kernel /
 // ad_ens_step_kernel) - every field pointer is member 0's, member m lies m * ms elements behind it; the caller has checked
 // nmem and ms.
 template <typename T>
-int launch_ad_masked(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* const* in, const T* const* in_adj,
-                     const T* zero, const T* eta, const T* traj_l, const T* traj_n, T* const* out_adj, double dt,
-                     hipStream_t stream, bool step, int nmem, int64_t ms) {
-    if (evap_on(p) || !fits_u32_offsets<T>(nz, ls)) return -2;
+int launch_ad_masked(const ADCall<T>& c) {
+    if (evap_on(*c.p) || !fits_u32_offsets<T>(c.nz, c.ls)) return -2;
+    const bool step = c.is(kStep);
+    const int nmem = c.is(kEns) ? c.members.nmem : 0;
     ADEnsArgs<T> ens;
-    ADMaskedArgs<T>& args = ens.m;
-    fill_ad_masked_args<T>(args, p, nx, nz, ls, in, in_adj, zero, eta, traj_l, traj_n, out_adj, dt);
-    const int bpm = (nx + kColBlock - 1) / kColBlock;
+    const ADMaskedArgs<T>& args = ens.m = fill_ad_masked_args<T>(c);
+    const int bpm = (c.nx + kColBlock - 1) / kColBlock;
     const dim3 grid(bpm);
-    const size_t smem = 2 * size_t(nz + 1) * sizeof(T) + (kADPark<T> ? size_t(CS2_AD_PARK_COUNT) * kColBlock * sizeof(T) : 0);
+    const size_t smem = 2 * size_t(c.nz + 1) * sizeof(T) + (kADPark<T> ? size_t(CS2_AD_PARK_COUNT) * kColBlock * sizeof(T) : 0);
     if (nmem > 0 && int64_t(nmem) * bpm > kMaxGrid) return -2;
-    ens.g.ms = ms; ens.g.bpm = bpm;
+    ens.g.ms = c.members.ms; ens.g.bpm = bpm;
     const dim3 egrid(unsigned(nmem > 0 ? nmem : 1) * unsigned(bpm));
     return with_flags(
         [&](auto REG, auto FIX, auto STEP, auto ENS) {
             if constexpr (ENS) {
                 constexpr auto kern = STEP ? ad_ens_step_kernel<T, REG, FIX> : ad_ens_kernel<T, REG, FIX>;
-                return launch_tail<kern>({egrid, smem, stream, step ? "cs2::ad_ens_step_kernel" : "cs2::ad_ens_kernel"}, ens);
+                return launch_tail<kern>({egrid, smem, c.stream, step ? "cs2::ad_ens_step_kernel" : "cs2::ad_ens_kernel"}, ens);
             } else {
                 constexpr auto kern = STEP ? ad_step_kernel<T, REG, FIX> : ad_masked_kernel<T, REG, FIX>;
-                return launch_tail<kern>({grid, smem, stream, step ? "cs2::ad_step_kernel" : "cs2::ad_masked_kernel"}, args);
+                return launch_tail<kern>({grid, smem, c.stream, step ? "cs2::ad_step_kernel" : "cs2::ad_masked_kernel"}, args);
             }
         },
-        p.LREGCL != 0, p.AD_TRAJ_FIX != 0, step, nmem > 0);
+        c.p->LREGCL != 0, c.p->AD_TRAJ_FIX != 0, step, nmem > 0);
 }
 
-template int launch_ad_masked<double>(const Cloudsc2Params&, int, int, int64_t, const double* const*, const double* const*,
-                                      const double*, const double*, const double*, const double*, double* const*, double,
-                                      hipStream_t, bool, int, int64_t);
-template int launch_ad_masked<float>(const Cloudsc2Params&, int, int, int64_t, const float* const*, const float* const*,
-                                     const float*, const float*, const float*, const float*, float* const*, double,
-                                     hipStream_t, bool, int, int64_t);
+template int launch_ad_masked<double>(const ADCall<double>&);
+template int launch_ad_masked<float>(const ADCall<float>&);
 
 // ------------------------------------------------------------------------------------------------------------------
 // Masked adjoint over `ndir` DIRECTIONS on one trajectory (BUILD EXTENSION, C ABI cloudsc2_ad_multi_* /
@@ -609,32 +604,28 @@ ad_dirs_step_kernel(const ADDirsArgs<T> A) {
 // launch_ad_masked for `ndir` directions (1 <= ndir <= kADMaxDirs, checked by the caller): in_adj[f] / out_adj[f] point at
 // direction 0; the strides are in elements
 template <typename T>
-int launch_ad_dirs(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* const* in, const T* const* in_adj,
-                   const T* zero, const T* eta, const T* traj_l, const T* traj_n, T* const* out_adj, double dt,
-                   hipStream_t stream, bool step, int ndir, int64_t in_ds, int64_t out_ds) {
-    if (evap_on(p) || !fits_u32_offsets<T>(nz, ls)) return -2;
+int launch_ad_dirs(const ADCall<T>& c) {
+    const int ndir = c.dirs.ndir;
+    if (evap_on(*c.p) || !fits_u32_offsets<T>(c.nz, c.ls)) return -2;
     if (ndir < 1 || ndir > kADMaxDirs) return -1;
+    const bool step = c.is(kStep);
     ADDirsArgs<T> args;
-    fill_ad_masked_args<T>(args.m, p, nx, nz, ls, in, in_adj, zero, eta, traj_l, traj_n, out_adj, dt);
-    args.in_ds = in_ds; args.out_ds = out_ds; args.ndir = ndir;
-    const dim3 grid((nx + kColBlock - 1) / kColBlock);
-    const size_t smem = ad_dirs_lds_bytes<T>(nz, ndir);
+    args.m = fill_ad_masked_args<T>(c);
+    args.in_ds = c.dirs.in_ds; args.out_ds = c.dirs.out_ds; args.ndir = ndir;
+    const dim3 grid((c.nx + kColBlock - 1) / kColBlock);
+    const size_t smem = ad_dirs_lds_bytes<T>(c.nz, ndir);
     // device_always: this launcher has looked the device up below 64 KiB of LDS as well since it was written (as
     // launch_tl_dirs does), so a device ordinal beyond kMaxDevices is refused here (-2) where the single-direction
     // launchers still run.  Nothing in the launch needs it; kept so that no call changes its outcome.
     return with_flags(
         [&](auto REG, auto FIX, auto STEP) {
             constexpr auto kern = STEP ? ad_dirs_step_kernel<T, REG, FIX> : ad_dirs_kernel<T, REG, FIX>;
-            return launch_tail<kern>({grid, smem, stream, step ? "cs2::ad_dirs_step_kernel" : "cs2::ad_dirs_kernel", true}, args);
+            return launch_tail<kern>({grid, smem, c.stream, step ? "cs2::ad_dirs_step_kernel" : "cs2::ad_dirs_kernel", true}, args);
         },
-        p.LREGCL != 0, p.AD_TRAJ_FIX != 0, step);
+        c.p->LREGCL != 0, c.p->AD_TRAJ_FIX != 0, step);
 }
 
-template int launch_ad_dirs<double>(const Cloudsc2Params&, int, int, int64_t, const double* const*, const double* const*,
-                                    const double*, const double*, const double*, const double*, double* const*, double,
-                                    hipStream_t, bool, int, int64_t, int64_t);
-template int launch_ad_dirs<float>(const Cloudsc2Params&, int, int, int64_t, const float* const*, const float* const*,
-                                   const float*, const float*, const float*, const float*, float* const*, double,
-                                   hipStream_t, bool, int, int64_t, int64_t);
+template int launch_ad_dirs<double>(const ADCall<double>&);
+template int launch_ad_dirs<float>(const ADCall<float>&);
 
 }  // namespace cs2

@@ -428,57 +428,50 @@ ad_cover_dirs_step_kernel(const ADCoverDirsArgs<T> A) {
 }
 
 // The caller (cloudsc2_capi.hip) has checked every argument: one of the evaporation switches is on, fields below 4 GiB,
-// `cover` not NULL, and with ndir > 0 the direction arguments (the multi-direction kernels; ndir == 0: the single ones).
-// `step`: in[NL_IN_QSAT] is not read, out_adj[NL_IN_QSAT] is NULL.  nmem > 0 (with ndir == 0 only): the ensemble form of the
+// `cover` not NULL, and under kMulti the direction arguments (the multi-direction kernels; without it the single ones).
+// kStep: in[NL_IN_QSAT] is not read, out_adj[NL_IN_QSAT] is NULL.  kEns (without kMulti only): the ensemble form of the
 // single kernels - every field pointer, `cover` included, is member 0's, member m lies m * ms elements behind it; the caller
 // has checked nmem and ms.
 template <typename T>
-int launch_ad_cover(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* const* in, const T* const* in_adj,
-                    const T* zero, const T* eta, const T* traj_l, const T* traj_n, T* const* out_adj, double dt,
-                    hipStream_t stream, bool step, int ndir, int64_t in_ds, int64_t out_ds, T* cover, int cover_ready,
-                    int nmem, int64_t ms) {
-    if (!evap_on(p) || !fits_u32_offsets<T>(nz, ls) || !cover) return -2;
+int launch_ad_cover(const ADCall<T>& c) {
+    const bool step = c.is(kStep);
+    const int ndir = c.is(kMulti) ? c.dirs.ndir : 0, nmem = c.is(kEns) ? c.members.nmem : 0;
+    if (!evap_on(*c.p) || !fits_u32_offsets<T>(c.nz, c.ls) || !c.cover.cover) return -2;
     if (ndir < 0 || ndir > kADMaxDirs || (ndir > 0 && nmem > 0)) return -1;
     ADCoverDirsArgs<T> dargs;
     ADCoverEnsArgs<T> eargs;
     ADCoverArgs<T>& sargs = eargs.c;
-    ADMaskedArgs<T>& m = ndir > 0 ? dargs.d.m : sargs.m;
-    fill_ad_masked_args<T>(m, p, nx, nz, ls, in, in_adj, zero, eta, traj_l, traj_n, out_adj, dt);
-    m.kc = make_nlk<T>(p, dt, true);
-    dargs.d.in_ds = in_ds; dargs.d.out_ds = out_ds; dargs.d.ndir = ndir;
-    dargs.cover = sargs.cover = cover;
-    dargs.cover_ready = sargs.cover_ready = cover_ready;
-    const int bpm = (nx + kColBlock - 1) / kColBlock;
+    (ndir > 0 ? dargs.d.m : sargs.m) = fill_ad_masked_args<T>(c);
+    dargs.d.in_ds = c.dirs.in_ds; dargs.d.out_ds = c.dirs.out_ds; dargs.d.ndir = ndir;
+    dargs.cover = sargs.cover = c.cover.cover;
+    dargs.cover_ready = sargs.cover_ready = c.cover.cover_ready != 0;
+    const int bpm = (c.nx + kColBlock - 1) / kColBlock;
     if (nmem > 0 && int64_t(nmem) * bpm > kMaxGrid) return -2;
-    eargs.g.ms = ms; eargs.g.bpm = bpm;
+    eargs.g.ms = c.members.ms; eargs.g.bpm = bpm;
     const dim3 grid(unsigned(nmem > 0 ? nmem : 1) * unsigned(bpm));
-    const size_t smem = ndir > 0 ? ad_cover_dirs_lds_bytes<T>(nz, ndir)
-                                 : 2 * size_t(nz + 1) * sizeof(T) + (kADPark<T> ? size_t(CS2_AD_PARK_COUNT) * kColBlock * sizeof(T) : 0);
+    const size_t smem = ndir > 0 ? ad_cover_dirs_lds_bytes<T>(c.nz, ndir)
+                                 : 2 * size_t(c.nz + 1) * sizeof(T) + (kADPark<T> ? size_t(CS2_AD_PARK_COUNT) * kColBlock * sizeof(T) : 0);
     return with_flags(
         [&](auto REG, auto FIX, auto STEP, auto DIRS, auto ENS) {
             if constexpr (DIRS && ENS) {
                 return -1;   // refused above: no such instantiation
             } else if constexpr (ENS) {
                 constexpr auto kern = STEP ? ad_cover_ens_step_kernel<T, REG, FIX> : ad_cover_ens_kernel<T, REG, FIX>;
-                return launch_tail<kern>({grid, smem, stream, step ? "cs2::ad_cover_ens_step_kernel" : "cs2::ad_cover_ens_kernel"},
+                return launch_tail<kern>({grid, smem, c.stream, step ? "cs2::ad_cover_ens_step_kernel" : "cs2::ad_cover_ens_kernel"},
                                          eargs);
             } else if constexpr (DIRS) {
                 constexpr auto kern = STEP ? ad_cover_dirs_step_kernel<T, REG, FIX> : ad_cover_dirs_kernel<T, REG, FIX>;
-                return launch_tail<kern>({grid, smem, stream, step ? "cs2::ad_cover_dirs_step_kernel" : "cs2::ad_cover_dirs_kernel"},
+                return launch_tail<kern>({grid, smem, c.stream, step ? "cs2::ad_cover_dirs_step_kernel" : "cs2::ad_cover_dirs_kernel"},
                                          dargs);
             } else {
                 constexpr auto kern = STEP ? ad_cover_step_kernel<T, REG, FIX> : ad_cover_kernel<T, REG, FIX>;
-                return launch_tail<kern>({grid, smem, stream, step ? "cs2::ad_cover_step_kernel" : "cs2::ad_cover_kernel"}, sargs);
+                return launch_tail<kern>({grid, smem, c.stream, step ? "cs2::ad_cover_step_kernel" : "cs2::ad_cover_kernel"}, sargs);
             }
         },
-        p.LREGCL != 0, p.AD_TRAJ_FIX != 0, step, ndir > 0, nmem > 0);
+        c.p->LREGCL != 0, c.p->AD_TRAJ_FIX != 0, step, ndir > 0, nmem > 0);
 }
 
-template int launch_ad_cover<double>(const Cloudsc2Params&, int, int, int64_t, const double* const*, const double* const*,
-                                     const double*, const double*, const double*, const double*, double* const*, double,
-                                     hipStream_t, bool, int, int64_t, int64_t, double*, int, int, int64_t);
-template int launch_ad_cover<float>(const Cloudsc2Params&, int, int, int64_t, const float* const*, const float* const*,
-                                    const float*, const float*, const float*, const float*, float* const*, double,
-                                    hipStream_t, bool, int, int64_t, int64_t, float*, int, int, int64_t);
+template int launch_ad_cover<double>(const ADCall<double>&);
+template int launch_ad_cover<float>(const ADCall<float>&);
 
 }  // namespace cs2

@@ -4,7 +4,7 @@
 // launchers end in cloudsc2_common.hpp's launch_tail).  Line numbers refer to the reference files named at the top of
 // cloudsc2_ad.hip.
 #pragma once
-#include "cloudsc2_common.hpp"
+#include "cloudsc2_launch.hpp"
 
 #ifndef CS2_AD_DIAG
 #define CS2_AD_DIAG 0   // diagnostics only (wrong results): 1 = the kernel's memory traffic without the physics
@@ -954,27 +954,29 @@ __device__ __forceinline__ void ad_store_masked(const FP& F, uint32_t want, uint
 // The arguments of a masked adjoint call as the kernels take them (launch_ad_masked; launch_ad_dirs for direction 0):
 // in_adj[f] == nullptr: forcing f is zero everywhere (read from `zero`) and not in `have`; out_adj[f] == nullptr: adjoint f
 // is not in `want`, not written.
+// kc follows the evaporation switches: off under launch_ad_masked / launch_ad_dirs, on under launch_ad_cover (each refuses
+// the other case before it gets here).
 template <typename T>
-static void fill_ad_masked_args(ADMaskedArgs<T>& args, const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* const* in,
-                                const T* const* in_adj, const T* zero, const T* eta, const T* traj_l, const T* traj_n,
-                                T* const* out_adj, double dt) {
-    args.e = make_ext<T>(p);
-    args.kc = make_nlk<T>(p, dt, false);
+static ADMaskedArgs<T> fill_ad_masked_args(const ADCall<T>& c) {
+    ADMaskedArgs<T> args;
+    args.e = make_ext<T>(*c.p);
+    args.kc = make_nlk<T>(*c.p, c.dt, evap_on(*c.p));
     args.xk = make_expk<T>();
-    args.nx = nx; args.nz = nz; args.ls = ls;
+    args.nx = c.nx; args.nz = c.nz; args.ls = c.ls;
     args.have = args.want = 0;
-    args.in = pack_ptrs<CPtrs<T, NL_NUM_IN>>(in);
-    args.oadj = pack_ptrs<MPtrs<T, NL_NUM_IN>>(out_adj);
+    args.in = pack_ptrs<CPtrs<T, NL_NUM_IN>>(c.in);
+    args.oadj = pack_ptrs<MPtrs<T, NL_NUM_IN>>(c.out_adj);
     for (int i = 0; i < NL_NUM_IN; ++i)
-        if (out_adj[i]) args.want |= 1u << i;
+        if (c.out_adj[i]) args.want |= 1u << i;
     for (int i = 0; i < NL_NUM_OUT; ++i) {
-        args.adj.p[i] = in_adj[i] ? in_adj[i] : zero;
-        if (in_adj[i]) args.have |= 1u << i;
+        args.adj.p[i] = c.in_adj[i] ? c.in_adj[i] : c.zero;
+        if (c.in_adj[i]) args.have |= 1u << i;
     }
-    args.eta = eta;
-    args.dt = static_cast<T>(dt);
-    args.traj_l = traj_l;
-    args.traj_n = traj_n;
+    args.eta = c.eta;
+    args.dt = static_cast<T>(c.dt);
+    args.traj_l = c.traj_l;
+    args.traj_n = c.traj_n;
+    return args;
 }
 
 // ---- the multi-direction adjoint's arguments (see ad_dirs_sweep in cloudsc2_ad.hip)

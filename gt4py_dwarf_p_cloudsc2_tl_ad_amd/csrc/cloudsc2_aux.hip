@@ -5,7 +5,7 @@
 //   perturbed_state  /root/reference/src/cloudsc2_gt4py/physics/common/_stencils/perturbed_state.py:75-91
 // All three are pure streaming kernels: grid.y walks the levels, grid.x the columns, so each wave
 // issues fully coalesced row segments of the [level][column] storage.
-#include "cloudsc2_common.hpp"
+#include "cloudsc2_launch.hpp"
 
 namespace cs2 {
 

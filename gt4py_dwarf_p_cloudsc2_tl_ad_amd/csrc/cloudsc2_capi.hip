@@ -4,58 +4,7 @@
 #include <cstdarg>
 #include <cstdio>
 
-#include "cloudsc2_common.hpp"
-
-namespace cs2 {
-template <typename T>
-int launch_nl(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T*, T* const*, double, hipStream_t,
-              const T* const*, double, T*, double*);
-template <typename T>
-int launch_nl_taylor_multi(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T* const*, int, const double*,
-                           const T*, const T* const*, double*, double, hipStream_t, double);
-int field_sums_blocks(int, int);
-int column_dots_chunks(int);
-template <typename T>
-int launch_field_sums(int, int, int64_t, int, const T* const*, const T* const*, double*, hipStream_t);
-template <typename T>
-int launch_column_dots(int, int, int64_t, int, const T* const*, const T* const*, double*, int, hipStream_t);
-template <typename T>
-int launch_tl(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T* const*, const T*, T* const*,
-              T* const*, double, hipStream_t, double);
-template <typename T>
-int launch_ad(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T* const*, const T*, T* const*,
-              T* const*, double, hipStream_t, const T* traj_l = nullptr, const T* traj_n = nullptr);
-template <typename T>
-int launch_tl_masked(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T* const*, const T*, const T*,
-                     T* const*, T* const*, double, hipStream_t, bool step, int nmem = 0, int64_t ms = 0);
-template <typename T>
-int launch_tl_dirs(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T* const*, const T*, const T*, T* const*,
-                   T* const*, double, hipStream_t, bool step, int ndir, int64_t in_ds, int64_t out_ds);
-template <typename T>
-int launch_ad_masked(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T* const*, const T*, const T*,
-                     const T*, const T*, T* const*, double, hipStream_t, bool step, int nmem = 0, int64_t ms = 0);
-template <typename T>
-int launch_ad_dirs(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T* const*, const T*, const T*, const T*,
-                   const T*, T* const*, double, hipStream_t, bool step, int ndir, int64_t in_ds, int64_t out_ds);
-template <typename T>
-int launch_ad_cover(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T* const*, const T*, const T*, const T*,
-                    const T*, T* const*, double, hipStream_t, bool step, int ndir, int64_t in_ds, int64_t out_ds, T* cover,
-                    int cover_ready, int nmem = 0, int64_t ms = 0);
-template <typename T>
-int launch_nl_ens(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T*, T* const*, double, hipStream_t, T*,
-                  int nmem, int64_t ms);
-template <typename T>
-int launch_saturation(const Cloudsc2Params&, int, int, int64_t, const T*, const T*, T*, hipStream_t);
-template <typename T>
-int launch_saturation_tl(const Cloudsc2Params&, int, int, int64_t, const T*, const T*, const T*, const T*, T*, T*,
-                         hipStream_t);
-template <typename T>
-int launch_saturation_ad(const Cloudsc2Params&, int, int, int64_t, const T*, const T*, const T*, T*, T*, int, hipStream_t);
-template <typename T>
-int launch_increment(const Cloudsc2Params&, int, int, int64_t, const T* const*, T* const*, double, hipStream_t);
-template <typename T>
-int launch_perturb(int, int, int64_t, const T* const*, const T* const*, T* const*, double, hipStream_t);
-}  // namespace cs2
+#include "cloudsc2_launch.hpp"
 
 namespace {
 
@@ -272,7 +221,8 @@ int ad_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t nz, int
     if (p->ICALL != 0) return fail(CLOUDSC2_E_UNSUPPORTED, "%s: ICALL=%d unsupported", fn, p->ICALL);
     if (!(dt > 0.0)) return fail(CLOUDSC2_E_ARG, "%s: dt=%g must be > 0", fn, dt);
     if (p->NLEV != nz) return fail(CLOUDSC2_E_ARG, "%s: NLEV=%d != nz=%d", fn, p->NLEV, nz);
-    return launched(fn, cs2::launch_ad<T>(*p, nx, nz, ls, in, in_adj, eta, out, out_adj, dt, static_cast<hipStream_t>(stream)));
+    return launched(fn, cs2::launch_ad<T>(*p, nx, nz, ls, in, in_adj, eta, out, out_adj, dt, static_cast<hipStream_t>(stream),
+                                          nullptr, nullptr));
 }
 
 template <typename T>
@@ -342,57 +292,52 @@ int check_step_saturation(const char* fn, const Cloudsc2Params* p) {
 }
 
 // the direction arguments of the cloudsc2_tl_multi_* / cloudsc2_ad_multi_* entries
-int check_dirs(const char* fn, int32_t nz, int64_t ls, int32_t ndir, int64_t in_ds, int64_t out_ds,
-               int max_dirs = CLOUDSC2_TL_MAX_DIRS, const char* max_name = "CLOUDSC2_TL_MAX_DIRS") {
-    if (ndir < 1 || ndir > max_dirs)
-        return fail(CLOUDSC2_E_ARG, "%s: ndir=%d outside [1, %d] (%s)", fn, ndir, max_dirs, max_name);
+int check_dirs(const char* fn, int32_t nz, int64_t ls, const cs2::CallDirs& d, int max_dirs, const char* max_name) {
+    if (d.ndir < 1 || d.ndir > max_dirs)
+        return fail(CLOUDSC2_E_ARG, "%s: ndir=%d outside [1, %d] (%s)", fn, d.ndir, max_dirs, max_name);
     const int64_t field = int64_t(nz + 1) * ls;
-    if (in_ds < field || out_ds < field)
+    if (d.in_ds < field || d.out_ds < field)
         return fail(CLOUDSC2_E_ARG, "%s: in_dir_stride=%lld / out_dir_stride=%lld < (nz+1) * lev_stride = %lld: the "
-                    "directions of a field would overlap", fn, (long long)in_ds, (long long)out_ds, (long long)field);
+                    "directions of a field would overlap", fn, (long long)d.in_ds, (long long)d.out_ds, (long long)field);
     return 0;
 }
 
-// `step`: the cloudsc2_tl_step_* entry (tl_step_kernel); `ndir` > 0: the cloudsc2_tl_multi_* entries (tl_dirs_kernel);
-// `ens`: the cloudsc2_tl_ens_* / cloudsc2_tl_step_ens_* entries (tl_ens_kernel / tl_ens_step_kernel)
+// The form of the entry (cs2::CallForm) - kStep: the cloudsc2_tl_step_* entry (tl_step_kernel); kMulti: the
+// cloudsc2_tl_multi_* entries (tl_dirs_kernel); kEns: the cloudsc2_tl_ens_* / cloudsc2_tl_step_ens_* entries (tl_ens_kernel /
+// tl_ens_step_kernel)
 template <typename T>
-int tl_masked_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,
-                   const T* const* in_i, const T* zero_line, const T* eta, T* const* out, T* const* out_i, double dt,
-                   void* stream, bool step = false, bool multi = false, int32_t ndir = 0, int64_t in_ds = 0,
-                   int64_t out_ds = 0, bool ens = false, int32_t nmem = 0, int64_t ms = 0) {
-    if (int rc = check_common(fn, p, nx, nz, ls)) return rc;
+int tl_masked_impl(const char* fn, const cs2::TLCall<T>& c) {
+    const bool step = c.is(cs2::kStep), multi = c.is(cs2::kMulti);
+    const Cloudsc2Params* const p = c.p;
+    if (int rc = check_common(fn, p, c.nx, c.nz, c.ls)) return rc;
     if (multi)
-        if (int rc = check_dirs(fn, nz, ls, ndir, in_ds, out_ds)) return rc;
-    if (int rc = check_members<T>(fn, ens, nx, nz, ls, nmem, ms)) return rc;
-    if (nx == 0) return CLOUDSC2_OK;
-    if (int rc = step ? check_step_trajectory(fn, in) : check_ptrs(fn, "in", in, NL_NUM_IN)) return rc;
-    if (step && in_i && in_i[NL_IN_QSAT])
+        if (int rc = check_dirs(fn, c.nz, c.ls, c.dirs, CLOUDSC2_TL_MAX_DIRS, "CLOUDSC2_TL_MAX_DIRS")) return rc;
+    if (int rc = check_members<T>(fn, c.is(cs2::kEns), c.nx, c.nz, c.ls, c.members.nmem, c.members.ms)) return rc;
+    if (c.nx == 0) return CLOUDSC2_OK;
+    if (int rc = step ? check_step_trajectory(fn, c.in) : check_ptrs(fn, "in", c.in, NL_NUM_IN)) return rc;
+    if (step && c.in_i && c.in_i[NL_IN_QSAT])
         return fail(CLOUDSC2_E_ARG, "%s: in_i[NL_IN_QSAT] (in_i[%d]) must be NULL: the qsat perturbation is formed in the "
                     "kernel from in_i[NL_IN_T] and in_i[NL_IN_AP] (use cloudsc2_tl_masked for an independent one)", fn,
                     NL_IN_QSAT);
-    if (step && in_i && !zero_line) {       // the one NULL entry that needs no zero line: it is not read at all
+    if (step && c.in_i && !c.zero) {       // the one NULL entry that needs no zero line: it is not read at all
         for (int i = 0; i < NL_NUM_IN; ++i)
-            if (!in_i[i] && i != NL_IN_QSAT)
+            if (!c.in_i[i] && i != NL_IN_QSAT)
                 return fail(CLOUDSC2_E_ARG, "%s: in_i[%d] is NULL (a zero field) but zero_line is NULL too", fn, i);
-    } else if (int rc = check_masked_inputs(fn, "in_i", in_i, NL_NUM_IN, zero_line)) {
+    } else if (int rc = check_masked_inputs(fn, "in_i", c.in_i, NL_NUM_IN, c.zero)) {
         return rc;
     }
-    if (out)
-        if (int rc = check_ptrs(fn, "out (all ten entries, or the array itself NULL)", const_cast<const T* const*>(out), NL_NUM_OUT))
+    if (c.out)
+        if (int rc = check_ptrs(fn, "out (all ten entries, or the array itself NULL)", const_cast<const T* const*>(c.out), NL_NUM_OUT))
             return rc;
-    if (int rc = check_masked_outputs(fn, "out_i", out_i, NL_NUM_OUT)) return rc;
-    if (!eta) return fail(CLOUDSC2_E_ARG, "%s: eta is NULL", fn);
+    if (int rc = check_masked_outputs(fn, "out_i", c.out_i, NL_NUM_OUT)) return rc;
+    if (!c.eta) return fail(CLOUDSC2_E_ARG, "%s: eta is NULL", fn);
     if (p->ICALL != 0) return fail(CLOUDSC2_E_UNSUPPORTED, "%s: ICALL=%d unsupported", fn, p->ICALL);
-    if (!(dt > 0.0)) return fail(CLOUDSC2_E_ARG, "%s: dt=%g must be > 0", fn, dt);
-    if (p->NLEV != nz) return fail(CLOUDSC2_E_ARG, "%s: NLEV=%d != nz=%d", fn, p->NLEV, nz);
+    if (!(c.dt > 0.0)) return fail(CLOUDSC2_E_ARG, "%s: dt=%g must be > 0", fn, c.dt);
+    if (p->NLEV != c.nz) return fail(CLOUDSC2_E_ARG, "%s: NLEV=%d != nz=%d", fn, p->NLEV, c.nz);
     if (step)
         if (int rc = check_step_saturation(fn, p)) return rc;
-    if (int rc = check_masked_size<T>(fn, nz, ls)) return rc;
-    if (multi)
-        return launched(fn, cs2::launch_tl_dirs<T>(*p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt,
-                                                   static_cast<hipStream_t>(stream), step, ndir, in_ds, out_ds));
-    return launched(fn, cs2::launch_tl_masked<T>(*p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt,
-                                                 static_cast<hipStream_t>(stream), step, ens ? nmem : 0, ms));
+    if (int rc = check_masked_size<T>(fn, c.nz, c.ls)) return rc;
+    return launched(fn, multi ? cs2::launch_tl_dirs<T>(c) : cs2::launch_tl_masked<T>(c));
 }
 
 // The evaporation ensemble entries: sweep 1 WRITES `cover` while every other field of the call is read (or written by sweep
@@ -408,54 +353,52 @@ bool member_ranges_overlap(const void* a, int64_t ea, int64_t na, const void* b,
 }
 
 template <typename T>
-int check_cover_disjoint(const char* fn, int32_t nx, int32_t nz, int64_t ls, const T* const* in, const T* const* in_adj,
-                         const T* zero_line, const T* eta, const T* traj_fplsl, const T* traj_fplsn, T* const* out_adj,
-                         const T* cover, int32_t nmem, int64_t ms) {
-    const int64_t ext = (int64_t(nz) * ls + nx) * int64_t(sizeof(T)), sb = ms * int64_t(sizeof(T));
+int check_cover_disjoint(const char* fn, const cs2::ADCall<T>& c) {
+    const int64_t nmem = c.members.nmem;
+    const int64_t ext = (int64_t(c.nz) * c.ls + c.nx) * int64_t(sizeof(T)), sb = c.members.ms * int64_t(sizeof(T));
     const auto hits = [&](const T* f, int64_t ef, int64_t nf) {
-        return f && member_ranges_overlap(cover, ext, nmem, f, ef, nf, sb);
+        return f && member_ranges_overlap(c.cover.cover, ext, nmem, f, ef, nf, sb);
     };
     const auto refuse = [&](const char* what, int i) {
         return fail(CLOUDSC2_E_ARG, "%s: cover overlaps %s[%d] in some member: cover must not share storage with any other "
                     "field of the call", fn, what, i);
     };
     for (int i = 0; i < NL_NUM_IN; ++i) {
-        if (hits(in[i], ext, nmem)) return refuse("in", i);
-        if (hits(out_adj[i], ext, nmem)) return refuse("out_adj", i);
+        if (hits(c.in[i], ext, nmem)) return refuse("in", i);
+        if (hits(c.out_adj[i], ext, nmem)) return refuse("out_adj", i);
     }
     for (int i = 0; i < NL_NUM_OUT; ++i)
-        if (hits(in_adj[i], ext, nmem)) return refuse("in_adj", i);
-    if (hits(traj_fplsl, ext, nmem) || hits(traj_fplsn, ext, nmem)) return refuse("traj_fplsl / traj_fplsn", 0);
-    if (hits(zero_line, 512, 1)) return refuse("zero_line", 0);
-    if (hits(eta, int64_t(nz + 1) * int64_t(sizeof(T)), 1)) return refuse("eta", 0);
+        if (hits(c.in_adj[i], ext, nmem)) return refuse("in_adj", i);
+    if (hits(c.traj_l, ext, nmem) || hits(c.traj_n, ext, nmem)) return refuse("traj_fplsl / traj_fplsn", 0);
+    if (hits(c.zero, 512, 1)) return refuse("zero_line", 0);
+    if (hits(c.eta, int64_t(c.nz + 1) * int64_t(sizeof(T)), 1)) return refuse("eta", 0);
     return 0;
 }
 
-// `step`: the cloudsc2_ad_step_* entry (ad_step_kernel); `multi`: the cloudsc2_ad_multi_* entries (ad_dirs_kernel);
-// `ens`: the cloudsc2_ad_ens_* / cloudsc2_ad_step_ens_* entries (ad_ens_kernel / ad_ens_step_kernel);
-// `evap`: the trajectory adjoints WITH the evaporation block (cloudsc2_ad_evap_* / _step_* / _multi_* / _multi_step_*:
-// ad_cover_kernel and its siblings) - the same checks, the switches required instead of refused, and the caller's cover field;
-// `evap` and `ens`: cloudsc2_ad_evap_ens_* / _step_ens_* (ad_cover_ens_kernel / ad_cover_ens_step_kernel), `cover` batched too.
+// The form of the entry (cs2::CallForm) - kStep: the cloudsc2_ad_step_* entry (ad_step_kernel); kMulti: the
+// cloudsc2_ad_multi_* entries (ad_dirs_kernel); kEns: the cloudsc2_ad_ens_* / cloudsc2_ad_step_ens_* entries (ad_ens_kernel /
+// ad_ens_step_kernel); kEvap: the trajectory adjoints WITH the evaporation block (cloudsc2_ad_evap_* / _step_* / _multi_* /
+// _multi_step_*: ad_cover_kernel and its siblings) - the same checks, the switches required instead of refused, and the
+// caller's cover field; kEvap and kEns: cloudsc2_ad_evap_ens_* / _step_ens_* (ad_cover_ens_kernel / ad_cover_ens_step_kernel),
+// `cover` batched too.
 template <typename T>
-int ad_masked_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,
-                   const T* const* in_adj, const T* zero_line, const T* eta, const T* traj_fplsl, const T* traj_fplsn,
-                   T* const* out_adj, double dt, void* stream, bool step = false, bool multi = false, int32_t ndir = 0,
-                   int64_t in_ds = 0, int64_t out_ds = 0, bool ens = false, int32_t nmem = 0, int64_t ms = 0,
-                   bool evap = false, T* cover = nullptr, int32_t cover_ready = 0) {
-    if (int rc = check_common(fn, p, nx, nz, ls)) return rc;
+int ad_masked_impl(const char* fn, const cs2::ADCall<T>& c) {
+    const bool step = c.is(cs2::kStep), multi = c.is(cs2::kMulti), ens = c.is(cs2::kEns), evap = c.is(cs2::kEvap);
+    const Cloudsc2Params* const p = c.p;
+    if (int rc = check_common(fn, p, c.nx, c.nz, c.ls)) return rc;
     if (multi)
-        if (int rc = check_dirs(fn, nz, ls, ndir, in_ds, out_ds, CLOUDSC2_AD_MAX_DIRS, "CLOUDSC2_AD_MAX_DIRS")) return rc;
-    if (int rc = check_members<T>(fn, ens, nx, nz, ls, nmem, ms)) return rc;
-    if (nx == 0) return CLOUDSC2_OK;
-    if (int rc = step ? check_step_trajectory(fn, in) : check_ptrs(fn, "in", in, NL_NUM_IN)) return rc;
-    if (int rc = check_masked_inputs(fn, "in_adj", in_adj, NL_NUM_OUT, zero_line)) return rc;
-    if (step && out_adj && out_adj[NL_IN_QSAT])
+        if (int rc = check_dirs(fn, c.nz, c.ls, c.dirs, CLOUDSC2_AD_MAX_DIRS, "CLOUDSC2_AD_MAX_DIRS")) return rc;
+    if (int rc = check_members<T>(fn, ens, c.nx, c.nz, c.ls, c.members.nmem, c.members.ms)) return rc;
+    if (c.nx == 0) return CLOUDSC2_OK;
+    if (int rc = step ? check_step_trajectory(fn, c.in) : check_ptrs(fn, "in", c.in, NL_NUM_IN)) return rc;
+    if (int rc = check_masked_inputs(fn, "in_adj", c.in_adj, NL_NUM_OUT, c.zero)) return rc;
+    if (step && c.out_adj && c.out_adj[NL_IN_QSAT])
         return fail(CLOUDSC2_E_ARG, "%s: out_adj[NL_IN_QSAT] (out_adj[%d]) must be NULL: the qsat adjoint is folded into "
                     "out_adj[NL_IN_T] and out_adj[NL_IN_AP] (use cloudsc2_ad_%s to have it stored)", fn, NL_IN_QSAT,
                     evap ? "evap" : "masked");
-    if (int rc = check_masked_outputs(fn, "out_adj", out_adj, NL_NUM_IN)) return rc;
-    if (!eta || !traj_fplsl || !traj_fplsn) return fail(CLOUDSC2_E_ARG, "%s: eta / traj_fplsl / traj_fplsn is NULL", fn);
-    if (evap && !cover)
+    if (int rc = check_masked_outputs(fn, "out_adj", c.out_adj, NL_NUM_IN)) return rc;
+    if (!c.eta || !c.traj_l || !c.traj_n) return fail(CLOUDSC2_E_ARG, "%s: eta / traj_fplsl / traj_fplsn is NULL", fn);
+    if (evap && !c.cover.cover)
         return fail(CLOUDSC2_E_ARG, "%s: cover is NULL (a caller-owned field of nz+1 levels at lev_stride)", fn);
     if (p->ICALL != 0) return fail(CLOUDSC2_E_UNSUPPORTED, "%s: ICALL=%d unsupported", fn, p->ICALL);
     if (!evap && (p->LEVAPLS2 || p->LDRAIN1D))
@@ -466,24 +409,14 @@ int ad_masked_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t 
         return fail(CLOUDSC2_E_UNSUPPORTED, "%s: neither LEVAPLS2 nor LDRAIN1D is set: without the evaporation block there is "
                     "no precipitation cover to carry - use cloudsc2_ad_%s", fn,
                     ens ? (step ? "step_ens" : "ens") : multi ? (step ? "multi_step" : "multi") : (step ? "step" : "masked"));
-    if (!(dt > 0.0)) return fail(CLOUDSC2_E_ARG, "%s: dt=%g must be > 0", fn, dt);
-    if (p->NLEV != nz) return fail(CLOUDSC2_E_ARG, "%s: NLEV=%d != nz=%d", fn, p->NLEV, nz);
+    if (!(c.dt > 0.0)) return fail(CLOUDSC2_E_ARG, "%s: dt=%g must be > 0", fn, c.dt);
+    if (p->NLEV != c.nz) return fail(CLOUDSC2_E_ARG, "%s: NLEV=%d != nz=%d", fn, p->NLEV, c.nz);
     if (step)
         if (int rc = check_step_saturation(fn, p)) return rc;
-    if (int rc = check_masked_size<T>(fn, nz, ls)) return rc;
+    if (int rc = check_masked_size<T>(fn, c.nz, c.ls)) return rc;
     if (evap && ens)
-        if (int rc = check_cover_disjoint<T>(fn, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn, out_adj, cover,
-                                             nmem, ms))
-            return rc;
-    if (evap)
-        return launched(fn, cs2::launch_ad_cover<T>(*p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn, out_adj, dt,
-                                                    static_cast<hipStream_t>(stream), step, multi ? ndir : 0, in_ds, out_ds, cover,
-                                                    cover_ready != 0, ens ? nmem : 0, ms));
-    if (multi)
-        return launched(fn, cs2::launch_ad_dirs<T>(*p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn, out_adj,
-                                                   dt, static_cast<hipStream_t>(stream), step, ndir, in_ds, out_ds));
-    return launched(fn, cs2::launch_ad_masked<T>(*p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn,
-                                                 out_adj, dt, static_cast<hipStream_t>(stream), step, ens ? nmem : 0, ms));
+        if (int rc = check_cover_disjoint<T>(fn, c)) return rc;
+    return launched(fn, evap ? cs2::launch_ad_cover<T>(c) : multi ? cs2::launch_ad_dirs<T>(c) : cs2::launch_ad_masked<T>(c));
 }
 
 template <typename T>
@@ -665,41 +598,6 @@ int32_t cloudsc2_ad_from_trajectory_f32(const Cloudsc2Params* p, int32_t nx, int
     return ad_traj_impl<float>("cloudsc2_ad_from_trajectory_f32", p, nx, nz, ls, in, in_adj, eta, traj_fplsl, traj_fplsn,
                                out_adj, dt, stream);
 }
-int32_t cloudsc2_tl_masked_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const double* const* in,
-                               const double* const* in_i, const double* zero_line, const double* eta, double* const* out,
-                               double* const* out_i, double dt, void* stream) {
-    return tl_masked_impl<double>("cloudsc2_tl_masked_f64", p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt, stream);
-}
-int32_t cloudsc2_tl_masked_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const float* const* in,
-                               const float* const* in_i, const float* zero_line, const float* eta, float* const* out,
-                               float* const* out_i, double dt, void* stream) {
-    return tl_masked_impl<float>("cloudsc2_tl_masked_f32", p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt, stream);
-}
-int32_t cloudsc2_ad_masked_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const double* const* in,
-                               const double* const* in_adj, const double* zero_line, const double* eta,
-                               const double* traj_fplsl, const double* traj_fplsn, double* const* out_adj, double dt,
-                               void* stream) {
-    return ad_masked_impl<double>("cloudsc2_ad_masked_f64", p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl,
-                                  traj_fplsn, out_adj, dt, stream);
-}
-int32_t cloudsc2_ad_masked_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const float* const* in,
-                               const float* const* in_adj, const float* zero_line, const float* eta,
-                               const float* traj_fplsl, const float* traj_fplsn, float* const* out_adj, double dt,
-                               void* stream) {
-    return ad_masked_impl<float>("cloudsc2_ad_masked_f32", p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl,
-                                 traj_fplsn, out_adj, dt, stream);
-}
-int32_t cloudsc2_tl_step_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const double* const* in,
-                             const double* const* in_i, const double* zero_line, const double* eta, double* const* out,
-                             double* const* out_i, double dt, void* stream) {
-    return tl_masked_impl<double>("cloudsc2_tl_step_f64", p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt, stream, true);
-}
-int32_t cloudsc2_ad_step_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const double* const* in,
-                             const double* const* in_adj, const double* zero_line, const double* eta, const double* traj_fplsl,
-                             const double* traj_fplsn, double* const* out_adj, double dt, void* stream) {
-    return ad_masked_impl<double>("cloudsc2_ad_step_f64", p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn,
-                               out_adj, dt, stream, true);
-}
 int32_t cloudsc2_saturation_tl_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const double* ap,
                                    const double* t, const double* ap_i, const double* t_i, double* qsat, double* qsat_i, void* stream) {
     return sat_tl_impl<double>("cloudsc2_saturation_tl_f64", p, nx, nz, ls, ap, t, ap_i, t_i, qsat, qsat_i, stream);
@@ -708,17 +606,6 @@ int32_t cloudsc2_saturation_ad_f64(const Cloudsc2Params* p, int32_t nx, int32_t 
                                    const double* t, const double* qsat_adj, double* ap_adj, double* t_adj, int32_t accumulate,
                                    void* stream) {
     return sat_ad_impl<double>("cloudsc2_saturation_ad_f64", p, nx, nz, ls, ap, t, qsat_adj, ap_adj, t_adj, accumulate, stream);
-}
-int32_t cloudsc2_tl_step_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const float* const* in,
-                             const float* const* in_i, const float* zero_line, const float* eta, float* const* out,
-                             float* const* out_i, double dt, void* stream) {
-    return tl_masked_impl<float>("cloudsc2_tl_step_f32", p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt, stream, true);
-}
-int32_t cloudsc2_ad_step_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const float* const* in,
-                             const float* const* in_adj, const float* zero_line, const float* eta, const float* traj_fplsl,
-                             const float* traj_fplsn, float* const* out_adj, double dt, void* stream) {
-    return ad_masked_impl<float>("cloudsc2_ad_step_f32", p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn,
-                               out_adj, dt, stream, true);
 }
 int32_t cloudsc2_saturation_tl_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const float* ap,
                                    const float* t, const float* ap_i, const float* t_i, float* qsat, float* qsat_i, void* stream) {
@@ -755,151 +642,137 @@ int32_t cloudsc2_perturbed_state_f32(const Cloudsc2Params* p, int32_t nx, int32_
                                      double f, void* stream) {
     return per_impl<float>("cloudsc2_perturbed_state_f32", p, nx, nz, ls, in, in_i, out, f, stream);
 }
-int32_t cloudsc2_tl_multi_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const double* const* in,
-                              const double* const* in_i, const double* zero_line, const double* eta, double* const* out,
-                              double* const* out_i, double dt, void* stream, int32_t ndir, int64_t in_ds, int64_t out_ds) {
-    return tl_masked_impl<double>("cloudsc2_tl_multi_f64", p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt, stream, false, true,
-                            ndir, in_ds, out_ds);
-}
-int32_t cloudsc2_tl_multi_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const float* const* in,
-                              const float* const* in_i, const float* zero_line, const float* eta, float* const* out,
-                              float* const* out_i, double dt, void* stream, int32_t ndir, int64_t in_ds, int64_t out_ds) {
-    return tl_masked_impl<float>("cloudsc2_tl_multi_f32", p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt, stream, false, true,
-                           ndir, in_ds, out_ds);
-}
-int32_t cloudsc2_tl_multi_step_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const double* const* in,
-                                   const double* const* in_i, const double* zero_line, const double* eta, double* const* out,
-                                   double* const* out_i, double dt, void* stream, int32_t ndir, int64_t in_ds, int64_t out_ds) {
-    return tl_masked_impl<double>("cloudsc2_tl_multi_step_f64", p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt, stream, true, true,
-                            ndir, in_ds, out_ds);
-}
-int32_t cloudsc2_tl_multi_step_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const float* const* in,
-                                   const float* const* in_i, const float* zero_line, const float* eta, float* const* out,
-                                   float* const* out_i, double dt, void* stream, int32_t ndir, int64_t in_ds, int64_t out_ds) {
-    return tl_masked_impl<float>("cloudsc2_tl_multi_step_f32", p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt, stream, true, true,
-                           ndir, in_ds, out_ds);
-}
-int32_t cloudsc2_ad_multi_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const double* const* in,
-        const double* const* in_adj, const double* zero_line, const double* eta, const double* traj_fplsl, const double* traj_fplsn,
-        double* const* out_adj, double dt, void* stream, int32_t ndir, int64_t in_ds, int64_t out_ds) {
-    return ad_masked_impl<double>("cloudsc2_ad_multi_f64", p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn, out_adj, dt,
-                           stream, false, true, ndir, in_ds, out_ds);
-}
-int32_t cloudsc2_ad_multi_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const float* const* in,
-        const float* const* in_adj, const float* zero_line, const float* eta, const float* traj_fplsl, const float* traj_fplsn,
-        float* const* out_adj, double dt, void* stream, int32_t ndir, int64_t in_ds, int64_t out_ds) {
-    return ad_masked_impl<float>("cloudsc2_ad_multi_f32", p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn, out_adj, dt,
-                           stream, false, true, ndir, in_ds, out_ds);
-}
-int32_t cloudsc2_ad_multi_step_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const double* const* in,
-        const double* const* in_adj, const double* zero_line, const double* eta, const double* traj_fplsl, const double* traj_fplsn,
-        double* const* out_adj, double dt, void* stream, int32_t ndir, int64_t in_ds, int64_t out_ds) {
-    return ad_masked_impl<double>("cloudsc2_ad_multi_step_f64", p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn, out_adj, dt,
-                           stream, true, true, ndir, in_ds, out_ds);
-}
-int32_t cloudsc2_ad_multi_step_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const float* const* in,
-        const float* const* in_adj, const float* zero_line, const float* eta, const float* traj_fplsl, const float* traj_fplsn,
-        float* const* out_adj, double dt, void* stream, int32_t ndir, int64_t in_ds, int64_t out_ds) {
-    return ad_masked_impl<float>("cloudsc2_ad_multi_step_f32", p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn, out_adj, dt,
-                           stream, true, true, ndir, in_ds, out_ds);
-}
-// ---- the ensemble entries: the single entry's arguments + (nmem, member_stride); one pair of definitions per precision
-#define CS2_ENS_ENTRIES(SFX, T)                                                                                                 \
+// ---- the masked TL / AD family, all twenty entries once per precision.  Every wrapper builds the call descriptor from its own
+// arguments: the head and the arrays by CS2_TL_CALL / CS2_AD_CALL under the entry's form, then the groups the entry has.
+#define CS2_TL_ARGS(T)                                                                                                         \
+    const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in, const T* const* in_i, const T* zero_line, \
+        const T* eta, T* const* out, T* const* out_i, double dt
+#define CS2_AD_ARGS(T)                                                                                                         \
+    const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in, const T* const* in_adj,                   \
+        const T* zero_line, const T* eta, const T* traj_fplsl, const T* traj_fplsn, T* const* out_adj, double dt
+#define CS2_DIRS_ARGS int32_t ndir, int64_t in_ds, int64_t out_ds
+#define CS2_ENS_ARGS int32_t nmem, int64_t ms
+#define CS2_COVER_ARGS(T) T* cover, int32_t cover_ready
+#define CS2_TL_CALL(T, FORM)                                                                                                   \
+    cs2::TLCall<T> c{{p, nx, nz, ls, in, zero_line, eta, dt, static_cast<hipStream_t>(stream), FORM}, in_i, out, out_i}
+#define CS2_AD_CALL(T, FORM)                                                                                                   \
+    cs2::ADCall<T> c{{p, nx, nz, ls, in, zero_line, eta, dt, static_cast<hipStream_t>(stream), FORM},                          \
+                     in_adj, traj_fplsl, traj_fplsn, out_adj}
+#define CS2_DIRS c.dirs = {ndir, in_ds, out_ds}
+#define CS2_ENS c.members = {nmem, ms}
+#define CS2_COVER c.cover = {cover, cover_ready}
+#define CS2_MASKED_ENTRIES(SFX, T)                                                                                             \
+    int32_t cloudsc2_tl_masked_##SFX(CS2_TL_ARGS(T), void* stream) {                                                           \
+        CS2_TL_CALL(T, cs2::kMasked);                                                                                          \
+        return tl_masked_impl<T>("cloudsc2_tl_masked_" #SFX, c);                                                               \
+    }                                                                                                                          \
+    int32_t cloudsc2_tl_step_##SFX(CS2_TL_ARGS(T), void* stream) {                                                             \
+        CS2_TL_CALL(T, cs2::kStep);                                                                                            \
+        return tl_masked_impl<T>("cloudsc2_tl_step_" #SFX, c);                                                                 \
+    }                                                                                                                          \
+    int32_t cloudsc2_tl_multi_##SFX(CS2_TL_ARGS(T), void* stream, CS2_DIRS_ARGS) {                                             \
+        CS2_TL_CALL(T, cs2::kMulti);                                                                                           \
+        CS2_DIRS;                                                                                                              \
+        return tl_masked_impl<T>("cloudsc2_tl_multi_" #SFX, c);                                                                \
+    }                                                                                                                          \
+    int32_t cloudsc2_tl_multi_step_##SFX(CS2_TL_ARGS(T), void* stream, CS2_DIRS_ARGS) {                                        \
+        CS2_TL_CALL(T, cs2::kStep | cs2::kMulti);                                                                              \
+        CS2_DIRS;                                                                                                              \
+        return tl_masked_impl<T>("cloudsc2_tl_multi_step_" #SFX, c);                                                           \
+    }                                                                                                                          \
+    int32_t cloudsc2_tl_ens_##SFX(CS2_TL_ARGS(T), void* stream, CS2_ENS_ARGS) {                                                \
+        CS2_TL_CALL(T, cs2::kEns);                                                                                             \
+        CS2_ENS;                                                                                                               \
+        return tl_masked_impl<T>("cloudsc2_tl_ens_" #SFX, c);                                                                  \
+    }                                                                                                                          \
+    int32_t cloudsc2_tl_step_ens_##SFX(CS2_TL_ARGS(T), void* stream, CS2_ENS_ARGS) {                                           \
+        CS2_TL_CALL(T, cs2::kStep | cs2::kEns);                                                                                \
+        CS2_ENS;                                                                                                               \
+        return tl_masked_impl<T>("cloudsc2_tl_step_ens_" #SFX, c);                                                             \
+    }                                                                                                                          \
+    int32_t cloudsc2_ad_masked_##SFX(CS2_AD_ARGS(T), void* stream) {                                                           \
+        CS2_AD_CALL(T, cs2::kMasked);                                                                                          \
+        return ad_masked_impl<T>("cloudsc2_ad_masked_" #SFX, c);                                                               \
+    }                                                                                                                          \
+    int32_t cloudsc2_ad_step_##SFX(CS2_AD_ARGS(T), void* stream) {                                                             \
+        CS2_AD_CALL(T, cs2::kStep);                                                                                            \
+        return ad_masked_impl<T>("cloudsc2_ad_step_" #SFX, c);                                                                 \
+    }                                                                                                                          \
+    int32_t cloudsc2_ad_multi_##SFX(CS2_AD_ARGS(T), void* stream, CS2_DIRS_ARGS) {                                             \
+        CS2_AD_CALL(T, cs2::kMulti);                                                                                           \
+        CS2_DIRS;                                                                                                              \
+        return ad_masked_impl<T>("cloudsc2_ad_multi_" #SFX, c);                                                                \
+    }                                                                                                                          \
+    int32_t cloudsc2_ad_multi_step_##SFX(CS2_AD_ARGS(T), void* stream, CS2_DIRS_ARGS) {                                        \
+        CS2_AD_CALL(T, cs2::kStep | cs2::kMulti);                                                                              \
+        CS2_DIRS;                                                                                                              \
+        return ad_masked_impl<T>("cloudsc2_ad_multi_step_" #SFX, c);                                                           \
+    }                                                                                                                          \
+    int32_t cloudsc2_ad_ens_##SFX(CS2_AD_ARGS(T), void* stream, CS2_ENS_ARGS) {                                                \
+        CS2_AD_CALL(T, cs2::kEns);                                                                                             \
+        CS2_ENS;                                                                                                               \
+        return ad_masked_impl<T>("cloudsc2_ad_ens_" #SFX, c);                                                                  \
+    }                                                                                                                          \
+    int32_t cloudsc2_ad_step_ens_##SFX(CS2_AD_ARGS(T), void* stream, CS2_ENS_ARGS) {                                           \
+        CS2_AD_CALL(T, cs2::kStep | cs2::kEns);                                                                                \
+        CS2_ENS;                                                                                                               \
+        return ad_masked_impl<T>("cloudsc2_ad_step_ens_" #SFX, c);                                                             \
+    }                                                                                                                          \
+    /* the trajectory adjoints with the evaporation block: + (cover, cover_ready), in front of `stream` in the single */       \
+    /* entries and their ensemble forms, behind the directions in the multi entries */                                         \
+    int32_t cloudsc2_ad_evap_##SFX(CS2_AD_ARGS(T), CS2_COVER_ARGS(T), void* stream) {                                          \
+        CS2_AD_CALL(T, cs2::kEvap);                                                                                            \
+        CS2_COVER;                                                                                                             \
+        return ad_masked_impl<T>("cloudsc2_ad_evap_" #SFX, c);                                                                 \
+    }                                                                                                                          \
+    int32_t cloudsc2_ad_evap_step_##SFX(CS2_AD_ARGS(T), CS2_COVER_ARGS(T), void* stream) {                                     \
+        CS2_AD_CALL(T, cs2::kStep | cs2::kEvap);                                                                               \
+        CS2_COVER;                                                                                                             \
+        return ad_masked_impl<T>("cloudsc2_ad_evap_step_" #SFX, c);                                                            \
+    }                                                                                                                          \
+    int32_t cloudsc2_ad_evap_multi_##SFX(CS2_AD_ARGS(T), void* stream, CS2_DIRS_ARGS, CS2_COVER_ARGS(T)) {                     \
+        CS2_AD_CALL(T, cs2::kMulti | cs2::kEvap);                                                                              \
+        CS2_DIRS; CS2_COVER;                                                                                                   \
+        return ad_masked_impl<T>("cloudsc2_ad_evap_multi_" #SFX, c);                                                           \
+    }                                                                                                                          \
+    int32_t cloudsc2_ad_evap_multi_step_##SFX(CS2_AD_ARGS(T), void* stream, CS2_DIRS_ARGS, CS2_COVER_ARGS(T)) {                \
+        CS2_AD_CALL(T, cs2::kStep | cs2::kMulti | cs2::kEvap);                                                                 \
+        CS2_DIRS; CS2_COVER;                                                                                                   \
+        return ad_masked_impl<T>("cloudsc2_ad_evap_multi_step_" #SFX, c);                                                      \
+    }                                                                                                                          \
+    int32_t cloudsc2_ad_evap_ens_##SFX(CS2_AD_ARGS(T), CS2_COVER_ARGS(T), void* stream, CS2_ENS_ARGS) {                        \
+        CS2_AD_CALL(T, cs2::kEns | cs2::kEvap);                                                                                \
+        CS2_ENS; CS2_COVER;                                                                                                    \
+        return ad_masked_impl<T>("cloudsc2_ad_evap_ens_" #SFX, c);                                                             \
+    }                                                                                                                          \
+    int32_t cloudsc2_ad_evap_step_ens_##SFX(CS2_AD_ARGS(T), CS2_COVER_ARGS(T), void* stream, CS2_ENS_ARGS) {                   \
+        CS2_AD_CALL(T, cs2::kStep | cs2::kEns | cs2::kEvap);                                                                   \
+        CS2_ENS; CS2_COVER;                                                                                                    \
+        return ad_masked_impl<T>("cloudsc2_ad_evap_step_ens_" #SFX, c);                                                        \
+    }                                                                                                                          \
+    /* the ensemble forms of the two NL entries: the single entry's arguments + (nmem, member_stride) */                       \
     int32_t cloudsc2_nl_ens_##SFX(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,             \
-                                  const T* eta, T* const* out, double dt, void* stream, int32_t nmem, int64_t ms) {            \
+                                  const T* eta, T* const* out, double dt, void* stream, CS2_ENS_ARGS) {                        \
         return nl_impl<T>("cloudsc2_nl_ens_" #SFX, p, nx, nz, ls, in, eta, out, dt, stream, true, nmem, ms);                   \
     }                                                                                                                          \
     int32_t cloudsc2_nl_fused_ens_##SFX(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,       \
                                         const T* const* in_i, double pf, T* qsat_out, const T* eta, T* const* out, double dt,  \
-                                        void* stream, int32_t nmem, int64_t ms) {                                              \
+                                        void* stream, CS2_ENS_ARGS) {                                                          \
         return nl_fused_impl<T>("cloudsc2_nl_fused_ens_" #SFX, p, nx, nz, ls, in, in_i, pf, qsat_out, eta, out, dt, stream,    \
                                 true, nmem, ms);                                                                               \
-    }                                                                                                                          \
-    int32_t cloudsc2_tl_ens_##SFX(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,             \
-                                  const T* const* in_i, const T* zero_line, const T* eta, T* const* out, T* const* out_i,      \
-                                  double dt, void* stream, int32_t nmem, int64_t ms) {                                         \
-        return tl_masked_impl<T>("cloudsc2_tl_ens_" #SFX, p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt, stream,     \
-                                 false, false, 0, 0, 0, true, nmem, ms);                                                       \
-    }                                                                                                                          \
-    int32_t cloudsc2_tl_step_ens_##SFX(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,        \
-                                       const T* const* in_i, const T* zero_line, const T* eta, T* const* out,                  \
-                                       T* const* out_i, double dt, void* stream, int32_t nmem, int64_t ms) {                   \
-        return tl_masked_impl<T>("cloudsc2_tl_step_ens_" #SFX, p, nx, nz, ls, in, in_i, zero_line, eta, out, out_i, dt,        \
-                                 stream, true, false, 0, 0, 0, true, nmem, ms);                                                \
-    }                                                                                                                          \
-    int32_t cloudsc2_ad_ens_##SFX(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,             \
-                                  const T* const* in_adj, const T* zero_line, const T* eta, const T* traj_fplsl,               \
-                                  const T* traj_fplsn, T* const* out_adj, double dt, void* stream, int32_t nmem,               \
-                                  int64_t ms) {                                                                                \
-        return ad_masked_impl<T>("cloudsc2_ad_ens_" #SFX, p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn,   \
-                                 out_adj, dt, stream, false, false, 0, 0, 0, true, nmem, ms);                                  \
-    }                                                                                                                          \
-    int32_t cloudsc2_ad_step_ens_##SFX(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,        \
-                                       const T* const* in_adj, const T* zero_line, const T* eta, const T* traj_fplsl,          \
-                                       const T* traj_fplsn, T* const* out_adj, double dt, void* stream, int32_t nmem,          \
-                                       int64_t ms) {                                                                           \
-        return ad_masked_impl<T>("cloudsc2_ad_step_ens_" #SFX, p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl,          \
-                                 traj_fplsn, out_adj, dt, stream, true, false, 0, 0, 0, true, nmem, ms);                       \
     }
-// ---- the trajectory adjoints with the evaporation block: the masked / step / multi entries' arguments + (cover, cover_ready)
-#define CS2_EVAP_ENTRIES(SFX, T)                                                                                                \
-    int32_t cloudsc2_ad_evap_##SFX(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,            \
-                                   const T* const* in_adj, const T* zero_line, const T* eta, const T* traj_fplsl,              \
-                                   const T* traj_fplsn, T* const* out_adj, double dt, T* cover, int32_t cover_ready,           \
-                                   void* stream) {                                                                             \
-        return ad_masked_impl<T>("cloudsc2_ad_evap_" #SFX, p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl, traj_fplsn,  \
-                                 out_adj, dt, stream, false, false, 0, 0, 0, false, 0, 0, true, cover, cover_ready);           \
-    }                                                                                                                          \
-    int32_t cloudsc2_ad_evap_step_##SFX(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,       \
-                                        const T* const* in_adj, const T* zero_line, const T* eta, const T* traj_fplsl,         \
-                                        const T* traj_fplsn, T* const* out_adj, double dt, T* cover, int32_t cover_ready,      \
-                                        void* stream) {                                                                        \
-        return ad_masked_impl<T>("cloudsc2_ad_evap_step_" #SFX, p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl,         \
-                                 traj_fplsn, out_adj, dt, stream, true, false, 0, 0, 0, false, 0, 0, true, cover, cover_ready); \
-    }                                                                                                                          \
-    int32_t cloudsc2_ad_evap_multi_##SFX(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,      \
-                                         const T* const* in_adj, const T* zero_line, const T* eta, const T* traj_fplsl,        \
-                                         const T* traj_fplsn, T* const* out_adj, double dt, void* stream, int32_t ndir,        \
-                                         int64_t in_ds, int64_t out_ds, T* cover, int32_t cover_ready) {                       \
-        return ad_masked_impl<T>("cloudsc2_ad_evap_multi_" #SFX, p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl,        \
-                                 traj_fplsn, out_adj, dt, stream, false, true, ndir, in_ds, out_ds, false, 0, 0, true, cover,  \
-                                 cover_ready);                                                                                 \
-    }                                                                                                                          \
-    int32_t cloudsc2_ad_evap_multi_step_##SFX(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in, \
-                                              const T* const* in_adj, const T* zero_line, const T* eta, const T* traj_fplsl,   \
-                                              const T* traj_fplsn, T* const* out_adj, double dt, void* stream, int32_t ndir,   \
-                                              int64_t in_ds, int64_t out_ds, T* cover, int32_t cover_ready) {                  \
-        return ad_masked_impl<T>("cloudsc2_ad_evap_multi_step_" #SFX, p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl,   \
-                                 traj_fplsn, out_adj, dt, stream, true, true, ndir, in_ds, out_ds, false, 0, 0, true, cover,   \
-                                 cover_ready);                                                                                 \
-    }
-// ---- their ensemble forms: the single evaporation entry's arguments + (nmem, member_stride)
-#define CS2_EVAP_ENS_ENTRIES(SFX, T)                                                                                            \
-    int32_t cloudsc2_ad_evap_ens_##SFX(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,        \
-                                       const T* const* in_adj, const T* zero_line, const T* eta, const T* traj_fplsl,          \
-                                       const T* traj_fplsn, T* const* out_adj, double dt, T* cover, int32_t cover_ready,       \
-                                       void* stream, int32_t nmem, int64_t ms) {                                               \
-        return ad_masked_impl<T>("cloudsc2_ad_evap_ens_" #SFX, p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl,          \
-                                 traj_fplsn, out_adj, dt, stream, false, false, 0, 0, 0, true, nmem, ms, true, cover,          \
-                                 cover_ready);                                                                                 \
-    }                                                                                                                          \
-    int32_t cloudsc2_ad_evap_step_ens_##SFX(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,   \
-                                            const T* const* in_adj, const T* zero_line, const T* eta, const T* traj_fplsl,     \
-                                            const T* traj_fplsn, T* const* out_adj, double dt, T* cover, int32_t cover_ready,  \
-                                            void* stream, int32_t nmem, int64_t ms) {                                          \
-        return ad_masked_impl<T>("cloudsc2_ad_evap_step_ens_" #SFX, p, nx, nz, ls, in, in_adj, zero_line, eta, traj_fplsl,     \
-                                 traj_fplsn, out_adj, dt, stream, true, false, 0, 0, 0, true, nmem, ms, true, cover,           \
-                                 cover_ready);                                                                                 \
-    }
-CS2_EVAP_ENS_ENTRIES(f64, double)
-CS2_EVAP_ENS_ENTRIES(f32, float)
-#undef CS2_EVAP_ENS_ENTRIES
-CS2_EVAP_ENTRIES(f64, double)
-CS2_EVAP_ENTRIES(f32, float)
-#undef CS2_EVAP_ENTRIES
-
-CS2_ENS_ENTRIES(f64, double)
-CS2_ENS_ENTRIES(f32, float)
-#undef CS2_ENS_ENTRIES
+CS2_MASKED_ENTRIES(f64, double)
+CS2_MASKED_ENTRIES(f32, float)
+#undef CS2_MASKED_ENTRIES
+#undef CS2_TL_ARGS
+#undef CS2_AD_ARGS
+#undef CS2_DIRS_ARGS
+#undef CS2_ENS_ARGS
+#undef CS2_COVER_ARGS
+#undef CS2_TL_CALL
+#undef CS2_AD_CALL
+#undef CS2_DIRS
+#undef CS2_ENS
+#undef CS2_COVER
 
 }  // extern "C"

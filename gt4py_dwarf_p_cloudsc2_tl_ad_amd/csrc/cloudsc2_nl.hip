@@ -17,7 +17,7 @@
 //
 // Template flags: EVAP = LEVAPLS2 or LDRAIN1D (precipitation evaporation block :288-321 and the
 // 1.9*RCLCRIT / 1e-4 thresholds :250-266), LIN = LPHYLIN or LDRAIN1D (:141-155).
-#include "cloudsc2_common.hpp"
+#include "cloudsc2_launch.hpp"
 
 #ifndef CS2_NL_DIAG
 #define CS2_NL_DIAG 0   // diagnostics only (wrong results): 1 = memory traffic without the physics,
@@ -752,8 +752,7 @@ nl_ring_kernel(Ext<T> e, NLK<T> kc, ExpK<T> xk, int nx, int nz, int64_t ls, CPtr
 
 template <typename T>
 int launch_nl(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* const* in, const T* eta, T* const* out,
-              double dt, hipStream_t stream, const T* const* in_i = nullptr, double pf = 0.0, T* qsat_out = nullptr,
-              double* partials = nullptr) {
+              double dt, hipStream_t stream, const T* const* in_i, double pf, T* qsat_out, double* partials) {
     const Ext<T> e = make_ext<T>(p);
     const auto ci = pack_ptrs<CPtrs<T, NL_NUM_IN>>(in), cii = pack_ptrs<CPtrs<T, NL_NUM_IN>>(in_i);
     const auto co = pack_ptrs<MPtrs<T, NL_NUM_OUT>>(out);

@@ -9,7 +9,7 @@
 // Template flags: REG = LREGCL (regularisations :294-301, :367-368, :444-448, :475-487, :667-668);
 // EVAP = LEVAPLS2 or LDRAIN1D (precipitation-evaporation block :528-616 and the 1.9 RCLCRIT / 1e-4
 // autoconversion thresholds; never enabled by the reference's own drivers).
-#include "cloudsc2_common.hpp"
+#include "cloudsc2_launch.hpp"
 
 #ifndef CS2_TL_DIAG
 #define CS2_TL_DIAG 0   // diagnostics only (wrong results): 1 = the kernel's memory traffic without the physics
@@ -1069,65 +1069,59 @@ tl_ens_step_kernel(const TLEnsArgs<T> A) {
 // in_i[f] == nullptr: perturbation f is zero everywhere (read from `zero`) and not in `have`; out == nullptr: no NL outputs;
 // out_i[f] == nullptr: not in `want`, not written.
 template <typename T>
-static void fill_tl_masked_args(TLMaskedArgs<T>& args, const Cloudsc2Params& p, bool evap, int nx, int nz, int64_t ls,
-                                const T* const* in, const T* const* in_i, const T* zero, const T* eta, T* const* out,
-                                T* const* out_i, double dt) {
-    args.e = make_ext<T>(p);
-    args.kc = make_nlk<T>(p, dt, evap);
+static TLMaskedArgs<T> fill_tl_masked_args(const TLCall<T>& c) {
+    TLMaskedArgs<T> args;
+    args.e = make_ext<T>(*c.p);
+    args.kc = make_nlk<T>(*c.p, c.dt, evap_on(*c.p));
     args.xk = make_expk<T>();
-    args.nx = nx; args.nz = nz; args.ls = ls;
+    args.nx = c.nx; args.nz = c.nz; args.ls = c.ls;
     args.have = 0;
-    args.want = out ? kTLWantNL : 0u;
-    args.in = pack_ptrs<CPtrs<T, NL_NUM_IN>>(in);
-    args.out = pack_ptrs<MPtrs<T, NL_NUM_OUT>>(out);
-    args.out_i = pack_ptrs<MPtrs<T, NL_NUM_OUT>>(out_i);
+    args.want = c.out ? kTLWantNL : 0u;
+    args.in = pack_ptrs<CPtrs<T, NL_NUM_IN>>(c.in);
+    args.out = pack_ptrs<MPtrs<T, NL_NUM_OUT>>(c.out);
+    args.out_i = pack_ptrs<MPtrs<T, NL_NUM_OUT>>(c.out_i);
     for (int i = 0; i < NL_NUM_IN; ++i) {
-        args.in_i.p[i] = in_i[i] ? in_i[i] : zero;
-        if (in_i[i]) args.have |= 1u << i;
+        args.in_i.p[i] = c.in_i[i] ? c.in_i[i] : c.zero;
+        if (c.in_i[i]) args.have |= 1u << i;
     }
     for (int i = 0; i < NL_NUM_OUT; ++i)
-        if (out_i[i]) args.want |= 1u << i;
-    args.eta = eta;
-    args.dt = static_cast<T>(dt);
+        if (c.out_i[i]) args.want |= 1u << i;
+    args.eta = c.eta;
+    args.dt = static_cast<T>(c.dt);
+    return args;
 }
 
-// Always the register path; 32-bit offsets only.  `step`: tl_step_kernel (in[NL_IN_QSAT] and in_i[NL_IN_QSAT] are not read).
-// nmem > 0: the ensemble form (tl_ens_kernel / tl_ens_step_kernel) - every field pointer is member 0's, member m lies
+// Always the register path; 32-bit offsets only.  kStep: tl_step_kernel (in[NL_IN_QSAT] and in_i[NL_IN_QSAT] are not read).
+// kEns: the ensemble form (tl_ens_kernel / tl_ens_step_kernel) - every field pointer is member 0's, member m lies
 // m * ms elements behind it; the caller has checked nmem and ms.
 template <typename T>
-int launch_tl_masked(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* const* in, const T* const* in_i,
-                     const T* zero, const T* eta, T* const* out, T* const* out_i, double dt, hipStream_t stream, bool step,
-                     int nmem, int64_t ms) {
-    if (!fits_u32_offsets<T>(nz, ls)) return -2;
-    const bool evap = evap_on(p);
+int launch_tl_masked(const TLCall<T>& c) {
+    if (!fits_u32_offsets<T>(c.nz, c.ls)) return -2;
+    const bool step = c.is(kStep);
+    const int nmem = c.is(kEns) ? c.members.nmem : 0;
     TLEnsArgs<T> ens;
-    TLMaskedArgs<T>& args = ens.m;
-    fill_tl_masked_args<T>(args, p, evap, nx, nz, ls, in, in_i, zero, eta, out, out_i, dt);
-    const int bpm = (nx + kColBlock - 1) / kColBlock;
+    const TLMaskedArgs<T>& args = ens.m = fill_tl_masked_args<T>(c);
+    const int bpm = (c.nx + kColBlock - 1) / kColBlock;
     const dim3 grid(bpm);
-    const size_t smem = 2 * size_t(nz + 1) * sizeof(T);
+    const size_t smem = 2 * size_t(c.nz + 1) * sizeof(T);
     if (nmem > 0 && int64_t(nmem) * bpm > kMaxGrid) return -2;
-    ens.g.ms = ms; ens.g.bpm = bpm;
+    ens.g.ms = c.members.ms; ens.g.bpm = bpm;
     const dim3 egrid(unsigned(nmem > 0 ? nmem : 1) * unsigned(bpm));
     return with_flags(
         [&](auto REG, auto EVAP, auto STEP, auto ENS) {
             if constexpr (ENS) {
                 constexpr auto kern = STEP ? tl_ens_step_kernel<T, REG, EVAP> : tl_ens_kernel<T, REG, EVAP>;
-                return launch_tail<kern>({egrid, smem, stream, step ? "cs2::tl_ens_step_kernel" : "cs2::tl_ens_kernel"}, ens);
+                return launch_tail<kern>({egrid, smem, c.stream, step ? "cs2::tl_ens_step_kernel" : "cs2::tl_ens_kernel"}, ens);
             } else {
                 constexpr auto kern = STEP ? tl_step_kernel<T, REG, EVAP> : tl_masked_kernel<T, REG, EVAP>;
-                return launch_tail<kern>({grid, smem, stream, step ? "cs2::tl_step_kernel" : "cs2::tl_masked_kernel"}, args);
+                return launch_tail<kern>({grid, smem, c.stream, step ? "cs2::tl_step_kernel" : "cs2::tl_masked_kernel"}, args);
             }
         },
-        p.LREGCL != 0, evap, step, nmem > 0);
+        c.p->LREGCL != 0, evap_on(*c.p), step, nmem > 0);
 }
 
-template int launch_tl_masked<double>(const Cloudsc2Params&, int, int, int64_t, const double* const*, const double* const*,
-                                      const double*, const double*, double* const*, double* const*, double, hipStream_t, bool,
-                                      int, int64_t);
-template int launch_tl_masked<float>(const Cloudsc2Params&, int, int, int64_t, const float* const*, const float* const*,
-                                     const float*, const float*, float* const*, float* const*, double, hipStream_t, bool, int,
-                                     int64_t);
+template int launch_tl_masked<double>(const TLCall<double>&);
+template int launch_tl_masked<float>(const TLCall<float>&);
 
 // ------------------------------------------------------------------------------------------------------------------
 // Masked tangent-linear over `ndir` DIRECTIONS on one trajectory (BUILD EXTENSION, C ABI cloudsc2_tl_multi_* /
@@ -1266,30 +1260,24 @@ tl_dirs_step_kernel(const TLDirsArgs<T> A) {
 // launch_tl_masked for `ndir` directions (1 <= ndir <= kTLMaxDirs, checked by the caller): in_i[f] / out_i[f] point at
 // direction 0; the strides are in elements
 template <typename T>
-int launch_tl_dirs(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* const* in, const T* const* in_i,
-                   const T* zero, const T* eta, T* const* out, T* const* out_i, double dt, hipStream_t stream, bool step,
-                   int ndir, int64_t in_ds, int64_t out_ds) {
-    if (!fits_u32_offsets<T>(nz, ls)) return -2;
-    const bool evap = evap_on(p);
+int launch_tl_dirs(const TLCall<T>& c) {
+    if (!fits_u32_offsets<T>(c.nz, c.ls)) return -2;
+    const bool step = c.is(kStep);
     TLDirsArgs<T> args;
-    fill_tl_masked_args<T>(args.m, p, evap, nx, nz, ls, in, in_i, zero, eta, out, out_i, dt);
-    args.in_ds = in_ds; args.out_ds = out_ds; args.ndir = ndir;
-    const dim3 grid((nx + kColBlock - 1) / kColBlock);
-    const size_t smem = tl_dirs_lds_bytes<T>(nz, ndir);
+    args.m = fill_tl_masked_args<T>(c);
+    args.in_ds = c.dirs.in_ds; args.out_ds = c.dirs.out_ds; args.ndir = c.dirs.ndir;
+    const dim3 grid((c.nx + kColBlock - 1) / kColBlock);
+    const size_t smem = tl_dirs_lds_bytes<T>(c.nz, c.dirs.ndir);
     // device_always: the device is looked up whatever the LDS demand (an ordinal beyond kMaxDevices is refused, -2)
     return with_flags(
         [&](auto REG, auto EVAP, auto STEP) {
             constexpr auto kern = STEP ? tl_dirs_step_kernel<T, REG, EVAP> : tl_dirs_kernel<T, REG, EVAP>;
-            return launch_tail<kern>({grid, smem, stream, step ? "cs2::tl_dirs_step_kernel" : "cs2::tl_dirs_kernel", true}, args);
+            return launch_tail<kern>({grid, smem, c.stream, step ? "cs2::tl_dirs_step_kernel" : "cs2::tl_dirs_kernel", true}, args);
         },
-        p.LREGCL != 0, evap, step);
+        c.p->LREGCL != 0, evap_on(*c.p), step);
 }
 
-template int launch_tl_dirs<double>(const Cloudsc2Params&, int, int, int64_t, const double* const*, const double* const*,
-                                    const double*, const double*, double* const*, double* const*, double, hipStream_t, bool,
-                                    int, int64_t, int64_t);
-template int launch_tl_dirs<float>(const Cloudsc2Params&, int, int, int64_t, const float* const*, const float* const*,
-                                   const float*, const float*, float* const*, float* const*, double, hipStream_t, bool, int,
-                                   int64_t, int64_t);
+template int launch_tl_dirs<double>(const TLCall<double>&);
+template int launch_tl_dirs<float>(const TLCall<float>&);
 
 }  // namespace cs2
