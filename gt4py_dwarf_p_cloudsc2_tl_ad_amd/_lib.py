@@ -122,6 +122,10 @@ ENS_LAYOUTS: Dict[str, str] = {"nl_ens": "nl", "nl_fused_ens": "nl_fused", "tl_e
 #: directly): name -> the `EVAP_LAYOUTS` entry whose argument list they repeat, followed by `nmem` and `member_stride`;
 #: `cover` is batched over the members like every other field of the call
 EVAP_ENS_LAYOUTS: Dict[str, str] = {"ad_evap_ens": "ad_evap", "ad_evap_step_ens": "ad_evap_step"}
+#: members times directions (autodiff.ad_multi_ens / ad_step_multi_ens call them directly): name -> the `MULTI_LAYOUTS` entry
+#: whose argument list they repeat, followed by `nmem`, `member_stride` (state and trajectory fluxes), `in_member_stride`
+#: (batched forcings) and `out_member_stride` (batched adjoints), all in elements
+MULTI_ENS_LAYOUTS: Dict[str, str] = {"ad_multi_ens": "ad_multi", "ad_multi_step_ens": "ad_multi_step"}
 #: CLOUDSC2_TL_MAX_DIRS of include/cloudsc2_hip.h
 TL_MAX_DIRS = 8
 #: CLOUDSC2_AD_MAX_DIRS of include/cloudsc2_hip.h
@@ -168,6 +172,8 @@ def _signatures() -> Dict[str, Tuple[Any, Tuple[Any, ...]]]:
                                                   + tuple(t for a in lay.args for t in _CTYPES[a.kind]))
         for ens, single in {**ENS_LAYOUTS, **EVAP_ENS_LAYOUTS}.items():
             sig[f"cloudsc2_{ens}_{sfx}"] = (c_int32, sig[f"cloudsc2_{single}_{sfx}"][1] + (c_int32, c_int64))
+        for ens, multi in MULTI_ENS_LAYOUTS.items():
+            sig[f"cloudsc2_{ens}_{sfx}"] = (c_int32, sig[f"cloudsc2_{multi}_{sfx}"][1] + (c_int32, c_int64, c_int64, c_int64))
     return sig
 
 

@@ -50,8 +50,19 @@ through `vmap` over the state - use them only when the module-level `EVAP_ENSEMB
 `"trajectory"`.  `EVAP_ENSEMBLE` is False by default: the looped launches are what shipped, and tests pin their kernel
 names under the existing settings; docs/TUNING_LOG.md 3.25 has the measurement of the one launch against the loop.
 
-Not supported: members TIMES directions in one call (nested `vmap`, e.g. `vmap(jacrev(f))`) and a batched `eta`
-(`NotImplementedError`), `torch.autograd.grad(..., is_grads_batched=True)` (the legacy vmap, which knows no `vmap` rule of a
+ENSEMBLE JACOBIANS: members TIMES directions.  `ad_multi_ens` / `ad_step_multi_ens` are `ad_multi` / `ad_step_multi` for all
+members of an ensemble (C ABI `cloudsc2_ad_multi_ens_*` / `cloudsc2_ad_multi_step_ens_*`): states and trajectory fluxes
+member-major `(nmem, nx, 1, nz+1)`, forcings and results `(nmem, ndir, nx, 1, nz+1)`, every chunk of `width` cotangents ONE
+launch for all members.  Under `torch.func` they are opt-in: with the module-level `ENSEMBLE_JACOBIANS` False, the default,
+nested `vmap` over states and directions raises the `NotImplementedError` it always has.  With it True, `vmap(jacrev(f))`
+and `vmap(vmap(vjp_fn))` over stacked states run those launches (LPHYLIN, no evaporation switches; with the switches, in
+either `EVAP_ADJOINT` mode, and for the non-LPHYLIN step the multi-direction path runs member by member), and
+`vmap(jacfwd(f))` / `vmap(vmap(jvp))` one `tl_masked_ens` / `tl_step_ens` launch per direction.  The STATE must be the outer
+batch level: `jacrev` / `jacfwd` applied OUTSIDE `cloudsc2_ensemble` (directions outer, members inner) stays refused, and so
+do a state batched in part, two batch levels over the state or over the directions, and `saturation` on its own under
+nesting.  docs/TUNING_LOG.md 3.26.
+
+Not supported: a batched `eta` (`NotImplementedError`), `torch.autograd.grad(..., is_grads_batched=True)` (the legacy vmap, which knows no `vmap` rule of a
 Function), second derivatives."""
 from __future__ import annotations
 
@@ -92,6 +103,13 @@ EVAP_ADJOINT = "dense"
 #: kernels' ensemble forms).  False, the default: the members are looped, one `ad_masked_evap` launch each, as before these
 #: kernels existed.  docs/TUNING_LOG.md 3.25 has the measurement.
 EVAP_ENSEMBLE = False
+#: whether members TIMES directions is served (`vmap(jacrev(f))`, `vmap(vmap(vjp_fn))`, `vmap(jacfwd(f))` over stacked states)
+#: instead of refused; read when the derivative rule runs.  False, the default: the `NotImplementedError` that shipped, which
+#: tests pin.  True: cotangents run `ad_multi_ens` / `ad_step_multi_ens` - one launch per `AD_MULTI_WIDTH` cotangents for ALL
+#: members - where the adjoint is one launch of the family (LPHYLIN, no evaporation switches), and the multi-direction path
+#: member by member elsewhere; tangents run one `tl_masked_ens` / `tl_step_ens` launch per direction (`MULTI_WIDTH` is 1).
+#: docs/TUNING_LOG.md 3.26 says for which shapes the one launch pays.
+ENSEMBLE_JACOBIANS = False
 
 
 class _Family(NamedTuple):
@@ -103,15 +121,19 @@ class _Family(NamedTuple):
     max_dirs: int                    # the most one launch takes
     adjoint: bool = False            # forcing (`NL_OUT` names) and `traj` in, adjoints of `names` out; else the tangent-linear
     ens: str = ""                    # its ensemble form (`_lib.ENS_LAYOUTS`, `_lib.EVAP_ENS_LAYOUTS`): + (nmem, member_stride)
+    mens: str = ""                   # members times directions (`_lib.MULTI_ENS_LAYOUTS`): the multi form + (nmem, 3 strides)
 
 
 _TL_MASKED = _Family("tl_masked", "tl_multi", NL_IN, MULTI_WIDTH, _lib.TL_MAX_DIRS, ens="tl_ens")
 _TL_STEP = _Family("tl_step", "tl_multi_step", STEP_IN, MULTI_WIDTH, _lib.TL_MAX_DIRS, ens="tl_step_ens")
-_AD_MASKED = _Family("ad_masked", "ad_multi", NL_IN, AD_MULTI_WIDTH, _lib.AD_MAX_DIRS, adjoint=True, ens="ad_ens")
-_AD_STEP = _Family("ad_step", "ad_multi_step", STEP_IN, AD_MULTI_WIDTH, _lib.AD_MAX_DIRS, adjoint=True, ens="ad_step_ens")
+_AD_MASKED = _Family("ad_masked", "ad_multi", NL_IN, AD_MULTI_WIDTH, _lib.AD_MAX_DIRS, adjoint=True, ens="ad_ens",
+                     mens="ad_multi_ens")
+_AD_STEP = _Family("ad_step", "ad_multi_step", STEP_IN, AD_MULTI_WIDTH, _lib.AD_MAX_DIRS, adjoint=True, ens="ad_step_ens",
+                   mens="ad_multi_step_ens")
 _AD_MASKED_EVAP = _Family("ad_evap", "ad_evap_multi", NL_IN, AD_MULTI_WIDTH, _lib.AD_MAX_DIRS, adjoint=True, ens="ad_evap_ens")
 _AD_STEP_EVAP = _Family("ad_evap_step", "ad_evap_multi_step", STEP_IN, AD_MULTI_WIDTH, _lib.AD_MAX_DIRS, adjoint=True,
                         ens="ad_evap_step_ens")
+_FAMILIES = {f.single: f for f in (_TL_MASKED, _TL_STEP, _AD_MASKED, _AD_STEP)}
 _ZERO_LINE_BYTES = 512
 _zero_lines: Dict[Tuple[torch.device, torch.dtype], torch.Tensor] = {}
 
@@ -355,6 +377,70 @@ def ad_step_evap_ens(states: Mapping[str, torch.Tensor], forcing: Mapping[str, t
                  cover_ready=cover_ready)
 
 
+def ad_multi_ens(states: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+                 externals: Optional[Mapping[str, Any]] = None, *, traj: Mapping[str, torch.Tensor], want: Iterable[str],
+                 width: Optional[int] = None):
+    """`ad_multi` for an ENSEMBLE of `nmem` states: members TIMES directions, an ensemble of Jacobian row blocks (C ABI
+    `cloudsc2_ad_multi_ens_*`).  `states` and `traj` map names to member-major `(nmem, nx, 1, nz+1)` tensors (see
+    `ad_masked_ens`), `forcing` maps `NL_OUT` names to `(nmem, ndir, nx, 1, nz+1)` tensors (a missing name is zero forcing in
+    every member and direction).  Returns `{name: (nmem, ndir, nx, 1, nz+1)}`: one allocation per wanted name, laid out as
+    `nmem` consecutive `storage.zeros_batched(ndir, ...)` blocks.
+
+    Directions are served in chunks of at most `width` (default `AD_MULTI_WIDTH` of the dtype); each chunk is ONE launch for
+    all members.  A chunk of one direction is the same entry with `ndir = 1`, not `ad_masked_ens`: that entry has one member
+    stride for every field of the call, and here states, forcings and results are three allocations with three strides.
+    A forcing that is not member-major with the first forcing's strides (packed, as `torch.stack` of `zeros_batched` fields
+    or a result of this call, if the first is in some other layout) is copied once.  LEVAPLS2 / LDRAIN1D are refused
+    (`ValueError`)."""
+    return _call(_AD_MASKED, True, states, forcing, eta, dt, externals, want, traj=traj, width=width, ens=True)
+
+
+def ad_step_multi_ens(states: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
+                      externals: Optional[Mapping[str, Any]] = None, *, traj: Mapping[str, torch.Tensor],
+                      want: Iterable[str], width: Optional[int] = None):
+    """`ad_step_multi` for an ensemble of states, one launch per chunk of cotangents (`cloudsc2_ad_multi_step_ens_*`;
+    `STEP_IN` names): see `ad_multi_ens`.  LPHYLIN only, and no LEVAPLS2 / LDRAIN1D."""
+    return _call(_AD_STEP, True, states, forcing, eta, dt, externals, want, traj=traj, width=width, ens=True)
+
+
+def _member_directions(what: str, noun: str, dirs, first: torch.Tensor, geo, nmem: int):
+    """the `(nmem, ndir, nx, 1, nlev)` forcings of a members-times-directions call -> (them in ONE member-major layout, ndir,
+    direction stride, member stride): the first tensor's own strides if it is such a batch of column-fastest fields of the
+    call's geometry whose directions lie inside its member stride, else packed; whatever differs is copied once"""
+    nx, nlev, ls = geo
+    field = nlev * ls
+    shapes = {tuple(getattr(f, "shape", ())) for f in dirs.values()}
+    shape = next(iter(shapes)) if len(shapes) == 1 else ()
+    if len(shape) != 5 or shape[0] != nmem or shape[1] < 1 or shape[2:] != (nx, 1, nlev):
+        raise ValueError(f"{what}: every {noun} must be a tensor of one shape ({nmem}, ndir, {nx}, 1, {nlev}), got "
+                         f"{ {n: tuple(getattr(f, 'shape', ())) for n, f in dirs.items()} }")
+    ndir = shape[1]
+
+    def strides(g):     # (direction stride, member stride) of a batch in a layout the kernel takes, else None
+        if g.dtype != first.dtype or g.device != first.device:
+            return None
+        try:
+            if field_geometry(g[0, 0]) != geo:
+                return None
+        except ValueError:
+            return None
+        ds = g.stride(1) if ndir > 1 else field
+        ms = g.stride(0) if nmem > 1 else (ndir - 1) * ds + field
+        return (ds, ms) if ds >= field and ms >= (ndir - 1) * ds + field else None
+
+    plain = {n: _plain(f) for n, f in dirs.items()}
+    ds, ms = strides(next(iter(plain.values()))) or (field, ndir * field)
+    out = {}
+    for n, g in plain.items():
+        if strides(g) != (ds, ms):
+            f = torch.zeros(nmem * ms, dtype=first.dtype, device=first.device).as_strided(
+                (nmem, ndir, nx, 1, nlev), (ms, ds, 1, field, ls))
+            f.copy_(g)
+            g = f
+        out[n] = g
+    return out, ndir, ds, ms
+
+
 def _batched_layout(g: torch.Tensor, ref: torch.Tensor, geo, stride: Optional[int] = None) -> torch.Tensor:
     """`g` as `ndir` fields of the call's geometry, one field behind the other (`stride` elements apart; by default packed,
     as `zeros_batched` gives): itself, or a copy into such an allocation (what `_in_layout` is for one direction)"""
@@ -429,7 +515,8 @@ def _tl_args(p, geo, state, pert, zero_line, eta, out, out_i, dt, stream, tail=(
 def _ad_args(p, geo, state, forcing, zero_line, eta, traj, out_adj, dt, stream, tail=(), cover=(), members=()):
     """the arguments of `cloudsc2_ad_masked_*` / `_ad_step_*`; `tail` as for `_tl_args`; `cover` = (pointer, cover_ready):
     those of the `cloudsc2_ad_evap_*` entries (`_lib.EVAP_LAYOUTS`) - in front of `stream`, or behind a multi entry's `tail`;
-    `members` = (nmem, member_stride): those of the ensemble form of either (`_lib.ENS_LAYOUTS`, `_lib.EVAP_ENS_LAYOUTS`)"""
+    `members` = (nmem, member_stride): those of the ensemble form of either (`_lib.ENS_LAYOUTS`, `_lib.EVAP_ENS_LAYOUTS`), or
+    with `tail` (nmem, member_stride, in_member_stride, out_member_stride) of `_lib.MULTI_ENS_LAYOUTS`"""
     nx, nlev, ls = geo
     head = (ctypes.byref(p), nx, nlev - 1, ls, _ptrs(state, NL_IN), _ptrs(forcing, NL_OUT), zero_line.data_ptr(),
             eta.data_ptr(), traj["fplsl"].data_ptr(), traj["fplsn"].data_ptr(), _ptrs(out_adj, NL_IN), float(dt))
@@ -438,7 +525,7 @@ def _ad_args(p, geo, state, forcing, zero_line, eta, traj, out_adj, dt, stream, 
 
 def _call(fam: _Family, batched: bool, state, dirs, eta, dt, externals, want, *, traj=None, write_nl=False, width=None,
           ens=False, cover=None, cover_ready=False):
-    """The launch path of the eighteen thin calls.  Everything is checked ONCE, up front; then the directions are served in
+    """The launch path of the twenty thin calls.  Everything is checked ONCE, up front; then the directions are served in
     chunks of at most `width`: a chunk of one direction by the single-direction entry, a wider one by the multi-direction
     entry.  `batched`: `dirs` maps names to (ndir, nx, 1, nlev) batches and so do the results, which are one `zeros_batched`
     allocation per wanted name that every chunk writes through the views `f[d0]`; otherwise `dirs` and the results are
@@ -446,9 +533,14 @@ def _call(fam: _Family, batched: bool, state, dirs, eta, dt, externals, want, *,
     `ens`: EVERY tensor of the call - state, `dirs`, `traj`, the results - is a member-major (nmem, nx, 1, nlev) batch of one
     layout (that of the first state tensor, `_ens_geometry`); the checks run on member 0 and ONE launch of the family's
     ensemble entry, given member 0's pointers and (nmem, member stride), serves all members.
+    `ens` and `batched` (the adjoint families without the evaporation block): members times directions - `dirs` and the
+    results are (nmem, ndir, nx, 1, nlev), and every chunk of `width` directions is ONE launch of the family's `mens` entry.
     `cover`, `cover_ready`: the evaporation families' cover field (a new one when None); every chunk behind the first reads
     what the first left in it.  With `ens` it is a member-major batch like every other tensor of the call."""
-    what = fam.ens if ens else fam.multi if batched else fam.single
+    mens = ens and batched     # members times directions: `dirs` and the results are (nmem, ndir, nx, 1, nlev)
+    what = (fam.mens if mens else fam.ens) if ens else fam.multi if batched else fam.single
+    if ens and not what:
+        raise ValueError(f"{fam.multi}: members times directions in one call has no kernel in this family")
     noun, dir_names, res_names = ("forcing", NL_OUT, fam.names) if fam.adjoint else ("perturbation", fam.names, NL_OUT)
     want = tuple(want)
     if not want or set(want) - set(res_names):
@@ -468,7 +560,15 @@ def _call(fam: _Family, batched: bool, state, dirs, eta, dt, externals, want, *,
 
         def members(fields):    # -> member 0 of every tensor, in the call's layout
             return {n: f[0] for n, f in laid_out(fields).items()}
-        state, dirs = members(state), members(dirs)
+        state = members(state)
+        if mens:
+            unknown = sorted(set(dirs) - set(dir_names))
+            if unknown or not dirs:
+                raise ValueError(f"{what}: unknown field names {unknown}" if unknown else f"{what}: no {noun} given")
+            dirs_all, _, in_ds, in_ms = _member_directions(what, noun, dirs, first, egeo, nmem)
+            dirs = {n: f[0] for n, f in dirs_all.items()}     # member 0's (ndir, nx, 1, nlev): what the checks below see
+        else:
+            dirs = members(dirs)
         traj = members(traj) if fam.adjoint else None
         if cover is not None:   # the checks below see member 0, the launch gets the batch
             cover_given, cover_all = cover, laid_out({"cover": cover})["cover"]
@@ -496,8 +596,9 @@ def _call(fam: _Family, batched: bool, state, dirs, eta, dt, externals, want, *,
         width = fam.width[dtype] if width is None else int(width)
         if not 1 <= width <= fam.max_dirs:
             raise ValueError(f"{what}: width={width} outside [1, {fam.max_dirs}]")
-        dirs = {n: _batched_layout(f, ref, geo) for n, f in dirs.items()}
-        res = {n: zeros_batched(ndir, nx, nz, dtype, device, ls) for n in want}
+        if not mens:
+            dirs = {n: _batched_layout(f, ref, geo) for n, f in dirs.items()}
+            res = {n: zeros_batched(ndir, nx, nz, dtype, device, ls) for n in want}
     elif not ens:
         width = 1
         res = {n: _new_like(ref, nx, nz, ls) for n in want}
@@ -507,6 +608,16 @@ def _call(fam: _Family, batched: bool, state, dirs, eta, dt, externals, want, *,
     stream = int(torch.cuda.current_stream(device).cuda_stream)
     if evap and not ens:
         cover = _new_like(ref, nx, nz, ls) if cover is None else _plain(cover)
+    if mens:     # one launch per chunk of directions, all members; the results packed: nmem blocks of `zeros_batched(ndir)`
+        res = {n: zeros_batched(nmem * ndir, nx, nz, dtype, device, ls).unflatten(0, (nmem, ndir)) for n in want}
+        with torch.cuda.device(device):
+            for d0 in range(0, ndir, width):
+                n = min(width, ndir - d0)
+                args = _ad_args(p, geo, state, {k: f[0, d0] for k, f in dirs_all.items()}, zero, eta, traj,
+                                {k: f[0, d0] for k, f in res.items()}, dt, stream, (n, in_ds, dstride),
+                                members=(nmem, mstride, in_ms, ndir * dstride))
+                _lib.check(getattr(lib, f"cloudsc2_{fam.mens}_{_SFX[dtype]}")(*args), fam.mens)
+        return res
     if ens:
         new = lambda: _zeros_members(nmem, geo, dtype, device, mstride)  # noqa: E731
         res, out = {n: new() for n in want}, ({n: new() for n in NL_OUT} if write_nl else None)
@@ -581,9 +692,13 @@ def _whole_state(dims) -> bool:
     return any(batched)
 
 
+def _nested(tensors) -> bool:
+    return any(isinstance(t, torch.Tensor) and torch._C._functorch.is_batchedtensor(t) for t in tensors)
+
+
 def _refuse_nested(tensors) -> None:
     """a tensor still wrapped for an OUTER `vmap` inside a `vmap` rule: members times directions"""
-    if any(isinstance(t, torch.Tensor) and torch._C._functorch.is_batchedtensor(t) for t in tensors):
+    if _nested(tensors):
         raise NotImplementedError(_BATCHED_STATE)
 
 
@@ -679,6 +794,8 @@ def _tl_rule(fam, call, tensors, info=None, in_dims=None):
     batched, step = info is not None, fam is _TL_STEP
     nfixed = len(fam.names) + step
     if batched:
+        if ENSEMBLE_JACOBIANS and _nested(tensors[:nfixed]) and not _batched_state(in_dims, nfixed):
+            return _members_times_directions(fam, call, tensors, info, in_dims, nfixed)
         _refuse_nested(tensors)
         if _batched_state(in_dims, nfixed):     # an ensemble of states: every tensor member-major, one ensemble launch
             outs = _tl_rule(fam, call._replace(geo=None), _members(info, in_dims[1:], tensors))
@@ -700,6 +817,69 @@ def _tl_rule(fam, call, tensors, info=None, in_dims=None):
     out_i = _call(fam, batched, state, pert, call.eta, call.dt, call.ext, NL_OUT)[1]
     outs = tuple(out_i[n] for n in NL_OUT)
     return (outs, (0,) * len(outs)) if batched else outs
+
+
+# ---- members times directions (opt-in: `ENSEMBLE_JACOBIANS`) ------------------------------------------------------------------
+# A direction-level `vmap` rule whose STATE is still wrapped for an outer `vmap` - the inner level of `vmap(jacrev(f))`, of
+# `vmap(vmap(vjp_fn))`, of `vmap(jacfwd(f))` - stacks its tangents / cotangents as ever and hands them, with the still-wrapped
+# state, to `_MembersDirs`: a Function of (call, the fixed tensors, stacked (ndir, nx, 1, nlev) directions) whose own `vmap`
+# rule is reached at the OUTER level, with a whole state batched.  Directions outer and members inner (`jacrev` applied outside
+# `cloudsc2_ensemble`) never gets here: there the state is plain and the cotangents carry two batch levels.
+def _members_times_directions(fam, call, tensors, info, in_dims, nfixed):
+    outs = _MembersDirs.apply(fam.single, call, nfixed, *tensors[:nfixed], *_stacked(info, in_dims, tensors, nfixed))
+    return tuple(outs), (0,) * len(outs)
+
+
+class _Directions(NamedTuple):
+    """what `_tl_rule` / `_ad_rule` read of a `vmap` rule's `info`: the number of stacked tangents / cotangents"""
+    batch_size: int
+
+
+def _one_state(fam, call, nfixed, tensors):
+    """the multi-direction path of the family for ONE state: `tensors` = the fixed tensors, then the directions stacked as
+    (ndir, nx, 1, nlev) - the family's rule as its `vmap` over the directions runs it"""
+    rule = _ad_rule if fam.adjoint else _tl_rule
+    dims = (call._replace(eta=None),) + (None,) * nfixed + (0,) * (len(tensors) - nfixed)
+    return tuple(rule(fam, call, tensors, _Directions(tensors[nfixed].shape[0]), dims)[0])
+
+
+class _MembersDirs(_InnerFunction):
+    """(the family's name, call, nfixed, the fixed tensors, present tangents / cotangents stacked as (ndir, nx, 1, nlev)) ->
+    the results as (ndir, nx, 1, nlev)"""
+    @staticmethod
+    def forward(family, call, nfixed, *tensors):
+        return _one_state(_FAMILIES[family], call, nfixed, tensors)
+
+    @staticmethod
+    def vmap(info, in_dims, family, call, nfixed, *tensors):
+        dims = in_dims[3:]
+        if in_dims[1].eta is not None:               # (the forward has refused a batched `eta` before any rule gets here)
+            raise NotImplementedError(_BATCHED_ETA)
+        if not _whole_state(dims[:nfixed]):          # the state is batched further out: this level is a second one of directions
+            raise NotImplementedError(_BATCHED_STATE)
+        _refuse_nested(tensors)                      # a third batch level
+        tensors = _members(info, dims, tensors)      # state (nmem, nx, 1, nlev), directions (nmem, ndir, nx, 1, nlev)
+        nmem, ndir = info.batch_size, tensors[nfixed].shape[1]
+        fam = _FAMILIES[family]
+        adjoint, step = fam.adjoint, fam.names is STEP_IN
+        ext = dict(call.ext, AD_TRAJ_FIX=1) if adjoint else call.ext
+        one_launch = (not step or bool(ext.get("LPHYLIN"))) and not (adjoint and _evap(ext))
+        if not one_launch:      # no kernel: the multi-direction path, member by member
+            rows = []
+            for m in range(nmem):
+                fields = [_as_field(_plain(t)[m]) for t in tensors[:nfixed]] + [_plain(t)[m] for t in tensors[nfixed:]]
+                rows.append(_one_state(fam, call._replace(geo=field_geometry(fields[0])), nfixed, fields))
+            outs = tuple(torch.stack([r[i] for r in rows]) for i in range(len(rows[0])))
+            return outs, (0,) * len(outs)
+        state, _, traj, dirs = _unpacked(fam.names, step, adjoint, call._replace(geo=None), tensors)
+        if adjoint:             # one launch per `width` cotangents, all members
+            adj = _call(fam, True, state, dirs, call.eta, call.dt, ext, call.want, traj=traj, ens=True)
+            outs = tuple(adj[n] for n in call.want)
+        else:                   # one ensemble launch per direction
+            rows = [_call(fam, False, state, {n: f[:, d] for n, f in dirs.items()}, call.eta, call.dt, ext, NL_OUT, ens=True)[1]
+                    for d in range(ndir)]
+            outs = tuple(torch.stack([r[n] for r in rows], dim=1) for n in NL_OUT)
+        return outs, (0,) * len(outs)
 
 
 class _TLMasked(_InnerFunction):
@@ -774,6 +954,8 @@ def _ad_rule(fam, call, tensors, info=None, in_dims=None):
     launch = (_AD_STEP_EVAP if step else _AD_MASKED_EVAP) if evap_traj else fam     # the family `_call` runs
     nfixed = len(fam.names) + step + 2
     if batched:
+        if ENSEMBLE_JACOBIANS and _nested(tensors[:nfixed]) and not _batched_state(in_dims, nfixed):
+            return _members_times_directions(fam, call, tensors, info, in_dims, nfixed)
         _refuse_nested(tensors)
         if one_launch and evap_traj and not evap_ens and _batched_state(in_dims, nfixed):   # an ensemble: member by member
             return _looped_adjoint(lambda c, *t: _ad_rule(fam, c, t), info, in_dims, call, tensors, nfixed, len(want))

@@ -479,8 +479,21 @@ inline size_t ad_dirs_lds_bytes(int nz, int ndir) {
             size_t(kADCarryWords) * ndir * kColBlock) * sizeof(T);
 }
 
-template <typename T, bool REG, bool FIX, bool STEP>
-__device__ __forceinline__ void ad_dirs_sweep(const ADDirsArgs<T>& A) {
+//
+// The same call for every MEMBER of an ensemble (ad_mdirs_kernel / ad_mdirs_step_kernel, C ABI cloudsc2_ad_multi_ens_* /
+// cloudsc2_ad_multi_step_ens_*): members times directions in one launch, an ensemble of Jacobian row blocks.  ENS on the sweep
+// below, as on ad_masked_sweep: one workgroup serves one column block of one member (ens_block).  The state and the two
+// trajectory fluxes of member m lie m * ms elements behind member 0 (ADMemberFields); direction d of member m of a present
+// forcing lies m * in_ms + d * in_ds elements behind the call's pointer, of a wanted adjoint m * out_ms + d * out_ds (member-
+// major batches; the three member strides are independent because states, cotangents and results are three allocations of
+// different sizes).  All bases are wave-uniform 64-bit scalars added to the pointer; nothing else differs from the single
+// form: the carry slots are per workgroup, and a workgroup sees one member only.
+// Words moved per member, level and column: 16 (STEP: 15) + 2 + ndir * (present in_adj + present out_adj) - the single
+// multi-direction call's; what the one launch saves over a loop over the members is nmem - 1 launches with their level
+// tables and pre-scans, and the idle CUs of a small member's grid.
+template <typename T, bool REG, bool FIX, bool STEP, bool ENS = false>
+__device__ __forceinline__ void ad_dirs_sweep(const ADDirsArgs<T>& A, const EnsGeom g = EnsGeom{}, const int64_t in_ms = 0,
+                                              const int64_t out_ms = 0) {
     Ext<T> e = A.m.e;
     NLK<T> kc = A.m.kc;
     ExpK<T> xk = A.m.xk;
@@ -489,7 +502,7 @@ __device__ __forceinline__ void ad_dirs_sweep(const ADDirsArgs<T>& A) {
     const T* __restrict__ eta = A.m.eta;
     T dt = A.m.dt;
     const uint32_t have = A.m.have, want = A.m.want;
-    ADMaskedFields<T> F;
+    typename std::conditional<ENS, ADMemberFields<T>, ADMaskedFields<T>>::type F;
     const auto F_in = [&](int i) { return F.in(i); };
     extern __shared__ __align__(16) unsigned char smem_raw[];
     T* s_eta = reinterpret_cast<T*>(smem_raw);
@@ -502,7 +515,17 @@ __device__ __forceinline__ void ad_dirs_sweep(const ADDirsArgs<T>& A) {
         pin_expk(xk);
     }
 
-    const int gcol = xcd_block() * kColBlock + threadIdx.x;
+    int gcol;
+    int64_t imb = 0, omb = 0;   // ENS: this member's base in the batched forcings / adjoints (elements; wave-uniform)
+    if constexpr (ENS) {
+        int member;
+        gcol = ens_block(g.bpm, member) * kColBlock + threadIdx.x;
+        F.mb = member * g.ms;
+        imb = member * in_ms;
+        omb = member * out_ms;
+    } else {
+        gcol = xcd_block() * kColBlock + threadIdx.x;
+    }
     T* const park_lds = s_scalm + (nz + 1) + threadIdx.x;
     // word w of direction d: s_carry[(w * ndir + d) * kColBlock], behind the parking slots
     T* const s_carry = park_lds + (kADPark<T> ? CS2_AD_PARK_COUNT * kColBlock : 0);
@@ -521,7 +544,7 @@ __device__ __forceinline__ void ad_dirs_sweep(const ADDirsArgs<T>& A) {
 
     // forcing words of direction d for the level at byte offset o
     const auto load_dir = [&](int d, O o) {
-        const ADDirFields<T> Fd{F, have, d * in_ds, int64_t(0)};
+        const ADDirFields<T> Fd{F, have, imb + d * in_ds, int64_t(0)};
         return ad_load_force_masked<T>(Fd, have, lsb, o, zo);
     };
     // ONE loop, k = nz .. 0, and no batch of loads outside it (see ad_masked_sweep: hipcc lays a prologue out around the loop
@@ -569,7 +592,7 @@ __device__ __forceinline__ void ad_dirs_sweep(const ADDirsArgs<T>& A) {
                 const ADOut<T> a = ad_backward<T, REG, FIX, false>(e, kc, xa, k, s_scalm[k], dt, sfl, r, fa, b, park_lds);
                 slot(0, d) = b.tmp_rfln_i; slot(1, d) = b.tmp_sfln_i; slot(2, d) = b.rfl_i; slot(3, d) = b.sfl_i;
                 slot(4, d) = b.daph_i; slot(5, d) = b.dp_i;
-                const ADDirFields<T> Fd{F, have, int64_t(0), d * out_ds};
+                const ADDirFields<T> Fd{F, have, int64_t(0), omb + d * out_ds};
                 ad_store_masked<T, STEP>(Fd, want, lsb, o, dt, a, g_ap * a.qsat, g_t * a.qsat);
                 drain_vmem();   // see drain_vmem
             }
@@ -583,7 +606,7 @@ __device__ __forceinline__ void ad_dirs_sweep(const ADDirsArgs<T>& A) {
     }
     // :982-986 top half level, per direction
     for (int d = 0; d < ndir; ++d) {
-        const int64_t ob = d * out_ds;
+        const int64_t ob = omb + d * out_ds;
         if (want >> NL_IN_APH & 1u) stg(F.oadj(NL_IN_APH) + ob, colb, slot(4, d) - slot(5, d));
         if (want >> NL_IN_LU & 1u) stg(F.oadj(NL_IN_LU) + ob, colb, T(0.0));
     }
@@ -601,8 +624,23 @@ ad_dirs_step_kernel(const ADDirsArgs<T> A) {
     ad_dirs_sweep<T, REG, FIX, true>(A);
 }
 
+// ad_dirs_kernel / ad_dirs_step_kernel for the members of an ensemble, one launch (BUILD EXTENSION, C ABI
+// cloudsc2_ad_multi_ens_* / cloudsc2_ad_multi_step_ens_*): see ad_dirs_sweep
+template <typename T, bool REG, bool FIX>
+__global__ void __launch_bounds__(kColBlock)
+ad_mdirs_kernel(const ADMDirsArgs<T> A) {
+    ad_dirs_sweep<T, REG, FIX, false, true>(A.d, A.g, A.in_ms, A.out_ms);
+}
+
+template <typename T, bool REG, bool FIX>
+__global__ void __launch_bounds__(kColBlock)
+ad_mdirs_step_kernel(const ADMDirsArgs<T> A) {
+    ad_dirs_sweep<T, REG, FIX, true, true>(A.d, A.g, A.in_ms, A.out_ms);
+}
+
 // launch_ad_masked for `ndir` directions (1 <= ndir <= kADMaxDirs, checked by the caller): in_adj[f] / out_adj[f] point at
-// direction 0; the strides are in elements
+// direction 0; the strides are in elements.  kEns: the ensemble form (ad_mdirs_kernel / ad_mdirs_step_kernel) - every pointer
+// is member 0's, direction 0's; the caller has checked nmem and the three member strides.
 template <typename T>
 int launch_ad_dirs(const ADCall<T>& c) {
     const int ndir = c.dirs.ndir;
@@ -612,17 +650,27 @@ int launch_ad_dirs(const ADCall<T>& c) {
     ADDirsArgs<T> args;
     args.m = fill_ad_masked_args<T>(c);
     args.in_ds = c.dirs.in_ds; args.out_ds = c.dirs.out_ds; args.ndir = ndir;
-    const dim3 grid((c.nx + kColBlock - 1) / kColBlock);
+    const int nmem = c.is(kEns) ? c.members.nmem : 0;
+    const int bpm = (c.nx + kColBlock - 1) / kColBlock;
+    if (nmem > 0 && int64_t(nmem) * bpm > kMaxGrid) return -2;   // as launch_ad_masked: the launcher holds its own grid
+    const dim3 grid(bpm), egrid(unsigned(nmem > 0 ? nmem : 1) * unsigned(bpm));
     const size_t smem = ad_dirs_lds_bytes<T>(c.nz, ndir);
     // device_always: this launcher has looked the device up below 64 KiB of LDS as well since it was written (as
     // launch_tl_dirs does), so a device ordinal beyond kMaxDevices is refused here (-2) where the single-direction
     // launchers still run.  Nothing in the launch needs it; kept so that no call changes its outcome.
     return with_flags(
-        [&](auto REG, auto FIX, auto STEP) {
-            constexpr auto kern = STEP ? ad_dirs_step_kernel<T, REG, FIX> : ad_dirs_kernel<T, REG, FIX>;
-            return launch_tail<kern>({grid, smem, c.stream, step ? "cs2::ad_dirs_step_kernel" : "cs2::ad_dirs_kernel", true}, args);
+        [&](auto REG, auto FIX, auto STEP, auto ENS) {
+            if constexpr (ENS) {
+                constexpr auto kern = STEP ? ad_mdirs_step_kernel<T, REG, FIX> : ad_mdirs_kernel<T, REG, FIX>;
+                const ADMDirsArgs<T> ens = {args, {c.members.ms, bpm}, c.members.in_ms, c.members.out_ms};
+                return launch_tail<kern>({egrid, smem, c.stream, step ? "cs2::ad_mdirs_step_kernel" : "cs2::ad_mdirs_kernel", true},
+                                         ens);
+            } else {
+                constexpr auto kern = STEP ? ad_dirs_step_kernel<T, REG, FIX> : ad_dirs_kernel<T, REG, FIX>;
+                return launch_tail<kern>({grid, smem, c.stream, step ? "cs2::ad_dirs_step_kernel" : "cs2::ad_dirs_kernel", true}, args);
+            }
         },
-        c.p->LREGCL != 0, c.p->AD_TRAJ_FIX != 0, step);
+        c.p->LREGCL != 0, c.p->AD_TRAJ_FIX != 0, step, nmem > 0);
 }
 
 template int launch_ad_dirs<double>(const ADCall<double>&);

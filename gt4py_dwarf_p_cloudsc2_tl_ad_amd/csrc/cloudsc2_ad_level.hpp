@@ -987,6 +987,23 @@ struct ADDirsArgs {
     int64_t in_ds, out_ds;         // direction strides, in elements
     int ndir;
 };
+// The ensemble form (ad_mdirs_kernel / ad_mdirs_step_kernel): + the member geometry.  `g.ms` is the member stride of the state
+// and the trajectory fluxes, in_ms / out_ms those of the batched forcings / adjoints (elements).
+template <typename T>
+struct ADMDirsArgs {
+    ADDirsArgs<T> d;               // at kernarg offset 0 (its ADMaskedArgs first)
+    EnsGeom g;
+    int64_t in_ms, out_ms;
+};
+// ADMaskedFields with the state and the trajectory fluxes moved to one member (`mb`: elements; wave-uniform).  adj / oadj
+// stay the call's pointers: ADDirFields adds member and direction base in one.
+template <typename T>
+struct ADMemberFields : ADMaskedFields<T> {
+    int64_t mb;
+    __device__ __forceinline__ const T* in(int i) const { return this->ka->in.p[i] + mb; }
+    __device__ __forceinline__ const T* traj_l() const { return this->ka->traj_l + mb; }
+    __device__ __forceinline__ const T* traj_n() const { return this->ka->traj_n + mb; }
+};
 // ADMaskedFields moved to one direction (what ad_load_force_masked / ad_store_masked are handed)
 template <typename T>
 struct ADDirFields {

@@ -302,6 +302,25 @@ int check_dirs(const char* fn, int32_t nz, int64_t ls, const cs2::CallDirs& d, i
     return 0;
 }
 
+// The two further member strides of the cloudsc2_ad_multi_ens_* / cloudsc2_ad_multi_step_ens_* entries (check_dirs and
+// check_members have passed): member-major batches only - the directions of one member lie inside its member stride
+int check_member_batches(const char* fn, int32_t nz, int64_t ls, const cs2::CallDirs& d, const cs2::CallMembers& m) {
+    const int64_t field = int64_t(nz + 1) * ls;
+    // (ndir-1) * dir_stride + field <= member_stride, by division: the strides are the caller's and their product may overflow
+    const auto fits = [&](int64_t ms, int64_t ds) {
+        return ms >= field && (d.ndir == 1 || ds <= (ms - field) / (d.ndir - 1));
+    };
+    if (!fits(m.in_ms, d.in_ds))
+        return fail(CLOUDSC2_E_ARG, "%s: in_member_stride=%lld < (ndir-1) * in_dir_stride + (nz+1) * lev_stride (ndir=%d, "
+                    "in_dir_stride=%lld, (nz+1) * lev_stride=%lld): the batches are member-major, a member's directions must "
+                    "not reach into the next member", fn, (long long)m.in_ms, d.ndir, (long long)d.in_ds, (long long)field);
+    if (!fits(m.out_ms, d.out_ds))
+        return fail(CLOUDSC2_E_ARG, "%s: out_member_stride=%lld < (ndir-1) * out_dir_stride + (nz+1) * lev_stride (ndir=%d, "
+                    "out_dir_stride=%lld, (nz+1) * lev_stride=%lld): the batches are member-major, a member's directions must "
+                    "not reach into the next member", fn, (long long)m.out_ms, d.ndir, (long long)d.out_ds, (long long)field);
+    return 0;
+}
+
 // The form of the entry (cs2::CallForm) - kStep: the cloudsc2_tl_step_* entry (tl_step_kernel); kMulti: the
 // cloudsc2_tl_multi_* entries (tl_dirs_kernel); kEns: the cloudsc2_tl_ens_* / cloudsc2_tl_step_ens_* entries (tl_ens_kernel /
 // tl_ens_step_kernel)
@@ -377,7 +396,8 @@ int check_cover_disjoint(const char* fn, const cs2::ADCall<T>& c) {
 
 // The form of the entry (cs2::CallForm) - kStep: the cloudsc2_ad_step_* entry (ad_step_kernel); kMulti: the
 // cloudsc2_ad_multi_* entries (ad_dirs_kernel); kEns: the cloudsc2_ad_ens_* / cloudsc2_ad_step_ens_* entries (ad_ens_kernel /
-// ad_ens_step_kernel); kEvap: the trajectory adjoints WITH the evaporation block (cloudsc2_ad_evap_* / _step_* / _multi_* /
+// ad_ens_step_kernel); kMulti and kEns: cloudsc2_ad_multi_ens_* / _multi_step_ens_* (ad_mdirs_kernel / ad_mdirs_step_kernel),
+// members times directions; kEvap: the trajectory adjoints WITH the evaporation block (cloudsc2_ad_evap_* / _step_* / _multi_* /
 // _multi_step_*: ad_cover_kernel and its siblings) - the same checks, the switches required instead of refused, and the
 // caller's cover field; kEvap and kEns: cloudsc2_ad_evap_ens_* / _step_ens_* (ad_cover_ens_kernel / ad_cover_ens_step_kernel),
 // `cover` batched too.
@@ -389,6 +409,8 @@ int ad_masked_impl(const char* fn, const cs2::ADCall<T>& c) {
     if (multi)
         if (int rc = check_dirs(fn, c.nz, c.ls, c.dirs, CLOUDSC2_AD_MAX_DIRS, "CLOUDSC2_AD_MAX_DIRS")) return rc;
     if (int rc = check_members<T>(fn, ens, c.nx, c.nz, c.ls, c.members.nmem, c.members.ms)) return rc;
+    if (multi && ens)
+        if (int rc = check_member_batches(fn, c.nz, c.ls, c.dirs, c.members)) return rc;
     if (c.nx == 0) return CLOUDSC2_OK;
     if (int rc = step ? check_step_trajectory(fn, c.in) : check_ptrs(fn, "in", c.in, NL_NUM_IN)) return rc;
     if (int rc = check_masked_inputs(fn, "in_adj", c.in_adj, NL_NUM_OUT, c.zero)) return rc;
@@ -642,7 +664,7 @@ int32_t cloudsc2_perturbed_state_f32(const Cloudsc2Params* p, int32_t nx, int32_
                                      double f, void* stream) {
     return per_impl<float>("cloudsc2_perturbed_state_f32", p, nx, nz, ls, in, in_i, out, f, stream);
 }
-// ---- the masked TL / AD family, all twenty entries once per precision.  Every wrapper builds the call descriptor from its own
+// ---- the masked TL / AD family, all twenty-two entries once per precision.  Every wrapper builds the call descriptor from its own
 // arguments: the head and the arrays by CS2_TL_CALL / CS2_AD_CALL under the entry's form, then the groups the entry has.
 #define CS2_TL_ARGS(T)                                                                                                         \
     const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in, const T* const* in_i, const T* zero_line, \
@@ -652,6 +674,7 @@ int32_t cloudsc2_perturbed_state_f32(const Cloudsc2Params* p, int32_t nx, int32_
         const T* zero_line, const T* eta, const T* traj_fplsl, const T* traj_fplsn, T* const* out_adj, double dt
 #define CS2_DIRS_ARGS int32_t ndir, int64_t in_ds, int64_t out_ds
 #define CS2_ENS_ARGS int32_t nmem, int64_t ms
+#define CS2_MENS_ARGS int32_t nmem, int64_t ms, int64_t in_ms, int64_t out_ms
 #define CS2_COVER_ARGS(T) T* cover, int32_t cover_ready
 #define CS2_TL_CALL(T, FORM)                                                                                                   \
     cs2::TLCall<T> c{{p, nx, nz, ls, in, zero_line, eta, dt, static_cast<hipStream_t>(stream), FORM}, in_i, out, out_i}
@@ -660,6 +683,7 @@ int32_t cloudsc2_perturbed_state_f32(const Cloudsc2Params* p, int32_t nx, int32_
                      in_adj, traj_fplsl, traj_fplsn, out_adj}
 #define CS2_DIRS c.dirs = {ndir, in_ds, out_ds}
 #define CS2_ENS c.members = {nmem, ms}
+#define CS2_MENS c.members = {nmem, ms, in_ms, out_ms}
 #define CS2_COVER c.cover = {cover, cover_ready}
 #define CS2_MASKED_ENTRIES(SFX, T)                                                                                             \
     int32_t cloudsc2_tl_masked_##SFX(CS2_TL_ARGS(T), void* stream) {                                                           \
@@ -718,6 +742,17 @@ int32_t cloudsc2_perturbed_state_f32(const Cloudsc2Params* p, int32_t nx, int32_
         CS2_ENS;                                                                                                               \
         return ad_masked_impl<T>("cloudsc2_ad_step_ens_" #SFX, c);                                                             \
     }                                                                                                                          \
+    /* members times directions: the multi entry's arguments + (nmem, member_stride, in_member_stride, out_member_stride) */   \
+    int32_t cloudsc2_ad_multi_ens_##SFX(CS2_AD_ARGS(T), void* stream, CS2_DIRS_ARGS, CS2_MENS_ARGS) {                          \
+        CS2_AD_CALL(T, cs2::kMulti | cs2::kEns);                                                                               \
+        CS2_DIRS; CS2_MENS;                                                                                                    \
+        return ad_masked_impl<T>("cloudsc2_ad_multi_ens_" #SFX, c);                                                            \
+    }                                                                                                                          \
+    int32_t cloudsc2_ad_multi_step_ens_##SFX(CS2_AD_ARGS(T), void* stream, CS2_DIRS_ARGS, CS2_MENS_ARGS) {                     \
+        CS2_AD_CALL(T, cs2::kStep | cs2::kMulti | cs2::kEns);                                                                  \
+        CS2_DIRS; CS2_MENS;                                                                                                    \
+        return ad_masked_impl<T>("cloudsc2_ad_multi_step_ens_" #SFX, c);                                                       \
+    }                                                                                                                          \
     /* the trajectory adjoints with the evaporation block: + (cover, cover_ready), in front of `stream` in the single */       \
     /* entries and their ensemble forms, behind the directions in the multi entries */                                         \
     int32_t cloudsc2_ad_evap_##SFX(CS2_AD_ARGS(T), CS2_COVER_ARGS(T), void* stream) {                                          \
@@ -768,11 +803,13 @@ CS2_MASKED_ENTRIES(f32, float)
 #undef CS2_AD_ARGS
 #undef CS2_DIRS_ARGS
 #undef CS2_ENS_ARGS
+#undef CS2_MENS_ARGS
 #undef CS2_COVER_ARGS
 #undef CS2_TL_CALL
 #undef CS2_AD_CALL
 #undef CS2_DIRS
 #undef CS2_ENS
+#undef CS2_MENS
 #undef CS2_COVER
 
 }  // extern "C"

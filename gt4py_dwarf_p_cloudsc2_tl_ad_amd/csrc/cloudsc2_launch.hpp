@@ -7,8 +7,8 @@
 
 namespace cs2 {
 
-// ---- the masked family (cloudsc2_{tl,ad}_{masked,step,multi,multi_step,ens,step_ens}_*, cloudsc2_ad_evap_*): one call
-// descriptor from the extern "C" wrapper through the checks to the launcher.
+// ---- the masked family (cloudsc2_{tl,ad}_{masked,step,multi,multi_step,ens,step_ens}_*, cloudsc2_ad_multi{,_step}_ens_*,
+// cloudsc2_ad_evap_*): one call descriptor from the extern "C" wrapper through the checks to the launcher.
 // What the ENTRY is, not what its arguments hold: a multi entry called with ndir = 0, an ensemble entry called with
 // nmem = 0 keep their bit (and are refused by the checks); an entry without the bit leaves its group zero.
 enum CallForm : unsigned {
@@ -25,6 +25,9 @@ struct CallDirs {      // direction d of a field lies d * in_ds (inputs) / d * o
 struct CallMembers {   // member m of every field lies m * ms elements behind member 0
     int nmem;
     int64_t ms;
+    // kMulti and kEns (cloudsc2_ad_multi_ens_* / _multi_step_ens_*): `ms` is the state's and the trajectory fluxes'; member m of
+    // a batched forcing / adjoint lies m * in_ms / m * out_ms elements behind member 0 (its directions inside the member)
+    int64_t in_ms, out_ms;
 };
 template <typename T>
 struct CallCover {     // the caller's precipitation-cover field; cover_ready: it already holds the forward sweep's values

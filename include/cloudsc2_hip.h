@@ -608,7 +608,8 @@ int32_t cloudsc2_ad_step_ens_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz
  * Words moved per level and column: the single entry's, per member - sweep 1 reads 16 (step: 15) + 2 and writes 1; sweep 2
  * moves 16 (15) + 2 + 1 + (present in_adj) + (wanted out_adj).  With cover_ready sweep 1's 19 (18) drop out.
  * Every member of every written adjoint and of `cover` equals what the single entry writes for that member alone, to
- * rounding (each kernel contracts the level functions itself).  Members times directions in one call: no such entry. */
+ * rounding (each kernel contracts the level functions itself).  Members times directions with the evaporation block: no such entry
+ * (cloudsc2_ad_multi_ens_* below covers the driver switches). */
 int32_t cloudsc2_ad_evap_ens_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
                                  const double* const* in, const double* const* in_adj, const double* zero_line,
                                  const double* eta, const double* traj_fplsl, const double* traj_fplsn,
@@ -629,6 +630,59 @@ int32_t cloudsc2_ad_evap_step_ens_f32(const Cloudsc2Params* p, int32_t nx, int32
                                       const float* eta, const float* traj_fplsl, const float* traj_fplsn,
                                       float* const* out_adj, double dt, float* cover, int32_t cover_ready, void* stream,
                                       int32_t nmem, int64_t member_stride);
+
+/* ---- ENSEMBLE JACOBIANS (BUILD EXTENSIONS): cloudsc2_ad_multi_* and cloudsc2_ad_multi_step_* for `nmem` MEMBERS in one launch
+ * - members times directions: a block of Jacobian rows for every member of an ensemble (`vmap(jacrev(f))` over stacked
+ * states), several observation functionals per member.  Arguments are those of the multi entry, followed by:
+ *   nmem               number of members, >= 1 (CLOUDSC2_E_ARG otherwise);
+ *   member_stride      in ELEMENTS, for in[] and the two trajectory fluxes: member m of each starts m * member_stride
+ *                      elements behind the pointer.  At least (nz+1) * lev_stride (CLOUDSC2_E_ARG);
+ *   in_member_stride   in ELEMENTS, for every present in_adj[f]: direction d of member m starts
+ *                      m * in_member_stride + d * in_dir_stride elements behind the pointer;
+ *   out_member_stride  in ELEMENTS, the same for every wanted out_adj[f] with out_dir_stride.
+ *       ensemble entry                  multi entry                kernel reported by cloudsc2_last_kernel
+ *       cloudsc2_ad_multi_ens_*         cloudsc2_ad_multi_*        cs2::ad_mdirs_kernel
+ *       cloudsc2_ad_multi_step_ens_*    cloudsc2_ad_multi_step_*   cs2::ad_mdirs_step_kernel
+ * All pointers are member 0 / direction 0.  The batches are MEMBER-MAJOR only: in_member_stride must be at least
+ * (ndir-1) * in_dir_stride + (nz+1) * lev_stride and out_member_stride at least (ndir-1) * out_dir_stride + (nz+1) * lev_stride
+ * (CLOUDSC2_E_ARG) - a member's directions lie inside its member stride.  `eta`, `dt`, the switches and the zero line are
+ * shared by all members and directions; a field is present or absent for all of them alike.
+ * Everything cloudsc2_ad_multi_* refuses is refused here, on the host and before any launch: LEVAPLS2 / LDRAIN1D
+ * (CLOUDSC2_E_UNSUPPORTED), the step without LPHYLIN (CLOUDSC2_E_UNSUPPORTED) or with out_adj[NL_IN_QSAT] (CLOUDSC2_E_ARG),
+ * ndir outside 1 .. CLOUDSC2_AD_MAX_DIRS (CLOUDSC2_E_ARG), an LDS demand above 160 KB (CLOUDSC2_E_UNSUPPORTED; the demand is
+ * the multi entry's, it does not grow with nmem).  A field stays below 4 GiB PER MEMBER AND DIRECTION (CLOUDSC2_E_UNSUPPORTED
+ * otherwise; member and direction bases are added to the field pointers as 64-bit scalars, the lanes' byte offsets are
+ * 32-bit); nmem * ceil(nx / 256) workgroups must fit a one-dimensional grid, 2^31 - 1 (CLOUDSC2_E_UNSUPPORTED).  nx == 0 is a
+ * successful no-op.
+ * One workgroup serves one column block of one member, all directions.  Every member and direction of every written field
+ * equals what the multi entry writes for that member alone, to rounding (each kernel contracts the level functions
+ * itself).  Elements between members and between directions are not touched.
+ * Words moved per level and column, per member: 16 (step: 15) + 2 + ndir * ((present in_adj) + (present out_adj)) - the multi
+ * entry's; one launch instead of nmem. */
+int32_t cloudsc2_ad_multi_ens_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                  const double* const* in, const double* const* in_adj, const double* zero_line,
+                                  const double* eta, const double* traj_fplsl, const double* traj_fplsn,
+                                  double* const* out_adj, double dt, void* stream,
+                                  int32_t ndir, int64_t in_dir_stride, int64_t out_dir_stride,
+                                  int32_t nmem, int64_t member_stride, int64_t in_member_stride, int64_t out_member_stride);
+int32_t cloudsc2_ad_multi_ens_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                  const float* const* in, const float* const* in_adj, const float* zero_line,
+                                  const float* eta, const float* traj_fplsl, const float* traj_fplsn,
+                                  float* const* out_adj, double dt, void* stream,
+                                  int32_t ndir, int64_t in_dir_stride, int64_t out_dir_stride,
+                                  int32_t nmem, int64_t member_stride, int64_t in_member_stride, int64_t out_member_stride);
+int32_t cloudsc2_ad_multi_step_ens_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                       const double* const* in, const double* const* in_adj, const double* zero_line,
+                                       const double* eta, const double* traj_fplsl, const double* traj_fplsn,
+                                       double* const* out_adj, double dt, void* stream,
+                                       int32_t ndir, int64_t in_dir_stride, int64_t out_dir_stride,
+                                       int32_t nmem, int64_t member_stride, int64_t in_member_stride, int64_t out_member_stride);
+int32_t cloudsc2_ad_multi_step_ens_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                       const float* const* in, const float* const* in_adj, const float* zero_line,
+                                       const float* eta, const float* traj_fplsl, const float* traj_fplsn,
+                                       float* const* out_adj, double dt, void* stream,
+                                       int32_t ndir, int64_t in_dir_stride, int64_t out_dir_stride,
+                                       int32_t nmem, int64_t member_stride, int64_t in_member_stride, int64_t out_member_stride);
 
 #ifdef __cplusplus
 }
