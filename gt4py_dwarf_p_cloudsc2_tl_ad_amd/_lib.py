@@ -118,6 +118,12 @@ EVAP_LAYOUTS: Dict[str, str] = {"ad_evap": "ad_masked", "ad_evap_step": "ad_step
 #: `nmem` and `member_stride` (elements; one stride for every field of the call)
 ENS_LAYOUTS: Dict[str, str] = {"nl_ens": "nl", "nl_fused_ens": "nl_fused", "tl_ens": "tl_masked", "tl_step_ens": "tl_step",
                                "ad_ens": "ad_masked", "ad_step_ens": "ad_step"}
+#: ensembles that share part of their state (autodiff calls them directly): name -> the `ENS_LAYOUTS` entry whose argument
+#: list they repeat, followed by `shared_mask` (bit i: state input NL_IN[i] is one field for all members; `ENSS_COLUMN_MAJOR` /
+#: `ENSS_MEMBER_MAJOR` choose the block order) and `eta_member_stride` (elements; 0: one `eta` for all members)
+ENSS_LAYOUTS: Dict[str, str] = {ens.replace("_ens", "_enss"): ens for ens in ENS_LAYOUTS}
+#: CLOUDSC2_ENSS_COLUMN_MAJOR / CLOUDSC2_ENSS_MEMBER_MAJOR of include/cloudsc2_hip.h
+ENSS_COLUMN_MAJOR, ENSS_MEMBER_MAJOR = 1 << 32, 1 << 33
 #: the ensemble forms of the two single evaporation entries (autodiff.ad_masked_evap_ens / ad_step_evap_ens call them
 #: directly): name -> the `EVAP_LAYOUTS` entry whose argument list they repeat, followed by `nmem` and `member_stride`;
 #: `cover` is batched over the members like every other field of the call
@@ -172,6 +178,8 @@ def _signatures() -> Dict[str, Tuple[Any, Tuple[Any, ...]]]:
                                                   + tuple(t for a in lay.args for t in _CTYPES[a.kind]))
         for ens, single in {**ENS_LAYOUTS, **EVAP_ENS_LAYOUTS}.items():
             sig[f"cloudsc2_{ens}_{sfx}"] = (c_int32, sig[f"cloudsc2_{single}_{sfx}"][1] + (c_int32, c_int64))
+        for enss, ens in ENSS_LAYOUTS.items():
+            sig[f"cloudsc2_{enss}_{sfx}"] = (c_int32, sig[f"cloudsc2_{ens}_{sfx}"][1] + (c_int64, c_int64))
         for ens, multi in MULTI_ENS_LAYOUTS.items():
             sig[f"cloudsc2_{ens}_{sfx}"] = (c_int32, sig[f"cloudsc2_{multi}_{sfx}"][1] + (c_int32, c_int64, c_int64, c_int64))
     return sig

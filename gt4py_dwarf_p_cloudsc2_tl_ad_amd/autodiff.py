@@ -62,7 +62,19 @@ batch level: `jacrev` / `jacfwd` applied OUTSIDE `cloudsc2_ensemble` (directions
 do a state batched in part, two batch levels over the state or over the directions, and `saturation` on its own under
 nesting.  docs/TUNING_LOG.md 3.26.
 
-Not supported: a batched `eta` (`NotImplementedError`), `torch.autograd.grad(..., is_grads_batched=True)` (the legacy vmap, which knows no `vmap` rule of a
+ENSEMBLES THAT SHARE PART OF THEIR STATE.  The members of an ensemble usually differ in a few fields (`t, q, ql, qi`) and share
+the rest.  `tl_masked_ens`, `tl_step_ens`, `ad_masked_ens`, `ad_step_ens`, `cloudsc2_ensemble` and `cloudsc2_step_ensemble` take
+`shared={name: plain (nx, 1, nz+1) field}` beside `states`, and an `eta` of shape `(nmem, nz+1)`: C ABI `cloudsc2_*_enss_*`,
+the ensemble kernels with a per-field choice of the member base and a per-member level table.  No field is copied per
+member.  `BLOCK_ORDER` chooses how workgroups are dealt to (member, column block) pairs (docs/TUNING_LOG.md 3.27).  The
+evaporation ensembles, members times directions, the non-LPHYLIN step and `saturation` keep whole members: there shared
+fields are expanded and copied, or the members looped, as before.  Under `torch.func.vmap` a state batched in part and a
+batched `eta` are refused (`NotImplementedError`) unless the module-level `SHARED_STATE` is True: then `vmap` over `cloudsc2` /
+`cloudsc2_step` with some state fields at `in_dims=None` runs these launches with those fields shared, and a batched `eta`
+with one level vector per member (`vmap(f)`, `vmap(grad(cost))`, `grad` through `vmap`, `vmap(jvp)`), and an `expand`ed field
+in `states` is recognised as shared.
+
+Not supported: `torch.autograd.grad(..., is_grads_batched=True)` (the legacy vmap, which knows no `vmap` rule of a
 Function), second derivatives."""
 from __future__ import annotations
 
@@ -110,6 +122,18 @@ EVAP_ENSEMBLE = False
 #: member by member elsewhere; tangents run one `tl_masked_ens` / `tl_step_ens` launch per direction (`MULTI_WIDTH` is 1).
 #: docs/TUNING_LOG.md 3.26 says for which shapes the one launch pays.
 ENSEMBLE_JACOBIANS = False
+#: how the shared-state ensemble launches (`shared=` / a per-member `eta`; C ABI `cloudsc2_*_enss_*`) deal workgroups to
+#: (member, column block) pairs; read at launch time.  None: the library's default (member-major, docs/TUNING_LOG.md 3.27);
+#: "member" / "column": member-major / column-block-major.  The results do not depend on it; it exists for the measurement.
+BLOCK_ORDER: Optional[str] = None
+#: whether `torch.func.vmap` over PART of the state of `cloudsc2` / `cloudsc2_step`, or over `eta`, is served instead of refused;
+#: read when the `vmap` rule runs.  False, the default: the two `NotImplementedError`s that shipped, which tests pin, and a
+#: stride-0 `expand`ed field in `states` is copied per member as before.  True: the fields at `in_dims=None` are passed as
+#: SHARED to the shared-state launches (`cloudsc2_*_enss_*`), a batched `eta` as one level vector per member, and a field of
+#: `states` that is an `expand` over the members (stride 0 over dimension 0) is recognised and passed as shared - for `vmap(f)`,
+#: `vmap(grad(cost))`, `grad` through `vmap` and `vmap(jvp)`.  Nesting, the evaporation switches in the adjoint, the non-LPHYLIN
+#: step and `saturation` stay refused or keep whole members as before.
+SHARED_STATE = False
 
 
 class _Family(NamedTuple):
@@ -326,33 +350,48 @@ def ad_step_multi_evap(state: Mapping[str, torch.Tensor], forcing: Mapping[str, 
 
 
 def tl_masked_ens(states: Mapping[str, torch.Tensor], perturbations: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
-                  externals: Optional[Mapping[str, Any]] = None, *, want: Iterable[str], write_nl: bool = False):
+                  externals: Optional[Mapping[str, Any]] = None, *, want: Iterable[str], write_nl: bool = False,
+                  shared: Optional[Mapping[str, torch.Tensor]] = None):
     """`tl_masked` for an ENSEMBLE of `nmem` states in ONE launch (`cloudsc2_tl_ens_*`): `states` and `perturbations` map
     names to member-major `(nmem, nx, 1, nz+1)` tensors - the layout of `storage.zeros_batched`, of `torch.stack` and of
     every `*_multi` result; `eta`, `dt` and the externals are shared.  Every member is an independent `tl_masked` call.
     Returns `(nl_outputs or None, {name: (nmem, nx, 1, nz+1)})`, one `storage.zeros_batched` allocation per name.  A tensor
-    that is not laid out like the first state field (as `zeros_batched` gives) is copied into such a field first."""
-    return _call(_TL_MASKED, False, states, perturbations, eta, dt, externals, want, write_nl=write_nl, ens=True)
+    that is not laid out like the first state field (as `zeros_batched` gives) is copied into such a field first.
+
+    `shared` maps state names to plain `(nx, 1, nz+1)` fields that ALL members read (C ABI `cloudsc2_tl_enss_*`): a name is in
+    exactly one of `states` and `shared` (`ValueError` otherwise); nothing is copied per member (a shared field in another
+    layout is copied once, as one field).  `eta` may be `(nmem, nz+1)` with contiguous rows: one level vector per member."""
+    return _call(_TL_MASKED, False, states, perturbations, eta, dt, externals, want, write_nl=write_nl, ens=True,
+                 shared=shared)
 
 
 def tl_step_ens(states: Mapping[str, torch.Tensor], perturbations: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
-                externals: Optional[Mapping[str, Any]] = None, *, want: Iterable[str], write_nl: bool = False):
-    """`tl_step` for an ensemble of states in one launch (`cloudsc2_tl_step_ens_*`; `STEP_IN` names): see `tl_masked_ens`."""
-    return _call(_TL_STEP, False, states, perturbations, eta, dt, externals, want, write_nl=write_nl, ens=True)
+                externals: Optional[Mapping[str, Any]] = None, *, want: Iterable[str], write_nl: bool = False,
+                shared: Optional[Mapping[str, torch.Tensor]] = None):
+    """`tl_step` for an ensemble of states in one launch (`cloudsc2_tl_step_ens_*`; `STEP_IN` names): see `tl_masked_ens`,
+    also for `shared` and a per-member `eta` (`cloudsc2_tl_step_enss_*`)."""
+    return _call(_TL_STEP, False, states, perturbations, eta, dt, externals, want, write_nl=write_nl, ens=True,
+                 shared=shared)
 
 
 def ad_masked_ens(states: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
-                  externals: Optional[Mapping[str, Any]] = None, *, traj: Mapping[str, torch.Tensor], want: Iterable[str]):
+                  externals: Optional[Mapping[str, Any]] = None, *, traj: Mapping[str, torch.Tensor], want: Iterable[str],
+                  shared: Optional[Mapping[str, torch.Tensor]] = None):
     """`ad_masked` for an ensemble of `nmem` states in ONE launch (`cloudsc2_ad_ens_*`): `states`, `forcing` and `traj` map
     names to member-major `(nmem, nx, 1, nz+1)` tensors (see `tl_masked_ens`); every member is an independent `ad_masked`
-    call.  Returns `{name: (nmem, nx, 1, nz+1)}`.  LEVAPLS2 / LDRAIN1D are refused (`ValueError`)."""
-    return _call(_AD_MASKED, False, states, forcing, eta, dt, externals, want, traj=traj, ens=True)
+    call.  Returns `{name: (nmem, nx, 1, nz+1)}`.  LEVAPLS2 / LDRAIN1D are refused (`ValueError`).
+    `shared` and a per-member `eta` as in `tl_masked_ens` (`cloudsc2_ad_enss_*`).  The adjoint of a shared input is returned
+    PER MEMBER like every other; the adjoint of the shared field itself is its sum over the members.  The evaporation
+    (`ad_masked_evap_ens`) and members-times-directions (`ad_multi_ens`) calls take no `shared`: materialise the members."""
+    return _call(_AD_MASKED, False, states, forcing, eta, dt, externals, want, traj=traj, ens=True, shared=shared)
 
 
 def ad_step_ens(states: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
-                externals: Optional[Mapping[str, Any]] = None, *, traj: Mapping[str, torch.Tensor], want: Iterable[str]):
-    """`ad_step` for an ensemble of states in one launch (`cloudsc2_ad_step_ens_*`; `STEP_IN` names): see `ad_masked_ens`."""
-    return _call(_AD_STEP, False, states, forcing, eta, dt, externals, want, traj=traj, ens=True)
+                externals: Optional[Mapping[str, Any]] = None, *, traj: Mapping[str, torch.Tensor], want: Iterable[str],
+                shared: Optional[Mapping[str, torch.Tensor]] = None):
+    """`ad_step` for an ensemble of states in one launch (`cloudsc2_ad_step_ens_*`; `STEP_IN` names): see `ad_masked_ens`,
+    also for `shared` and a per-member `eta` (`cloudsc2_ad_step_enss_*`)."""
+    return _call(_AD_STEP, False, states, forcing, eta, dt, externals, want, traj=traj, ens=True, shared=shared)
 
 
 def ad_masked_evap_ens(states: Mapping[str, torch.Tensor], forcing: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
@@ -523,8 +562,55 @@ def _ad_args(p, geo, state, forcing, zero_line, eta, traj, out_adj, dt, stream, 
     return (head + (stream,) + tail + cover if tail else head + cover + (stream,)) + members
 
 
+def _eta_members(what: str, eta, nz: int, nmem: int, dtype, device) -> Tuple[torch.Tensor, int]:
+    """`eta` of an ensemble call -> (it, its member stride in elements): 1-D, one level vector for all members (stride 0), or
+    `(nmem, >= nz+1)` with contiguous rows, one per member (packed, or rows of a wider buffer)"""
+    if isinstance(eta, torch.Tensor) and eta.dim() == 2:
+        if (eta.shape[0] != nmem or eta.shape[1] < nz + 1 or eta.dtype != dtype or eta.device != device or eta.stride(1) != 1
+                or (nmem > 1 and eta.stride(0) < nz + 1)):
+            raise ValueError(f"{what}: a per-member eta must be a ({nmem}, >= {nz + 1}) {dtype} tensor on {device} with "
+                             f"contiguous rows, got shape {tuple(eta.shape)}, strides {eta.stride()}, {eta.dtype} on {eta.device}")
+        return eta, (eta.stride(0) if nmem > 1 else eta.shape[1])
+    return _eta(what, eta, nz, dtype, device), 0
+
+
+def _shared_entry(what: str, fam_names, states, shared, eta) -> bool:
+    """does an ensemble call take the shared-state entry (`_lib.ENSS_LAYOUTS`)?  With `shared` given, or a 2-D `eta`.  A name
+    must be in exactly one of `states` and `shared`."""
+    if shared is None:
+        return isinstance(eta, torch.Tensor) and eta.dim() == 2
+    both, missing = sorted(set(states) & set(shared)), sorted(set(fam_names) - set(states) - set(shared))
+    unknown = sorted(set(shared) - set(fam_names))
+    if both or missing or unknown:
+        raise ValueError(f"{what}: every state field must be in exactly one of `states` and `shared`: in both {both}, in "
+                         f"neither {missing}, unknown shared names {unknown}")
+    return True
+
+
+def _block_order_bits() -> int:
+    if BLOCK_ORDER not in (None, "member", "column"):
+        raise ValueError(f"autodiff.BLOCK_ORDER must be None, 'member' or 'column', got {BLOCK_ORDER!r}")
+    return {None: 0, "member": _lib.ENSS_MEMBER_MAJOR, "column": _lib.ENSS_COLUMN_MAJOR}[BLOCK_ORDER]
+
+
+def _shared_fields(what: str, shared, ref: torch.Tensor, geo) -> Dict[str, torch.Tensor]:
+    """the shared fields of an ensemble call as plain `(nx, 1, nlev)` fields of the call's geometry: themselves, or ONE copy
+    each (never one per member)"""
+    nx, nlev, _ = geo
+    for n, f in shared.items():
+        if not isinstance(f, torch.Tensor) or tuple(f.shape) != (nx, 1, nlev):
+            raise ValueError(f"{what}: shared field {n} must be a plain ({nx}, 1, {nlev}) field like one member of the state, "
+                             f"got {tuple(getattr(f, 'shape', ()))}")
+    if ref is None:       # the shapes only
+        return {}
+    for n, f in shared.items():
+        if not f.is_cuda:
+            raise ValueError(f"{what}: {n} lives on {f.device}; fields must live on the GPU (there is no host path)")
+    return {n: _in_layout(f, ref, geo) for n, f in shared.items()}
+
+
 def _call(fam: _Family, batched: bool, state, dirs, eta, dt, externals, want, *, traj=None, write_nl=False, width=None,
-          ens=False, cover=None, cover_ready=False):
+          ens=False, cover=None, cover_ready=False, shared=None):
     """The launch path of the twenty thin calls.  Everything is checked ONCE, up front; then the directions are served in
     chunks of at most `width`: a chunk of one direction by the single-direction entry, a wider one by the multi-direction
     entry.  `batched`: `dirs` maps names to (ndir, nx, 1, nlev) batches and so do the results, which are one `zeros_batched`
@@ -538,7 +624,15 @@ def _call(fam: _Family, batched: bool, state, dirs, eta, dt, externals, want, *,
     `cover`, `cover_ready`: the evaporation families' cover field (a new one when None); every chunk behind the first reads
     what the first left in it.  With `ens` it is a member-major batch like every other tensor of the call."""
     mens = ens and batched     # members times directions: `dirs` and the results are (nmem, ndir, nx, 1, nlev)
+    if ens and not mens and fam.ens in _lib.ENS_LAYOUTS:
+        state, shared = _expanded_as_shared(state, shared)
     what = (fam.mens if mens else fam.ens) if ens else fam.multi if batched else fam.single
+    enss = ens and not mens and what in _lib.ENS_LAYOUTS and _shared_entry(what, fam.names, state, shared, eta)
+    if (shared is not None or (ens and isinstance(eta, torch.Tensor) and eta.dim() == 2)) and not enss:
+        raise ValueError(f"{what}: shared state fields and a per-member eta are served by the six plain ensemble families "
+                         f"only ({sorted(_lib.ENSS_LAYOUTS)}): materialise the members for this call")
+    if enss:
+        what = what.replace("_ens", "_enss")
     if ens and not what:
         raise ValueError(f"{fam.multi}: members times directions in one call has no kernel in this family")
     noun, dir_names, res_names = ("forcing", NL_OUT, fam.names) if fam.adjoint else ("perturbation", fam.names, NL_OUT)
@@ -548,7 +642,12 @@ def _call(fam: _Family, batched: bool, state, dirs, eta, dt, externals, want, *,
     nmem = mstride = 0
     cover_given = cover_all = None
     if ens:
+        # the first tensor that has members: of the state, or (every state field shared) of the forcing / perturbations
         first = state.get(fam.names[0])
+        if enss:
+            first = next((state[n] for n in fam.names if n in state), next(iter(dirs.values()), None))
+        if shared and isinstance(first, torch.Tensor) and first.dim() == 4:     # shapes first: they need no device
+            _shared_fields(what, shared, None, (first.shape[1], first.shape[3], 0))
         nmem, egeo, mstride = _ens_geometry(what, first)
 
         def laid_out(fields):    # -> every tensor in the call's layout
@@ -561,6 +660,8 @@ def _call(fam: _Family, batched: bool, state, dirs, eta, dt, externals, want, *,
         def members(fields):    # -> member 0 of every tensor, in the call's layout
             return {n: f[0] for n, f in laid_out(fields).items()}
         state = members(state)
+        if shared:
+            state.update(_shared_fields(what, shared, _plain(first), egeo))
         if mens:
             unknown = sorted(set(dirs) - set(dir_names))
             if unknown or not dirs:
@@ -590,7 +691,7 @@ def _call(fam: _Family, batched: bool, state, dirs, eta, dt, externals, want, *,
     nx, nlev, ls = geo
     nz = nlev - 1
     ndir = _batch_size(what, noun, dirs, dir_names, geo) if batched else 1
-    eta = _eta(what, eta, nz, dtype, device)
+    eta, eta_ms = _eta_members(what, eta, nz, nmem, dtype, device) if enss else (_eta(what, eta, nz, dtype, device), 0)
     ref = state[NL_IN[0]]
     if batched:
         width = fam.width[dtype] if width is None else int(width)
@@ -622,16 +723,19 @@ def _call(fam: _Family, batched: bool, state, dirs, eta, dt, externals, want, *,
         new = lambda: _zeros_members(nmem, geo, dtype, device, mstride)  # noqa: E731
         res, out = {n: new() for n in want}, ({n: new() for n in NL_OUT} if write_nl else None)
         r0, o0 = {n: f[0] for n, f in res.items()}, (None if out is None else {n: f[0] for n, f in out.items()})
+        park = ()
+        if fam.adjoint and evap:
+            cover_all = new() if cover_all is None else cover_all
+            park = (cover_all[0].data_ptr(), int(bool(cover_ready)))
+        group = (nmem, mstride)     # + (shared_mask, eta_member_stride) for the shared-state entries
+        if enss:
+            group += (sum(1 << NL_IN.index(n) for n in shared or ()) | _block_order_bits(), eta_ms)
         if fam.adjoint:
-            park = ()
-            if evap:
-                cover_all = new() if cover_all is None else cover_all
-                park = (cover_all[0].data_ptr(), int(bool(cover_ready)))
-            args = _ad_args(p, geo, state, dirs, zero, eta, traj, r0, dt, stream, cover=park, members=(nmem, mstride))
+            args = _ad_args(p, geo, state, dirs, zero, eta, traj, r0, dt, stream, cover=park, members=group)
         else:
-            args = _tl_args(p, geo, state, dirs, zero, eta, o0, r0, dt, stream, (nmem, mstride))
+            args = _tl_args(p, geo, state, dirs, zero, eta, o0, r0, dt, stream, group)
         with torch.cuda.device(device):
-            _lib.check(getattr(lib, f"cloudsc2_{fam.ens}_{_SFX[dtype]}")(*args), fam.ens)
+            _lib.check(getattr(lib, f"cloudsc2_{what}_{_SFX[dtype]}")(*args), what)
         if cover_given is not None and not cover_ready and cover_all.data_ptr() != cover_given.data_ptr():
             _plain(cover_given).copy_(cover_all)     # the caller's field was in another layout: hand back what was parked
         return res if fam.adjoint else (out, res)
@@ -727,10 +831,25 @@ class _Launch(NamedTuple):
 
 def _batched_state(in_dims, nfixed) -> bool:
     """in_dims[0] belongs to the `_Launch` (a tuple like it: `eta` is its one tensor), the next `nfixed` to the state and
-    the trajectory: is any of those batched (an ensemble)?  A batched `eta` is refused."""
+    the trajectory: is any of those batched (an ensemble)?  A batched `eta` is refused, and so is a state batched in part -
+    unless `SHARED_STATE` is set: then either makes an ensemble, whose unbatched state fields the members share."""
+    if not SHARED_STATE:
+        if in_dims[0].eta is not None:
+            raise NotImplementedError(_BATCHED_ETA)
+        return _whole_state(in_dims[1:1 + nfixed])
+    return in_dims[0].eta is not None or any(d is not None for d in in_dims[1:1 + nfixed])
+
+
+def _ens_members(info, in_dims, call, tensors, nstate=0):
+    """what a `vmap` rule hands the ensemble path: (`call` with a batched `eta` as contiguous (batch, nlev) rows, every tensor
+    member-major as `_members` gives).  `SHARED_STATE`: an unbatched tensor among the first `nstate`, the state's fields, stays a
+    plain (nx, 1, nlev) field - the members share it - as long as another tensor of the call carries the members."""
     if in_dims[0].eta is not None:
-        raise NotImplementedError(_BATCHED_ETA)
-    return _whole_state(in_dims[1:1 + nfixed])
+        call = call._replace(eta=call.eta.movedim(in_dims[0].eta, 0).contiguous())
+    dims = in_dims[1:]
+    keep = nstate if SHARED_STATE and any(d is not None for d in dims) else 0
+    return call, [t if d is None and i < keep else t.unsqueeze(0).expand(info.batch_size, *t.shape) if d is None
+                  else t.movedim(d, 0) for i, (t, d) in enumerate(zip(tensors, dims))]
 
 
 def _stacked(info, in_dims, tensors, nfixed):
@@ -777,13 +896,22 @@ def _saturation_tl_stacked(ap, t, pert, ext, geo):
     return qsat_i
 
 
+def _split_shared(state, dirs):
+    """the state of an ensemble Function -> (its member-major fields, its shared `(nx, 1, nlev)` fields or None, nmem)"""
+    shared = {n: f for n, f in state.items() if f.dim() == 3}
+    members = {n: f for n, f in state.items() if f.dim() != 3}
+    nmem = max((t.shape[0] for t in list(members.values()) + list(dirs.values()) if t.dim() == 4), default=1)
+    return members, (shared or None), nmem
+
+
 def _looped_members(one, call, tensors, nout):
     """an ensemble where there is no ensemble kernel (the evaporation switches in the adjoint, the non-LPHYLIN step): the
     single path `one(call, *fields)` member by member, results stacked member-major"""
     rows = []
-    for m in range(tensors[0].shape[0]):
-        fields = [_as_field(_plain(t)[m]) for t in tensors]
-        rows.append(one(call._replace(geo=field_geometry(fields[0])), *fields))
+    for m in range(max(t.shape[0] for t in tensors if t.dim() == 4)):     # a (nx, 1, nlev) tensor is shared by the members
+        fields = [_as_field(_plain(t)[m] if t.dim() == 4 else _plain(t)) for t in tensors]
+        eta = call.eta[m] if call.eta is not None and call.eta.dim() == 2 else call.eta     # `saturation` has none
+        rows.append(one(call._replace(geo=field_geometry(fields[0]), eta=eta), *fields))
     return tuple(torch.stack([r[i] for r in rows]) for i in range(nout))
 
 
@@ -798,13 +926,16 @@ def _tl_rule(fam, call, tensors, info=None, in_dims=None):
             return _members_times_directions(fam, call, tensors, info, in_dims, nfixed)
         _refuse_nested(tensors)
         if _batched_state(in_dims, nfixed):     # an ensemble of states: every tensor member-major, one ensemble launch
-            outs = _tl_rule(fam, call._replace(geo=None), _members(info, in_dims[1:], tensors))
+            call, members = _ens_members(info, in_dims, call, tensors, len(fam.names))
+            outs = _tl_rule(fam, call._replace(geo=None), members)
             return outs, (0,) * len(outs)
     if call.geo is None:
         if step and not call.ext.get("LPHYLIN"):     # no ensemble kernel: the single path, member by member
             return _looped_members(lambda c, *t: _tl_rule(fam, c, t), call, tensors, len(NL_OUT))
         state, _, _, pert = _unpacked(fam.names, step, False, call, tensors)
-        out_i = _call(fam, False, state, pert, call.eta, call.dt, call.ext, NL_OUT, ens=True)[1]
+        state, shared, nmem = _split_shared(state, pert)
+        pert = {n: t if t.dim() == 4 else t.unsqueeze(0).expand(nmem, *t.shape) for n, t in pert.items()}
+        out_i = _call(fam, False, state, pert, call.eta, call.dt, call.ext, NL_OUT, ens=True, shared=shared)[1]
         return tuple(out_i[n] for n in NL_OUT)
     state, qsat, _, pert = _unpacked(fam.names, step, False, call, tensors, info, in_dims)
     if step and not call.ext.get("LPHYLIN"):
@@ -928,7 +1059,8 @@ def _looped_adjoint(one, info, in_dims, call, tensors, nfixed, nout):
     Function's own `forward`"""
     _refuse_nested(tensors)
     if _batched_state(in_dims, nfixed):     # an ensemble of states: the single launch member by member
-        return _looped_members(one, call, _members(info, in_dims[1:], tensors), nout), (0,) * nout
+        call, members = _ens_members(info, in_dims, call, tensors)
+        return _looped_members(one, call, members, nout), (0,) * nout
     cot = _stacked(info, in_dims, tensors, nfixed)
     rows = [one(call, *tensors[:nfixed], *(g[b] for g in cot)) for b in range(info.batch_size)]
     return tuple(torch.stack([r[i] for r in rows]) for i in range(nout)), (0,) * nout
@@ -960,13 +1092,18 @@ def _ad_rule(fam, call, tensors, info=None, in_dims=None):
         if one_launch and evap_traj and not evap_ens and _batched_state(in_dims, nfixed):   # an ensemble: member by member
             return _looped_adjoint(lambda c, *t: _ad_rule(fam, c, t), info, in_dims, call, tensors, nfixed, len(want))
         if one_launch and _batched_state(in_dims, nfixed):   # an ensemble of states: one ensemble launch
-            outs = _ad_rule(fam, call._replace(geo=None), _members(info, in_dims[1:], tensors))
+            call, members = _ens_members(info, in_dims, call, tensors, len(fam.names))
+            outs = _ad_rule(fam, call._replace(geo=None), members)
             return outs, (0,) * len(outs)
     if call.geo is None:
         if not one_launch:
             return _looped_members(lambda c, *t: _ad_rule(fam, c, t), call, tensors, len(want))
         state, _, traj, forcing = _unpacked(fam.names, step, True, call, tensors)
-        adj = _call(launch, False, state, forcing, call.eta, call.dt, ext, want, traj=traj, ens=True)
+        state, shared, _ = _split_shared(state, forcing)
+        if shared is not None and launch is not fam:     # the evaporation ensemble launch takes whole members only
+            state = {**state, **{n: f.unsqueeze(0).expand(traj["fplsl"].shape[0], *f.shape) for n, f in shared.items()}}
+            shared = None
+        adj = _call(launch, False, state, forcing, call.eta, call.dt, ext, want, traj=traj, ens=True, shared=shared)
         return tuple(adj[n] for n in want)
     if batched and not one_launch:
         return _looped_adjoint(lambda c, *t: _ad_rule(fam, c, t), info, in_dims, call, tensors, len(fam.names) + step + 2,
@@ -1074,6 +1211,10 @@ class _NLFunction(torch.autograd.Function):
         want = tuple(n for n, w in zip(cls.names, need) if w)
         adj = dict(zip(want, cls.ad.apply(ctx.call._replace(have=have, want=want), *(f.detach() for f in ctx.saved_tensors),
                                           *(g for g in grads if g is not None))))
+        if cls.ensemble is None:      # an ensemble Function: the adjoint of a SHARED input is the sum of the members' adjoints
+            for n, f in zip(cls.names, ctx.saved_tensors):
+                if n in adj and f.dim() == 3:
+                    adj[n] = adj[n].sum(0)
         return (None, None, None) + tuple(adj.get(n) for n in cls.names)
 
     @classmethod
@@ -1091,13 +1232,24 @@ class _NLFunction(torch.autograd.Function):
     def vmap(cls, info, in_dims, eta, dt, externals, *fields):
         """`vmap` over the WHOLE state (every field batched; a state batched in part is refused): the fields are moved to
         dimension 0 and the ensemble Function runs on the member-major batch - one launch, and differentiable like this one"""
-        if in_dims[0] is not None:
+        if in_dims[0] is not None and not SHARED_STATE:
             raise NotImplementedError(_BATCHED_ETA)
         if cls.ensemble is None:
             raise NotImplementedError(_BATCHED_STATE)
-        _refuse_nested(fields)
-        _whole_state(in_dims[3:])
-        outs = cls.ensemble.apply(eta, dt, externals, *_members(info, in_dims[3:], fields))
+        _refuse_nested(fields + (eta,))
+        if not SHARED_STATE:
+            _whole_state(in_dims[3:])
+            members = _members(info, in_dims[3:], fields)
+        else:   # the fields at in_dims=None are shared by the members; a batched eta is one level vector per member
+            if in_dims[0] is not None:
+                eta = eta.movedim(in_dims[0], 0).contiguous()
+            dims = list(in_dims[3:])
+            if all(d is None for d in dims):    # only eta is batched: one field has to carry the members
+                at = cls.names.index("t")
+                fields = fields[:at] + (fields[at].unsqueeze(0).expand(info.batch_size, *fields[at].shape),) + fields[at + 1:]
+                dims[at] = 0
+            members = [f if d is None else f.movedim(d, 0) for f, d in zip(fields, dims)]
+        outs = cls.ensemble.apply(eta, dt, externals, *members)
         return outs, (0,) * len(outs)
 
 
@@ -1380,22 +1532,32 @@ class _ADStepEns(_InnerFunction):
 def _nl_ens(what, single, names, inputs, eta, dt, externals):
     """forward of the ensemble Functions: ONE `cloudsc2_nl_ens_*` launch (`names` = NL_IN) or one `cloudsc2_nl_fused_ens_*`
     launch (`names` = STEP_IN: `saturation` fused in, `qsat` returned behind the ten outputs).  The non-LPHYLIN step has no
-    fused kernel: it loops over the members through `single`, the forward of the single Function."""
+    fused kernel: it loops over the members through `single`, the forward of the single Function.
+    An input that is a plain `(nx, 1, nlev)` field is SHARED by the members, and `eta` may be `(nmem, nz+1)`: the launch is
+    then `cloudsc2_nl_enss_*` / `cloudsc2_nl_fused_enss_*`, and nothing is copied per member."""
     ext, step = _ext_of(externals), names is STEP_IN
+    shared = {n: f for n, f in zip(names, inputs) if isinstance(f, torch.Tensor) and f.dim() == 3}
+    batched = {n: f for n, f in zip(names, inputs) if n not in shared}
+    if not batched:
+        raise ValueError(f"{what}: every state field is shared: at least one must be member-major (nmem, nx, 1, nz+1)")
     if step and not ext.get("LPHYLIN"):
-        rows = [single(eta, dt, externals, *(_as_field(_plain(f)[m]) for f in inputs)) for m in range(inputs[0].shape[0])]
+        rows = [single(eta[m] if isinstance(eta, torch.Tensor) and eta.dim() == 2 else eta, dt, externals,
+                       *(_as_field(_plain(f) if n in shared else _plain(f)[m]) for n, f in zip(names, inputs)))
+                for m in range(next(iter(batched.values())).shape[0])]
         return tuple(torch.stack([r[i] for r in rows]) for i in range(len(rows[0])))
-    first = _plain(inputs[0])
+    first = _plain(next(iter(batched.values())))
     nmem, geo, ms = _ens_geometry(what, first)
     nx, nlev, ls = geo
-    for n, f in zip(names, inputs):
+    for n, f in batched.items():
         if not isinstance(f, torch.Tensor) or tuple(f.shape) != (nmem, nx, 1, nlev):
             raise ValueError(f"{what}: {n} must be a tensor of shape {(nmem, nx, 1, nlev)} like {names[0]}, got "
                              f"{tuple(getattr(f, 'shape', ()))}")
-    fields = {n: _batched_layout(f, first, geo, ms) for n, f in zip(names, inputs)}
+    fields = {n: _batched_layout(f, first, geo, ms) for n, f in batched.items()}
     member0 = {n: f[0] for n, f in fields.items()}
+    member0.update(_shared_fields(what, shared, first, geo))
     _, dtype, device = _checked(what, ((member0, names, True),))
-    eta = _eta(what, eta, nlev - 1, dtype, device)
+    enss = bool(shared) or (isinstance(eta, torch.Tensor) and eta.dim() == 2)
+    eta, eta_ms = _eta_members(what, eta, nlev - 1, nmem, dtype, device)
     new = lambda: _zeros_members(nmem, geo, dtype, device, ms)  # noqa: E731
     out = {n: new() for n in NL_OUT}
     qsat = (new(),) if step else ()
@@ -1403,11 +1565,14 @@ def _nl_ens(what, single, names, inputs, eta, dt, externals):
     head = (ctypes.byref(p), nx, nlev - 1, ls, _ptrs(member0, NL_IN))
     tail = (eta.data_ptr(), _ptrs({n: f[0] for n, f in out.items()}, NL_OUT), float(dt),
             int(torch.cuda.current_stream(device).cuda_stream), nmem, ms)
+    if enss:
+        tail += (sum(1 << NL_IN.index(n) for n in shared) | _block_order_bits(), eta_ms)
+    ens = "enss_" if enss else "ens_"
     with torch.cuda.device(device):
         if step:
-            rc = getattr(_lib.load(), "cloudsc2_nl_fused_ens_" + _SFX[dtype])(*head, None, 0.0, qsat[0][0].data_ptr(), *tail)
+            rc = getattr(_lib.load(), "cloudsc2_nl_fused_" + ens + _SFX[dtype])(*head, None, 0.0, qsat[0][0].data_ptr(), *tail)
         else:
-            rc = getattr(_lib.load(), "cloudsc2_nl_ens_" + _SFX[dtype])(*head, *tail)
+            rc = getattr(_lib.load(), "cloudsc2_nl_" + ens + _SFX[dtype])(*head, *tail)
     _lib.check(rc, what)
     return tuple(out[n] for n in NL_OUT) + qsat
 
@@ -1431,25 +1596,62 @@ class _Cloudsc2StepEns(_NLFunction):
 _Cloudsc2.ensemble, _Cloudsc2Step.ensemble = _Cloudsc2Ens, _Cloudsc2StepEns
 
 
+def _expanded_as_shared(states, shared):
+    """`SHARED_STATE`: a field of `states` that is an `expand` over the members (stride 0 over dimension 0) whose member 0 is a
+    column-fastest field moves to `shared` as that member - as long as another field keeps the members.  Differentiable:
+    autograd sums the members' gradients through the `expand`."""
+    if not SHARED_STATE:
+        return states, shared
+    found = {n: f[0] for n, f in states.items() if isinstance(f, torch.Tensor) and f.dim() == 4 and f.shape[0] > 1
+             and f.stride(0) == 0 and _geometry(f[0])[0] >= 0}
+    if not found or len(found) == len(states):
+        return states, shared
+    return {n: f for n, f in states.items() if n not in found}, {**(shared or {}), **found}
+
+
+def _with_shared(what, states, shared, names):
+    """`states` and `shared` of the public ensemble calls as one mapping (a shared field stays a plain (nx, 1, nz+1) field)"""
+    states, shared = _expanded_as_shared(states, shared)
+    if shared is None:
+        return states
+    _shared_entry(what, names, states, shared, None)
+    for n, f in shared.items():
+        if not isinstance(f, torch.Tensor) or f.dim() != 3:
+            raise ValueError(f"{what}: shared field {n} must be a plain (nx, 1, nz+1) field, got "
+                             f"{tuple(getattr(f, 'shape', ()))}")
+    return {**states, **shared}
+
+
 def cloudsc2_ensemble(states: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
-                      externals: Optional[Mapping[str, Any]] = None) -> Dict[str, torch.Tensor]:
+                      externals: Optional[Mapping[str, Any]] = None, *,
+                      shared: Optional[Mapping[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
     """`cloudsc2` for an ENSEMBLE of `nmem` states: the 16 inputs as member-major `(nmem, nx, 1, nz+1)` tensors (the layout
     of `storage.zeros_batched` and of `torch.stack`; anything else is copied into it) -> the 10 NL outputs, member-major;
     `eta`, `dt` and the externals are shared.  Every member is an independent `cloudsc2` call with `cloudsc2`'s contract
     (`AD_TRAJ_FIX=1` forced for the adjoint, `once_differentiable`).  Forward is ONE `cloudsc2_nl_ens` launch, `backward` one
     `cloudsc2_ad_ens` launch, `jvp` one `cloudsc2_tl_ens` launch; with LEVAPLS2 / LDRAIN1D the backward loops over the
-    members through the dense `cloudsc2_ad`.  `torch.func.vmap` of `cloudsc2` over the state runs this Function."""
+    members through the dense `cloudsc2_ad`.  `torch.func.vmap` of `cloudsc2` over the state runs this Function.
+
+    `shared` maps state names to plain `(nx, 1, nz+1)` fields that all members read; a name is in exactly one of `states` and
+    `shared`.  `eta` may be `(nmem, nz+1)`, one level vector per member.  Either runs the shared-state launches
+    (`cloudsc2_nl_enss`, `cloudsc2_ad_enss`, `cloudsc2_tl_enss`): no field is copied per member, and the gradient with respect
+    to a shared input is the sum over the members of the per-member adjoints - one launch and one `sum(0)`.  With LEVAPLS2 /
+    LDRAIN1D the backward keeps its paths of whole members (shared fields are expanded, or the members looped)."""
+    states = _with_shared("cloudsc2_ensemble", states, shared, NL_IN)
     outs = _Cloudsc2Ens.apply(eta, dt, externals, *_state_fields("cloudsc2_ensemble", states, NL_IN))
     return dict(zip(NL_OUT, outs))
 
 
 def cloudsc2_step_ensemble(states: Mapping[str, torch.Tensor], eta: torch.Tensor, dt: float,
-                           externals: Optional[Mapping[str, Any]] = None) -> Dict[str, torch.Tensor]:
+                           externals: Optional[Mapping[str, Any]] = None, *,
+                           shared: Optional[Mapping[str, torch.Tensor]] = None) -> Dict[str, torch.Tensor]:
     """`cloudsc2_step` for an ensemble of states (`STEP_IN` names, member-major; see `cloudsc2_ensemble`) -> the 10 NL
     outputs plus `"qsat"`, which is not differentiable.  With LPHYLIN and without LEVAPLS2 / LDRAIN1D every call is one
     launch: `cloudsc2_nl_fused_ens`, `cloudsc2_ad_step_ens`, `cloudsc2_tl_step_ens`.  Otherwise the part that has no
-    ensemble kernel loops over the members through the paths of `cloudsc2_step`."""
-    if "qsat" in states:
+    ensemble kernel loops over the members through the paths of `cloudsc2_step`.  `shared` and a per-member `eta` as in
+    `cloudsc2_ensemble` (`cloudsc2_nl_fused_enss`, `cloudsc2_ad_step_enss`, `cloudsc2_tl_step_enss`)."""
+    if "qsat" in states or (shared is not None and "qsat" in shared):
         raise ValueError("cloudsc2_step_ensemble: `states` holds `qsat`, which the step forms itself from `ap` and `t`")
+    states = _with_shared("cloudsc2_step_ensemble", states, shared, STEP_IN)
     outs = _Cloudsc2StepEns.apply(eta, dt, externals, *_state_fields("cloudsc2_step_ensemble", states, STEP_IN))
     return dict(zip(NL_OUT + ("qsat",), outs))

@@ -281,8 +281,13 @@ template int launch_ad<float>(const Cloudsc2Params&, int, int, int64_t, const fl
 // (`pt`, `pap`: two words) are kept beside its adjoints and the derivative is formed where those are stored, one iteration
 // late and before the next level's arithmetic starts.
 // ENS: one member of an ensemble per workgroup (`g`: EnsGeom; the field pointers are ADEnsFields').
-template <typename T, bool REG, bool FIX, bool STEP, bool ENS = false>
-__device__ __forceinline__ void ad_masked_sweep(const ADMaskedArgs<T>& A, const EnsGeom g = EnsGeom{}) {
+// G = EnssGeom: the members share part of their state and may each have an `eta` (C ABI cloudsc2_ad_enss_* /
+// cloudsc2_ad_step_enss_*; see EnssGeom).  The member is decoded in front of the level table, which is built from the member's
+// own level vector; the field pointers are ADEnssFields'.  Nothing else differs: the level loop is the ensemble form's.
+template <typename T, bool REG, bool FIX, bool STEP, bool ENS = false, typename G = EnsGeom>
+__device__ __forceinline__ void ad_masked_sweep(const ADMaskedArgs<T>& A, const G g = G{}) {
+    constexpr bool SH = kSharedGeom<G>;
+    static_assert(ENS || !SH, "shared state is an ensemble form");
     Ext<T> e = A.e;
     NLK<T> kc = A.kc;
     ExpK<T> xk = A.xk;
@@ -291,12 +296,17 @@ __device__ __forceinline__ void ad_masked_sweep(const ADMaskedArgs<T>& A, const 
     const T* __restrict__ eta = A.eta;
     T dt = A.dt;
     const uint32_t have = A.have, want = A.want;
-    typename std::conditional<ENS, ADEnsFields<T>, ADMaskedFields<T>>::type F;
+    typename std::conditional<SH, ADEnssFields<T>, typename std::conditional<ENS, ADEnsFields<T>, ADMaskedFields<T>>::type>::type F;
     const auto F_in = [&](int i) { return F.in(i); };
     extern __shared__ __align__(16) unsigned char smem_raw[];
     T* s_eta = reinterpret_cast<T*>(smem_raw);
     T* s_scalm = s_eta + (nz + 1);
     int klo, khi;
+    int member = 0, cblock = 0;
+    if constexpr (SH) {
+        cblock = enss_block(g, member);
+        eta += member * g.eta_ms;
+    }
     build_level_table<T>(eta, nz, e, s_eta, s_scalm, klo, khi);
     if constexpr (sizeof(T) == 8) {
         pin_vgprs(e.RCPD, e.RLSTT, e.RLVTT, e.R4LES, e.R4IES, e.RTT, e.R3IES, e.R3LES, e.R2ES, e.ZQMAX, e.RETV, e.R5LES,
@@ -306,10 +316,11 @@ __device__ __forceinline__ void ad_masked_sweep(const ADMaskedArgs<T>& A, const 
 
     int gcol;
     if constexpr (ENS) {
-        int member;
-        gcol = ens_block(g.bpm, member) * kColBlock + threadIdx.x;
+        if constexpr (!SH) cblock = ens_block(g.bpm, member);
+        gcol = cblock * kColBlock + threadIdx.x;
         F.mb = member * g.ms;
         F.have = have;
+        if constexpr (SH) F.sh = g.shared;
     } else {
         gcol = xcd_block() * kColBlock + threadIdx.x;
     }
@@ -413,16 +424,31 @@ ad_ens_step_kernel(const ADEnsArgs<T> A) {
     ad_masked_sweep<T, REG, FIX, true, true>(A.m, A.g);
 }
 
+// ad_ens_kernel / ad_ens_step_kernel for members that share part of their state (BUILD EXTENSION, C ABI cloudsc2_ad_enss_* /
+// cloudsc2_ad_step_enss_*): see EnssGeom
+template <typename T, bool REG, bool FIX>
+__global__ void __launch_bounds__(kColBlock, sizeof(T) == 4 ? 3 : 1)
+ad_enss_kernel(const ADEnsArgs<T, EnssGeom> A) {
+    ad_masked_sweep<T, REG, FIX, false, true, EnssGeom>(A.m, A.g);
+}
+
+template <typename T, bool REG, bool FIX>
+__global__ void __launch_bounds__(kColBlock, sizeof(T) == 4 ? 3 : 1)
+ad_enss_step_kernel(const ADEnsArgs<T, EnssGeom> A) {
+    ad_masked_sweep<T, REG, FIX, true, true, EnssGeom>(A.m, A.g);
+}
+
 
 // The caller (cloudsc2_capi.hip) has refused the evaporation switches and fields of 4 GiB and more.  kStep: ad_step_kernel
 // (in[NL_IN_QSAT] is not read, out_adj[NL_IN_QSAT] is NULL).  kEns: the ensemble form (ad_ens_kernel /
 // ad_ens_step_kernel) - every field pointer is member 0's, member m lies m * ms elements behind it; the caller has checked
-// nmem and ms.
+// nmem and ms.  kShared (with kEns): ad_enss_kernel / ad_enss_step_kernel - the geometry is enss_geom's.
 template <typename T>
 int launch_ad_masked(const ADCall<T>& c) {
     if (evap_on(*c.p) || !fits_u32_offsets<T>(c.nz, c.ls)) return -2;
     const bool step = c.is(kStep);
     const int nmem = c.is(kEns) ? c.members.nmem : 0;
+    if (c.is(kShared) && nmem < 1) return -1;
     ADEnsArgs<T> ens;
     const ADMaskedArgs<T>& args = ens.m = fill_ad_masked_args<T>(c);
     const int bpm = (c.nx + kColBlock - 1) / kColBlock;
@@ -432,8 +458,12 @@ int launch_ad_masked(const ADCall<T>& c) {
     ens.g.ms = c.members.ms; ens.g.bpm = bpm;
     const dim3 egrid(unsigned(nmem > 0 ? nmem : 1) * unsigned(bpm));
     return with_flags(
-        [&](auto REG, auto FIX, auto STEP, auto ENS) {
-            if constexpr (ENS) {
+        [&](auto REG, auto FIX, auto STEP, auto ENS, auto SH) {
+            if constexpr (ENS && SH) {
+                constexpr auto kern = STEP ? ad_enss_step_kernel<T, REG, FIX> : ad_enss_kernel<T, REG, FIX>;
+                const ADEnsArgs<T, EnssGeom> enss = {args, enss_geom(c.members, bpm)};
+                return launch_tail<kern>({egrid, smem, c.stream, step ? "cs2::ad_enss_step_kernel" : "cs2::ad_enss_kernel"}, enss);
+            } else if constexpr (ENS) {
                 constexpr auto kern = STEP ? ad_ens_step_kernel<T, REG, FIX> : ad_ens_kernel<T, REG, FIX>;
                 return launch_tail<kern>({egrid, smem, c.stream, step ? "cs2::ad_ens_step_kernel" : "cs2::ad_ens_kernel"}, ens);
             } else {
@@ -441,7 +471,7 @@ int launch_ad_masked(const ADCall<T>& c) {
                 return launch_tail<kern>({grid, smem, c.stream, step ? "cs2::ad_step_kernel" : "cs2::ad_masked_kernel"}, args);
             }
         },
-        c.p->LREGCL != 0, c.p->AD_TRAJ_FIX != 0, step, nmem > 0);
+        c.p->LREGCL != 0, c.p->AD_TRAJ_FIX != 0, step, nmem > 0, c.is(kShared));
 }
 
 template int launch_ad_masked<double>(const ADCall<double>&);

@@ -891,10 +891,10 @@ struct ADMaskedFields : KernArgs<ADMaskedArgs<T>> {
 // The ensemble forms (ad_ens_kernel / ad_ens_step_kernel in cloudsc2_ad.hip, ad_cover_ens_kernel / ad_cover_ens_step_kernel in
 // cloudsc2_ad_evap.hip): ADMaskedFields moved to one member, see ad_masked_sweep.  Any argument struct whose ADMaskedArgs
 // stands at kernarg offset 0 is read through this view.
-template <typename T>
+template <typename T, typename G = EnsGeom>
 struct ADEnsArgs {
     ADMaskedArgs<T> m;           // at kernarg offset 0
-    EnsGeom g;
+    G g;                         // EnssGeom: the shared-state form (ad_enss_kernel / ad_enss_step_kernel)
 };
 template <typename T>
 struct ADEnsFields : KernArgs<ADEnsArgs<T>> {
@@ -905,6 +905,15 @@ struct ADEnsFields : KernArgs<ADEnsArgs<T>> {
     __device__ __forceinline__ T* oadj(int i) const { return this->ka->m.oadj.p[i] + mb; }
     __device__ __forceinline__ const T* traj_l() const { return this->ka->m.traj_l + mb; }
     __device__ __forceinline__ const T* traj_n() const { return this->ka->m.traj_n + mb; }
+};
+// ADEnsFields whose SHARED state inputs (bit i of `sh`, EnssGeom::shared) keep the call's pointer: the base is selected the
+// way `adj` selects the zero line's, a scalar compare and select in front of the 64-bit scalar add
+template <typename T>
+struct ADEnssFields : ADEnsFields<T> {
+    uint32_t sh;
+    __device__ __forceinline__ const T* in(int i) const {
+        return this->ka->m.in.p[i] + ((sh >> i & 1u) ? int64_t(0) : this->mb);
+    }
 };
 
 // ad_load_force with a per-field offset: the field's own `o`, or `zo` into the zero line (raw words, as there)

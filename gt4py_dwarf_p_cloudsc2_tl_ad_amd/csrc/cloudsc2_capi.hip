@@ -69,12 +69,85 @@ int check_members(const char* fn, bool ens, int32_t nx, int32_t nz, int64_t ls, 
     return 0;
 }
 
-// `ens`: the cloudsc2_nl_ens_* entry (nl_ens_kernel)
+// Overlap of batched fields, judged on bounding ranges (check_shared: a written field against a shared input;
+// check_cover_disjoint: the evaporation ensemble entries' `cover`): one member of a field spans
+// `ea` / `eb` bytes, member m starts m * `sb` bytes behind member 0; `a` has `na` members, `b` has `nb` (1: the zero line, eta,
+// a shared input).  Member i of `a` meets member j of `b` iff -ea < (a - b) + (i - j) * sb < eb.
+bool member_ranges_overlap(const void* a, int64_t ea, int64_t na, const void* b, int64_t eb, int64_t nb, int64_t sb) {
+    const int64_t delta = int64_t(reinterpret_cast<intptr_t>(a) - reinterpret_cast<intptr_t>(b));
+    const auto floor_div = [](int64_t x, int64_t y) { return x / y - ((x % y != 0 && x < 0) ? 1 : 0); };   // y > 0
+    const int64_t dmin = floor_div(-ea - delta, sb) + 1;       // the d = i - j with -ea < delta + d * sb ...
+    const int64_t dmax = -floor_div(delta - eb, sb) - 1;       // ... and delta + d * sb < eb
+    return std::max(dmin, -(nb - 1)) <= std::min(dmax, na - 1);
+}
+
+// The two further member arguments of the cloudsc2_*_enss_* entries (include/cloudsc2_hip.h "ENSEMBLES THAT SHARE PART OF THEIR
+// STATE"; check_members has passed).  `in`: the state inputs.  `written` calls its argument with (array name, index,
+// pointer) of every field the call writes; NULL pointers are skipped.  A shared input has ONE range, member 0's; a written
+// field has nmem.
+template <typename T, typename W>
+int check_shared(const char* fn, const cs2::CallMembers& m, int32_t nx, int32_t nz, int64_t ls, const T* const* in,
+                 const T* eta, const W& written) {
+    const int64_t known = int64_t(0xFFFF) | CLOUDSC2_ENSS_COLUMN_MAJOR | CLOUDSC2_ENSS_MEMBER_MAJOR;
+    if (m.shared_mask & ~known) {
+        int bit = 0;
+        while (!((uint64_t(m.shared_mask & ~known) >> bit) & 1u)) ++bit;
+        return fail(CLOUDSC2_E_ARG, "%s: shared_mask bit %d is set: beyond the %d state inputs (bits 0 .. %d) and the two "
+                    "block-order bits", fn, bit, NL_NUM_IN, NL_NUM_IN - 1);
+    }
+    if ((m.shared_mask & CLOUDSC2_ENSS_COLUMN_MAJOR) && (m.shared_mask & CLOUDSC2_ENSS_MEMBER_MAJOR))
+        return fail(CLOUDSC2_E_ARG, "%s: shared_mask asks for both block orders (CLOUDSC2_ENSS_COLUMN_MAJOR and _MEMBER_MAJOR)", fn);
+    if (m.eta_ms != 0 && m.eta_ms < int64_t(nz) + 1)
+        return fail(CLOUDSC2_E_ARG, "%s: eta_member_stride=%lld must be 0 (one eta for all members) or >= nz + 1 = %d: the "
+                    "members' level vectors would overlap", fn, (long long)m.eta_ms, nz + 1);
+    if (nx == 0) return 0;
+    const int64_t ext = (int64_t(nz) * ls + nx) * int64_t(sizeof(T)), sb = m.ms * int64_t(sizeof(T));
+    for (int i = 0; i < NL_NUM_IN; ++i) {
+        if (!(m.shared_mask >> i & 1)) continue;
+        if (!in || !in[i])
+            return fail(CLOUDSC2_E_ARG, "%s: shared_mask bit %d is set but in[%d] is NULL: an absent field cannot be shared", fn,
+                        i, i);
+        const char* what = nullptr;
+        int at = 0;
+        written([&](const char* name, int j, const T* f) {
+            if (!what && f && member_ranges_overlap(f, ext, m.nmem, in[i], ext, 1, sb)) {
+                what = name;
+                at = j;
+            }
+        });
+        if (what)
+            return fail(CLOUDSC2_E_ARG, "%s: %s[%d] overlaps the shared input in[%d] in some member: every member reads a "
+                        "shared input for the whole launch, no written field may share storage with it", fn, what, at, i);
+    }
+    if (eta && m.eta_ms != 0) {     // the members' level vectors, first to last, as ONE range: read for the whole launch too
+        const int64_t rows = ((int64_t(m.nmem) - 1) * m.eta_ms + nz + 1) * int64_t(sizeof(T));
+        const char* what = nullptr;
+        int at = 0;
+        written([&](const char* name, int j, const T* f) {
+            if (!what && f && member_ranges_overlap(f, ext, m.nmem, eta, rows, 1, sb)) {
+                what = name;
+                at = j;
+            }
+        });
+        if (what)
+            return fail(CLOUDSC2_E_ARG, "%s: %s[%d] overlaps eta (the %d members' level vectors, eta_member_stride=%lld) in some "
+                        "member: no written field may share storage with them", fn, what, at, m.nmem, (long long)m.eta_ms);
+    }
+    return 0;
+}
+
+// `ens`: the cloudsc2_nl_ens_* entry (nl_ens_kernel); `shared` too: cloudsc2_nl_enss_* (the same kernel on EnssGeom)
 template <typename T>
 int nl_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,
-            const T* eta, T* const* out, double dt, void* stream, bool ens = false, int32_t nmem = 0, int64_t ms = 0) {
+            const T* eta, T* const* out, double dt, void* stream, bool ens = false, const cs2::CallMembers& m = {},
+            bool shared = false) {
     if (int rc = check_common(fn, p, nx, nz, ls)) return rc;
-    if (int rc = check_members<T>(fn, ens, nx, nz, ls, nmem, ms)) return rc;
+    if (int rc = check_members<T>(fn, ens, nx, nz, ls, m.nmem, m.ms)) return rc;
+    if (shared)
+        if (int rc = check_shared<T>(fn, m, nx, nz, ls, in, eta, [&](auto&& hit) {
+                for (int i = 0; out && i < NL_NUM_OUT; ++i) hit("out", i, out[i]);
+            }))
+            return rc;
     if (nx == 0) return CLOUDSC2_OK;   // empty call: nothing to check or launch (zero-size tensors carry NULL pointers)
     if (int rc = check_ptrs(fn, "in", in, NL_NUM_IN)) return rc;
     if (int rc = check_ptrs(fn, "out", const_cast<const T* const*>(out), NL_NUM_OUT)) return rc;
@@ -83,7 +156,7 @@ int nl_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t nz, int
     if (!(dt > 0.0)) return fail(CLOUDSC2_E_ARG, "%s: dt=%g must be > 0", fn, dt);
     if (ens)
         return launched(fn, cs2::launch_nl_ens<T>(*p, nx, nz, ls, in, eta, out, dt, static_cast<hipStream_t>(stream), nullptr,
-                                                  nmem, ms));
+                                                  m, shared));
     return launched(fn, cs2::launch_nl<T>(*p, nx, nz, ls, in, eta, out, dt, static_cast<hipStream_t>(stream), nullptr,
                                           0.0, nullptr, nullptr));
 }
@@ -93,9 +166,15 @@ int nl_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t nz, int
 template <typename T>
 int nl_fused_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,
                   const T* const* in_i, double pf, T* qsat_out, const T* eta, T* const* out, double dt, void* stream,
-                  bool ens = false, int32_t nmem = 0, int64_t ms = 0) {
+                  bool ens = false, const cs2::CallMembers& m = {}, bool shared = false) {
     if (int rc = check_common(fn, p, nx, nz, ls)) return rc;
-    if (int rc = check_members<T>(fn, ens, nx, nz, ls, nmem, ms)) return rc;
+    if (int rc = check_members<T>(fn, ens, nx, nz, ls, m.nmem, m.ms)) return rc;
+    if (shared)      // cloudsc2_nl_fused_enss_*
+        if (int rc = check_shared<T>(fn, m, nx, nz, ls, in, eta, [&](auto&& hit) {
+                for (int i = 0; out && i < NL_NUM_OUT; ++i) hit("out", i, out[i]);
+                hit("qsat_out", 0, qsat_out);
+            }))
+            return rc;
     if (nx == 0) return CLOUDSC2_OK;   // empty call: nothing to check or launch (zero-size tensors carry NULL pointers)
     if (int rc = check_ptrs(fn, "out", const_cast<const T* const*>(out), NL_NUM_OUT)) return rc;
     if (!in) return fail(CLOUDSC2_E_ARG, "%s: in is NULL", fn);
@@ -115,7 +194,7 @@ int nl_fused_impl(const char* fn, const Cloudsc2Params* p, int32_t nx, int32_t n
     if (!(dt > 0.0)) return fail(CLOUDSC2_E_ARG, "%s: dt=%g must be > 0", fn, dt);
     if (ens)
         return launched(fn, cs2::launch_nl_ens<T>(*p, nx, nz, ls, in, eta, out, dt, static_cast<hipStream_t>(stream), qsat_out,
-                                                  nmem, ms));
+                                                  m, shared));
     return launched(fn, cs2::launch_nl<T>(*p, nx, nz, ls, in, eta, out, dt, static_cast<hipStream_t>(stream), in_i, pf,
                                           qsat_out, nullptr));
 }
@@ -332,6 +411,12 @@ int tl_masked_impl(const char* fn, const cs2::TLCall<T>& c) {
     if (multi)
         if (int rc = check_dirs(fn, c.nz, c.ls, c.dirs, CLOUDSC2_TL_MAX_DIRS, "CLOUDSC2_TL_MAX_DIRS")) return rc;
     if (int rc = check_members<T>(fn, c.is(cs2::kEns), c.nx, c.nz, c.ls, c.members.nmem, c.members.ms)) return rc;
+    if (c.is(cs2::kShared))   // cloudsc2_tl_enss_* / cloudsc2_tl_step_enss_* (tl_enss_kernel / tl_enss_step_kernel)
+        if (int rc = check_shared<T>(fn, c.members, c.nx, c.nz, c.ls, c.in, c.eta, [&](auto&& hit) {
+                for (int i = 0; c.out && i < NL_NUM_OUT; ++i) hit("out", i, c.out[i]);
+                for (int i = 0; c.out_i && i < NL_NUM_OUT; ++i) hit("out_i", i, c.out_i[i]);
+            }))
+            return rc;
     if (c.nx == 0) return CLOUDSC2_OK;
     if (int rc = step ? check_step_trajectory(fn, c.in) : check_ptrs(fn, "in", c.in, NL_NUM_IN)) return rc;
     if (step && c.in_i && c.in_i[NL_IN_QSAT])
@@ -360,17 +445,7 @@ int tl_masked_impl(const char* fn, const cs2::TLCall<T>& c) {
 }
 
 // The evaporation ensemble entries: sweep 1 WRITES `cover` while every other field of the call is read (or written by sweep
-// 2), so a `cover` that shares storage with one of them is refused.  Judged on bounding ranges: one member of a field spans
-// `ea` / `eb` bytes, member m starts m * `sb` bytes behind member 0; `a` has `na` members, `b` has `nb` (1: the zero line, eta).
-// Member i of `a` meets member j of `b` iff -ea < (a - b) + (i - j) * sb < eb.
-bool member_ranges_overlap(const void* a, int64_t ea, int64_t na, const void* b, int64_t eb, int64_t nb, int64_t sb) {
-    const int64_t delta = int64_t(reinterpret_cast<intptr_t>(a) - reinterpret_cast<intptr_t>(b));
-    const auto floor_div = [](int64_t x, int64_t y) { return x / y - ((x % y != 0 && x < 0) ? 1 : 0); };   // y > 0
-    const int64_t dmin = floor_div(-ea - delta, sb) + 1;       // the d = i - j with -ea < delta + d * sb ...
-    const int64_t dmax = -floor_div(delta - eb, sb) - 1;       // ... and delta + d * sb < eb
-    return std::max(dmin, -(nb - 1)) <= std::min(dmax, na - 1);
-}
-
+// 2), so a `cover` that shares storage with one of them is refused (member_ranges_overlap, above).
 template <typename T>
 int check_cover_disjoint(const char* fn, const cs2::ADCall<T>& c) {
     const int64_t nmem = c.members.nmem;
@@ -411,6 +486,11 @@ int ad_masked_impl(const char* fn, const cs2::ADCall<T>& c) {
     if (int rc = check_members<T>(fn, ens, c.nx, c.nz, c.ls, c.members.nmem, c.members.ms)) return rc;
     if (multi && ens)
         if (int rc = check_member_batches(fn, c.nz, c.ls, c.dirs, c.members)) return rc;
+    if (c.is(cs2::kShared))   // cloudsc2_ad_enss_* / cloudsc2_ad_step_enss_* (ad_enss_kernel / ad_enss_step_kernel)
+        if (int rc = check_shared<T>(fn, c.members, c.nx, c.nz, c.ls, c.in, c.eta, [&](auto&& hit) {
+                for (int i = 0; c.out_adj && i < NL_NUM_IN; ++i) hit("out_adj", i, c.out_adj[i]);
+            }))
+            return rc;
     if (c.nx == 0) return CLOUDSC2_OK;
     if (int rc = step ? check_step_trajectory(fn, c.in) : check_ptrs(fn, "in", c.in, NL_NUM_IN)) return rc;
     if (int rc = check_masked_inputs(fn, "in_adj", c.in_adj, NL_NUM_OUT, c.zero)) return rc;
@@ -664,7 +744,7 @@ int32_t cloudsc2_perturbed_state_f32(const Cloudsc2Params* p, int32_t nx, int32_
                                      double f, void* stream) {
     return per_impl<float>("cloudsc2_perturbed_state_f32", p, nx, nz, ls, in, in_i, out, f, stream);
 }
-// ---- the masked TL / AD family, all twenty-two entries once per precision.  Every wrapper builds the call descriptor from its own
+// ---- the masked TL / AD family, all twenty-eight entries once per precision.  Every wrapper builds the call descriptor from its own
 // arguments: the head and the arrays by CS2_TL_CALL / CS2_AD_CALL under the entry's form, then the groups the entry has.
 #define CS2_TL_ARGS(T)                                                                                                         \
     const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in, const T* const* in_i, const T* zero_line, \
@@ -674,6 +754,7 @@ int32_t cloudsc2_perturbed_state_f32(const Cloudsc2Params* p, int32_t nx, int32_
         const T* zero_line, const T* eta, const T* traj_fplsl, const T* traj_fplsn, T* const* out_adj, double dt
 #define CS2_DIRS_ARGS int32_t ndir, int64_t in_ds, int64_t out_ds
 #define CS2_ENS_ARGS int32_t nmem, int64_t ms
+#define CS2_ENSS_ARGS int32_t nmem, int64_t ms, int64_t shared_mask, int64_t eta_ms
 #define CS2_MENS_ARGS int32_t nmem, int64_t ms, int64_t in_ms, int64_t out_ms
 #define CS2_COVER_ARGS(T) T* cover, int32_t cover_ready
 #define CS2_TL_CALL(T, FORM)                                                                                                   \
@@ -683,6 +764,8 @@ int32_t cloudsc2_perturbed_state_f32(const Cloudsc2Params* p, int32_t nx, int32_
                      in_adj, traj_fplsl, traj_fplsn, out_adj}
 #define CS2_DIRS c.dirs = {ndir, in_ds, out_ds}
 #define CS2_ENS c.members = {nmem, ms}
+#define CS2_ENSS_MEMBERS {nmem, ms, 0, 0, shared_mask, eta_ms}
+#define CS2_ENSS c.members = CS2_ENSS_MEMBERS
 #define CS2_MENS c.members = {nmem, ms, in_ms, out_ms}
 #define CS2_COVER c.cover = {cover, cover_ready}
 #define CS2_MASKED_ENTRIES(SFX, T)                                                                                             \
@@ -742,6 +825,27 @@ int32_t cloudsc2_perturbed_state_f32(const Cloudsc2Params* p, int32_t nx, int32_
         CS2_ENS;                                                                                                               \
         return ad_masked_impl<T>("cloudsc2_ad_step_ens_" #SFX, c);                                                             \
     }                                                                                                                          \
+    /* members that share part of their state: the ensemble entry's arguments + (shared_mask, eta_member_stride) */            \
+    int32_t cloudsc2_tl_enss_##SFX(CS2_TL_ARGS(T), void* stream, CS2_ENSS_ARGS) {                                              \
+        CS2_TL_CALL(T, cs2::kEns | cs2::kShared);                                                                              \
+        CS2_ENSS;                                                                                                              \
+        return tl_masked_impl<T>("cloudsc2_tl_enss_" #SFX, c);                                                                 \
+    }                                                                                                                          \
+    int32_t cloudsc2_tl_step_enss_##SFX(CS2_TL_ARGS(T), void* stream, CS2_ENSS_ARGS) {                                         \
+        CS2_TL_CALL(T, cs2::kStep | cs2::kEns | cs2::kShared);                                                                 \
+        CS2_ENSS;                                                                                                              \
+        return tl_masked_impl<T>("cloudsc2_tl_step_enss_" #SFX, c);                                                            \
+    }                                                                                                                          \
+    int32_t cloudsc2_ad_enss_##SFX(CS2_AD_ARGS(T), void* stream, CS2_ENSS_ARGS) {                                              \
+        CS2_AD_CALL(T, cs2::kEns | cs2::kShared);                                                                              \
+        CS2_ENSS;                                                                                                              \
+        return ad_masked_impl<T>("cloudsc2_ad_enss_" #SFX, c);                                                                 \
+    }                                                                                                                          \
+    int32_t cloudsc2_ad_step_enss_##SFX(CS2_AD_ARGS(T), void* stream, CS2_ENSS_ARGS) {                                         \
+        CS2_AD_CALL(T, cs2::kStep | cs2::kEns | cs2::kShared);                                                                 \
+        CS2_ENSS;                                                                                                              \
+        return ad_masked_impl<T>("cloudsc2_ad_step_enss_" #SFX, c);                                                            \
+    }                                                                                                                          \
     /* members times directions: the multi entry's arguments + (nmem, member_stride, in_member_stride, out_member_stride) */   \
     int32_t cloudsc2_ad_multi_ens_##SFX(CS2_AD_ARGS(T), void* stream, CS2_DIRS_ARGS, CS2_MENS_ARGS) {                          \
         CS2_AD_CALL(T, cs2::kMulti | cs2::kEns);                                                                               \
@@ -788,13 +892,24 @@ int32_t cloudsc2_perturbed_state_f32(const Cloudsc2Params* p, int32_t nx, int32_
     /* the ensemble forms of the two NL entries: the single entry's arguments + (nmem, member_stride) */                       \
     int32_t cloudsc2_nl_ens_##SFX(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,             \
                                   const T* eta, T* const* out, double dt, void* stream, CS2_ENS_ARGS) {                        \
-        return nl_impl<T>("cloudsc2_nl_ens_" #SFX, p, nx, nz, ls, in, eta, out, dt, stream, true, nmem, ms);                   \
+        return nl_impl<T>("cloudsc2_nl_ens_" #SFX, p, nx, nz, ls, in, eta, out, dt, stream, true, {nmem, ms});                 \
     }                                                                                                                          \
     int32_t cloudsc2_nl_fused_ens_##SFX(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,       \
                                         const T* const* in_i, double pf, T* qsat_out, const T* eta, T* const* out, double dt,  \
                                         void* stream, CS2_ENS_ARGS) {                                                          \
         return nl_fused_impl<T>("cloudsc2_nl_fused_ens_" #SFX, p, nx, nz, ls, in, in_i, pf, qsat_out, eta, out, dt, stream,    \
-                                true, nmem, ms);                                                                               \
+                                true, {nmem, ms});                                                                             \
+    }                                                                                                                          \
+    /* ... and their shared-state forms: + (shared_mask, eta_member_stride) */                                                 \
+    int32_t cloudsc2_nl_enss_##SFX(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,            \
+                                   const T* eta, T* const* out, double dt, void* stream, CS2_ENSS_ARGS) {                      \
+        return nl_impl<T>("cloudsc2_nl_enss_" #SFX, p, nx, nz, ls, in, eta, out, dt, stream, true, CS2_ENSS_MEMBERS, true);    \
+    }                                                                                                                          \
+    int32_t cloudsc2_nl_fused_enss_##SFX(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t ls, const T* const* in,      \
+                                         const T* const* in_i, double pf, T* qsat_out, const T* eta, T* const* out, double dt, \
+                                         void* stream, CS2_ENSS_ARGS) {                                                        \
+        return nl_fused_impl<T>("cloudsc2_nl_fused_enss_" #SFX, p, nx, nz, ls, in, in_i, pf, qsat_out, eta, out, dt, stream,   \
+                                true, CS2_ENSS_MEMBERS, true);                                                                 \
     }
 CS2_MASKED_ENTRIES(f64, double)
 CS2_MASKED_ENTRIES(f32, float)
@@ -810,6 +925,9 @@ CS2_MASKED_ENTRIES(f32, float)
 #undef CS2_DIRS
 #undef CS2_ENS
 #undef CS2_MENS
+#undef CS2_ENSS
+#undef CS2_ENSS_MEMBERS
+#undef CS2_ENSS_ARGS
 #undef CS2_COVER
 
 }  // extern "C"

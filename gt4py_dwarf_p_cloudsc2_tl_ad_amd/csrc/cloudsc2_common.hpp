@@ -58,6 +58,33 @@ struct EnsGeom {
 };
 constexpr int64_t kMaxGrid = 0x7FFFFFFF;   // workgroups of a one-dimensional grid
 
+// Ensembles that SHARE part of their state (the *_enss_kernel families; C ABI cloudsc2_*_enss_*): EnsGeom plus
+//   shared   bit i: state input i (NL_IN_*) is ONE field, the call's pointer, read by every member - its base is 0 instead of
+//            member * ms.  The select is wave-uniform (a scalar compare and select where the pointer is formed); the lanes'
+//            offsets do not change;
+//   eta_ms   0: one `eta` for all members; otherwise member m's level vector starts m * eta_ms elements behind `eta`.  A
+//            workgroup serves one member and builds its level table from that member's vector;
+//   order    how the remapped block index is split (enss_block): kMemberMajor as ens_block (member * bpm + column block),
+//            kColumnMajor as column block * nmem + member - the nmem workgroups that read one column block of a shared
+//            field are then neighbours in dispatch order.
+// A kernel templated on its geometry G compiles the shared form where G is EnssGeom; with EnsGeom nothing of it exists.
+enum EnsOrder : int { kMemberMajor = 0, kColumnMajor = 1 };
+constexpr int kEnssDefaultOrder = kMemberMajor;   // docs/TUNING_LOG.md 3.27
+struct EnssGeom : EnsGeom {
+    uint32_t shared;
+    int nmem;
+    int order;
+    int64_t eta_ms;
+};
+template <typename G>
+constexpr bool kSharedGeom = std::is_same<G, EnssGeom>::value;
+__device__ __forceinline__ int enss_block(const EnssGeom& g, int& member) {
+    if (g.order == kMemberMajor) return ens_block(g.bpm, member);
+    const uint32_t v = uint32_t(xcd_block()), cb = v / uint32_t(g.nmem);
+    member = __builtin_amdgcn_readfirstlane(int(v - cb * uint32_t(g.nmem)));
+    return __builtin_amdgcn_readfirstlane(int(cb));
+}
+
 // ---- math in the working precision --------------------------------------------------------
 template <typename T> __device__ __forceinline__ T rexp(T x);
 template <> __device__ __forceinline__ double rexp<double>(double x) { return exp(x); }

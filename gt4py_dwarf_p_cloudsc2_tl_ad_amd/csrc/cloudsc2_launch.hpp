@@ -17,6 +17,7 @@ enum CallForm : unsigned {
     kMulti = 2u,   // has the directions group
     kEns = 4u,     // has the members group
     kEvap = 8u,    // has the cover group: the adjoints WITH the evaporation block
+    kShared = 16u, // with kEns: the *_enss_* entries - the members group carries shared_mask and eta_ms too
 };
 struct CallDirs {      // direction d of a field lies d * in_ds (inputs) / d * out_ds (outputs) elements behind direction 0
     int ndir;
@@ -28,7 +29,16 @@ struct CallMembers {   // member m of every field lies m * ms elements behind me
     // kMulti and kEns (cloudsc2_ad_multi_ens_* / _multi_step_ens_*): `ms` is the state's and the trajectory fluxes'; member m of
     // a batched forcing / adjoint lies m * in_ms / m * out_ms elements behind member 0 (its directions inside the member)
     int64_t in_ms, out_ms;
+    // kShared (cloudsc2_*_enss_*): bit i of shared_mask - state input i is ONE field read by every member; the two
+    // CLOUDSC2_ENSS_*_MAJOR bits choose the block order of the launch; eta_ms: 0, or the member stride of `eta` (elements)
+    int64_t shared_mask, eta_ms;
 };
+// the kernels' geometry of a kShared call (the checks have passed); bpm: column blocks per member
+inline EnssGeom enss_geom(const CallMembers& m, int bpm) {
+    const int order = (m.shared_mask & CLOUDSC2_ENSS_COLUMN_MAJOR) ? kColumnMajor
+                      : (m.shared_mask & CLOUDSC2_ENSS_MEMBER_MAJOR) ? kMemberMajor : kEnssDefaultOrder;
+    return EnssGeom{{m.ms, bpm}, uint32_t(m.shared_mask & 0xFFFF), m.nmem, order, m.eta_ms};
+}
 template <typename T>
 struct CallCover {     // the caller's precipitation-cover field; cover_ready: it already holds the forward sweep's values
     T* cover;
@@ -82,7 +92,7 @@ int launch_nl(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T
               const T* const*, double, T*, double*);
 template <typename T>
 int launch_nl_ens(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T*, T* const*, double, hipStream_t, T*,
-                  int nmem, int64_t ms);
+                  const CallMembers&, bool shared);
 template <typename T>
 int launch_nl_taylor_multi(const Cloudsc2Params&, int, int, int64_t, const T* const*, const T* const*, int, const double*,
                            const T*, const T* const*, double*, double, hipStream_t, double);

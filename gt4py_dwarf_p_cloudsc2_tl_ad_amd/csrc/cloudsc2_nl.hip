@@ -532,6 +532,73 @@ nl_ens_kernel(Ext<T> e, NLK<T> kc, ExpK<T> xk, int nx, int nz, int64_t ls, CPtrs
     }
 }
 
+// nl_ens_kernel for members that SHARE part of their state and may each have an `eta` (BUILD EXTENSION, C ABI
+// cloudsc2_nl_enss_* / cloudsc2_nl_fused_enss_*; see EnssGeom).  The member is decoded in front of the level table, which is
+// built from the member's own level vector, and a shared input keeps the call's pointer; the bases are formed here, once.
+// A body of its own again, for the reason given above nl_ens_kernel: that kernel hoisted into a function both call lost
+// an fp32 wave per SIMD (71 -> 73 VGPRs, measured on the ISA), so it is left exactly as it was.
+template <typename T, bool EVAP, bool LIN, bool PINK, int FUSE>
+__global__ void __launch_bounds__(kColBlock, (sizeof(T) == 4 ? kF32Waves : 1))
+nl_enss_kernel(Ext<T> e, NLK<T> kc, ExpK<T> xk, int nx, int nz, int64_t ls, CPtrs<T, NL_NUM_IN> in, const T* __restrict__ eta,
+               MPtrs<T, NL_NUM_OUT> out, T dt, T* __restrict__ qsat_out, int keepq, EnssGeom g) {
+    static_assert(FUSE == 0 || FUSE == 1, "the perturbed variants have no ensemble form");
+    extern __shared__ __align__(16) unsigned char smem_raw[];
+    T* s_eta = reinterpret_cast<T*>(smem_raw);
+    T* s_scalm = s_eta + (nz + 1);
+    int klo, khi;
+    int member;
+    const int cblock = enss_block(g, member);
+    eta += member * g.eta_ms;
+    build_level_table<T>(eta, nz, e, s_eta, s_scalm, klo, khi);
+    if constexpr (PINK) pin_nl_constants(e, kc, xk, dt);
+
+    const int gcol = cblock * kColBlock + threadIdx.x;
+    if (gcol >= nx) return;   // see nl_kernel
+    const int64_t mb = member * g.ms;
+#pragma unroll
+    for (int i = 0; i < NL_NUM_IN; ++i) in.p[i] += (g.shared >> i & 1u) ? int64_t(0) : mb;   // FUSE 1: in_qsat is NULL, not read
+#pragma unroll
+    for (int i = 0; i < NL_NUM_OUT; ++i) out.p[i] += mb;
+    if constexpr (FUSE == 1) qsat_out += mb;
+    using O = uint32_t;
+    const O lsb = O(ls) * O(sizeof(T));
+    const O colb = O(gcol) * O(sizeof(T));
+    const T trpaus = trpaus_prescan<T, false, O>(in.p[NL_IN_T], in.p[NL_IN_TND_CML_T], lsb, colb, dt, s_eta, klo, khi);
+    const CrhCol<T> crh = crh_setup<T>(trpaus);
+
+    // :93-100
+    NLCarry<T> c;
+    c.rfl = T(0.0);
+    c.sfl = T(0.0);
+    c.covptot = T(0.0);
+    c.aph_k = ldg(in.p[NL_IN_APH], colb);
+    T aph_s = EVAP ? ldg(in.p[NL_IN_APH], O(nz) * lsb + colb) : T(1.0);
+    stg(out.p[NL_OUT_FPLSL], colb, T(0.0));   // top half level: see nl_kernel
+    stg(out.p[NL_OUT_FPLSN], colb, T(0.0));
+    stg(out.p[NL_OUT_FHPSL], colb, T(0.0));
+    stg(out.p[NL_OUT_FHPSN], colb, T(0.0));
+
+    // the level sweep of nl_kernel: one level of software prefetch, handed over by register copies
+    LevelIn<T> xa = load_level<T, O>(in, lsb, colb, FUSE == 1, keepq != 0);
+    landed(c.aph_k);   // first read inside the loop: see landed()
+    if constexpr (EVAP) landed(aph_s);
+    O o = colb;
+    for (int k = 0; k < nz; ++k) {
+        LevelIn<T> xn = xa;
+        if (k + 1 < nz) xn = load_level<T, O>(in, lsb, o + lsb, FUSE == 1, keepq != 0);
+        LevelIn<T> x = xa;
+        if constexpr (FUSE == 1) {
+            x.qsat = nl_saturation<T>(e, xk, x.ap, x.t);
+            stg(qsat_out, o, x.qsat);
+        }
+        const NLOut<T> r = nl_level<T, EVAP, LIN>(e, kc, xk, x, s_eta[k], s_scalm[k], crh, dt, aph_s, c);
+        nl_store<T, O>(out, e, lsb, o, r);
+        drain_vmem();   // see drain_vmem
+        xa = xn;
+        o += lsb;
+    }
+}
+
 // ------------------------------------------------------------------------------------------------
 // LDS-ring variant of the sweep (plain cloudsc2_nl, FUSE = 0).  Same prologue, same nl_level / nl_store; only the
 // way the 16 input words of a level reach the lane differs:
@@ -823,10 +890,13 @@ template int launch_nl<float>(const Cloudsc2Params&, int, int, int64_t, const fl
 
 // cloudsc2_nl (qsat_out == nullptr) or `saturation` + cloudsc2_nl (qsat_out given) for `nmem` members in one launch: always
 // the register path (nl_ens_kernel), 32-bit offsets within a member.  Every field pointer is member 0's, member m lies
-// m * ms elements behind it; the caller has checked nmem and ms.
+// m * ms elements behind it; the caller has checked nmem and ms.  `shared`: the cloudsc2_nl_enss_* / _nl_fused_enss_* entries
+// (nl_enss_kernel; the geometry is enss_geom's).
 template <typename T>
 int launch_nl_ens(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* const* in, const T* eta, T* const* out,
-                  double dt, hipStream_t stream, T* qsat_out, int nmem, int64_t ms) {
+                  double dt, hipStream_t stream, T* qsat_out, const CallMembers& members, bool shared) {
+    const int nmem = members.nmem;
+    const int64_t ms = members.ms;
     if (!fits_u32_offsets<T>(nz, ls)) return -2;
     if (qsat_out && !p.LPHYLIN) return -2;    // only the LPHYLIN form of `saturation` is fused
     const int bpm = (nx + kColBlock - 1) / kColBlock;
@@ -844,18 +914,23 @@ int launch_nl_ens(const Cloudsc2Params& p, int nx, int nz, int64_t ls, const T* 
     const int keepq = static_cast<uint64_t>(nmem) * static_cast<uint64_t>(ms) * sizeof(T) <= (uint64_t(128) << 20) ? 1 : 0;
     const EnsGeom g{ms, bpm};
     const Launch l{grid, smem, stream, qsat_out ? "cs2::nl_ens_kernel<saturation>" : "cs2::nl_ens_kernel"};
+    const Launch ls_{grid, smem, stream, qsat_out ? "cs2::nl_enss_kernel<saturation>" : "cs2::nl_enss_kernel"};
     return with_flags(
-        [&](auto EV, auto LN, auto SF) {
-            return launch_tail<nl_ens_kernel<T, EV, LN, sizeof(T) == 8, (SF ? 1 : 0)>>(l, e, kc, xk, nx, nz, ls, ci, eta, co, tdt,
-                                                                                       qsat_out, keepq, g);
+        [&](auto EV, auto LN, auto SF, auto SH) {
+            if constexpr (SH)
+                return launch_tail<nl_enss_kernel<T, EV, LN, sizeof(T) == 8, (SF ? 1 : 0)>>(
+                    ls_, e, kc, xk, nx, nz, ls, ci, eta, co, tdt, qsat_out, keepq, enss_geom(members, bpm));
+            else
+                return launch_tail<nl_ens_kernel<T, EV, LN, sizeof(T) == 8, (SF ? 1 : 0)>>(l, e, kc, xk, nx, nz, ls, ci, eta, co,
+                                                                                           tdt, qsat_out, keepq, g);
         },
-        evap, lin, qsat_out != nullptr);
+        evap, lin, qsat_out != nullptr, shared);
 }
 
 template int launch_nl_ens<double>(const Cloudsc2Params&, int, int, int64_t, const double* const*, const double*,
-                                   double* const*, double, hipStream_t, double*, int, int64_t);
+                                   double* const*, double, hipStream_t, double*, const CallMembers&, bool);
 template int launch_nl_ens<float>(const Cloudsc2Params&, int, int, int64_t, const float* const*, const float*,
-                                  float* const*, double, hipStream_t, float*, int, int64_t);
+                                  float* const*, double, hipStream_t, float*, const CallMembers&, bool);
 
 // ------------------------------------------------------------------------------------------------
 // The Taylor test's perturbed runs for NF step sizes in ONE launch (build extension, C ABI cloudsc2_nl_taylor_multi_*;

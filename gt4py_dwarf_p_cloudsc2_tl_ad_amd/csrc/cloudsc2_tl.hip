@@ -881,10 +881,10 @@ struct TLMaskedFields : KernArgs<TLMaskedArgs<T>> {
 // cloudsc2_tl_step_ens_*): see ens_block.  TLEnsFields is TLMaskedFields moved to one member: the member's base `mb`
 // (elements; wave-uniform) is added to the field pointer as a 64-bit scalar, the way tl_dirs_sweep adds the direction base;
 // an absent perturbation keeps the zero line's pointer (the line is 512 bytes long).  An unwanted output's pointer is never used.
-template <typename T>
+template <typename T, typename G = EnsGeom>
 struct TLEnsArgs {
     TLMaskedArgs<T> m;            // at kernarg offset 0
-    EnsGeom g;
+    G g;                          // EnssGeom: the shared-state form (tl_enss_kernel / tl_enss_step_kernel)
 };
 template <typename T>
 struct TLEnsFields : KernArgs<TLEnsArgs<T>> {
@@ -894,6 +894,15 @@ struct TLEnsFields : KernArgs<TLEnsArgs<T>> {
     __device__ __forceinline__ const T* in_i(int i) const { return this->ka->m.in_i.p[i] + ((have >> i & 1u) ? mb : int64_t(0)); }
     __device__ __forceinline__ T* out(int i) const { return this->ka->m.out.p[i] + mb; }
     __device__ __forceinline__ T* out_i(int i) const { return this->ka->m.out_i.p[i] + mb; }
+};
+// TLEnsFields whose SHARED state inputs (bit i of `sh`, EnssGeom::shared) keep the call's pointer: the base is selected the
+// way `in_i` selects the zero line's.  Perturbations and outputs stay per member.
+template <typename T>
+struct TLEnssFields : TLEnsFields<T> {
+    uint32_t sh;
+    __device__ __forceinline__ const T* in(int i) const {
+        return this->ka->m.in.p[i] + ((sh >> i & 1u) ? int64_t(0) : this->mb);
+    }
 };
 
 // load_level with a per-field offset: the field's own, or `zo` into the zero line.  SKIPQ: the qsat word is not read (the
@@ -971,8 +980,13 @@ __device__ __forceinline__ void tl_zero_top_flux(const FP& F, uint32_t want, O c
 // the level's t and ap words (LPHYLIN form, what cloudsc2_nl_fused_* computes) and the perturbation the level function
 // sees is g_t * t_i + g_ap * ap_i - formed at the head of the level's arithmetic, behind the prefetch of the next level.
 // ENS: one member of an ensemble per workgroup (`g`: EnsGeom; the field pointers are TLEnsFields').
-template <typename T, bool REG, bool EVAP, bool STEP, bool ENS = false>
-__device__ __forceinline__ void tl_masked_sweep(const TLMaskedArgs<T>& A, const EnsGeom g = EnsGeom{}) {
+// G = EnssGeom: the members share part of their state and may each have an `eta` (C ABI cloudsc2_tl_enss_* /
+// cloudsc2_tl_step_enss_*; see EnssGeom): the member is decoded in front of the level table, which is built from the member's
+// own level vector; the field pointers are TLEnssFields'.
+template <typename T, bool REG, bool EVAP, bool STEP, bool ENS = false, typename G = EnsGeom>
+__device__ __forceinline__ void tl_masked_sweep(const TLMaskedArgs<T>& A, const G g = G{}) {
+    constexpr bool SH = kSharedGeom<G>;
+    static_assert(ENS || !SH, "shared state is an ensemble form");
     Ext<T> e = A.e;
     NLK<T> kc = A.kc;
     ExpK<T> xk = A.xk;
@@ -981,22 +995,28 @@ __device__ __forceinline__ void tl_masked_sweep(const TLMaskedArgs<T>& A, const 
     const T* __restrict__ eta = A.eta;
     T dt = A.dt;
     const uint32_t have = A.have, want = A.want;
-    typename std::conditional<ENS, TLEnsFields<T>, TLMaskedFields<T>>::type F;
+    typename std::conditional<SH, TLEnssFields<T>, typename std::conditional<ENS, TLEnsFields<T>, TLMaskedFields<T>>::type>::type F;
     const auto F_in = [&](int i) { return F.in(i); };
     const auto F_in_i = [&](int i) { return F.in_i(i); };
     extern __shared__ __align__(16) unsigned char smem_raw[];
     T* s_eta = reinterpret_cast<T*>(smem_raw);
     T* s_scalm = s_eta + (nz + 1);
     int klo, khi;
+    int member = 0, cblock = 0;
+    if constexpr (SH) {
+        cblock = enss_block(g, member);
+        eta += member * g.eta_ms;
+    }
     build_level_table<T>(eta, nz, e, s_eta, s_scalm, klo, khi);
     if constexpr (sizeof(T) == 8) pin_tl_constants(e, kc, xk, dt);
 
     int gcol;
     if constexpr (ENS) {
-        int member;
-        gcol = ens_block(g.bpm, member) * kColBlock + threadIdx.x;
+        if constexpr (!SH) cblock = ens_block(g.bpm, member);
+        gcol = cblock * kColBlock + threadIdx.x;
         F.mb = member * g.ms;
         F.have = have;
+        if constexpr (SH) F.sh = g.shared;
     } else {
         gcol = xcd_block() * kColBlock + threadIdx.x;
     }
@@ -1065,6 +1085,20 @@ tl_ens_step_kernel(const TLEnsArgs<T> A) {
     tl_masked_sweep<T, REG, EVAP, true, true>(A.m, A.g);
 }
 
+// tl_ens_kernel / tl_ens_step_kernel for members that share part of their state (BUILD EXTENSION, C ABI cloudsc2_tl_enss_* /
+// cloudsc2_tl_step_enss_*): see EnssGeom
+template <typename T, bool REG, bool EVAP>
+__global__ void __launch_bounds__(kColBlock)
+tl_enss_kernel(const TLEnsArgs<T, EnssGeom> A) {
+    tl_masked_sweep<T, REG, EVAP, false, true, EnssGeom>(A.m, A.g);
+}
+
+template <typename T, bool REG, bool EVAP>
+__global__ void __launch_bounds__(kColBlock)
+tl_enss_step_kernel(const TLEnsArgs<T, EnssGeom> A) {
+    tl_masked_sweep<T, REG, EVAP, true, true, EnssGeom>(A.m, A.g);
+}
+
 // The arguments of a masked tangent-linear call as the kernels take them (launch_tl_masked; launch_tl_dirs for direction 0):
 // in_i[f] == nullptr: perturbation f is zero everywhere (read from `zero`) and not in `have`; out == nullptr: no NL outputs;
 // out_i[f] == nullptr: not in `want`, not written.
@@ -1093,12 +1127,14 @@ static TLMaskedArgs<T> fill_tl_masked_args(const TLCall<T>& c) {
 
 // Always the register path; 32-bit offsets only.  kStep: tl_step_kernel (in[NL_IN_QSAT] and in_i[NL_IN_QSAT] are not read).
 // kEns: the ensemble form (tl_ens_kernel / tl_ens_step_kernel) - every field pointer is member 0's, member m lies
-// m * ms elements behind it; the caller has checked nmem and ms.
+// m * ms elements behind it; the caller has checked nmem and ms.  kShared (with kEns): tl_enss_kernel / tl_enss_step_kernel -
+// the geometry is enss_geom's.
 template <typename T>
 int launch_tl_masked(const TLCall<T>& c) {
     if (!fits_u32_offsets<T>(c.nz, c.ls)) return -2;
     const bool step = c.is(kStep);
     const int nmem = c.is(kEns) ? c.members.nmem : 0;
+    if (c.is(kShared) && nmem < 1) return -1;
     TLEnsArgs<T> ens;
     const TLMaskedArgs<T>& args = ens.m = fill_tl_masked_args<T>(c);
     const int bpm = (c.nx + kColBlock - 1) / kColBlock;
@@ -1108,8 +1144,12 @@ int launch_tl_masked(const TLCall<T>& c) {
     ens.g.ms = c.members.ms; ens.g.bpm = bpm;
     const dim3 egrid(unsigned(nmem > 0 ? nmem : 1) * unsigned(bpm));
     return with_flags(
-        [&](auto REG, auto EVAP, auto STEP, auto ENS) {
-            if constexpr (ENS) {
+        [&](auto REG, auto EVAP, auto STEP, auto ENS, auto SH) {
+            if constexpr (ENS && SH) {
+                constexpr auto kern = STEP ? tl_enss_step_kernel<T, REG, EVAP> : tl_enss_kernel<T, REG, EVAP>;
+                const TLEnsArgs<T, EnssGeom> enss = {args, enss_geom(c.members, bpm)};
+                return launch_tail<kern>({egrid, smem, c.stream, step ? "cs2::tl_enss_step_kernel" : "cs2::tl_enss_kernel"}, enss);
+            } else if constexpr (ENS) {
                 constexpr auto kern = STEP ? tl_ens_step_kernel<T, REG, EVAP> : tl_ens_kernel<T, REG, EVAP>;
                 return launch_tail<kern>({egrid, smem, c.stream, step ? "cs2::tl_ens_step_kernel" : "cs2::tl_ens_kernel"}, ens);
             } else {
@@ -1117,7 +1157,7 @@ int launch_tl_masked(const TLCall<T>& c) {
                 return launch_tail<kern>({grid, smem, c.stream, step ? "cs2::tl_step_kernel" : "cs2::tl_masked_kernel"}, args);
             }
         },
-        c.p->LREGCL != 0, evap_on(*c.p), step, nmem > 0);
+        c.p->LREGCL != 0, evap_on(*c.p), step, nmem > 0, c.is(kShared));
 }
 
 template int launch_tl_masked<double>(const TLCall<double>&);

@@ -41,7 +41,7 @@
 extern "C" {
 #endif
 
-/* Stays 4 with the cloudsc2_saturation_tl_* / _ad_* and cloudsc2_tl_step_* / _ad_step_* entries: they are purely additive
+/* Stays 4 with the cloudsc2_saturation_tl_* / _ad_*, cloudsc2_tl_step_* / _ad_step_* and cloudsc2_*_enss_* entries: they are purely additive
  * (no existing prototype, enum or struct changed), so a caller built against the earlier version 4 header runs unchanged. */
 #define CLOUDSC2_ABI_VERSION 4
 
@@ -585,6 +585,92 @@ int32_t cloudsc2_ad_step_ens_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz
                                  const float* const* in, const float* const* in_adj, const float* zero_line,
                                  const float* eta, const float* traj_fplsl, const float* traj_fplsn,
                                  float* const* out_adj, double dt, void* stream, int32_t nmem, int64_t member_stride);
+
+/* ---- ENSEMBLES THAT SHARE PART OF THEIR STATE (BUILD EXTENSIONS): the six ensemble entries above for members that differ in
+ * a few state fields (t, q, ql, qi of an ensemble of analyses) and share the rest (pressures, convective inputs, supsat, the
+ * tnd_cml_*), and whose `eta` may differ per member.  Nothing is copied: a shared field is ONE field, read by every member.
+ * Arguments are those of the ensemble entry named in the table, followed by:
+ *   shared_mask        bit i (i = NL_IN_*, 0 .. 15; the step and the fused entries use the same indices) set: in[i] is ONE
+ *                      field, the call's pointer, read by every member; clear: in[i] is batched, member m lies
+ *                      m * member_stride elements behind it, as above.  Only the state inputs `in` can be shared:
+ *                      perturbations, forcings, the trajectory fluxes, every result and qsat_out stay per member.
+ *                      A set bit on a NULL entry of `in` (in[NL_IN_QSAT] of the step and fused entries), or any bit
+ *                      other than bits 0 .. 15 and the two below, is CLOUDSC2_E_ARG.  (Signed in the prototype, like
+ *                      every integer of this header; a negative value has bits that are refused.)
+ *                      CLOUDSC2_ENSS_COLUMN_MAJOR / CLOUDSC2_ENSS_MEMBER_MAJOR (at most one, CLOUDSC2_E_ARG otherwise)
+ *                      choose how workgroups are dealt to (member, column block) pairs: column block * nmem + member - the
+ *                      workgroups that read one column block of a shared field are neighbours in dispatch order - or
+ *                      member * ceil(nx / 256) + column block as in the entries above.  Neither bit: the library's
+ *                      default (member-major; docs/TUNING_LOG.md 3.27).  The results do not depend on the order.
+ *   eta_member_stride  0: one `eta` for all members; >= nz + 1: member m's level vector starts m * eta_member_stride
+ *                      ELEMENTS behind `eta`; anything else is CLOUDSC2_E_ARG.
+ *       shared-state entry          ensemble entry               kernel reported by cloudsc2_last_kernel
+ *       cloudsc2_nl_enss_*          cloudsc2_nl_ens_*            cs2::nl_enss_kernel
+ *       cloudsc2_nl_fused_enss_*    cloudsc2_nl_fused_ens_*      cs2::nl_enss_kernel<saturation>
+ *       cloudsc2_tl_enss_*          cloudsc2_tl_ens_*            cs2::tl_enss_kernel
+ *       cloudsc2_tl_step_enss_*     cloudsc2_tl_step_ens_*       cs2::tl_enss_step_kernel
+ *       cloudsc2_ad_enss_*          cloudsc2_ad_ens_*            cs2::ad_enss_kernel
+ *       cloudsc2_ad_step_enss_*     cloudsc2_ad_step_ens_*       cs2::ad_enss_step_kernel
+ * Every rule of the ensemble entry holds (the 4 GiB bound is per member, as there).  In addition a written field - a result,
+ * out / out_i / out_adj, or qsat_out - whose extent in ANY member overlaps a shared input, or the per-member eta rows, is refused (CLOUDSC2_E_ARG): every
+ * member reads that input for the whole launch.  With shared_mask = 0 and eta_member_stride = 0 the results are those of
+ * the ensemble entry bit for bit; in general member m's results are what the single entry writes for member m's state (its
+ * own fields and the shared ones) and member m's `eta`.  The adjoint entries write PER-MEMBER adjoints of shared inputs too
+ * (out_adj is batched): the adjoint of the shared field itself is their sum over the members, left to the caller.
+ * Not available for the evaporation-switch ensembles (cloudsc2_ad_evap*_ens_*) and members times directions
+ * (cloudsc2_ad_multi*_ens_*): materialise the members for those. */
+#define CLOUDSC2_ENSS_COLUMN_MAJOR (INT64_C(1) << 32)
+#define CLOUDSC2_ENSS_MEMBER_MAJOR (INT64_C(1) << 33)
+int32_t cloudsc2_nl_enss_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                             const double* const* in, const double* eta, double* const* out, double dt, void* stream,
+                             int32_t nmem, int64_t member_stride, int64_t shared_mask, int64_t eta_member_stride);
+int32_t cloudsc2_nl_enss_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                             const float* const* in, const float* eta, float* const* out, double dt, void* stream,
+                             int32_t nmem, int64_t member_stride, int64_t shared_mask, int64_t eta_member_stride);
+int32_t cloudsc2_nl_fused_enss_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                   const double* const* in, const double* const* in_i, double pf, double* qsat_out,
+                                   const double* eta, double* const* out, double dt, void* stream,
+                                   int32_t nmem, int64_t member_stride, int64_t shared_mask, int64_t eta_member_stride);
+int32_t cloudsc2_nl_fused_enss_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                   const float* const* in, const float* const* in_i, double pf, float* qsat_out,
+                                   const float* eta, float* const* out, double dt, void* stream,
+                                   int32_t nmem, int64_t member_stride, int64_t shared_mask, int64_t eta_member_stride);
+int32_t cloudsc2_tl_enss_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                             const double* const* in, const double* const* in_i, const double* zero_line,
+                             const double* eta, double* const* out, double* const* out_i, double dt, void* stream,
+                             int32_t nmem, int64_t member_stride, int64_t shared_mask, int64_t eta_member_stride);
+int32_t cloudsc2_tl_enss_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                             const float* const* in, const float* const* in_i, const float* zero_line,
+                             const float* eta, float* const* out, float* const* out_i, double dt, void* stream,
+                             int32_t nmem, int64_t member_stride, int64_t shared_mask, int64_t eta_member_stride);
+int32_t cloudsc2_tl_step_enss_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                  const double* const* in, const double* const* in_i, const double* zero_line,
+                                  const double* eta, double* const* out, double* const* out_i, double dt, void* stream,
+                                  int32_t nmem, int64_t member_stride, int64_t shared_mask, int64_t eta_member_stride);
+int32_t cloudsc2_tl_step_enss_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                  const float* const* in, const float* const* in_i, const float* zero_line,
+                                  const float* eta, float* const* out, float* const* out_i, double dt, void* stream,
+                                  int32_t nmem, int64_t member_stride, int64_t shared_mask, int64_t eta_member_stride);
+int32_t cloudsc2_ad_enss_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                             const double* const* in, const double* const* in_adj, const double* zero_line,
+                             const double* eta, const double* traj_fplsl, const double* traj_fplsn,
+                             double* const* out_adj, double dt, void* stream, int32_t nmem, int64_t member_stride,
+                             int64_t shared_mask, int64_t eta_member_stride);
+int32_t cloudsc2_ad_enss_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                             const float* const* in, const float* const* in_adj, const float* zero_line,
+                             const float* eta, const float* traj_fplsl, const float* traj_fplsn,
+                             float* const* out_adj, double dt, void* stream, int32_t nmem, int64_t member_stride,
+                             int64_t shared_mask, int64_t eta_member_stride);
+int32_t cloudsc2_ad_step_enss_f64(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                  const double* const* in, const double* const* in_adj, const double* zero_line,
+                                  const double* eta, const double* traj_fplsl, const double* traj_fplsn,
+                                  double* const* out_adj, double dt, void* stream, int32_t nmem, int64_t member_stride,
+                                  int64_t shared_mask, int64_t eta_member_stride);
+int32_t cloudsc2_ad_step_enss_f32(const Cloudsc2Params* p, int32_t nx, int32_t nz, int64_t lev_stride,
+                                  const float* const* in, const float* const* in_adj, const float* zero_line,
+                                  const float* eta, const float* traj_fplsl, const float* traj_fplsn,
+                                  float* const* out_adj, double dt, void* stream, int32_t nmem, int64_t member_stride,
+                                  int64_t shared_mask, int64_t eta_member_stride);
 
 /* ---- ENSEMBLES WITH THE EVAPORATION BLOCK (BUILD EXTENSIONS): cloudsc2_ad_evap_* and cloudsc2_ad_evap_step_* for `nmem`
  * members in one launch, one cotangent per member.  Arguments are those of the single entry, `cover` and `cover_ready` in
