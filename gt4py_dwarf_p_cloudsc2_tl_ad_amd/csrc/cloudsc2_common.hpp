@@ -236,10 +236,14 @@ __device__ __forceinline__ T logistic_sech2(T ex, T rr) {
 // the levels below (docs/TUNING_LOG.md 3.14: which of the two happened depended on the last bit of an exp).  For that
 // case the same derivative is arranged as f_i + f / prtot (dpr_i - prtot_i): its second term is exactly 0 when the
 // capped dpr_i equals prtot_i, so the perturbation left is exactly 0.  The trajectory keeps the reference's dpr f / prtot.
+// The last term is formed from the ratios dpr / prtot and f / prtot: as dpr * f * prtot_i * rpr * rpr its first two products
+// are of three small numbers (a residual flux of 5e-17 beside a prtot of 1e-10 and a prtot_i of 5e-12 gave 1e-38) and went
+// subnormal in float32 before rpr^2 brought them back, which cost the term its last bits and the kernel its exact
+// homogeneity in the perturbation (tests/test_metamorphic_linearity.py).
 template <typename T>
 __device__ __forceinline__ T evaporated_i(T dpr, T dpr_i, T f, T f_i, T prtot, T prtot_i, T rpr) {
     const T all = f_i + f * rpr * (dpr_i - prtot_i);
-    const T part = (dpr_i * f + dpr * f_i) * rpr - dpr * f * prtot_i * rpr * rpr;
+    const T part = (dpr_i * f + dpr * f_i) * rpr - (dpr * rpr) * (f * rpr) * prtot_i;
     return dpr == prtot ? all : part;
 }
 
